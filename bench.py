@@ -11,6 +11,8 @@ temperature update, rate-table refresh and interface-list evaluation every 20 st
 `value` = EXECUTED events per second of that loop (= steps/s: one event per sweep, exactly like the
 reference).  The candidate-event rate (entries of get_event_rates' list per second), the exact
 incremental loop and Mode B (several events per sweep) are reported beside it under their own names.
+`--dump-outputs DIR` writes what the timed steps computed as DIR/<name>.npy (dump_outputs), so that two builds can be
+compared output for output: the inputs depend only on the arguments.
 
 `--gpus N` runs BASELINE.json's configurations: N=1 config 3 (256^3), N=2/4 config 4 (the SAME 256^3
 lattice in 2/4 axis-0 slabs: strong scaling), N=8 config 5 (512^3, impurity_c=0.2, defect mask refreshed
@@ -41,6 +43,9 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 B_ALG_SWEEP = 9.0              # bytes/voxel/sweep: census class u8 + rate-table entry f64, each read once
 IMPURITY_C, DEFECT_FRACTION, SEED = 0.2, 3e-3, 42
 DEFECT_REFRESH_EVERY = 200     # kmc_simulation.py:335-338 (METRIC_UPDATE_STEP)
+DUMP_BYTES_MAX = 64 * 2 ** 20  # --dump-outputs: all .npy files together
+DUMP_SAMPLE_VOXELS = 2 ** 19   # --dump-outputs: seeded sample of the lattice (40 B per voxel over the six arrays)
+DUMP_STEPS_MAX = 200000        # --dump-outputs: per-step arrays of at most the last this many timed steps (~160 B per step)
 
 
 def streams(n, seed):
@@ -86,6 +91,52 @@ def cpu_baseline(L, fields, n_gpu_events, budget_s=15.0):
     ev = np.concatenate(ev_all)
     nev = np.concatenate(nev_all)
     return dict(steps=done, events=ev, n_events=nev, legs=legs)
+
+
+def dump_outputs(out_dir, eng, r, step0, L):
+    """--dump-outputs DIR: what the timed batch computed, as DIR/<name>.npy (float32 where the values are small integers,
+    float64 otherwise), so that two builds can be compared output for output.
+      events_* / n_events / totals / step_index: what cetkmc_run_steps handed back for the timed steps (event log, candidate
+        counts, total rates), the last DUMP_STEPS_MAX of them at most;
+      run_result: done, status, np_used, q_used, nucleation_count, full_sweeps of that call;
+      lattice_*: the lattice the last timed step left behind on this rank's owned planes, at a fixed sample of
+        DUMP_SAMPLE_VOXELS voxels (RandomState(SEED), global row-major indices in lattice_index);
+      site_*: the same fields at every voxel a logged event names (pos and target), sorted by index.
+    Called right after the timed region: downloading the planes does not change the device state."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_all = len(r["events"])
+    k0 = max(0, n_all - DUMP_STEPS_MAX)
+    ev = r["events"][k0:]
+    out = {
+        "step_index": np.arange(step0 + k0, step0 + n_all, dtype=np.float64),
+        "events_type": ev["type"].astype(np.float32), "events_pos": ev["pos"].astype(np.float32),
+        "events_target": ev["target"].astype(np.float32), "events_atom": ev["atom"].astype(np.float32),
+        "events_rate": ev["rate"].astype(np.float64), "events_dep_rank": ev["dep_rank"].astype(np.float64),
+        "events_theta": ev["theta"].astype(np.float64), "events_phi": ev["phi"].astype(np.float64),
+        "n_events": r["n_events"][k0:].astype(np.float64), "totals": r["totals"][k0:].astype(np.float64),
+        "run_result": np.array([r[k] for k in ("done", "status", "np_used", "q_used", "nucleation_count", "full_sweeps")],
+                               dtype=np.float64),
+    }
+    d = eng.download_planes(eng.i0, eng.i1, state=True, theta=True, phi=True, T=True, defects=True)
+    n_own = (eng.i1 - eng.i0) * L * L
+    rs = np.random.RandomState(SEED)
+    pick = np.sort(rs.choice(n_own, DUMP_SAMPLE_VOXELS, replace=False)) if n_own > DUMP_SAMPLE_VOXELS else np.arange(n_own)
+    sites = np.concatenate([ev["pos"], ev["target"]]).astype(np.int64)
+    sites = sites[np.all((sites >= 0) & (sites < L), axis=1) & (sites[:, 0] >= eng.i0) & (sites[:, 0] < eng.i1)]
+    sites = np.unique(((sites[:, 0] - eng.i0) * L + sites[:, 1]) * L + sites[:, 2])
+    for prefix, idx in (("lattice", pick), ("site", sites)):
+        out[f"{prefix}_index"] = (idx + eng.i0 * L * L).astype(np.float64)
+        for f in ("state", "defects"):
+            out[f"{prefix}_{f}"] = d[f].reshape(-1)[idx].astype(np.float32)
+        for f in ("theta", "phi", "T"):
+            out[f"{prefix}_{f}"] = d[f].reshape(-1)[idx].astype(np.float64)
+    del d
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES_MAX, f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES_MAX} byte budget"
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": os.path.abspath(out_dir), "files": len(out), "bytes": int(total), "steps_logged": n_all - k0,
+            "lattice_sample_voxels": int(len(pick)), "event_sites": int(len(sites))}
 
 
 def live_traffic(L, steps=20, timeout=90):
@@ -168,6 +219,9 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--force-dist", action="store_true",
                     help="take the multi-process code path (gloo rendezvous + RCCL communicator) even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (event log, totals, seeded lattice sample; rank 0) "
+                         "as DIR/<name>.npy, at most 64 MB")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -386,6 +440,7 @@ def main():
         dist.all_gather_object(box, digest)
         ranks_agree = all(x == box[0] for x in box)
         assert ranks_agree, f"ranks disagree on the timed steps' event log: {box}"
+    dumped = dump_outputs(a.dump_outputs, eng, r, step - a.steps, L) if (a.dump_outputs and rank == 0) else None
 
     # ---- after the timed region: per-phase device time (hipEvents at every phase boundary, cetkmc_get_counters)
     extras_errors = {}
@@ -767,6 +822,8 @@ def main():
                                     "note": "self-test: patterned all-gather + neighbour exchange verified before timing (wall "
                                             "microseconds per call incl. the stream synchronisation); event log: sha256 of the "
                                             "timed steps' events / totals / counts equal on every rank"}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if extras_errors:
         out["extras_errors"] = extras_errors
     sys.stdout.flush()
