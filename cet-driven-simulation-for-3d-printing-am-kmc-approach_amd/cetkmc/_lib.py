@@ -84,8 +84,25 @@ class RunResult(C.Structure):
     ]
 
 
+class EnsArgs(C.Structure):
+    _fields_ = [
+        ("step0", C.c_int64), ("n_steps", C.c_int64), ("defect_fraction", C.POINTER(C.c_double)),
+        ("u_pick", C.POINTER(C.c_double)), ("u_defect", C.POINTER(C.c_double)), ("u_np", C.POINTER(C.c_double)),
+        ("np_stride", C.c_int64), ("seed", C.POINTER(C.c_uint64)), ("rng_mode", C.c_int32), ("thermal_mode", C.c_int32),
+        ("thermal_dt", C.c_double),
+    ]
+
+
+class EnsAnalysis(C.Structure):
+    _fields_ = [
+        ("threshold", C.c_double), ("species", C.c_int32), ("pad", C.c_int32), ("n_clusters", C.POINTER(C.c_int64)),
+        ("species_counts", C.POINTER(C.c_int64)), ("nucleation_count", C.POINTER(C.c_int64)), ("n_gathered", C.POINTER(C.c_int64)),
+    ]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
-                  "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm}
+                  "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
+                  "ens_analysis": EnsAnalysis}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -132,6 +149,12 @@ PROTOTYPES = {
     "cetkmc_time_sweeps": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double)]),
     "cetkmc_event_overhead": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double)]),
     "cetkmc_comm_selftest": (C.c_int, [C.c_void_p, C.c_int64, _P(C.c_double)]),
+    "cetkmc_create_ensemble": (C.c_int, [_P(Params), C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
+    "cetkmc_ensemble_replica": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_void_p)]),
+    "cetkmc_run_ensemble": (C.c_int, [C.c_void_p, _P(EnsArgs), _P(RunResult), C.c_void_p, C.c_void_p]),
+    "cetkmc_ensemble_analyze": (C.c_int, [C.c_void_p, _P(EnsAnalysis)]),
+    "cetkmc_ensemble_analysis_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_ensemble_set_defects_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Counters, Event, Params, RunArgs, RunResult, SuperArgs, SweepInfo, build_library  # noqa: F401
+from ._lib import Counters, EnsAnalysis, EnsArgs, Event, Params, RunArgs, RunResult, SuperArgs, SweepInfo, build_library  # noqa: F401
 
 EVENT_DTYPE = np.dtype([("type", "<i4"), ("pos", "<i4", 3), ("target", "<i4", 3), ("atom", "<i4"),
                         ("rate", "<f8"), ("dep_rank", "<i8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
@@ -392,3 +392,139 @@ class Engine:
 
     def sync(self):
         self._ck(self.lib.cetkmc_sync(self.h))
+
+
+class _Replica(Engine):
+    """Replica r of an :class:`Ensemble`: every per-lattice call of :class:`Engine` on that lattice.  The handle belongs to
+    the ensemble (closing the replica does not release it)."""
+
+    def __init__(self, ens, r, handle):       # noqa: D107 -- no Engine.__init__: the lattice exists already
+        self.lib, self.L, self.params = ens.lib, ens.L, ens.params[r]
+        self.h = handle
+        self.i0, self.i1 = 0, ens.L
+        self._ens = ens                        # keeps the ensemble alive while the replica is in use
+
+    def close(self):
+        self.h = None
+
+
+class Ensemble:
+    """R independent lattices of edge L (1 <= L <= 128) on one GPU, stepped together (cetkmc_create_ensemble /
+    cetkmc_run_ensemble).  ``params`` is one cetkmc_params per replica (they may differ in
+    impurity_c and nu_dep only); ``replica(r)`` is an :class:`Engine` view of lattice r for uploads, downloads and the
+    analysis calls."""
+
+    def __init__(self, L, params, device=0):
+        self.lib = _lib.load()
+        self.L, self.R = int(L), len(params)
+        self.params = list(params)
+        self.h = C.c_void_p()
+        n = C.c_int(0)
+        if self.lib.cetkmc_device_count(C.byref(n)) or n.value <= 0:
+            raise RuntimeError("cetkmc: no usable HIP device (there is no CPU fallback): " + self.error())
+        arr = (Params * max(self.R, 1))(*self.params)
+        if self.lib.cetkmc_create_ensemble(arr, self.L, self.R, int(device), C.byref(self.h)):
+            self.h = None
+            raise RuntimeError("cetkmc_create_ensemble: " + self.error())
+        self._reps = []
+        for r in range(self.R):
+            hr = C.c_void_p()
+            self._ck(self.lib.cetkmc_ensemble_replica(self.h, r, C.byref(hr)))
+            self._reps.append(_Replica(self, r, hr))
+
+    def error(self):
+        return self.lib.cetkmc_last_error().decode(errors="replace")
+
+    def _ck(self, rc):
+        if rc:
+            raise RuntimeError("cetkmc: " + self.error())
+
+    def replica(self, r):
+        return self._reps[r]
+
+    def close(self):
+        if getattr(self, "h", None):
+            for e in self._reps:
+                e.h = None
+            self.lib.cetkmc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, step0, n, defect_fraction, u_pick=None, u_defect=None, u_np=None, rng_mode=0, seeds=None, thermal_mode=1,
+            thermal_dt=1e-6):
+        """n lockstep steps of every live replica from global step step0.  rng_mode 0: u_pick / u_defect (R, n) and
+        u_np (R, np_stride >= n * (L*L + 2)) from each replica's own generators; rng_mode 2: ``seeds`` (R,).  Returns
+        dict(done, status, np_used, nucleation_count, min_margin (R,), totals (R, n + 1), dt (R, n) (rng_mode 2), wall_ms)."""
+        R, n = self.R, int(n)
+        df = np.ascontiguousarray(np.broadcast_to(np.asarray(defect_fraction, dtype=np.float64), (R,)))
+        a = EnsArgs()
+        a.step0, a.n_steps, a.defect_fraction = int(step0), n, _dptr(df)
+        keep = [df]
+        if rng_mode == 0:
+            u_pick = np.ascontiguousarray(u_pick, dtype=np.float64).reshape(R, n)
+            u_np = np.ascontiguousarray(u_np, dtype=np.float64).reshape(R, -1)
+            u_defect = None if u_defect is None else np.ascontiguousarray(u_defect, dtype=np.float64).reshape(R, n)
+            a.u_pick, a.u_defect, a.u_np, a.np_stride = _dptr(u_pick), _dptr(u_defect), _dptr(u_np), u_np.shape[1]
+            keep += [u_pick, u_np, u_defect]
+        else:
+            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(R))
+            a.seed = sd.ctypes.data_as(C.POINTER(C.c_uint64))
+            keep.append(sd)
+        a.rng_mode, a.thermal_mode, a.thermal_dt = int(rng_mode), int(thermal_mode), float(thermal_dt)
+        res = (RunResult * R)()
+        totals = np.zeros((R, n + 1), np.float64)
+        dt = np.zeros((R, max(n, 1)), np.float64)
+        self._ck(self.lib.cetkmc_run_ensemble(self.h, C.byref(a), res, _ptr(totals), _ptr(dt) if rng_mode == 2 else None))
+        return dict(done=np.array([x.steps_done for x in res], np.int64), status=np.array([x.status for x in res], np.int32),
+                    np_used=np.array([x.np_used for x in res], np.int64),
+                    nucleation_count=np.array([x.nucleation_count for x in res], np.int64),
+                    min_margin=np.array([x.min_margin for x in res], np.float64), totals=totals, dt=dt[:, :n],
+                    wall_ms=float(res[0].wall_ms) if R else 0.0)
+
+    def analyze(self, threshold=0.5, species=-1, labels=True):
+        """Clustering, species counts, nucleation counts and (species >= 0) the sorted (index, T) gather of every replica,
+        in launches that do not depend on R.  Returns one dict per replica: clusters (as Engine.clusters), counts (as
+        Engine.species_counts), nucleation_count and, for species >= 0, gather (as Engine.gather_species)."""
+        R, n = self.R, self.L ** 3
+        nc, cnt, nuc, ng = (np.zeros(R, np.int64), np.zeros((R, 6), np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64))
+        a = EnsAnalysis()
+        a.threshold, a.species = float(threshold), int(species)
+        a.n_clusters, a.species_counts = nc.ctypes.data_as(C.POINTER(C.c_int64)), cnt.ctypes.data_as(C.POINTER(C.c_int64))
+        a.nucleation_count, a.n_gathered = nuc.ctypes.data_as(C.POINTER(C.c_int64)), ng.ctypes.data_as(C.POINTER(C.c_int64))
+        self._ck(self.lib.cetkmc_ensemble_analyze(self.h, C.byref(a)))
+        tot, gt = int(nc.sum()), int(ng.sum())
+        first = np.zeros((max(tot, 1), 3), np.int32)
+        size = np.zeros(max(tot, 1), np.int64)
+        bbox = np.zeros((max(tot, 1), 6), np.int32)
+        lab = np.zeros((R,) + (self.L,) * 3, np.int32) if labels else None
+        gi, gT = np.zeros(max(gt, 1), np.int64), np.zeros(max(gt, 1), np.float64)
+        self._ck(self.lib.cetkmc_ensemble_analysis_data(self.h, _ptr(first), _ptr(size), _ptr(bbox), _ptr(lab),
+                                                        _ptr(gi) if species >= 0 else None, _ptr(gT) if species >= 0 else None))
+        out, c0, g0 = [], 0, 0
+        for r in range(R):
+            k = int(nc[r])
+            cl = dict(first=first[c0:c0 + k], size=size[c0:c0 + k], bbox=bbox[c0:c0 + k])
+            if labels:
+                cl["labels"] = lab[r]
+            d = dict(clusters=cl, counts=cnt[r], nucleation_count=int(nuc[r]))
+            if species >= 0:
+                m = int(ng[r])
+                idx, Tv = gi[g0:g0 + m], gT[g0:g0 + m]
+                order = np.argsort(idx, kind="stable")
+                d["gather"] = (idx[order], Tv[order])
+                g0 += m
+            c0 += k
+            out.append(d)
+        return out
+
+    def set_defects_sparse(self, lists):
+        """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""
+        counts = np.array([-1 if x is None else len(x) for x in lists], np.int64)
+        idx = [np.asarray(x, np.int64) for x in lists if x is not None and len(x)]
+        flat = np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(1, np.int64))
+        self._ck(self.lib.cetkmc_ensemble_set_defects_sparse(self.h, _ptr(counts), _ptr(flat)))

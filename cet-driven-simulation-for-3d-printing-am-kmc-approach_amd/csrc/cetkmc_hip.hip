@@ -16,12 +16,15 @@
 #include <climits>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "kernels.hpp"
 #include "cluster.hpp"
 #include "superstep.hpp"
+#include "ensemble.hpp"
 
 using namespace cetkmc;
 
@@ -188,6 +191,10 @@ struct Handle {
     unsigned long long* d_sup_cnt = nullptr; size_t cap_sup_cnt = 0;
     cetkmc_event* d_sup_log = nullptr; size_t cap_sup_log = 0;
     double* d_sup_rmax = nullptr; size_t cap_sup_rmax = 0;
+    bool own_streams = true;     // false: a replica of an ensemble, on the streams of replica 0
+    bool ens_member = false;     // replica r >= 1 of an ensemble (released with it)
+    bool in_ensemble = false;    // any replica: stepped by cetkmc_run_ensemble only
+    int64_t state_uploads = 0;   // lattice (state) uploads so far: a new lattice in a replica unfreezes it
 };
 
 KParams make_kparams(const cetkmc_params& p)
@@ -247,7 +254,7 @@ int ensure_scratch(Handle* h, size_t bytes)
 }
 
 int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int, int>>& ranges, int dev,
-                  int G, int my_first, void** out)
+                  int G, int my_first, void** out, const Handle* share = nullptr)
 {
     if (!p || !out) return fail("null argument");
     if (L < 1) return fail("L must be >= 1");
@@ -268,7 +275,9 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
     h->shmem_stream = (size_t)STREAM_SLOTS * (SWEEP_TJ + 4) * h->pitchC;
     if (h->shmem_stream > 64 * 1024 || (SWEEP_TJ + 4) * h->pitchC > 16 * 256 * STREAM_MAXPF) { delete h; return fail("L too large for the LDS ring"); }
     h->dev = dev; h->G = G; h->my_first = my_first;
-    {   // the stepping loop's stream at the highest priority, the look-ahead stream at the lowest: its workgroups are
+    if (share) {     // a replica of an ensemble: every replica's work is ordered on one stream
+        h->stream = share->stream; h->stream2 = share->stream2; h->own_streams = false;
+    } else {   // the stepping loop's stream at the highest priority, the look-ahead stream at the lowest: its workgroups are
         // dispatched into what the main stream leaves free (the one-block selection kernels leave almost everything)
         int least = 0, greatest = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -464,6 +473,7 @@ int upload_impl(Handle* h, int i_begin, int i_end, const I* state, const double*
         if (a < i_begin || b > i_end) return fail("upload range does not cover the slab's planes + halo");
         if (state) {
             CHK(h2d_u8<I>(h, s, s.v.state, state, i_begin, a, b, true, 1));
+            ++h->state_uploads;
             HIPCHK(hipMemcpyAsync(s.prev, s.v.state, s.nS, hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(hipMemsetAsync(s.v.row_chg, 0, (size_t)(s.v.nloc + 4) * h->L, h->stream));      // prev_state == state
             HIPCHK(hipMemsetAsync(s.v.ifc_in, 0, s.nT, h->stream));
@@ -1019,9 +1029,75 @@ void destroy_impl(Handle* h)
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_main) (void)hipEventDestroy(h->ev_main);
     if (h->ev_spec) (void)hipEventDestroy(h->ev_spec);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->stream2 && h->own_streams) (void)hipStreamDestroy(h->stream2);
+    if (h->stream && h->own_streams) (void)hipStreamDestroy(h->stream);
     delete h;
+}
+
+// ---- replica ensembles (ensemble.hpp) ------------------------------------------------------------
+struct Ens {
+    int L = 0, R = 0;
+    std::vector<Handle*> reps;           // reps[0] is the ensemble's handle; all share its streams
+    std::vector<uint8_t> frozen;         // terminated in an earlier call (until a new lattice is uploaded into the replica)
+    std::vector<int64_t> uploads_seen;   // Handle::state_uploads when the replica was last stepped
+    std::vector<EnsRep> table;
+    EnsRep* d_table = nullptr;
+    double *d_u_pick = nullptr, *d_u_defect = nullptr, *d_u_np = nullptr, *d_log_total = nullptr;
+    cetkmc_event* d_log_event = nullptr;
+    int64_t* d_log_nev = nullptr;
+    size_t cap_pick = 0, cap_defect = 0, cap_np = 0, cap_total = 0, cap_event = 0, cap_nev = 0;
+    StepState* d_ss_out = nullptr;
+    int* d_n_out = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // batched analysis (cetkmc_ensemble_analyze): [R][L^3] label arrays, results kept until the next call
+    int *d_cc_parent = nullptr, *d_cc_cid = nullptr, *d_cc_roots = nullptr, *d_cc_labels = nullptr, *d_cc_n = nullptr, *d_cc_stats = nullptr;
+    size_t cap_cc_stats = 0;
+    long long *d_cc_offs = nullptr, *d_sc_offs = nullptr, *d_sc_idx = nullptr, *d_g_idx = nullptr;
+    size_t cap_sc_idx = 0;
+    double* d_g_T = nullptr;
+    unsigned long long *d_counts = nullptr, *d_g_n = nullptr;
+    std::vector<int64_t> an_clusters, an_gathered;     // per replica, of the last analysis (-1: none yet)
+    int an_species = -1;
+};
+std::mutex g_ens_mu;
+std::map<const void*, Ens*> g_ens;        // ensemble handle (= replica 0's handle) -> ensemble
+
+Ens* ens_of(const void* handle)
+{
+    std::lock_guard<std::mutex> lk(g_ens_mu);
+    auto it = g_ens.find(handle);
+    return it == g_ens.end() ? nullptr : it->second;
+}
+
+void destroy_ens(Ens* e)
+{
+    if (!e->reps.empty()) {
+        (void)hipSetDevice(e->reps[0]->dev);
+        (void)hipStreamSynchronize(e->reps[0]->stream);
+    }
+    void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev,
+                    e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
+                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (e->ev0) (void)hipEventDestroy(e->ev0);
+    if (e->ev1) (void)hipEventDestroy(e->ev1);
+    for (size_t r = e->reps.size(); r-- > 0;) destroy_impl(e->reps[r]);     // replica 0 (owner of the streams) last
+    delete e;
+}
+
+// cetkmc_destroy of an ensemble handle: true if it was one (and is gone now)
+bool destroy_ensemble_of(void* handle)
+{
+    Ens* e = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_ens_mu);
+        auto it = g_ens.find(handle);
+        if (it == g_ens.end()) return false;
+        e = it->second;
+        g_ens.erase(it);
+    }
+    destroy_ens(e);
+    return true;
 }
 
 }  // namespace
@@ -1044,7 +1120,7 @@ int cetkmc_struct_size(const char* name)
 #define SZ(n, t) if (!strcmp(name, n)) return (int)sizeof(t)
     SZ("params", cetkmc_params); SZ("event", cetkmc_event); SZ("sweep_info", cetkmc_sweep_info);
     SZ("run_args", cetkmc_run_args); SZ("run_result", cetkmc_run_result); SZ("super_args", cetkmc_super_args);
-    SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm);
+    SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm); SZ("ens_args", cetkmc_ens_args); SZ("ens_analysis", cetkmc_ens_analysis);
 #undef SZ
     return -1;
 }
@@ -1125,7 +1201,13 @@ int cetkmc_create_rank_host(const cetkmc_params* p, int L, int rank, int nranks,
     return 0;
 }
 
-int cetkmc_destroy(void* handle) { destroy_impl((Handle*)handle); return 0; }
+int cetkmc_destroy(void* handle)
+{
+    if (destroy_ensemble_of(handle)) return 0;
+    if (handle && ((Handle*)handle)->ens_member) return fail("a replica handle is released with its ensemble");
+    destroy_impl((Handle*)handle);
+    return 0;
+}
 
 int cetkmc_set_params(void* handle, const cetkmc_params* p)
 {
@@ -1476,6 +1558,7 @@ int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* a)
 {
     Handle* h = (Handle*)handle;
     if (!h || !a) return fail("null argument");
+    if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     int64_t n_therm = 0;
     h->staged.valid = false;
     CHK(check_run_args(h, a, true, &n_therm));
@@ -1493,6 +1576,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
 {
     Handle* h = (Handle*)handle;
     if (!h || !a || !res) return fail("null argument");
+    if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     const int64_t n = a->n_steps;
     // all input pointers NULL: the batch's inputs were put on the device by cetkmc_stage_inputs (same batch shape)
     const bool staged = n > 0 && a->rng_mode != 2 && !a->u_pick && !a->u_defect && !a->u_np && !a->q_planes;
@@ -1700,6 +1784,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
 {
     Handle* h = (Handle*)handle;
     if (!h || !a || !res) return fail("null argument");
+    if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps needs a streaming sweep_variant (1 or 2)");
@@ -2126,6 +2211,402 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us)
         }
     }
     HIPCHK(hipFree(d));
+    return 0;
+}
+
+// ---- replica ensembles (ensemble.hpp) ----------------------------------------------------------
+int cetkmc_create_ensemble(const cetkmc_params* p, int L, int R, int device_id, void** handle)
+{
+    if (!p || !handle) return fail("null argument");
+    *handle = nullptr;
+    if (R < 1) return fail("an ensemble needs R >= 1 replicas");
+    if (L < 1 || L > 128) return fail("ensembles cover 1 <= L <= 128 (one lattice of L > 128 already fills the GPU)");
+    {   // grid limits: the replica rides in y (z for the temperature march: z = replica x plane groups of THERM_NI planes)
+        const int64_t nz = (L + THERM_NI - 1) / THERM_NI;
+        if ((int64_t)R * nz > 65535) return fail("too many replicas for this L: R * ceil(L / " + std::to_string(THERM_NI) + ") must be <= 65535");
+        // device memory: fields, tables and lists of a handle + the batched analysis arrays, against what is free now
+        const int64_t L2 = (int64_t)L * L, RJ = round_up(L, SWEEP_TJ) + 4, pT = round_up(L, 8);
+        const int64_t per = 3 * (L + 4) * RJ * round_up(KOFF + L + 4, 16) + (L + 4) * RJ * round_up(KOFFC + L + 12, 16) +
+                            (L + 4) * L * pT * (8 * 10 + 1 + 4) + L2 * L * 4 + 2 * L2 * pT * 8 + L * 3 * L * 12 +
+                            L2 * L * (4 * 4 + 16) + (1 << 20);
+        size_t free_b = 0, total_b = 0;
+        if (hipSetDevice(device_id) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+            (double)per * R > 0.9 * (double)free_b)
+            return fail("ensemble does not fit in device memory: ~" + std::to_string((long long)(per * R >> 20)) + " MiB needed, " +
+                        std::to_string((long long)(free_b >> 20)) + " MiB free");
+    }
+    Ens* e = new Ens();
+    e->L = L; e->R = R;
+    auto bail = [&](int rc) { destroy_ens(e); return rc; };
+    for (int r = 1; r < R; ++r) {      // every field but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
+        cetkmc_params a = p[0], b = p[r];
+        a.impurity_c = b.impurity_c = 0.0; a.nu_dep = b.nu_dep = 0.0;
+        if (memcmp(&a, &b, sizeof a)) return bail(fail("ensemble replicas may differ in impurity_c and nu_dep only (cetkmc_params)"));
+    }
+    const std::vector<std::pair<int, int>> ranges{{0, L}};
+    for (int r = 0; r < R; ++r) {
+        void* hv = nullptr;
+        if (int rc = create_common(&p[r], L, ranges, device_id, 1, 0, &hv, r ? e->reps[0] : nullptr)) return bail(rc);
+        Handle* h = (Handle*)hv;
+        h->ens_member = r > 0;
+        h->in_ensemble = true;
+        e->reps.push_back(h);
+    }
+    e->frozen.assign((size_t)R, 0);
+    e->uploads_seen.assign((size_t)R, 0);
+    e->table.resize((size_t)R);
+    if (hipMalloc((void**)&e->d_table, (size_t)R * sizeof(EnsRep)) != hipSuccess ||
+        hipMalloc((void**)&e->d_ss_out, (size_t)R * sizeof(StepState)) != hipSuccess ||
+        hipMalloc((void**)&e->d_n_out, (size_t)R * sizeof(int)) != hipSuccess ||
+        hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess)
+        return bail(fail("cetkmc_create_ensemble: device allocation failed"));
+    {
+        std::lock_guard<std::mutex> lk(g_ens_mu);
+        g_ens[e->reps[0]] = e;
+    }
+    *handle = e->reps[0];
+    return 0;
+}
+
+int cetkmc_ensemble_replica(void* handle, int r, void** replica)
+{
+    if (!handle || !replica) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (r < 0 || r >= e->R) return fail("replica index out of range");
+    *replica = e->reps[(size_t)r];
+    return 0;
+}
+
+int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_result* res, double* totals, double* dt)
+{
+    if (!handle || !a || !res) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    const int R = e->R, L = e->L;
+    const int64_t n = a->n_steps;
+    if (n < 0) return fail("n_steps < 0");
+    if (a->rng_mode != 0 && a->rng_mode != 2) return fail("ensembles run rng_mode 0 (reference streams) or 2 (all counter based)");
+    if (a->thermal_mode != 0 && a->thermal_mode != 1) return fail("ensembles run thermal_mode 0 or 1 (no laser source)");
+    if (!a->defect_fraction) return fail("defect_fraction[R] required");
+    bool any_defect = false;
+    for (int r = 0; r < R; ++r) any_defect |= a->defect_fraction[r] > 0.0;
+    const int64_t per_step = (int64_t)L * L + 2;         // at most L^2 deposition candidates + two orientation draws
+    if (a->rng_mode == 0 && n > 0) {
+        if (!a->u_pick || !a->u_np) return fail("rng_mode 0: u_pick[R][n] and u_np[R][np_stride] required");
+        if (any_defect && !a->u_defect) return fail("rng_mode 0: u_defect[R][n] required when a defect_fraction is > 0");
+        if (a->np_stride < n * per_step) return fail("rng_mode 0: np_stride must be >= n_steps * (L*L + 2)");
+    }
+    if (a->rng_mode == 2 && !a->seed) return fail("rng_mode 2: seed[R] required");
+    for (Handle* h : e->reps)
+        if (h->sweep_variant != 1 || !h->sweep_auto || h->thermal_variant != 1 || h->ifc_every_step || h->thermal_ahead)
+            return fail("ensembles run the default kernel variants only (sweep_variant / thermal_variant / interface options untouched)");
+    Handle* h0 = e->reps[0];
+    for (Handle* h : e->reps) {        // cetkmc_set_params on a replica must keep the shared fields shared
+        cetkmc_params x = h0->p, y = h->p;
+        x.impurity_c = y.impurity_c = 0.0; x.nu_dep = y.nu_dep = 0.0;
+        if (memcmp(&x, &y, sizeof x)) return fail("ensemble replicas may differ in impurity_c and nu_dep only (cetkmc_params)");
+    }
+    HIPCHK(hipSetDevice(h0->dev));
+    HIPCHK(hipStreamSynchronize(h0->stream));
+    hipStream_t st = h0->stream;
+    const size_t nn = (size_t)std::max<int64_t>(n, 1);
+    CHK(grow(&e->d_log_total, &e->cap_total, (size_t)R * nn));
+    CHK(grow(&e->d_log_event, &e->cap_event, (size_t)R * nn));
+    CHK(grow(&e->d_log_nev, &e->cap_nev, (size_t)R * nn));
+    const bool streams = a->rng_mode == 0 && n > 0;
+    const int64_t stride = streams ? a->np_stride : 0;
+    if (streams) {
+        CHK(grow(&e->d_u_pick, &e->cap_pick, (size_t)R * nn));
+        CHK(grow(&e->d_u_np, &e->cap_np, (size_t)R * (size_t)stride));
+        HIPCHK(hipMemcpyAsync(e->d_u_pick, a->u_pick, (size_t)R * n * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e->d_u_np, a->u_np, (size_t)R * stride * 8, hipMemcpyHostToDevice, st));
+        if (any_defect) {
+            CHK(grow(&e->d_u_defect, &e->cap_defect, (size_t)R * nn));
+            HIPCHK(hipMemcpyAsync(e->d_u_defect, a->u_defect, (size_t)R * n * 8, hipMemcpyHostToDevice, st));
+        }
+    }
+    for (int r = 0; r < R; ++r)      // a new lattice uploaded into a terminated replica steps again
+        if (e->reps[(size_t)r]->state_uploads != e->uploads_seen[(size_t)r]) {
+            e->frozen[(size_t)r] = 0;
+            e->uploads_seen[(size_t)r] = e->reps[(size_t)r]->state_uploads;
+        }
+    // per-replica table: both buffer pairs of each replica, relative to the pair current now (rel 0)
+    for (int r = 0; r < R; ++r) {
+        Handle* h = e->reps[(size_t)r];
+        EnsRep& t = e->table[(size_t)r];
+        t.kp = h->kp;
+        for (int rel = 0; rel < 2; ++rel) {
+            t.view[rel] = view_of(h, 0, h->cur ^ rel);
+            t.sa[rel] = stream_args(h, t.view[rel]);
+        }
+        t.cfg = BatchCfg{};
+        t.cfg.step0 = a->step0; t.cfg.defect_fraction = a->defect_fraction[r]; t.cfg.rng_mode = a->rng_mode; t.cfg.batch = 1;
+        t.cfg.seed = a->rng_mode == 2 ? a->seed[r] : 0;
+        t.cfg.np_cap = a->rng_mode == 2 ? INT64_MAX / 2 : stride;
+        t.prev = h->slabs[0].prev; t.ss = h->d_ss; t.blocks = h->d_blocks; t.ktab = h->d_ktab; t.my_event = h->d_events_all;
+        t.u_pick = streams ? e->d_u_pick + (size_t)r * n : nullptr;
+        t.u_defect = (streams && any_defect) ? e->d_u_defect + (size_t)r * n : nullptr;
+        t.u_np = streams ? e->d_u_np + (size_t)r * stride : nullptr;
+        t.log_total = e->d_log_total + (size_t)r * nn; t.log_event = e->d_log_event + (size_t)r * nn; t.log_nev = e->d_log_nev + (size_t)r * nn;
+        t.active = e->frozen[(size_t)r] ? 0 : 1;
+    }
+    HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)R * sizeof(EnsRep), hipMemcpyHostToDevice, st));
+    // launch shapes: those of the single-lattice path (launch_sweep / launch_table / launch_interface / launch_thermal)
+    // with the replica in y (z for the temperature kernel)
+    const Handle* hs = h0;
+    int ifc_blocks = 0;
+    for (Handle* h : e->reps) ifc_blocks = std::max(ifc_blocks, h->ifc_blocks);
+    const int ni = hs->therm_ni, nz = (L + ni - 1) / ni;
+    const dim3 g_therm((L + THERM_KT - 1) / THERM_KT, (L + THERM_TJ - 1) / THERM_TJ, (unsigned)(nz * R));
+    const int64_t pairs = (int64_t)L * L * (hs->pitchT / 2);
+    const dim3 g_table((unsigned)std::min<int64_t>((pairs + 255) / 256, 8192), (unsigned)R);
+    const dim3 g_ifc((unsigned)ifc_blocks, (unsigned)R);
+    const dim3 g_sweep((unsigned)L, (unsigned)R);
+    const uint32_t shm_sweep = (uint32_t)(3 * L * (sizeof(double) + sizeof(int)));
+    // shared arguments: rate constants / thermal settings of replica 0 (equal in every replica but impurity_c, nu_dep)
+    const StreamArgs sa0{};
+    const KParams kp0 = h0->kp;
+    const double K0 = host_k_eff(h0->p, 0, 0);
+    const SlabView v0{};
+    const ThermalCfg tc0 = thermal_cfg(h0, a->thermal_dt, 0, 0, 1);
+    const BatchCfg cfg0{};
+    EnsSel sel{e->d_table, 0, nz};
+    auto table_and_interface = [&]() {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rate_table<EnsSel>), g_table, dim3(256), 0, st, kp0, v0, K0, (const StepState*)nullptr, sel);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_interface<EnsSel>), g_ifc, dim3(256), 0, st, kp0, v0, (const double*)nullptr,
+                           (const StepState*)nullptr, sel);
+    };
+    HIPCHK(hipEventRecord(e->ev0, st));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_reset<EnsSel>), dim3((unsigned)R), dim3(1), 0, st, (StepState*)nullptr, sel);
+    // rate table + interface sums of the fields as they stand (an upload, a defect refresh or a per-replica call may
+    // have left them stale; recomputing fresh ones gives the same values) -- unless the first step's update does it
+    if (!(a->thermal_mode && n > 0 && a->step0 % 20 == 0)) table_and_interface();
+    int flips = 0;
+    for (int64_t s = 0; s < n; ++s) {
+        const int64_t g = a->step0 + s;
+        if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_thermal_march<EnsSel>), g_therm, dim3(256), 0, st, v0, (const double*)nullptr,
+                               (double*)nullptr, (uint8_t*)nullptr, (const double*)nullptr, tc0, (const StepState*)nullptr, sel);
+            sel.rel ^= 1;
+            ++flips;
+            table_and_interface();
+        }
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_plane<true, false, EnsSel>), g_sweep, dim3(1024), shm_sweep, st, sa0,
+                           (const StepState*)nullptr, (BlockEnt*)nullptr, sel);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_apply<true, EnsSel>), dim3((unsigned)R), dim3(256), 0, st, kp0,
+                           (const SlabView*)nullptr, 1, L, hs->PB, (const BlockEnt*)nullptr, (StepState*)nullptr, cfg0,
+                           (const double*)nullptr, (const double*)nullptr, (cetkmc_event*)nullptr, 1, (const double*)nullptr,
+                           (const double*)nullptr, (double*)nullptr, (cetkmc_event*)nullptr, (int64_t*)nullptr, 1, (int*)nullptr,
+                           (long long)s, sel);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->ev1, st));
+    hipLaunchKernelGGL(k_ens_collect, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, (const EnsRep*)e->d_table, R, e->d_ss_out, e->d_n_out);
+    HIPCHK(hipGetLastError());
+    std::vector<StepState> ss((size_t)R);
+    std::vector<int> list_len((size_t)R);
+    std::vector<double> tot(n > 0 ? (size_t)R * n : 0);
+    HIPCHK(hipMemcpyAsync(ss.data(), e->d_ss_out, (size_t)R * sizeof(StepState), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(list_len.data(), e->d_n_out, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (n > 0) HIPCHK(hipMemcpy2DAsync(tot.data(), (size_t)n * 8, e->d_log_total, nn * 8, (size_t)n * 8, (size_t)R, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    for (int r = 0; r < R; ++r)       // (cannot happen: np_stride covers the worst case) -- checked before any replica changes
+        if (ss[(size_t)r].status == 2) return fail("ensemble replica ran out of its NumPy stream (np_stride too small)");
+    for (int r = 0; r < R; ++r) {
+        Handle* h = e->reps[(size_t)r];
+        const StepState& q = ss[(size_t)r];
+        h->cur ^= flips & 1;
+        // the replica's freshness flags describe nothing the ensemble kernels maintained: recompute on demand
+        h->table_fresh = false; h->ifc_fresh = false; h->swept = false; h->therm_applied_g = -1;
+        h->ifc_blocks = std::max(h->ifc_blocks, std::min(8192, (list_len[(size_t)r] + 255) / 256 + 64));
+        h->cnt.steps += q.cur;
+        if (q.status == 1) e->frozen[(size_t)r] = 1;
+        cetkmc_run_result& o = res[r];
+        o = cetkmc_run_result{};
+        o.steps_done = q.cur; o.status = q.status; o.np_used = a->rng_mode == 0 ? q.np_pos : 0;
+        o.nucleation_count = q.nuc_count; o.min_margin = q.min_margin; o.wall_ms = ms; o.full_sweeps = q.cur;
+        const int64_t done = q.cur;
+        if (totals) {
+            double* row = totals + (size_t)r * (n + 1);
+            for (int64_t s = 0; s < done; ++s) row[s] = tot[(size_t)r * n + s];
+            if (q.status == 1 && done <= n) row[done] = q.total;
+        }
+        if (dt && a->rng_mode == 2)
+            for (int64_t s = 0; s < done; ++s) dt[(size_t)r * n + s] = superstep_dt_event(a->seed[r], a->step0 + s, tot[(size_t)r * n + s]);
+    }
+    return 0;
+}
+
+// ---- batched analysis of every replica (metrics rows of run_kmc_ensemble): launches independent of R ----------------------
+static int ens_push_views(Ens* e)
+{
+    for (int r = 0; r < e->R; ++r) {
+        Handle* h = e->reps[(size_t)r];
+        e->table[(size_t)r].view[0] = view_of(h, 0, h->cur);
+        e->table[(size_t)r].view[1] = view_of(h, 0, h->cur ^ 1);
+    }
+    HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)e->R * sizeof(EnsRep), hipMemcpyHostToDevice, e->reps[0]->stream));
+    return 0;
+}
+
+int cetkmc_ensemble_analyze(void* handle, cetkmc_ens_analysis* a)
+{
+    if (!handle || !a) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (!a->n_clusters || !a->species_counts || !a->nucleation_count || (a->species >= 0 && !a->n_gathered)) return fail("null output array");
+    const int R = e->R, L = e->L;
+    const int64_t n = (int64_t)L * L * L;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    if (!e->d_cc_parent) {
+        const size_t m = (size_t)R * n;
+        HIPCHK(hipMalloc((void**)&e->d_cc_parent, m * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&e->d_cc_cid, m * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&e->d_cc_roots, m * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&e->d_cc_labels, m * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&e->d_cc_n, (size_t)R * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&e->d_cc_offs, (size_t)(R + 1) * sizeof(long long)));
+        HIPCHK(hipMalloc((void**)&e->d_counts, (size_t)R * 6 * sizeof(unsigned long long)));
+        HIPCHK(hipMalloc((void**)&e->d_g_n, (size_t)R * sizeof(unsigned long long)));
+    }
+    if (a->species >= 0 && !e->d_g_idx) {         // worst case: every voxel of a replica in the species
+        HIPCHK(hipMalloc((void**)&e->d_g_idx, (size_t)R * n * sizeof(long long)));
+        HIPCHK(hipMalloc((void**)&e->d_g_T, (size_t)R * n * sizeof(double)));
+    }
+    CHK(ens_push_views(e));
+    EnsSel sel{e->d_table, 0, 0, n, e->d_cc_offs};
+    const SlabView v0{};
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
+    const dim3 g(grid, (unsigned)R), gs(std::min(grid, 256u), (unsigned)R);
+    HIPCHK(hipMemsetAsync(e->d_cc_n, 0, (size_t)R * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(e->d_counts, 0, (size_t)R * 6 * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(e->d_g_n, 0, (size_t)R * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cc_init<EnsSel>), g, dim3(256), 0, st, v0, e->d_cc_parent, sel);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cc_hook<EnsSel>), g, dim3(256), 0, st, v0, e->d_cc_parent, a->threshold, sel);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cc_compress<EnsSel>), g, dim3(256), 0, st, n, e->d_cc_parent, e->d_cc_roots, e->d_cc_n, sel);
+    hipLaunchKernelGGL(k_ens_cc_rank, dim3((unsigned)R), dim3(1024), 0, st, (const int*)e->d_cc_parent, e->d_cc_cid, e->d_cc_roots,
+                       e->d_cc_n, n);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_species_counts<EnsSel>), gs, dim3(256), 0, st, v0, e->d_counts, sel);
+    if (a->species >= 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_species<EnsSel>), gs, dim3(256), 0, st, v0, (int)a->species, e->d_g_idx, e->d_g_T,
+                           (unsigned long long)n, e->d_g_n, sel);
+    hipLaunchKernelGGL(k_ens_collect, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, (const EnsRep*)e->d_table, R, e->d_ss_out, e->d_n_out);
+    HIPCHK(hipGetLastError());
+    std::vector<int> nr((size_t)R);
+    std::vector<unsigned long long> cnt((size_t)R * 6), gn((size_t)R);
+    std::vector<StepState> ss((size_t)R);
+    HIPCHK(hipMemcpyAsync(nr.data(), e->d_cc_n, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(cnt.data(), e->d_counts, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(gn.data(), e->d_g_n, gn.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ss.data(), e->d_ss_out, (size_t)R * sizeof(StepState), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // per-cluster size / bounding box: the replicas' clusters concatenated (entry offs[r] + id - 1)
+    std::vector<long long> offs((size_t)R + 1, 0);
+    for (int r = 0; r < R; ++r) offs[(size_t)r + 1] = offs[(size_t)r] + nr[(size_t)r];
+    const int64_t total = offs[(size_t)R];
+    CHK(grow(&e->d_cc_stats, &e->cap_cc_stats, (size_t)std::max<int64_t>(total, 1) * 8));
+    HIPCHK(hipMemcpyAsync(e->d_cc_offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (total > 0) hipLaunchKernelGGL(k_cc_stats_init, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, e->d_cc_stats);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cc_stats<EnsSel>), g, dim3(256), 0, st, v0, (const int*)e->d_cc_parent, (const int*)e->d_cc_cid,
+                       e->d_cc_labels, e->d_cc_stats, sel);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    e->an_clusters.assign((size_t)R, 0);
+    e->an_gathered.assign((size_t)R, 0);
+    e->an_species = a->species;
+    for (int r = 0; r < R; ++r) {
+        e->an_clusters[(size_t)r] = a->n_clusters[r] = nr[(size_t)r];
+        for (int c = 0; c < 6; ++c) a->species_counts[6 * r + c] = (int64_t)cnt[(size_t)6 * r + c];
+        a->nucleation_count[r] = ss[(size_t)r].nuc_count;
+        if (a->species >= 0) e->an_gathered[(size_t)r] = a->n_gathered[r] = (int64_t)gn[(size_t)r];
+    }
+    return 0;
+}
+
+int cetkmc_ensemble_analysis_data(void* handle, int32_t* first_voxel, int64_t* size, int32_t* bbox, int32_t* labels, int64_t* lin_idx,
+                                  double* T_vals)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_analysis_data needs a preceding cetkmc_ensemble_analyze");
+    const int R = e->R, L = e->L;
+    const int64_t n = (int64_t)L * L * L;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    int64_t total = 0, maxc = 0, maxg = 0;
+    for (int r = 0; r < R; ++r) { total += e->an_clusters[(size_t)r]; maxc = std::max(maxc, e->an_clusters[(size_t)r]); maxg = std::max(maxg, e->an_gathered[(size_t)r]); }
+    std::vector<int> roots, stats((size_t)std::max<int64_t>(total, 1) * 8);
+    std::vector<long long> gi;
+    std::vector<double> gT;
+    if (maxc > 0 && (first_voxel || size || bbox)) {
+        roots.resize((size_t)R * maxc);
+        HIPCHK(hipMemcpy2DAsync(roots.data(), (size_t)maxc * 4, e->d_cc_roots, (size_t)n * 4, (size_t)maxc * 4, (size_t)R, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stats.data(), e->d_cc_stats, (size_t)total * 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    if (labels) HIPCHK(hipMemcpyAsync(labels, e->d_cc_labels, (size_t)R * n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (maxg > 0 && e->an_species >= 0 && (lin_idx || T_vals)) {
+        gi.resize((size_t)R * maxg); gT.resize((size_t)R * maxg);
+        HIPCHK(hipMemcpy2DAsync(gi.data(), (size_t)maxg * 8, e->d_g_idx, (size_t)n * 8, (size_t)maxg * 8, (size_t)R, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpy2DAsync(gT.data(), (size_t)maxg * 8, e->d_g_T, (size_t)n * 8, (size_t)maxg * 8, (size_t)R, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t q = 0, p = 0;
+    for (int r = 0; r < R; ++r) {
+        for (int64_t c = 0; c < e->an_clusters[(size_t)r] && !roots.empty(); ++c, ++q) {
+            const int v = roots[(size_t)r * maxc + c];
+            if (first_voxel) { first_voxel[3 * q] = v / (L * L); first_voxel[3 * q + 1] = (v / L) % L; first_voxel[3 * q + 2] = v % L; }
+            if (size) size[q] = stats[(size_t)8 * q];
+            if (bbox) for (int k = 0; k < 6; ++k) bbox[6 * q + k] = stats[(size_t)8 * q + 1 + k];
+        }
+        for (int64_t c = 0; c < e->an_gathered[(size_t)r] && !gi.empty(); ++c, ++p) {
+            if (lin_idx) lin_idx[p] = gi[(size_t)r * maxg + c];
+            if (T_vals) T_vals[p] = gT[(size_t)r * maxg + c];
+        }
+    }
+    return 0;
+}
+
+int cetkmc_ensemble_set_defects_sparse(void* handle, const int64_t* counts, const int64_t* lin_idx)
+{
+    if (!handle || !counts) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    const int R = e->R, L = e->L;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    std::vector<long long> offs((size_t)2 * R);
+    int64_t total = 0, maxn = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t c = counts[r];
+        offs[(size_t)2 * r] = c < 0 ? -1 : total;
+        offs[(size_t)2 * r + 1] = c < 0 ? -1 : total + c;
+        if (c > 0) { total += c; maxn = std::max(maxn, c); }
+    }
+    if (total > 0 && !lin_idx) return fail("null argument");
+    for (int64_t q = 0; q < total; ++q)
+        if (lin_idx[q] < 0 || lin_idx[q] >= (int64_t)L * L * L) return fail("linear index out of range");
+    if (!e->d_sc_offs) HIPCHK(hipMalloc((void**)&e->d_sc_offs, (size_t)2 * R * sizeof(long long)));
+    CHK(grow(&e->d_sc_idx, &e->cap_sc_idx, (size_t)std::max<int64_t>(total, 1)));
+    CHK(ens_push_views(e));
+    HIPCHK(hipMemcpyAsync(e->d_sc_offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (total > 0) HIPCHK(hipMemcpyAsync(e->d_sc_idx, lin_idx, (size_t)total * sizeof(long long), hipMemcpyHostToDevice, st));
+    EnsSel sel{e->d_table, 0, 0, 0, e->d_sc_offs};
+    hipLaunchKernelGGL(k_ens_clear_defects, dim3(256, (unsigned)R), dim3(256), 0, st, (const EnsRep*)e->d_table, (const long long*)e->d_sc_offs);
+    if (maxn > 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scatter_defects<EnsSel>), dim3((unsigned)std::min<int64_t>((maxn + 255) / 256, 4096), (unsigned)R),
+                           dim3(256), 0, st, SlabView{}, (const long long*)e->d_sc_idx, 0LL, sel);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int r = 0; r < R; ++r)
+        if (counts[r] >= 0) { e->reps[(size_t)r]->swept = false; e->reps[(size_t)r]->ifc_fresh = false; }
     return 0;
 }
 

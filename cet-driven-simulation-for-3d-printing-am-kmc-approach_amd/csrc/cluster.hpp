@@ -9,6 +9,7 @@
 // then per-cluster size and bounding box by atomics.  Single slab only (whole lattice on one GPU).
 #pragma once
 #include "voxel.hpp"
+#include "kernels.hpp"
 
 namespace cetkmc {
 
@@ -37,8 +38,12 @@ __device__ __forceinline__ void cc_unite(int* parent, int a, int b)
 }
 
 // parent[v] = v for occupied voxels, -1 for empty ones; v = (lp*L + j)*L + k over the owned planes
-__global__ void k_cc_init(SlabView S, int* parent)
+// (variadic trailing EnsSel: the replica-ensemble instantiation, ensemble.hpp -- replica = blockIdx.y, per-replica arrays
+// at r * stride; the single-lattice instantiation has no trailing argument)
+template <class... E>
+__global__ void k_cc_init(SlabView S, int* parent, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) { S = ens_rep(blockIdx.y, ens...).view[0]; parent += blockIdx.y * ens_stride(ens...); }
     const int L = S.L;
     const int64_t n = (int64_t)S.nloc * L * L;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
@@ -47,8 +52,10 @@ __global__ void k_cc_init(SlabView S, int* parent)
     }
 }
 // one thread per voxel: unite with the 7 "forward" neighbours (the other 7 are covered from the other side)
-__global__ void k_cc_hook(SlabView S, int* parent, double threshold)
+template <class... E>
+__global__ void k_cc_hook(SlabView S, int* parent, double threshold, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) { S = ens_rep(blockIdx.y, ens...).view[0]; parent += blockIdx.y * ens_stride(ens...); }
     const int L = S.L;
     const int64_t n = (int64_t)S.nloc * L * L;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
@@ -73,8 +80,13 @@ __global__ void k_cc_hook(SlabView S, int* parent, double threshold)
     }
 }
 // flatten + collect roots
-__global__ void k_cc_compress(int64_t n, int* parent, int* roots, int* n_roots)
+template <class... E>
+__global__ void k_cc_compress(int64_t n, int* parent, int* roots, int* n_roots, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {
+        const int64_t o = blockIdx.y * ens_stride(ens...);
+        parent += o; roots += o; n_roots += blockIdx.y;
+    }
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
         if (parent[v] < 0) continue;
         const int r = cc_find(parent, (int)v);
@@ -89,8 +101,13 @@ __global__ void k_cc_ids(const int* __restrict__ sorted_roots, int n_roots, int*
     if (q < n_roots) cid[sorted_roots[q]] = q + 1;
 }
 // labels + per-cluster size / bounding box.  stats[id-1] = {size, imin,jmin,kmin, imax,jmax,kmax, pad}
-__global__ void k_cc_stats(SlabView S, const int* __restrict__ parent, const int* __restrict__ cid, int* labels, int* stats)
+template <class... E>
+__global__ void k_cc_stats(SlabView S, const int* __restrict__ parent, const int* __restrict__ cid, int* labels, int* stats, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {       // stats: the replica's clusters start at entry offs[r]
+        const int64_t o = blockIdx.y * ens_stride(ens...);
+        S = ens_rep(blockIdx.y, ens...).view[0]; parent += o; cid += o; labels += o; stats += 8 * ens_offs(ens...)[blockIdx.y];
+    }
     const int L = S.L;
     const int64_t n = (int64_t)S.nloc * L * L;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
@@ -116,8 +133,10 @@ __global__ void k_cc_stats_init(int n_roots, int* stats)
 
 // ---- sparse site queries for the host-side defect model (defects.track_defects, defects.py:4-19) ----
 // counts[s] = number of owned voxels in state s (0..4), counts[5] = anything else
-__global__ void k_species_counts(SlabView S, unsigned long long* counts)
+template <class... E>
+__global__ void k_species_counts(SlabView S, unsigned long long* counts, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) { S = ens_rep(blockIdx.y, ens...).view[0]; counts += 6 * blockIdx.y; }
     __shared__ unsigned int hist[6];
     if (threadIdx.x < 6) hist[threadIdx.x] = 0;
     __syncthreads();
@@ -132,8 +151,13 @@ __global__ void k_species_counts(SlabView S, unsigned long long* counts)
     if (threadIdx.x < 6) atomicAdd(counts + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
 }
 // (global linear index, T) of every owned voxel in state `species` (unordered; the host sorts)
-__global__ void k_gather_species(SlabView S, int species, long long* idx, double* Tv, unsigned long long cap, unsigned long long* n_out)
+template <class... E>
+__global__ void k_gather_species(SlabView S, int species, long long* idx, double* Tv, unsigned long long cap, unsigned long long* n_out,
+                                 E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {       // per-replica rows of `cap` entries
+        S = ens_rep(blockIdx.y, ens...).view[0]; idx += blockIdx.y * cap; Tv += blockIdx.y * cap; n_out += blockIdx.y;
+    }
     const int L = S.L;
     const int64_t n = (int64_t)S.nloc * L * L;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
@@ -143,8 +167,15 @@ __global__ void k_gather_species(SlabView S, int species, long long* idx, double
         if (pos < cap) { idx[pos] = ((long long)(S.gi0 + lp) * L + j) * L + k; Tv[pos] = S.T[S.tidx(lp + 2, j, k)]; }
     }
 }
-__global__ void k_scatter_defects(SlabView S, const long long* __restrict__ idx, long long n)
+template <class... E>
+__global__ void k_scatter_defects(SlabView S, const long long* __restrict__ idx, long long n, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {       // replica r's indices: idx[offs[2r] .. offs[2r + 1]) (offs[2r] < 0: left alone)
+        const long long* o = ens_offs(ens...);
+        const long long a = o[2 * blockIdx.y], b = o[2 * blockIdx.y + 1];
+        if (a < 0) return;
+        S = ens_rep(blockIdx.y, ens...).view[0]; idx += a; n = b - a;
+    }
     const int L = S.L;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long long)gridDim.x * blockDim.x) {
         const long long g = idx[q];

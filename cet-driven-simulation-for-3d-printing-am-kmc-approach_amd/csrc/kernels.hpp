@@ -36,6 +36,18 @@ struct StepState {
     double  min_margin; // batch: smallest distance of a pick r from the boundaries of the chosen event's interval, / total
 };
 
+// replica-ensemble argument (ensemble.hpp defines EnsSel / EnsRep; the accessors resolve at instantiation)
+template <class S> __device__ __forceinline__ const auto& ens_rep(unsigned r, const S& sel) { return sel.reps[r]; }
+template <class S> __device__ __forceinline__ int ens_rel(const S& sel) { return sel.rel; }
+template <class S> __device__ __forceinline__ unsigned ens_nz(const S& sel) { return (unsigned)sel.nz; }
+template <class S> __device__ __forceinline__ int64_t ens_stride(const S& sel) { return sel.stride; }
+template <class S> __device__ __forceinline__ const long long* ens_offs(const S& sel) { return sel.offs; }
+// the rate constants a kernel reads: its KParams argument, or (ensemble) replica r's copy in the device table -- by
+// reference, so that the atom-type-indexed E_b / E_diff stay plain loads (a modified by-value copy would go to scratch)
+struct KParams;
+__device__ __forceinline__ const KParams& ens_kp(unsigned, const KParams& P) { return P; }
+template <class S> __device__ __forceinline__ const auto& ens_kp(unsigned r, const KParams&, const S& sel) { return sel.reps[r].kp; }
+
 struct BatchCfg {
     int64_t step0;
     int64_t np_cap;
@@ -844,9 +856,19 @@ __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_table(StreamArg
 // which therefore holds all of the plane's row sums when its last row is done: the three block sums (balanced tree over j,
 // exactly plane_reduce_wave()) are folded from LDS by three of its waves -- no k_plane_reduce launch, no hand-off between
 // workgroups.  Same bits as variants 1 / 3 (+ k_plane_reduce).
-template <bool HW, bool CH2>
-__global__ __launch_bounds__(1024) CETKMC_SWEEP_ATTR void k_sweep_plane(StreamArgs A, const StepState* __restrict__ ss, BlockEnt* __restrict__ blocks)
+//
+// Replica ensembles (ensemble.hpp): the kernels of a Mode A step at L <= 128 are variadic in a trailing EnsSel argument.
+// The single-lattice instantiation has none (E empty: the code is what it was); the ensemble one takes the replica
+// index from a grid dimension the kernel leaves free and reads its arguments from the replica's EnsRep.  The thermal
+// settings and the rate-table constants of the call's arguments are the ones all replicas share; the model inputs that
+// differ per replica (impurity_c, nu_dep) come from the EnsRep (ens_kp).
+template <bool HW, bool CH2, class... E>
+__global__ __launch_bounds__(1024) CETKMC_SWEEP_ATTR void k_sweep_plane(StreamArgs A, const StepState* __restrict__ ss, BlockEnt* __restrict__ blocks, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {           // replica = blockIdx.y
+        const auto& e = ens_rep(blockIdx.y, ens...);
+        A = e.sa[ens_rel(ens...)]; ss = e.ss; blocks = e.blocks;
+    }
     if (ss && ss->status) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -950,8 +972,13 @@ __global__ __launch_bounds__(256) void k_rows_eval(StreamArgs A, const int* __re
 // Per-voxel rate table (SlabView::vval) + plane L-1 deposition rates (dep_val) from the temperature field: run after
 // every temperature change (upload, thermal update) and parameter change, BEFORE k_interface (which then overwrites
 // the entries of the listed voxels with their interface sums).  Two voxels per thread; 16 B/voxel.
-__global__ __launch_bounds__(256) void k_rate_table(KParams P, SlabView S, double K0, const StepState* __restrict__ ss)
+template <class... E>
+__global__ __launch_bounds__(256) void k_rate_table(KParams P, SlabView S, double K0, const StepState* __restrict__ ss, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {           // replica = blockIdx.y
+        const auto& e = ens_rep(blockIdx.y, ens...);
+        P.impurity_c = e.kp.impurity_c; P.nu_dep = e.kp.nu_dep; S = e.view[ens_rel(ens...)]; ss = e.ss;
+    }
     if (ss && ss->status) return;          // terminated batch: T was passed through unchanged, the table stands
     const int L = S.L, half = S.pitchT >> 1;
     const int64_t n = (int64_t)S.nloc * L * half;
@@ -1602,9 +1629,15 @@ __device__ __forceinline__ void ifc_touch(const KParams& P, const SlabView& S, c
 // Latency-bound gather kernel: all loads of a phase are issued together (own fields + 14
 // neighbour states, then 7 neighbours' vectors / temperatures at a time from clamped-safe
 // addresses), so a voxel costs ~3 memory round trips instead of one per event.
+template <class... E>
 __global__ __launch_bounds__(256) void k_interface(KParams P, SlabView S, const double* __restrict__ ktab_g,
-                                                   const StepState* __restrict__ ss)
+                                                   const StepState* __restrict__ ss, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {           // replica = blockIdx.y
+        const auto& e = ens_rep(blockIdx.y, ens...);
+        S = e.view[ens_rel(ens...)]; ktab_g = e.ktab; ss = e.ss;
+    }
+    const KParams& Pr = ens_kp(blockIdx.y, P, ens...);
     if (ss && ss->status) return;
     __shared__ double ktab[225];
     for (int t = threadIdx.x; t < 225; t += blockDim.x) ktab[t] = ktab_g[t];
@@ -1619,8 +1652,8 @@ __global__ __launch_bounds__(256) void k_interface(KParams P, SlabView S, const 
         const double Tc = pymax(S.T[t], 1.0);
         double sum = 0.0;
         int cnt = 0;
-        if (st == 0) ifc_eval_empty(P, S, ktab, lp, j, k, t, code, Tc, sum, cnt);
-        else if (st != 4) ifc_eval_atom(P, S, lp, j, k, t, code, st, Tc, sum, cnt);
+        if (st == 0) ifc_eval_empty(Pr, S, ktab, lp, j, k, t, code, Tc, sum, cnt);
+        else if (st != 4) ifc_eval_atom(Pr, S, lp, j, k, t, code, st, Tc, sum, cnt);
         ifc_store(S, lp + 2, j, k, t, sum, cnt, code);
     }
 }
@@ -1870,23 +1903,29 @@ __global__ __launch_bounds__(64) void k_apply_batch(KParams P, const SlabView* _
 }
 // Single-process batched loop: selection and application in one launch (the event record never leaves the block's
 // view of memory; threads >= 64 only take part in the barriers of the apply part).
-template <bool IFC>
+template <bool IFC, class... E>
 __global__ __launch_bounds__(256) void k_select_apply(KParams P, const SlabView* __restrict__ slabs, int nslabs, int L,
                                                       int PB, const BlockEnt* __restrict__ blocks, StepState* ss,
                                                       BatchCfg cfg, const double* __restrict__ u_pick,
                                                       const double* __restrict__ ktab_g, cetkmc_event* my_event, int ifc_ready,
                                                       const double* __restrict__ u_defect, const double* __restrict__ u_np,
                                                       double* log_total, cetkmc_event* log_event, int64_t* log_nev,
-                                                      int eval_touched, int* dirty, long long cur_hint)
+                                                      int eval_touched, int* dirty, long long cur_hint, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {           // replica = blockIdx.x (one block each); one slab, L / PB / flags from the call
+        const auto& e = ens_rep(blockIdx.x, ens...);
+        slabs = &e.view[ens_rel(ens...)]; blocks = e.blocks; ss = e.ss; cfg = e.cfg; u_pick = e.u_pick;
+        ktab_g = e.ktab; my_event = e.my_event; u_defect = e.u_defect; u_np = e.u_np;
+        log_total = e.log_total; log_event = e.log_event; log_nev = e.log_nev;
+    }
     __shared__ cetkmc_event sh_sel;            // the chosen event goes from the selection to the application through LDS,
     __shared__ SelCarry sh_carry;              // and so do the step state and the uniforms the selection requested early
     (void)my_event;
     if (threadIdx.x == 0) sh_sel.type = -1;
     __syncthreads();
-    select_body<IFC>(P, slabs, nslabs, L, PB, blocks, ss, cfg, u_pick, 0.0, ktab_g, &sh_sel, 0, ifc_ready, cur_hint, &sh_carry, u_defect, u_np);
+    select_body<IFC>(ens_kp(blockIdx.x, P, ens...), slabs, nslabs, L, PB, blocks, ss, cfg, u_pick, 0.0, ktab_g, &sh_sel, 0, ifc_ready, cur_hint, &sh_carry, u_defect, u_np);
     __syncthreads();
-    apply_batch_body(P, slabs, nslabs, L, &sh_sel, 1, ss, cfg, u_defect, u_np, log_total, log_event, log_nev, ktab_g,
+    apply_batch_body(ens_kp(blockIdx.x, P, ens...), slabs, nslabs, L, &sh_sel, 1, ss, cfg, u_defect, u_np, log_total, log_event, log_nev, ktab_g,
                      eval_touched, dirty, &sh_carry);
 }
 
@@ -1905,8 +1944,14 @@ __global__ __launch_bounds__(64) void k_apply_direct(KParams P, const SlabView* 
 __global__ void k_empty() {}
 
 // start of a batch: the batch part of the step state (nucleation_count persists) -- on the stream, no host round trip
-__global__ void k_batch_reset(StepState* ss)
+template <class... E>
+__global__ void k_batch_reset(StepState* ss, E... ens)
 {
+    if constexpr (sizeof...(E) > 0) {           // replica = blockIdx.x; a frozen replica (terminated earlier) stays terminated
+        const auto& e = ens_rep(blockIdx.x, ens...);
+        ss = e.ss;
+        if (!e.active) { ss->cur = 0; ss->status = 1; ss->np_pos = 0; ss->min_margin = 1.0; return; }
+    }
     ss->cur = 0; ss->status = 0; ss->np_pos = 0; ss->min_margin = 1.0;
 }
 
@@ -2054,16 +2099,25 @@ __global__ __launch_bounds__(256) void k_thermal_fix(KParams P, SlabView S, cons
 // (8 voxels per thread), plane i additionally in an LDS tile with a one-voxel rim for the j+-1 / k+-1
 // neighbours.  Every T value is read ~1.4x and written once (k_thermal: 7 reads through L2).
 constexpr int THERM_TJ = 8, THERM_NI = 4, THERM_KT = 256;
+template <class... E>
 __global__ __launch_bounds__(256) void k_thermal_march(SlabView S, const double* __restrict__ Tin, double* __restrict__ Tout,
                                                        uint8_t* __restrict__ prev_state, const double* __restrict__ q_top,
-                                                       ThermalCfg C, const StepState* __restrict__ ss)
+                                                       ThermalCfg C, const StepState* __restrict__ ss, E... ens)
 {
+    unsigned bz = blockIdx.z;                   // plane group of the block
+    if constexpr (sizeof...(E) > 0) {           // x and y are taken: replica = blockIdx.z / ens_nz (plane groups per replica)
+        const unsigned nz = ens_nz(ens...), r = blockIdx.z / nz;
+        bz = blockIdx.z - r * nz;
+        const auto& e = ens_rep(r, ens...);
+        const int rel = ens_rel(ens...);
+        S = e.view[rel]; Tin = e.view[rel].T; Tout = e.view[rel ^ 1].T; prev_state = e.prev; ss = e.ss;
+    }
     constexpr int TJ = THERM_TJ, KT = THERM_KT, LW = KT + 2;
     __shared__ double tile[(TJ + 2) * LW];
     const int L = S.L;
     const int tid = threadIdx.x;
     const int kc = blockIdx.x * KT, j0 = blockIdx.y * TJ;
-    const int lp0 = blockIdx.z * C.ni, lp1 = min(lp0 + C.ni, S.nloc);
+    const int lp0 = bz * C.ni, lp1 = min(lp0 + C.ni, S.nloc);
     const bool passthrough = ss && ss->status;
     const int col = 2 * (tid & 127), rbase = tid >> 7;          // thread: columns kc+col, kc+col+1 of rows rbase+2q
     const int k0 = kc + col;

@@ -62,6 +62,17 @@ def refresh_defects_device(engine, rank_counts=None, rank=0):
     if rank_counts is not None:
         counts = list(rank_counts(len(idx)))
         n_before, n_total = int(sum(counts[:rank])), int(sum(counts))
+    flagged = draw_defect_sites(idx, t_here, n_before, n_total)
+    engine.set_defects_sparse(flagged)
+    volume = (L ** 3) * (5e-6 ** 3)
+    return int(len(flagged)), (len(flagged) / volume if volume > 0 else 0.0)
+
+
+def draw_defect_sites(idx, t_here, n_before=0, n_total=None):
+    """The Bernoulli draws of refresh_defects_device (defects.py:8-18) from NumPy's global stream: the sorted carbon sites
+    ``idx`` with temperatures ``t_here`` (this rank's slice [n_before, n_before + len(idx)) of n_total sites) -> the
+    flagged linear indices."""
+    n_total = len(idx) if n_total is None else n_total
     flagged = np.zeros(0, dtype=np.int64)
     if n_total:
         u = np.random.random(n_total)[n_before:n_before + len(idx)]
@@ -71,6 +82,4 @@ def refresh_defects_device(engine, rank_counts=None, rank=0):
                 p = DEFECT_PROB_BASE * np.exp(-0.3 / (K_T * t_here))
             p = np.clip(p, 0.0, 1.0)
             flagged = idx[u < p]
-    engine.set_defects_sparse(flagged)
-    volume = (L ** 3) * (5e-6 ** 3)
-    return int(len(flagged)), (len(flagged) / volume if volume > 0 else 0.0)
+    return flagged

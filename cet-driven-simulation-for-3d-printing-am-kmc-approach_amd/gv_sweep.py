@@ -7,34 +7,73 @@ run_kmc (initial T ramp, lattice_init.py:31) for G, and the deposition attempt f
 collects the CET classification of the last metrics row of every run into ``outputs/gv_sweep/gv_map.csv``.
 
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
-                       [--mode B --box 8]
+                       [--mode B --box 8] [--seeds K] [--ensemble [--rng counter]]
+
+``--seeds K`` runs every point with the seeds RANDOM_SEED .. RANDOM_SEED + K - 1 (one gv_map.csv row per point and seed, with
+a ``seed`` column when K > 1); ``--ensemble`` runs all of them as one replica ensemble (run_kmc_ensemble): with the default
+``--rng reference`` it writes the files of the sequential run, ``--rng counter`` runs every point like ``--mode B --box L``
+with the super-step thermal cadence.
 """
 import argparse
 import os
 
 import pandas as pd
 
-from constants import ATOMIC_SPACING_W, DEFECT_PROB, N_SEEDS, T_MELT, VOXEL_SIZE
-from kmc_simulation import run_kmc
+from constants import ATOMIC_SPACING_W, DEFECT_PROB, N_SEEDS, RANDOM_SEED, T_MELT, VOXEL_SIZE
+from kmc_simulation import run_kmc, run_kmc_ensemble
+
+
+def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw):
+    """Driver arguments, checked before any device call."""
+    if rng not in ("reference", "counter"):
+        raise ValueError("rng must be 'reference' or 'counter'")
+    if int(seeds) < 1:
+        raise ValueError("seeds must be >= 1")
+    if ensemble:
+        if run_kw:
+            raise ValueError(f"--ensemble takes no run_kmc options ({sorted(run_kw)}): the RNG setting picks the mode")
+        if not 1 <= L <= 128:
+            raise ValueError("--ensemble covers 1 <= L <= 128")
+    elif rng != "reference":
+        raise ValueError("--rng counter needs --ensemble (the sequential equivalent is --mode B --box L)")
+    if n_steps < 0 or not temps or not nu_deps:
+        raise ValueError("need n_steps >= 0, at least one temperature and one nu_dep")
 
 
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
-             defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", **run_kw):
+             defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
+             **run_kw):
     """``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
-    engine (same metrics.csv columns; n_steps stays the number of executed events)."""
-    rows = []
+    engine (same metrics.csv columns; n_steps stays the number of executed events).  ``seeds=K`` runs every point with the
+    seeds RANDOM_SEED .. RANDOM_SEED + K - 1; ``ensemble=True`` runs all runs of the map as one replica ensemble."""
+    check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw)
+    seeds = int(seeds)
+    runs = []
     for T_sub in temps:
         for nu_dep in nu_deps:
-            prefix = f"gv_sweep/T{int(T_sub)}_V{nu_dep:.0e}_c_{int(carbon * 100)}"
-            run_kmc(L=L, n_steps=n_steps, temp=T_sub, defect_fraction=defect_fraction, n_seeds=n_seeds,
-                    impurity_c=carbon, output_prefix=prefix, nu_dep=nu_dep, **run_kw)
-            last = pd.read_csv(f"outputs/{prefix}/metrics.csv").iloc[-1]
-            G = (T_MELT - T_sub) / (L * VOXEL_SIZE)                 # gradient of the initial ramp of this run
-            V = nu_dep * ATOMIC_SPACING_W
-            rows.append({"T_sub": T_sub, "nu_dep": nu_dep, "G_K_per_m": G, "V_m_per_s": V, "G_over_V": G / V,
-                         "AspectRatio": last["AspectRatio"], "EquiaxedFraction": last["EquiaxedFraction"],
-                         "GrainCount": last["GrainCount"], "NucleationCount": last["NucleationCount"],
-                         "CET_Class": last["CET_Class"], "CET_Detected": last["CET_Detected"]})
+            for s in range(seeds):
+                prefix = f"gv_sweep/T{int(T_sub)}_V{nu_dep:.0e}_c_{int(carbon * 100)}" + (f"_seed{RANDOM_SEED + s}" if seeds > 1 else "")
+                runs.append((T_sub, nu_dep, RANDOM_SEED + s, prefix))
+    cfg = [dict(temp=T_sub, defect_fraction=defect_fraction, n_seeds=n_seeds, impurity_c=carbon, output_prefix=prefix,
+                nu_dep=nu_dep, **({"seed": seed} if seeds > 1 else {})) for T_sub, nu_dep, seed, prefix in runs]
+    if ensemble:
+        run_kmc_ensemble(cfg, L, n_steps, rng=rng)
+    else:
+        for c in cfg:
+            run_kmc(L=L, n_steps=n_steps, **c, **run_kw)
+    rows = []
+    for T_sub, nu_dep, seed, prefix in runs:
+        last = pd.read_csv(f"outputs/{prefix}/metrics.csv").iloc[-1]
+        G = (T_MELT - T_sub) / (L * VOXEL_SIZE)                 # gradient of the initial ramp of this run
+        V = nu_dep * ATOMIC_SPACING_W
+        row = {"T_sub": T_sub, "nu_dep": nu_dep}
+        if seeds > 1:
+            row["seed"] = seed
+        row.update({"G_K_per_m": G, "V_m_per_s": V, "G_over_V": G / V,
+                    "AspectRatio": last["AspectRatio"], "EquiaxedFraction": last["EquiaxedFraction"],
+                    "GrainCount": last["GrainCount"], "NucleationCount": last["NucleationCount"],
+                    "CET_Class": last["CET_Class"], "CET_Detected": last["CET_Detected"]})
+        rows.append(row)
     os.makedirs(out_dir, exist_ok=True)
     df = pd.DataFrame(rows)
     df.to_csv(os.path.join(out_dir, "gv_map.csv"), index=False)
@@ -50,6 +89,11 @@ if __name__ == "__main__":
     ap.add_argument("--carbon", type=float, default=0.2)
     ap.add_argument("--mode", choices=("A", "B"), default="A", help="A: exact loop (one event per sweep); B: super-steps")
     ap.add_argument("--box", type=int, default=8)
+    ap.add_argument("--seeds", type=int, default=1, help="runs per point (seeds RANDOM_SEED ..); 1 = one run, no seed column")
+    ap.add_argument("--ensemble", action="store_true", help="run the whole map as one replica ensemble")
+    ap.add_argument("--rng", choices=("reference", "counter"), default="reference",
+                    help="--ensemble: reference streams (= the sequential run's files) or counter uniforms (= --mode B --box L)")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
-    print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, **kw).to_string(index=False))
+    print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
+                   **kw).to_string(index=False))

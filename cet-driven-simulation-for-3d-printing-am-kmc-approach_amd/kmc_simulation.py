@@ -27,10 +27,11 @@ import pandas as pd
 from constants import (ATOMIC_SPACING_W, CET_CHECK_INTERVAL, DEFECT_ID, LATTICE_SIZE,  # noqa: F401
                        METRIC_UPDATE_STEP, N_STEPS, NU_DEP, RANDOM_SEED, RATE_THRESHOLD, T_MELT, T_SUB,
                        VOXEL_SIZE)
-from defects import introduce_defects, refresh_defects_device
+from defects import draw_defect_sites, introduce_defects, refresh_defects_device
 from kmc_event_rates import get_event_rates  # noqa: F401  (re-exported like the reference)
 from lattice_init import initialize_lattice
-from metrics import compute_CET, compute_metrics, compute_metrics_device, detect_CET_transition  # noqa: F401
+from metrics import (compute_CET, compute_metrics, compute_metrics_device, compute_metrics_from_clusters,  # noqa: F401
+                     detect_CET_transition)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
 
@@ -99,6 +100,52 @@ def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, inc
                 raise RuntimeError("pre-drawn NumPy stream too small for a single step")
             slack = min(L * L, 4 * slack + 64)       # the estimate was short (candidates appeared): widen and retry
     return step - first, terminated, last_total, dts
+
+
+
+def _metrics_row(cl, counts, nuc, L, step, total_time, n_flagged, nuc_offset, cet_detected, G, R, R_phys, G_over_R_phys):
+    """One metrics.csv row (kmc_simulation.py:339-389) of a lattice after event index ``step`` from its clustering ``cl``,
+    species ``counts`` and nucleation count ``nuc`` (computed on the device)."""
+    m = compute_metrics_from_clusters(cl, L ** 3, defects_count=n_flagged, voxel_size=VOXEL_SIZE)
+    defect_voxels = int(counts[DEFECT_ID])
+    m["Defect_voxel_count"] = defect_voxels
+    m["DefectDensity"] = float(defect_voxels / (L ** 3))
+    if (not cet_detected) and detect_CET_transition(m):
+        cet_detected = True
+        print(f"CET detected at step {step} (G/R={G / R:.2e})")
+    return {
+        "Step": step,
+        "Time": total_time,
+        "AspectRatio": m["AspectRatio"],
+        "EquiaxedFraction": m["EquiaxedFraction"],
+        "NucleationDensity": m["NucleationDensity"],
+        "DefectDensity": m["DefectDensity"],
+        "AvgGrainSize": m["AvgGrainSize"],
+        "GrainCount": m["GrainCount"],
+        "W_Count": int(counts[1]),
+        "Re_Count": int(counts[2]),
+        "C_Count": int(counts[3]),
+        "NucleationCount": nuc_offset + nuc,
+        "G_over_R": (G / R) if R > 0 else np.inf,
+        "G_phys": G,
+        "R_phys": R_phys,
+        "G_over_R_phys": G_over_R_phys,
+        # compute_CET re-clusters the same lattice (metrics.py:99-101): same AR / equiaxed fraction
+        "CET_Class": "Equiaxed" if (m["AspectRatio"] < CET_AR_THRESHOLD and m["EquiaxedFraction"] > CET_EQ_THRESHOLD) else "Columnar",
+        "CET_Detected": cet_detected,
+    }
+
+
+def _print_row(step, row):
+    print(
+        f"Step {step}: AR={row['AspectRatio']:.2f}, "
+        f"EqFrac={row['EquiaxedFraction']:.2f}, "
+        f"NucDens={row['NucleationDensity']:.3e}, "
+        f"DefectDens={row['DefectDensity']:.3e}, "
+        f"CET={row['CET_Class']}, "
+        f"Detected={row['CET_Detected']}, "
+        f"Time={row['Time']:.2e}s"
+    )
 
 
 def save_checkpoint(path, fields, defects_mask, next_step, total_time, nucleation_count, metrics_data, cet_detected, extra=None):
@@ -238,45 +285,11 @@ def run_kmc(
         nonlocal n_flagged, cet_detected
         if refresh_defects:
             n_flagged, _ = refresh_defects_device(engine)       # kmc_simulation.py:335-338
-        m = compute_metrics_device(engine, L ** 3, defects_count=n_flagged, voxel_size=VOXEL_SIZE)
-        counts = engine.species_counts()
-        defect_voxels = int(counts[DEFECT_ID])
-        m["Defect_voxel_count"] = defect_voxels
-        m["DefectDensity"] = float(defect_voxels / (L ** 3))
-        if (not cet_detected) and detect_CET_transition(m):
-            cet_detected = True
-            print(f"CET detected at step {step} (G/R={G / R:.2e})")
-        row = {
-            "Step": step,
-            "Time": total_time,
-            "AspectRatio": m["AspectRatio"],
-            "EquiaxedFraction": m["EquiaxedFraction"],
-            "NucleationDensity": m["NucleationDensity"],
-            "DefectDensity": m["DefectDensity"],
-            "AvgGrainSize": m["AvgGrainSize"],
-            "GrainCount": m["GrainCount"],
-            "W_Count": int(counts[1]),
-            "Re_Count": int(counts[2]),
-            "C_Count": int(counts[3]),
-            "NucleationCount": nuc_offset + engine.nucleation_count(),
-            "G_over_R": (G / R) if R > 0 else np.inf,
-            "G_phys": G,
-            "R_phys": R_phys,
-            "G_over_R_phys": G_over_R_phys,
-            # compute_CET re-clusters the same lattice (metrics.py:99-101): same AR / equiaxed fraction
-            "CET_Class": "Equiaxed" if (m["AspectRatio"] < CET_AR_THRESHOLD and m["EquiaxedFraction"] > CET_EQ_THRESHOLD) else "Columnar",
-            "CET_Detected": cet_detected,
-        }
+        row = _metrics_row(engine.clusters(0.5, labels=True), engine.species_counts(), engine.nucleation_count(), L, step,
+                           total_time, n_flagged, nuc_offset, cet_detected, G, R, R_phys, G_over_R_phys)
+        cet_detected = row["CET_Detected"]
         metrics_data.append(row)
-        print(
-            f"Step {step}: AR={row['AspectRatio']:.2f}, "
-            f"EqFrac={row['EquiaxedFraction']:.2f}, "
-            f"NucDens={row['NucleationDensity']:.3e}, "
-            f"DefectDens={row['DefectDensity']:.3e}, "
-            f"CET={row['CET_Class']}, "
-            f"Detected={row['CET_Detected']}, "
-            f"Time={row['Time']:.2e}s"
-        )
+        _print_row(step, row)
 
     while mode == "A" and next_step < n_steps:
         # next step after which the host has work: metrics (and, on multiples of
@@ -385,3 +398,229 @@ def run_kmc(
               "event boundary may differ from the reference's sequential scan")
     print(f"Completed {step + 1} steps in {total_time:.2e} s")
     return state, atom_type, total_time, theta, phi
+
+
+# ---- replica ensembles: many independent runs in the same launches -----------------------------
+_C_SITE = 3                 # carbon state (defects.py: only carbon sites can become defects)
+ENSEMBLE_KEYS = ("temp", "defect_fraction", "n_seeds", "impurity_c", "output_prefix", "nu_dep", "seed")
+_RUN_DEFAULTS = dict(temp=T_SUB, defect_fraction=0.0, n_seeds=5, impurity_c=0.0, output_prefix="cet_run", nu_dep=None, seed=None)
+# per-replica generators and counters of the last run_kmc_ensemble call (the return tuples have no room for them):
+# random_state / np_state (where run_kmc would have left the global generators), executed_events, min_margin
+last_ensemble_info = []
+
+
+def _ensemble_configs(configs, L, n_steps, rng, metrics_every):
+    """Argument validation of run_kmc_ensemble (before any device call); returns the completed per-replica configs."""
+    if rng not in ("reference", "counter"):
+        raise ValueError("rng must be 'reference' (run_kmc's exact loop) or 'counter' (run_kmc mode 'B', box = L)")
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= 128:
+        raise ValueError("ensembles cover 1 <= L <= 128")
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < 0:
+        raise ValueError("n_steps must be an integer >= 0")
+    if int(metrics_every) < 1:
+        raise ValueError("metrics_every must be >= 1")
+    if not isinstance(configs, (list, tuple)) or len(configs) < 1:
+        raise ValueError("configs must be a non-empty list of dicts (one per replica)")
+    out = []
+    for i, c in enumerate(configs):
+        if not isinstance(c, dict):
+            raise ValueError(f"configs[{i}] is not a dict")
+        bad = set(c) - set(ENSEMBLE_KEYS)
+        if bad:
+            raise ValueError(f"configs[{i}]: unknown keys {sorted(bad)} (allowed: {', '.join(ENSEMBLE_KEYS)})")
+        d = dict(_RUN_DEFAULTS, **c)
+        if not (float(d["defect_fraction"]) >= 0.0):
+            raise ValueError(f"configs[{i}]: defect_fraction must be >= 0")
+        out.append(d)
+    if rng == "reference" and len(out) * (int(L) * int(L) + 2) > _MAX_STREAM_DOUBLES:
+        raise ValueError(f"rng='reference': R * (L*L + 2) must stay within {_MAX_STREAM_DOUBLES} pre-drawn doubles per step "
+                         "(split the ensemble)")
+    prefixes = [d["output_prefix"] for d in out]
+    if len(set(prefixes)) != len(prefixes):
+        raise ValueError("every replica needs its own output_prefix (outputs/<prefix>/metrics.csv)")
+    return out
+
+
+class _GlobalRNG:
+    """Swaps a replica's private generator states into the global ``random`` / ``np.random`` for a host call that draws
+    from them (initialize_lattice, introduce_defects, refresh_defects_device), and takes the advanced states back."""
+
+    def __init__(self, py_state, np_state):
+        self.py, self.np = py_state, np_state
+
+    def __enter__(self):
+        random.setstate(self.py)
+        np.random.set_state(self.np)
+        return self
+
+    def __exit__(self, *exc):
+        self.py, self.np = random.getstate(), np.random.get_state()
+        return False
+
+
+def _replica_prefix(cfg, L):
+    """run_kmc's host prefix (kmc_simulation.py:222-227) for one replica, under the global generators: returns the initial
+    fields, the defect mask and the generator states it leaves behind."""
+    run_seed = RANDOM_SEED if cfg["seed"] is None else int(cfg["seed"])
+    np.random.seed(run_seed)
+    random.seed(run_seed)
+    state, theta, phi, T, atom_type = initialize_lattice(
+        lattice_size=L, n_seeds=cfg["n_seeds"], T_sub=cfg["temp"], impurity_c=cfg["impurity_c"])
+    defects_mask, _ = introduce_defects(state, atom_type, T, apply_to_state=False)
+    return dict(state=state, theta=theta, phi=phi, T=T, defects=defects_mask, seed=run_seed,
+                py_state=random.getstate(), np_state=np.random.get_state())
+
+
+def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True):
+    """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
+
+    ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
+    output_prefix, nu_dep, seed).  Returns one run_kmc return tuple per replica and writes each replica's
+    ``outputs/<prefix>/metrics.csv`` and ``metrics_<tag>.csv``.
+
+    ``rng="reference"``: replica r equals ``run_kmc(L=L, n_steps=n_steps, **configs[r])`` bit for bit (arrays, total_time,
+    CSV; its private generators end where run_kmc leaves the global ones: ``last_ensemble_info``).
+    ``rng="counter"``: replica r equals ``run_kmc(L=L, n_steps=n_steps, mode="B", box=L, thermal_cadence="supersteps",
+    **configs[r])`` -- all-counter uniforms, the host draws nothing per step.  The caller's global generator states are
+    restored on return.  One completion line is printed per replica (no per-row progress)."""
+    import cetkmc
+    cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every)
+    L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
+    caller_py, caller_np = random.getstate(), np.random.get_state()
+    ens = None
+    try:
+        pre = [_replica_prefix(c, L) for c in cfgs]
+        gens = [_GlobalRNG(p["py_state"], p["np_state"]) for p in pre]
+        params = []
+        for c in cfgs:
+            p = cetkmc.default_params(c["impurity_c"])
+            p.nu_dep = NU_DEP if c["nu_dep"] is None else float(c["nu_dep"])
+            params.append(p)
+        ens = cetkmc.Ensemble(L, params)
+        for r, p in enumerate(pre):
+            ens.replica(r).upload(p["state"], p["theta"], p["phi"], p["T"], p["defects"])
+        n_flagged = [int(np.sum(p["defects"])) for p in pre]
+        geo = []
+        for c in cfgs:
+            nu = NU_DEP if c["nu_dep"] is None else float(c["nu_dep"])
+            G = (T_MELT - T_SUB) / (L * VOXEL_SIZE)
+            Rg = nu * 2.74e-10 / VOXEL_SIZE
+            R_phys = nu * ATOMIC_SPACING_W
+            geo.append((G, Rg, R_phys, G / R_phys))
+        for c in cfgs:
+            os.makedirs(f"outputs/{c['output_prefix']}", exist_ok=True)
+        df = np.array([float(c["defect_fraction"]) for c in cfgs])
+        seeds = np.array([p["seed"] for p in pre], dtype=np.uint64)
+        per = [3 if d > 0.0 else 2 for d in df]
+        per_step = L * L + 2
+        alive = [True] * R
+        total_time = [0.0] * R
+        last_step = [-1] * R
+        min_margin = [1.0] * R
+        metrics = [[] for _ in range(R)]
+        cet = [False] * R
+        thermal_mode = 1 if thermal_updates else 0
+        cap = _MAX_STREAM_DOUBLES // (R * per_step) if rng == "reference" else 4096
+        next_step = 0
+        while next_step < n_steps and any(alive):
+            # the same stops as run_kmc: every metrics row (and the defect refresh on its multiples) -- kmc_simulation.py:335-341
+            stop = next_step if next_step % me == 0 else min((next_step // me + 1) * me, n_steps - 1)
+            stop = min(stop, n_steps - 1)
+            s0 = next_step
+            while s0 <= stop and any(alive):
+                n = min(stop - s0 + 1, cap)
+                if rng == "reference":
+                    u_pick = np.zeros((R, n))
+                    u_def = np.zeros((R, n)) if np.any(df > 0.0) else None
+                    u_np = np.zeros((R, n * per_step))
+                    draws, saved = [None] * R, [None] * R
+                    for r in range(R):
+                        if not alive[r]:
+                            continue
+                        g = gens[r]
+                        with g:          # the same draws _advance_to takes, from the replica's generators
+                            py_state = random.getstate()
+                            draws[r] = np.array([random.random() for _ in range(per[r] * n)], dtype=np.float64).reshape(n, per[r])
+                            np_state = np.random.get_state()
+                            u_np[r] = np.random.random(n * per_step)
+                        saved[r] = (py_state, np_state)
+                        u_pick[r] = draws[r][:, 0]
+                        if per[r] == 3:
+                            u_def[r] = draws[r][:, 1]
+                    res = ens.run(s0, n, df, u_pick, u_def, u_np, rng_mode=0, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT)
+                else:
+                    res = ens.run(s0, n, df, rng_mode=2, seeds=seeds, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT)
+                for r in range(R):
+                    if not alive[r]:
+                        continue
+                    done = int(res["done"][r])
+                    min_margin[r] = min(min_margin[r], float(res["min_margin"][r]))
+                    if rng == "reference":
+                        g = gens[r]
+                        py_state, np_state = saved[r]
+                        with g:          # rewind both generators to what the executed steps consumed (as _advance_to)
+                            np.random.set_state(np_state)
+                            if res["np_used"][r]:
+                                np.random.random(int(res["np_used"][r]))
+                            if done < n:
+                                random.setstate(py_state)
+                                for _ in range(per[r] * done):
+                                    random.random()
+                        for s in range(done):
+                            total_time[r] += max(-np.log(max(1e-12, draws[r][s, per[r] - 1])) / res["totals"][r, s], 1e-12)
+                    else:
+                        for s in range(done):
+                            total_time[r] += 1 * float(res["dt"][r, s])
+                    if res["status"][r] == 1:
+                        alive[r] = False
+                        # the step index run_kmc reports: the terminating step in mode "A", the last executed one in mode "B"
+                        last_step[r] = s0 + done if rng == "reference" else s0 + done - 1
+                        print(f"[{cfgs[r]['output_prefix']}] terminating at step {s0 + done}: no valid events "
+                              f"(rate={float(res['totals'][r, done]):.2e})")
+                s0 += n
+            # the metrics row of every live replica: one batched analysis (clustering, species and nucleation counts,
+            # carbon gather) and one batched defect scatter -- launches independent of R
+            if not any(alive):
+                break
+            refresh = stop % me == 0
+            an = ens.analyze(0.5, species=_C_SITE if refresh else -1, labels=True)
+            if refresh:                  # kmc_simulation.py:335-338, the draws from each replica's own NumPy stream
+                lists = [None] * R
+                for r in range(R):
+                    if alive[r]:
+                        with gens[r]:
+                            lists[r] = draw_defect_sites(*an[r]["gather"])
+                        n_flagged[r] = int(len(lists[r]))
+                ens.set_defects_sparse(lists)
+            for r in range(R):
+                if not alive[r]:
+                    continue
+                last_step[r] = stop
+                G, Rg, R_phys, GoR = geo[r]
+                row = _metrics_row(an[r]["clusters"], an[r]["counts"], an[r]["nucleation_count"], L, stop, total_time[r],
+                                   n_flagged[r], 0, cet[r], G, Rg, R_phys, GoR)
+                cet[r] = row["CET_Detected"]
+                metrics[r].append(row)
+            next_step = stop + 1
+
+        out = []
+        last_ensemble_info.clear()
+        for r, c in enumerate(cfgs):
+            output_dir = f"outputs/{c['output_prefix']}"
+            if metrics[r]:
+                frame = pd.DataFrame(metrics[r])
+                frame.to_csv(os.path.join(output_dir, "metrics.csv"), index=False)
+                tag = c["output_prefix"].split("_")[-1]
+                frame.to_csv(os.path.join(output_dir, f"metrics_{tag}.csv"), index=False)
+            fields = ens.replica(r).download()
+            state = fields["state"]
+            out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))
+            last_ensemble_info.append(dict(random_state=gens[r].py, np_state=gens[r].np, executed_events=last_step[r] + 1,
+                                           min_margin=min_margin[r] if rng == "reference" else None))
+            print(f"[{c['output_prefix']}] completed {last_step[r] + 1} steps in {total_time[r]:.2e} s")
+        return out
+    finally:
+        if ens is not None:
+            ens.close()
+        random.setstate(caller_py)
+        np.random.set_state(caller_np)

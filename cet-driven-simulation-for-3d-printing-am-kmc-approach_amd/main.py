@@ -6,6 +6,10 @@ only imported when ``--plots`` is given); the reference's visualization / graphs
 outside the accelerated path and are not part of this package.
 
     python main.py [--L 30] [--steps 20000] [--levels 0.0 0.1 0.2] [--plots] [--mode B --box 8]
+    python main.py --ensemble [--rng counter]     # all carbon levels as one replica ensemble (run_kmc_ensemble)
+
+``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
+every level like ``--mode B --box L`` with the super-step thermal cadence.
 """
 import argparse
 import os
@@ -15,26 +19,61 @@ import numpy as np
 import pandas as pd
 
 from constants import DEFECT_PROB, LATTICE_SIZE, N_SEEDS, N_STEPS, T_SUB
-from kmc_simulation import run_kmc
+from kmc_simulation import run_kmc, run_kmc_ensemble
 from lattice_init import initialize_lattice, save_lattice
 from metrics import detect_CET_transition
 
 
-def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, **run_kw):
+def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
+    """Driver arguments, checked before any device call."""
+    if rng not in ("reference", "counter"):
+        raise ValueError("rng must be 'reference' or 'counter'")
+    if ensemble:
+        if run_kw:
+            raise ValueError(f"--ensemble takes no run_kmc options ({sorted(run_kw)}): the RNG setting picks the mode")
+        if not 1 <= L <= 128:
+            raise ValueError("--ensemble covers 1 <= L <= 128")
+        prefixes = [f"impurity_c_{int(c * 100)}" for c in carbon_levels]
+        if len(set(prefixes)) != len(prefixes):
+            raise ValueError("--ensemble: two carbon levels map to the same output directory")
+    elif rng != "reference":
+        raise ValueError("--rng counter needs --ensemble (the sequential equivalent is --mode B --box L)")
+    if n_steps < 0 or not carbon_levels:
+        raise ValueError("need n_steps >= 0 and at least one carbon level")
+
+
+def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", **run_kw):
+    check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
     summary = {"carbon_levels": [], "grain_sizes": [], "defect_densities": [], "aspect_ratios": []}
-    for c in carbon_levels:
+    ens_out, ens_t = None, 0.0
+    if ensemble:                  # every level in one replica ensemble; the per-level epilogue below reads its results
+        for c in carbon_levels:
+            prefix = f"impurity_c_{int(c * 100)}"
+            os.makedirs(f"outputs/{prefix}/microstructures", exist_ok=True)
+            init = initialize_lattice(lattice_size=L, n_seeds=N_SEEDS, T_sub=T_SUB, random_seed=42, impurity_c=c)
+            save_lattice(*init[:4], init[4], prefix=f"outputs/{prefix}/init")
+        t0 = time.time()
+        ens_out = run_kmc_ensemble([dict(temp=T_SUB, defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, impurity_c=c,
+                                         output_prefix=f"impurity_c_{int(c * 100)}") for c in carbon_levels], L, n_steps, rng=rng)
+        ens_t = time.time() - t0
+    for q, c in enumerate(carbon_levels):
         prefix = f"impurity_c_{int(c * 100)}"
         print(f"\nRunning simulation with {c * 100:.1f}% carbon")
         out_dir = f"outputs/{prefix}"
         os.makedirs(f"{out_dir}/microstructures", exist_ok=True)
         os.makedirs("output_images", exist_ok=True)
-        init = initialize_lattice(lattice_size=L, n_seeds=N_SEEDS, T_sub=T_SUB, random_seed=42, impurity_c=c)
-        save_lattice(*init[:4], init[4], prefix=f"{out_dir}/init")
         t0 = time.time()
-        state, atom_type, total_time, theta, phi = run_kmc(L=L, n_steps=n_steps, temp=T_SUB, defect_fraction=DEFECT_PROB,
-                                                           n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw)
+        if ens_out is None:
+            init = initialize_lattice(lattice_size=L, n_seeds=N_SEEDS, T_sub=T_SUB, random_seed=42, impurity_c=c)
+            save_lattice(*init[:4], init[4], prefix=f"{out_dir}/init")
+            t0 = time.time()
+            state, atom_type, total_time, theta, phi = run_kmc(L=L, n_steps=n_steps, temp=T_SUB, defect_fraction=DEFECT_PROB,
+                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw)
+        else:
+            state, atom_type, total_time, theta, phi = ens_out[q]
+            t0 -= ens_t / len(carbon_levels)
         t1 = time.time()
         csv_path = f"outputs/{prefix}/metrics.csv"
         status = "Undetected"
@@ -66,5 +105,9 @@ if __name__ == "__main__":
     ap.add_argument("--plots", action="store_true")
     ap.add_argument("--mode", choices=("A", "B"), default="A", help="A: exact loop (one event per sweep); B: super-steps")
     ap.add_argument("--box", type=int, default=8)
+    ap.add_argument("--ensemble", action="store_true", help="run all carbon levels as one replica ensemble")
+    ap.add_argument("--rng", choices=("reference", "counter"), default="reference",
+                    help="--ensemble: reference streams (= the sequential run's files) or counter uniforms (= --mode B --box L)")
     a = ap.parse_args()
-    main(a.L, a.steps, tuple(a.levels), a.plots, **(dict(mode="B", box=a.box) if a.mode == "B" else {}))
+    main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng,
+         **(dict(mode="B", box=a.box) if a.mode == "B" else {}))

@@ -110,7 +110,12 @@ def compute_metrics_device(engine, n_voxels, defects_count=0, voxel_size=VOXEL_S
     clustering runs on the GPU on the lattice resident in ``engine`` (cetkmc_cluster: connected
     components, numbered like the reference's DFS, utils.py:28-84).  Only the per-cluster sizes /
     bounding boxes and the int32 label volume (for the d50/d90 quirk, metrics.py:76) cross PCIe."""
-    cl = engine.clusters(0.5, labels=True)
+    return compute_metrics_from_clusters(engine.clusters(0.5, labels=True), n_voxels, defects_count, voxel_size, rng_seed)
+
+
+def compute_metrics_from_clusters(cl, n_voxels, defects_count=0, voxel_size=VOXEL_SIZE, rng_seed=None):
+    """compute_metrics_device's dict from an already computed clustering (Engine.clusters(0.5, labels=True) or one
+    replica's entry of Ensemble.analyze)."""
     n = len(cl["size"])
     if n == 0:
         return {

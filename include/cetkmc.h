@@ -331,6 +331,65 @@ int cetkmc_event_overhead(void* handle, int n, double* ms_avg);
  * all-gathers [0] and neighbour exchanges [1] of that size, stream synchronisation included.  Single-process handle: no-op. */
 int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
 
+/* Replica ensembles: R independent lattices of the same edge L (1 <= L <= 128) on one GPU, each
+ * with its own parameters, fields, defect mask, random streams and step state, advanced one Mode A step per launch
+ * sequence.  Every replica follows exactly the trajectory a single handle would (full sweep every step; thermal_mode 0
+ * or 1, the update every 20 global steps shared by all replicas).  A replica whose step ends in the termination branch
+ * (status 1) freezes: later calls leave it as it is and report it with status 1 and no steps.
+ * res[r].full_sweeps = the replica's executed steps.
+ *
+ * cetkmc_create_ensemble: p[R] (one parameter set per replica).  The returned handle addresses replica 0 in the
+ * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
+ * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
+ * thermal_cet, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*) except the
+ * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
+ * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
+ * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
+ * cetkmc_run_ensemble: n_steps steps of every live replica from global step step0.  res[R]; totals[R][n_steps + 1]
+ * (totals[r][s] = total rate of replica r's step s, [steps_done] = the terminating total); dt[R][n_steps] (may be NULL;
+ * rng_mode 2 only): the time increment of each step from the counter uniform of key KEY_DT, as cetkmc_run_supersteps'
+ * dt_event for box == L.  All per-replica arrays are row-major with replica-major rows. */
+typedef struct cetkmc_ens_args {
+    int64_t step0;
+    int64_t n_steps;
+    const double* defect_fraction;  /* [R] */
+    const double* u_pick;           /* [R][n_steps]   rng_mode 0 */
+    const double* u_defect;         /* [R][n_steps]   rng_mode 0; may be NULL when every defect_fraction is 0 */
+    const double* u_np;             /* [R][np_stride] rng_mode 0 */
+    int64_t np_stride;              /* rng_mode 0: >= n_steps * (L*L + 2), the worst case -- no replica can run short */
+    const uint64_t* seed;           /* [R]            rng_mode 2 */
+    int32_t rng_mode;               /* 0 (reference streams) or 2 (all counter based) */
+    int32_t thermal_mode;           /* 0 or 1 */
+    double thermal_dt;
+} cetkmc_ens_args;
+
+int cetkmc_create_ensemble(const cetkmc_params* p, int L, int R, int device_id, void** handle);
+int cetkmc_ensemble_replica(void* handle, int r, void** replica);
+int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_result* res, double* totals, double* dt);
+
+/* Batched analysis of every replica (the metrics rows of run_kmc_ensemble) in a number of launches that does not depend
+ * on R.  cetkmc_ensemble_analyze: grain clustering (as cetkmc_cluster, misorientation threshold), species counts (as
+ * cetkmc_species_counts), the nucleation counts and, for species >= 0, the (index, T) gather of cetkmc_gather_species.
+ * cetkmc_ensemble_analysis_data then copies the results of the last analysis, concatenated over replicas in replica
+ * order: sum(n_clusters) entries of first voxel (i,j,k) / size / bounding box (clusters numbered as cetkmc_cluster_stats
+ * does), labels [R][L^3], sum(n_gathered) gathered entries (unordered within a replica).  Any output may be NULL.
+ * cetkmc_ensemble_set_defects_sparse: cetkmc_set_defects_sparse for every replica r with counts[r] >= 0, its indices the
+ * next counts[r] entries of lin_idx (replicas with counts[r] < 0 are left alone). */
+typedef struct cetkmc_ens_analysis {
+    double threshold;               /* in: clustering misorientation threshold (radians) */
+    int32_t species;                /* in: state gathered; -1: no gather */
+    int32_t pad;
+    int64_t* n_clusters;            /* [R] out */
+    int64_t* species_counts;        /* [R][6] out */
+    int64_t* nucleation_count;      /* [R] out */
+    int64_t* n_gathered;            /* [R] out (species >= 0) */
+} cetkmc_ens_analysis;
+
+int cetkmc_ensemble_analyze(void* handle, cetkmc_ens_analysis* a);
+int cetkmc_ensemble_analysis_data(void* handle, int32_t* first_voxel, int64_t* size, int32_t* bbox, int32_t* labels,
+                                  int64_t* lin_idx, double* T_vals);
+int cetkmc_ensemble_set_defects_sparse(void* handle, const int64_t* counts, const int64_t* lin_idx);
+
 #ifdef __cplusplus
 }
 #endif
