@@ -1346,14 +1346,18 @@ __device__ __forceinline__ void select_body(const KParams& P, const SlabView* __
     SEL_STAMP(6);
     const TreeSel tc = tree_select(lf, fm, npk, tb.base, [&](double) { return r; }, X, tid);
     SEL_STAMP(7);
+    // deposition rank = events of the rows below j + of the voxels below k (one each): summed by all lanes of wave 0
+    // (an integer sum, so the lane split does not change it) instead of by thread 0 alone
+    int rank = 0;
+    if (c == CAT_DEP && tid < 64) {
+        for (int jj = tid; jj < j; jj += 64) rank += rowcnt_l[jj];
+        for (int kk = tid; kk < tc.leaf; kk += 64) rank += voxcnt_l[kk] & 255;
+#pragma unroll
+        for (int l = 0; l < 6; ++l) rank += __shfl_xor(rank, 1 << l);
+    }
     if (tid == 0) {
         const int k = tc.leaf;
         const double base = tc.base;
-        long long rank = 0;
-        if (c == CAT_DEP) {
-            for (int jj = 0; jj < j; ++jj) rank += rowcnt_l[jj];
-            for (int kk = 0; kk < k; ++kk) rank += voxcnt_l[kk] & 255;
-        }
         // slot scan (kmc_simulation.py:268-274 restricted to this voxel's slots)
         int p_type = -1, p_m = -1, p_atom = 0;
         double p_rate = 0.0, p_cum = 0.0;          // p_cum: running sum including the chosen event
