@@ -114,6 +114,11 @@ struct Handle {
     cetkmc_event* d_events_all = nullptr;
     StepState* d_ss = nullptr;
     int* d_dirty = nullptr;      // [1 + DIRTY_MAX] rows made stale by the last applied event (incremental mode)
+    PendRec* d_pend = nullptr;   // the event of a deferred step, applied by the next sweep launch (k_select_pend -> k_sweep_stream_apply)
+    RowPatch* d_patch = nullptr; // that launch's re-evaluated stale rows (k_sweep_stream_apply -> k_plane_reduce)
+    int apply_in_sweep = 1;      // option "apply_in_sweep": defer the application of eligible batched steps into the next sweep
+    bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
+    BatchCfg pend_cfg{};         // ... with this batch configuration
     double* d_ktab = nullptr;
     KParams* d_kp = nullptr;
     void* d_scratch = nullptr;
@@ -346,6 +351,10 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
     HIPCHK(hipMemsetAsync(h->d_ss, 0, sizeof(StepState), h->stream));
     HIPCHK(hipMalloc((void**)&h->d_dirty, (1 + 2 * DIRTY_MAX) * sizeof(int)));     // list + per-plane arrival counters
     HIPCHK(hipMemsetAsync(h->d_dirty, 0, (1 + 2 * DIRTY_MAX) * sizeof(int), h->stream));
+    HIPCHK(hipMalloc((void**)&h->d_pend, sizeof(PendRec)));
+    HIPCHK(hipMemsetAsync(h->d_pend, 0, sizeof(PendRec), h->stream));
+    HIPCHK(hipMalloc((void**)&h->d_patch, sizeof(RowPatch)));
+    HIPCHK(hipMemsetAsync(h->d_patch, 0, sizeof(RowPatch), h->stream));
     HIPCHK(hipMalloc((void**)&h->d_ktab, 225 * sizeof(double)));
     HIPCHK(hipMalloc((void**)&h->d_kp, sizeof(KParams)));
     HIPCHK(hipMalloc((void**)&h->d_flag, sizeof(int)));
@@ -658,6 +667,8 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
     const StepState* ss = batch ? h->d_ss : nullptr;
     const int njt = (h->L + SWEEP_TJ - 1) / SWEEP_TJ;
     if (h->sweep_variant >= 1) {
+        // a pending event is applied inside the sweep launch: nothing may read the lattice before it
+        if (h->pend_live && (!h->table_fresh || !h->ifc_fresh)) return fail("internal: rate table / interface sums stale under a pending event");
         CHK(ensure_table(h, h->stream, ss));
         if (!h->ifc_fresh || h->ifc_every_step) {
             CHK(launch_interface(h, batch, h->stream, long_list));
@@ -716,7 +727,21 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream<TAB, HW, NPF, CH2>), g, dim3(256), h->shmem_stream, h->stream, sa, ss); \
     } while (0)
             const bool ch2 = h->Pk > 512;       // L > 512: pitchC >= 544, so npf >= 2
-            if (hw) { if (tab) CETKMC_LAUNCH_STREAM(true, true, 1, false); else CETKMC_LAUNCH_STREAM(false, true, 1, false); }
+            if (h->pend_live) {
+                // the previous step's event is applied by one extra workgroup (blockIdx 0) of this launch
+                ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_patch, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
+                            (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
+                const dim3 ga(g.x + 1);
+#define CETKMC_LAUNCH_STREAM_APPLY(HW, NPF, CH2)                                                                                  \
+    do {                                                                                                                         \
+        if (ext) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream_apply<HW, NPF, CH2>), ga, dim3(256), (uint32_t)h->shmem_stream, \
+                                       h->stream, ev_a, ev_b, 0, sa, (const StepState*)h->d_ss, X);                              \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream_apply<HW, NPF, CH2>), ga, dim3(256), h->shmem_stream, h->stream, sa, \
+                                (const StepState*)h->d_ss, X);                                                                   \
+    } while (0)
+                CETKMC_LAUNCH_STREAM_APPLY(true, 1, false);      // (run_steps defers only where rows are half-wave rows)
+#undef CETKMC_LAUNCH_STREAM_APPLY
+            } else if (hw) { if (tab) CETKMC_LAUNCH_STREAM(true, true, 1, false); else CETKMC_LAUNCH_STREAM(false, true, 1, false); }
             else if (npf == 1) { if (tab) CETKMC_LAUNCH_STREAM(true, false, 1, false); else CETKMC_LAUNCH_STREAM(false, false, 1, false); }
             else if (npf == 2 && !ch2) { if (tab) CETKMC_LAUNCH_STREAM(true, false, 2, false); else CETKMC_LAUNCH_STREAM(false, false, 2, false); }
             else if (npf == 2) { if (tab) CETKMC_LAUNCH_STREAM(true, false, 2, true); else CETKMC_LAUNCH_STREAM(false, false, 2, true); }
@@ -730,7 +755,8 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
     if (sv != 4)          // (variant 4 folds the block sums in the sweep launch)
         for (size_t s = 0; s < h->slabs.size(); ++s) {
             SlabView v = view_of(h, (int)s);
-            hipLaunchKernelGGL(k_plane_reduce, dim3(3 * v.nloc), dim3(64), 0, h->stream, v, h->d_blocks, ss);
+            hipLaunchKernelGGL(k_plane_reduce, dim3(3 * v.nloc), dim3(64), 0, h->stream, v, h->d_blocks, ss,
+                               (const RowPatch*)(h->pend_live ? h->d_patch : nullptr));
         }
     HIPCHK(hipGetLastError());
     if (multi_rank(h)) CHK(comm_allgather(h, h->d_blocks, (size_t)3 * (h->L / h->nranks) * sizeof(BlockEnt)));
@@ -771,6 +797,17 @@ int launch_select_apply(Handle* h, const BatchCfg& cfg, int eval_touched, int* d
                        (int)h->slabs.size(), h->L, (const cetkmc_event*)h->d_events_all, h->G, h->d_ss, cfg,
                        (const double*)h->d_u_defect, (const double*)h->d_u_np, h->d_log_total, h->d_log_event,
                        h->d_log_nev, (const double*)h->d_ktab, eval_touched, dirty);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// selection of a deferred step (single process): the event and its carry go to d_pend, the next sweep launch applies them
+int launch_select_pend(Handle* h, const BatchCfg& cfg, int64_t cur_hint)
+{
+    hipLaunchKernelGGL(k_select_pend, dim3(1), dim3(256), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+                       (int)h->slabs.size(), h->L, h->PB, (const BlockEnt*)h->d_blocks, h->d_ss, cfg,
+                       (const double*)h->d_u_pick, (const double*)h->d_ktab, h->d_pend, (const double*)h->d_u_defect,
+                       (const double*)h->d_u_np, (long long)cur_hint);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1017,7 +1054,7 @@ void destroy_impl(Handle* h)
     }
     void* ccp[] = {h->d_cc_parent, h->d_cc_roots, h->d_cc_cid, h->d_cc_labels, h->d_cc_stats, h->d_cc_n};
     for (void* p : ccp) if (p) (void)hipFree(p);
-    void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_ktab, h->d_kp, h->d_scratch,
+    void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_patch, h->d_ktab, h->d_kp, h->d_scratch,
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1242,6 +1279,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         return 0;
     }
     if (!strcmp(key, "thermal_lookahead")) { h->thermal_ahead = value ? 1 : 0; return 0; }
+    if (!strcmp(key, "apply_in_sweep")) { h->apply_in_sweep = value ? 1 : 0; return 0; }
     if (!strcmp(key, "thermal_table")) { h->thermal_table = value ? 1 : 0; return 0; }
     if (!strcmp(key, "reserve_batch")) {
         // device buffers (uniform streams, per-step logs, one laser source plane per temperature update) and hipEvents of a
@@ -1624,6 +1662,13 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     // current between temperature updates (the interface kernel then runs only after one); off: the interface kernel
     // re-evaluates the whole list before every full sweep
     const int eval_touched = (h->sweep_variant >= 1 && !h->ifc_every_step) ? 1 : 0;
+    // apply_in_sweep: a full-sweep step whose successor is no temperature-update step launches its selection alone; the next
+    // sweep launch (the streaming kernel with the rate table, one slab, one process) applies the event.  The last step of the
+    // call stays immediate, so no event is pending when the call returns.
+    const bool pend_ok = h->apply_in_sweep && !incr && eval_touched && !multi_rank(h) && h->slabs.size() == 1 &&
+                         h->sweep_variant == 1 && !(h->sweep_auto && h->L <= 128) && h->Pk <= 256;
+    h->pend_live = false;
+    h->pend_cfg = cfg;
     res->full_sweeps = 0;
     // continuation of a batch that ran out of stream on a temperature-update step: that update is already in the field
     const int64_t therm_skip_g = h->therm_applied_g;
@@ -1659,10 +1704,18 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
                 CHK(launch_thermal_ahead(h, g + 20, a->thermal_dt, laser, laser ? h->d_q + (size_t)q_idx * L2 : nullptr, latent, 1));
             if (a->profile == 2) was_thermal[s] = 1;
         }
-        if (a->profile == 2) CHK(launch_sweep(h, true, pev(s, 2), pev(s, 3), false, pev(s, 1), pev(s, 4)));
-        else if (sampled(s)) CHK(launch_sweep(h, true, h->prof[2 * (s / pstride)], h->prof[2 * (s / pstride) + 1]));
-        else CHK(launch_sweep(h, true));
-        CHK(launch_select_apply(h, cfg, (incr || eval_touched) ? 1 : 0, incr ? h->d_dirty : nullptr, s));
+        int rc_sw;
+        if (a->profile == 2) rc_sw = launch_sweep(h, true, pev(s, 2), pev(s, 3), false, pev(s, 1), pev(s, 4));
+        else if (sampled(s)) rc_sw = launch_sweep(h, true, h->prof[2 * (s / pstride)], h->prof[2 * (s / pstride) + 1]);
+        else rc_sw = launch_sweep(h, true);
+        h->pend_live = false;
+        CHK(rc_sw);
+        if (pend_ok && s + 1 < n && !(a->thermal_mode && (g + 1) % 20 == 0)) {
+            CHK(launch_select_pend(h, cfg, s));
+            h->pend_live = true;
+        } else {
+            CHK(launch_select_apply(h, cfg, (incr || eval_touched) ? 1 : 0, incr ? h->d_dirty : nullptr, s));
+        }
         if (!(incr || eval_touched)) h->ifc_fresh = false;
         if (a->profile == 2) HIPCHK(hipEventRecord(pev(s, 5), h->stream));
         h->swept = false;
@@ -2106,6 +2159,12 @@ int cetkmc_debug_sel_stamps(long long out[16])      /* alternative builds only (
 {
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(cetkmc::g_sel_stamps), 16 * sizeof(long long)));
+    return 0;
+}
+int cetkmc_debug_pend_stamps(unsigned long long out[8])     /* the apply block of k_sweep_stream_apply (tools/pend_stamps.py) */
+{
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(cetkmc::g_pend_stamps), 8 * sizeof(unsigned long long)));
     return 0;
 }
 #endif

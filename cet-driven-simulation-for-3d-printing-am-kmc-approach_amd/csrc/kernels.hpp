@@ -235,15 +235,22 @@ constexpr int STREAM_MAXPF = 3;   // 16-B chunks of a class slab per thread (L <
 
 // Block sum of (owned plane lp, category c) by one wave: balanced tree over j of the row sums.  COH: some row sums
 // were written by other blocks of the SAME launch (k_rows_eval's in-launch reduction) -> agent-scope loads.
+struct RowPatch;
+__device__ __forceinline__ unsigned long long patch_plane(const RowPatch* patch, int gi, int lane, int& pe);
+__device__ __forceinline__ void patch_rows(const RowPatch* patch, unsigned long long pm, int pe, int j, int c, double& v, int& cv,
+                                           double* rowsum_w, int32_t* rowcnt_w);
 template <bool COH>
 __device__ __forceinline__ void plane_reduce_wave(const double* rowsum, const int32_t* rowcnt, BlockEnt* blocks,
-                                                  int L, int Pk, int gi0, int lp, int c, int lane)
+                                                  int L, int Pk, int gi0, int lp, int c, int lane,
+                                                  const RowPatch* patch = nullptr, double* rowsum_w = nullptr, int32_t* rowcnt_w = nullptr)
 {
     const int b = lp * 3 + c;
     const int nch = Pk > 64 ? (Pk >> 6) : 1;
     double stk[5];
     double tot = 0.0;
     int64_t cnt = 0;
+    int pe = 0;                                                  // patch: this plane's entries (lane q = entry q)
+    const unsigned long long pm = patch ? patch_plane(patch, gi0 + lp, lane, pe) : 0ull;
     for (int m = 0; m < nch; ++m) {
         const int j = (m << 6) + lane;
         double v = 0.0;
@@ -256,6 +263,7 @@ __device__ __forceinline__ void plane_reduce_wave(const double* rowsum, const in
                 v = rowsum[(int64_t)b * L + j]; cv = rowcnt[(int64_t)b * L + j];
             }
         }
+        if (pm) patch_rows(patch, pm, pe, j, c, v, cv, rowsum_w + (int64_t)b * L, rowcnt_w + (int64_t)b * L);
         v = wave_tree_sum(v);
         cnt += wave_sum_i(cv);
         tot = stack_push(stk, v, m);
@@ -525,18 +533,32 @@ __device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li
     }
 }
 
-// NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682)
-template <bool TAB, bool HW, int NPF, bool CH2>
-__global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
+// (di, dj) of a row whose sums change when voxel (i, j, k) changes: the rows of the voxel and of its 14 neighbours (11 rows).
+// The one definition of "dirty" for the incremental mode's list and for the rows the sweep leaves to its apply block.
+__host__ __device__ __forceinline__ bool dirty_offset(int di, int dj)
 {
-    if (ss && ss->status) return;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int a = di < 0 ? -di : di, c = dj < 0 ? -dj : dj;
+    return a + c <= 2 && !(a == 1 && c == 0);
+}
+// The stale rows of an event applied inside a sweep launch (k_sweep_stream_apply), re-evaluated by its apply block after
+// the event: k_plane_reduce folds these sums instead of what the launch's tiles stored for those rows, and stores them
+constexpr int PATCH_MAX = 22;      // 11 rows around each of <= 2 changed sites
+struct RowPatch {
+    int n;
+    int row[PATCH_MAX];            // (global plane << 16) | row
+    double sum[PATCH_MAX][3];      // by category
+    int cnt[PATCH_MAX][3];
+};
+// NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682).  One tile (b = its index among the
+// launch's tiles)
+template <bool TAB, bool HW, int NPF, bool CH2>
+__device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, unsigned char* smem)
+{
     constexpr int TJ = SWEEP_TJ, TR = TJ + 4;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int L = A.L;
     const int njt = (L + TJ - 1) / TJ;
     const int nblk = njt * A.group_count;
-    int b = blockIdx.x;
     if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);   // contiguous block ranges per XCD
     const int ibr = b / njt, jt = b - ibr * njt;
     const int j0 = jt * TJ;
@@ -643,6 +665,13 @@ __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamAr
         for (int lp = lp0; lp < lp1; ++lp) plane(lp, va, vb);     // two passes: va -> vb -> va
     }
 }
+template <bool TAB, bool HW, int NPF, bool CH2>
+__global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
+{
+    if (ss && ss->status) return;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    sweep_stream_tile<TAB, HW, NPF, CH2>(A, blockIdx.x, smem);
+}
 
 // ----------------------------------------------------------------------------------------
 // k_sweep_table (variant 3): the rate sweep WITHOUT a neighbour census.  What the census of k_sweep_stream decides --
@@ -672,7 +701,8 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
 }
 template <bool HW, bool CH2>
 __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, int jrow, bool top, int lane, const double (&v0)[8],
-                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */)
+                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */,
+                                          RowPatch* patch = nullptr, int pq = 0 /* patch: slot pq instead of rowsum / rowcnt */)
 {
     static_assert(!(HW && CH2), "half-wave rows have one chunk");
     const int L = A.L;
@@ -761,7 +791,13 @@ __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, i
         n2 += packed & 0xFFFF;
         n1 = packed >> 16;
     }
-    if (sl == 0 && jrow < L) {
+    if (patch) {
+        if (sl == 0 && jrow < L) {
+            patch->row[pq] = ((A.gi0 + lp) << 16) | jrow;
+            patch->sum[pq][0] = r0; patch->sum[pq][1] = r1; patch->sum[pq][2] = r2;
+            patch->cnt[pq][0] = n0; patch->cnt[pq][1] = n1; patch->cnt[pq][2] = n2;
+        }
+    } else if (sl == 0 && jrow < L) {
         const int64_t o = (int64_t)lp * 3 * L + jrow;
         A.rowsum[o] = r0; A.rowsum[o + L] = r1; A.rowsum[o + 2 * (int64_t)L] = r2;
         A.rowcnt[o] = n0; A.rowcnt[o + L] = n1; A.rowcnt[o + 2 * (int64_t)L] = n2;
@@ -1002,12 +1038,32 @@ __global__ __launch_bounds__(256) void k_rate_table(KParams P, SlabView S, doubl
 }
 
 // k_plane_reduce: one wave per (owned plane, category): balanced tree over j of the row sums.
+// patch (after k_sweep_stream_apply): the apply block's sums of the rows its event made stale replace the tiles' ones
+__device__ __forceinline__ unsigned long long patch_plane(const RowPatch* patch, int gi, int lane, int& pe)
+{
+    const int n = patch->n;                                      // <= PATCH_MAX < 64
+    pe = lane < n ? patch->row[lane] : -1;
+    return __ballot(lane < n && (pe >> 16) == gi);
+}
+// (called by the whole wave; pm: the patch entries of this plane) row j's sums replaced by and stored from the patch
+__device__ __forceinline__ void patch_rows(const RowPatch* patch, unsigned long long pm, int pe, int j, int c, double& v, int& cv,
+                                           double* rowsum_w, int32_t* rowcnt_w)
+{
+    while (pm) {
+        const int q = __builtin_ctzll(pm);
+        pm &= pm - 1;
+        if (j == (__builtin_amdgcn_readlane(pe, q) & 0xFFFF)) {
+            v = patch->sum[q][c]; cv = patch->cnt[q][c];
+            rowsum_w[j] = v; rowcnt_w[j] = cv;
+        }
+    }
+}
 __global__ __launch_bounds__(64) void k_plane_reduce(SlabView S, BlockEnt* __restrict__ blocks,
-                                                     const StepState* __restrict__ ss)
+                                                     const StepState* __restrict__ ss, const RowPatch* __restrict__ patch)
 {
     if (ss && ss->status) return;
     const int b = blockIdx.x;
-    plane_reduce_wave<false>(S.rowsum, S.rowcnt, blocks, S.L, S.Pk, S.gi0, b / 3, b % 3, (int)threadIdx.x);
+    plane_reduce_wave<false>(S.rowsum, S.rowcnt, blocks, S.L, S.Pk, S.gi0, b / 3, b % 3, (int)threadIdx.x, patch, S.rowsum, S.rowcnt);
 }
 
 // ---- counter-based uniforms (DESIGN.md "RNG"): u(seed, step, key) in [0, 1); the oracle's orc_counter_uniform ----------
@@ -1578,6 +1634,7 @@ __device__ __forceinline__ void ifc_store(const SlabView& S, int li, int j, int 
 // defer_centre (single neighbourhood only): the centre voxel (lane 14), if it is an atom, is NOT evaluated here:
 // centre_atom_eval() spreads its <= 14 diffusion items over the lanes of a wave (another wave of the block, where
 // there is one, so that it runs beside this function instead of after it).
+template <int EB = 8>      // EB: neighbour gathers per batch of an empty voxel's evaluation
 __device__ __forceinline__ void ifc_touch(const KParams& P, const SlabView& S, const double* ktab, int i, int j, int k, int lane,
                                           int eval, bool dedupe, bool defer_centre)
 {
@@ -1618,7 +1675,7 @@ __device__ __forceinline__ void ifc_touch(const KParams& P, const SlabView& S, c
         if (!(defer_centre && lane == 14 && st >= 1 && st <= 3)) {
             double sum = 0.0;
             int cnt = 0;
-            if (st == 0) ifc_eval_empty<8>(P, S, ktab, lp, aj, ak, t, code, Tc, sum, cnt);     // one wave: registers are free
+            if (st == 0) ifc_eval_empty<EB>(P, S, ktab, lp, aj, ak, t, code, Tc, sum, cnt);    // one wave: registers are free
             else if (st != 4) ifc_eval_atom(P, S, lp, aj, ak, t, code, st, Tc, sum, cnt);
             ifc_store(S, li, aj, ak, t, sum, cnt, code);
         }
@@ -1797,6 +1854,7 @@ __device__ __forceinline__ void centre_atom_eval(const KParams& P, const SlabVie
 // tid / nthreads: the calling block's thread index and size (whole waves).  Wave 0: lanes 0..14 the neighbourhood of the
 // event site, lanes 16..30 the neighbourhood of a diffusion target; the atom a dep / nuc / att event placed is
 // evaluated by wave 1 (wave 0 in a one-wave block).
+template <int EB = 8>
 __device__ __forceinline__ void apply_touch(const KParams& P, const SlabView* slabs, int nslabs, const double* ktab,
                                             const cetkmc_event& ev, int tid, int eval, int nthreads)
 {
@@ -1807,8 +1865,8 @@ __device__ __forceinline__ void apply_touch(const KParams& P, const SlabView* sl
     for (int s = 0; s < nslabs; ++s) {
         const SlabView& S = slabs[s];
         if (wave == 0) {
-            if (lane < 16) ifc_touch(P, S, ktab, ev.pos[0], ev.pos[1], ev.pos[2], lane, eval, two, defer);
-            else if (two) ifc_touch(P, S, ktab, ev.target[0], ev.target[1], ev.target[2], lane - 16, eval, two, false);
+            if (lane < 16) ifc_touch<EB>(P, S, ktab, ev.pos[0], ev.pos[1], ev.pos[2], lane, eval, two, defer);
+            else if (two) ifc_touch<EB>(P, S, ktab, ev.target[0], ev.target[1], ev.target[2], lane - 16, eval, two, false);
         }
         if (defer && wave == cw) centre_atom_eval(P, S, ev.pos[0], ev.pos[1], ev.pos[2], lane);
     }
@@ -1816,7 +1874,8 @@ __device__ __forceinline__ void apply_touch(const KParams& P, const SlabView* sl
 
 // Batched apply: RNG bookkeeping of one step + lattice update + per-step logs (lane 0), then the
 // interface-list update for the touched voxels (whole wave).  Launched with ONE 64-thread block.
-__device__ __forceinline__ void apply_batch_body(const KParams& P, const SlabView* __restrict__ slabs, int nslabs, int L,
+template <int EB = 8>
+__device__ __forceinline__ int apply_batch_body(const KParams& P, const SlabView* __restrict__ slabs, int nslabs, int L,
                                                  const cetkmc_event* events_all, int G, StepState* ss,
                                                  const BatchCfg& cfg, const double* __restrict__ u_defect,
                                                  const double* __restrict__ u_np, double* log_total,
@@ -1872,27 +1931,28 @@ __device__ __forceinline__ void apply_batch_body(const KParams& P, const SlabVie
     }
     SEL_STAMP(10);
     __syncthreads();
-    if (sh_ok) apply_touch(P, slabs, nslabs, ktab_g, sh_ev, threadIdx.x, eval_touched, blockDim.x);
+    if (sh_ok) apply_touch<EB>(P, slabs, nslabs, ktab_g, sh_ev, threadIdx.x, eval_touched, blockDim.x);
     SEL_STAMP(11);
     if (dirty && threadIdx.x == 0) {
         // rows whose rates may have changed: the rows of the changed voxel(s) and of their 14 neighbours
         int n = 0;
         if (sh_ok) {
-            const int di[11] = {0, 1, 1, -1, -1, 0, 0, 2, -2, 0, 0}, dj[11] = {0, 1, -1, 1, -1, 1, -1, 0, 0, 2, -2};
             for (int v = 0; v < (sh_ev.type == EV_DIFF ? 2 : 1); ++v) {
                 const int ci = v ? sh_ev.target[0] : sh_ev.pos[0], cj = v ? sh_ev.target[1] : sh_ev.pos[1];
-                for (int q = 0; q < 11; ++q) {
-                    const int i = ci + di[q], j = cj + dj[q];
-                    if (i < 0 || i >= L || j < 0 || j >= L) continue;
-                    const int e = (i << 16) | j;
-                    bool dup = false;
-                    for (int t = 1; t <= n; ++t) dup |= (dirty[t] == e);
-                    if (!dup && n < DIRTY_MAX) dirty[++n] = e;
-                }
+                for (int di = -2; di <= 2; ++di)
+                    for (int dj = -2; dj <= 2; ++dj) {
+                        const int i = ci + di, j = cj + dj;
+                        if (!dirty_offset(di, dj) || i < 0 || i >= L || j < 0 || j >= L) continue;
+                        const int e = (i << 16) | j;
+                        bool dup = false;
+                        for (int t = 1; t <= n; ++t) dup |= (dirty[t] == e);
+                        if (!dup && n < DIRTY_MAX) dirty[++n] = e;
+                    }
             }
         }
         dirty[0] = n;
     }
+    return sh_ok;
 }
 
 __global__ __launch_bounds__(64) void k_apply_batch(KParams P, const SlabView* __restrict__ slabs, int nslabs, int L,
@@ -1931,6 +1991,129 @@ __global__ __launch_bounds__(256) void k_select_apply(KParams P, const SlabView*
     __syncthreads();
     apply_batch_body(ens_kp(blockIdx.x, P, ens...), slabs, nslabs, L, &sh_sel, 1, ss, cfg, u_defect, u_np, log_total, log_event, log_nev, ktab_g,
                      eval_touched, dirty, &sh_carry);
+}
+
+// ---- apply inside the next sweep (single process, one slab, streaming sweep with the rate table, full sweeps) ---------------
+// A deferred step launches the selection alone (k_select_pend): the event and what k_select_apply carries in LDS go to a
+// device record.  The next sweep launch (k_sweep_stream_apply) carries one extra workgroup, blockIdx 0, that applies that
+// event exactly as k_select_apply would have and then re-evaluates the rows the event made stale (dirty_offset() around
+// the changed sites) into a RowPatch.  The tiles are those of k_sweep_stream: every row that is not stale does not depend on
+// whether a tile read the lattice before or after the event; k_plane_reduce replaces the stale rows' sums by the patch.
+// Stream order between the launches is unchanged.
+struct PendRec {
+    cetkmc_event ev;
+    SelCarry carry;
+};
+struct ApplyArgs {
+    KParams P;
+    const SlabView* slabs;      // the handle's device views (one slab)
+    const PendRec* pend;
+    RowPatch* patch;
+    StepState* ss;
+    BatchCfg cfg;
+    const double* u_defect;
+    const double* u_np;
+    const double* ktab_g;
+    double* log_total;
+    cetkmc_event* log_event;
+    int64_t* log_nev;
+};
+
+// A/B instrumentation (tools/pend_stamps.py, the -DCETKMC_SEL_STAMPS build): the apply block's thread 0 records start (0),
+// lattice written (1), upkeep done (2) and stale rows done (3); every tile raises [4] to its own end
+#ifdef CETKMC_SEL_STAMPS
+__device__ unsigned long long g_pend_stamps[8];
+#define PEND_STAMP(q) do { if (threadIdx.x == 0) g_pend_stamps[q] = wall_clock64(); } while (0)
+#else
+#define PEND_STAMP(q) do { } while (0)
+#endif
+
+// the selection half of k_select_apply<true>: the chosen event and the carry go to *pend
+__global__ __launch_bounds__(256) void k_select_pend(KParams P, const SlabView* __restrict__ slabs, int nslabs, int L,
+                                                     int PB, const BlockEnt* __restrict__ blocks, StepState* ss,
+                                                     BatchCfg cfg, const double* __restrict__ u_pick,
+                                                     const double* __restrict__ ktab_g, PendRec* pend,
+                                                     const double* __restrict__ u_defect, const double* __restrict__ u_np,
+                                                     long long cur_hint)
+{
+    select_body<true>(P, slabs, nslabs, L, PB, blocks, ss, cfg, u_pick, 0.0, ktab_g, &pend->ev, 0, 1, cur_hint, &pend->carry,
+                      u_defect, u_np);
+}
+
+// The apply block: apply_batch_body of the fused launch (carry from the record instead of LDS), then the stale rows, one
+// per wave (HW: the first half-wave), with the census-free row reduction of the incremental mode's k_rows_eval.  It is
+// latency-bound beside the tiles, so an empty voxel's neighbour gathers go one at a time: the kernel keeps the tiles'
+// register budget (5 waves per SIMD).
+constexpr int PEND_EB = 1;
+template <bool HW, bool CH2>
+__device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const ApplyArgs& X, unsigned char* smem)
+{
+    PEND_STAMP(0);
+    // the rate constants and the slab view are read from LDS (the tiles' ring, unused by this block): vector registers
+    // instead of the scalar ones the apply would otherwise pin
+    static_assert(sizeof(KParams) % 8 == 0 && sizeof(SlabView) % 8 == 0, "8-byte copies");
+    KParams* Pl = reinterpret_cast<KParams*>(smem);
+    SlabView* Sl = reinterpret_cast<SlabView*>(smem + ((sizeof(KParams) + 15) & ~(size_t)15));
+    for (int q = threadIdx.x; q < (int)(sizeof(KParams) / 8); q += blockDim.x)
+        reinterpret_cast<uint64_t*>(Pl)[q] = reinterpret_cast<const uint64_t*>(&X.P)[q];
+    for (int q = threadIdx.x; q < (int)(sizeof(SlabView) / 8); q += blockDim.x)
+        reinterpret_cast<uint64_t*>(Sl)[q] = reinterpret_cast<const uint64_t*>(X.slabs)[q];
+    __syncthreads();
+    const int ok = apply_batch_body<PEND_EB>(*Pl, Sl, 1, A.L, &X.pend->ev, 1, X.ss, X.cfg, X.u_defect, X.u_np, X.log_total,
+                                             X.log_event, X.log_nev, X.ktab_g, 1, nullptr, &X.pend->carry);
+#ifdef CETKMC_SEL_STAMPS
+    if (threadIdx.x == 0) g_pend_stamps[1] = g_sel_stamps[10];
+#endif
+    // the rows below read what this block has just stored: release, barrier, then an agent-scope acquire, which also drops
+    // whatever the CU's vector L1 holds of those lines from the tiles beside this block
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    PEND_STAMP(2);
+    const cetkmc_event& ev = X.pend->ev;
+    const int nsite = ok ? (ev.type == EV_DIFF ? 2 : 1) : 0;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, L = A.L;
+    const int i0 = ev.pos[0], j0 = ev.pos[1];
+    int q = 0;
+    for (int v = 0; v < nsite; ++v) {
+        const int ci = v ? ev.target[0] : i0, cj = v ? ev.target[1] : j0;
+        for (int di = -2; di <= 2; ++di)
+            for (int dj = -2; dj <= 2; ++dj) {
+                const int gi = ci + di, j = cj + dj;
+                if (!dirty_offset(di, dj) || gi < 0 || gi >= L || j < 0 || j >= L) continue;
+                if (v && dirty_offset(gi - i0, j - j0)) continue;       // a row of the first site as well
+                const int pq = q++;
+                if ((pq & 3) != w) continue;
+                const int lp = gi - A.gi0, li = lp + 2;
+                const int jrow = (HW && lane >= 32) ? L_INACTIVE : j;
+                double v0[8];
+                load_vals<true, HW>(A, li, jrow, lane, 0, v0);
+                table_row<HW, CH2>(A, li, lp, jrow, gi == L - 1, lane, v0, load_cls8(A, li, jrow, HW ? (lane & 31) : lane, 0),
+                                   nullptr, nullptr, X.patch, pq);
+            }
+    }
+    if (threadIdx.x == 0) X.patch->n = q;
+#ifdef CETKMC_SEL_STAMPS
+    __syncthreads();
+    PEND_STAMP(3);
+#endif
+}
+
+template <bool HW, int NPF, bool CH2>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_sweep_stream_apply(StreamArgs A,
+                                                                                                    const StepState* __restrict__ ss,
+                                                                                                    ApplyArgs X)
+{
+    if (ss->status) return;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (blockIdx.x != 0) {
+        sweep_stream_tile<true, HW, NPF, CH2>(A, (int)blockIdx.x - 1, smem);
+#ifdef CETKMC_SEL_STAMPS
+        if (threadIdx.x == 0) atomicMax(&g_pend_stamps[4], (unsigned long long)wall_clock64());
+#endif
+        return;
+    }
+    sweep_apply_block<HW, CH2>(A, X, smem);
 }
 
 // Direct apply (cetkmc_apply): everything decided by the host.  ONE 64-thread block.

@@ -226,7 +226,10 @@ int cetkmc_sync(void* handle);
  * exactly, else k_thermal_march), 2 = k_thermal_march everywhere, 3 = 16-row tiles with 4 rows per thread, 4 = the 8-row
  * k_thermal_tiles (round-2 kernel), 5 = 16 x 128 tiles (A/B variants);
  * "thermal_planes_per_block" (march / 8-row tiles), "thermal_planes_per_block16" (16-row tiles); "reserve_batch" n = allocate the
- * device buffers and hipEvents of a batch of n steps now (a bench keeps hipMalloc / hipEventCreate out of its timed region) */
+ * device buffers and hipEvents of a batch of n steps now (a bench keeps hipMalloc / hipEventCreate out of its timed region);
+ * "apply_in_sweep" 1 (default) = cetkmc_run_steps applies the event of a step whose successor is no temperature-update step
+ * (and is not the call's last) inside the next sweep launch (one process, one slab, sweep_variant 1, 128 < L <= 256, full
+ * sweeps; same bits), 0 = every step's event applied by its own selection launch */
 int cetkmc_set_option(void* handle, const char* key, int64_t value);
 /* planes [*i0,*i1) owned by this handle (whole lattice unless created with create_rank) */
 int cetkmc_owned_planes(void* handle, int* i0, int* i1);
