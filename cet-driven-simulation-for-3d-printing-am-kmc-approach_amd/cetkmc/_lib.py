@@ -65,7 +65,7 @@ class Counters(C.Structure):
                                          "bytes_d2h", "alg_bytes_sweep", "alg_bytes_thermal", "profiled_steps")] + \
                [(n, C.c_double) for n in ("ms_thermal", "ms_interface", "ms_sweep", "ms_dirty_rows", "ms_reduce", "ms_select_apply")] + \
                [(n, C.c_int64) for n in ("alg_bytes_table", "table_updates", "interface_launches")] + \
-               [("ms_comm", C.c_double), ("comm_calls", C.c_int64)]
+               [("ms_comm", C.c_double), ("comm_calls", C.c_int64), ("deferred_steps", C.c_int64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -111,6 +111,7 @@ PROTOTYPES = {
     "cetkmc_abi_version": (C.c_int, []),
     "cetkmc_source_hash": (C.c_char_p, []),
     "cetkmc_struct_size": (C.c_int, [C.c_char_p]),
+    "cetkmc_dirty_offset": (C.c_int, [C.c_int, C.c_int]),
     "cetkmc_device_count": (C.c_int, [_P(C.c_int)]),
     "cetkmc_create": (C.c_int, [_P(Params), C.c_int, C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "cetkmc_get_unique_id": (C.c_int, [C.c_char_p]),

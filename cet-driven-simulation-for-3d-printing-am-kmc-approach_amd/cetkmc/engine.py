@@ -286,7 +286,8 @@ class Engine:
         return out
 
     def counters(self, reset=False):
-        """cetkmc_get_counters as a dict: work issued, bytes moved, per-phase device ms of the profile=2 runs."""
+        """cetkmc_get_counters as a dict: work issued (deferred_steps: steps whose event the next sweep launch applied),
+        bytes moved, per-phase device ms of the profile=2 runs."""
         c = Counters()
         self._ck(self.lib.cetkmc_get_counters(self.h, C.byref(c), int(bool(reset))))
         return {n: getattr(c, n) for n, _ in Counters._fields_}

@@ -1162,6 +1162,9 @@ int cetkmc_struct_size(const char* name)
     return -1;
 }
 
+// the kernels' own stale-row rule (kernels.hpp), for host-side checks of its footprint
+int cetkmc_dirty_offset(int di, int dj) { return dirty_offset(di, dj) ? 1 : 0; }
+
 int cetkmc_device_count(int* n)
 {
     if (!n) return fail("null argument");
@@ -1713,6 +1716,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
         if (pend_ok && s + 1 < n && !(a->thermal_mode && (g + 1) % 20 == 0)) {
             CHK(launch_select_pend(h, cfg, s));
             h->pend_live = true;
+            ++h->cnt.deferred_steps;
         } else {
             CHK(launch_select_apply(h, cfg, (incr || eval_touched) ? 1 : 0, incr ? h->d_dirty : nullptr, s));
         }
@@ -1752,6 +1756,14 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
         h->time_comm = false; h->comm_ev_used = 0;
     }
     res->steps_done = ss.cur; res->status = ss.status; res->np_used = ss.np_pos; res->q_used = q_idx;
+    if (ss.status != 0 && a->thermal_mode == 2) {
+        // q_idx counts the planes of every update the host queued; behind an early stop those updates ran as pass-throughs
+        // and read no plane.  Consumed: the updates of the executed steps and of the step the batch stopped in (its update
+        // precedes the selection that noticed the stop).
+        int64_t q = 0;
+        for (int64_t s = 0; s <= ss.cur && s < n; ++s) q += (a->step0 + s) % 20 == 0;
+        res->q_used = q;
+    }
     res->nucleation_count = ss.nuc_count;
     res->min_margin = ss.min_margin;
     float ms = 0.f;

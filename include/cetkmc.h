@@ -115,7 +115,9 @@ typedef struct cetkmc_run_result {
     int64_t steps_done;
     int32_t status;           /* 0 ok, 1 terminated (no valid events, :260-262), 2 u_np exhausted */
     int64_t np_used;          /* doubles of u_np consumed                               */
-    int64_t q_used;
+    int64_t q_used;           /* thermal_mode 2: source planes consumed by the executed steps (and by the step a batch
+                                 stopped in: its update precedes the selection); planes queued behind an early stop
+                                 are not counted, their updates pass through */
     int64_t nucleation_count; /* running total on the handle (:310)                     */
     double  sweep_ms_total;   /* profile: sum of rate-sweep kernel durations            */
     int64_t sweep_launches;
@@ -174,6 +176,9 @@ typedef struct cetkmc_counters {
                                    collective of the profiled steps (block-sum / event all-gathers, temperature-halo and
                                    boundary-layer exchanges); part of ms_reduce / ms_select_apply / ms_thermal above   */
     int64_t comm_calls;         /* collectives those pairs bracketed                               */
+    int64_t deferred_steps;     /* cetkmc_run_steps: steps launched as a selection alone, their event applied inside the next
+                                   rate-sweep launch (option apply_in_sweep); counts launches issued, so a batch that stops
+                                   early still counts every deferred step the host queued                           */
 } cetkmc_counters;
 
 const char* cetkmc_last_error(void);
@@ -184,6 +189,10 @@ const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
+/* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
+ * list and the apply-in-sweep row patch are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
+ * device. */
+int cetkmc_dirty_offset(int di, int dj);
 int cetkmc_device_count(int* n);
 
 /* Lifetime.  n_slabs > 1 with all device_ids equal splits the lattice into axis-0 slabs

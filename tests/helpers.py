@@ -184,3 +184,124 @@ def random_lattice(L, seed, fill=0.3, t_lo=2600.0, t_hi=3690.0, hot_frac=0.05):
     T[hot] = rs.uniform(3690.0, 4064.5, int(hot.sum()))
     defects = ((state == 3) & (rs.random_sample((L, L, L)) < 0.3)).astype(np.int64)
     return state, theta, phi, T, defects
+
+
+# ---- batched stepping at 128 < L <= 256: deferred apply ("apply in sweep") ---------------------------
+APPLY_IN_SWEEP_BATCHES = (7, 1, 13, 1, 20, 26, 2, 19, 3, 1)      # batches that start and end at many offsets modulo 20
+FOUR_KIND_PARAMS = dict(I0=1e11)      # at the default I0 = 5e13 nucleation swamps diffusion and attachment; with 1e11 all four fire
+
+
+def face_lattice(L, seed, n_atoms):
+    """synthetic.planes plus n_atoms random atoms in the empty part, some on the lattice faces and in the top plane: events
+    whose stale rows are clipped.  uint8 planes, as Engine.upload_planes takes them."""
+    from cetkmc import synthetic
+    st, th, ph, T, df = synthetic.planes(L, 0, L, seed=seed)
+    rs = np.random.RandomState(seed)
+    idx = rs.randint(0, L, (n_atoms, 3))
+    st[idx[:, 0], idx[:, 1], idx[:, 2]] = rs.randint(1, 5, n_atoms)
+    for f in range(8):
+        st[0, rs.randint(L), rs.randint(L)] = 1 + f % 3
+        st[L - 1, rs.randint(L), rs.randint(L)] = 1 + f % 3
+        st[rs.randint(L), 0, rs.randint(L)] = 1 + f % 3
+        st[rs.randint(L), L - 1, rs.randint(L)] = 1 + f % 3
+    return st, th, ph, T, df
+
+
+def step_uniforms(seed, n, n_np):
+    rs = np.random.RandomState(seed)
+    return rs.random_sample(n), rs.random_sample(n), rs.random_sample(n_np)
+
+
+def batch_calls(batches, seed0=100, step0=0):
+    """(step0, n, u_pick, u_def, u_np) per batch, back to back from step0; rng_mode 1 streams (two orientation draws a step)."""
+    calls, s = [], step0
+    for k, n in enumerate(batches):
+        calls.append((s, n) + step_uniforms(seed0 + k, n, 2 * n + 2))
+        s += n
+    return calls
+
+
+def is_deferred(step0, n, x, thermal_mode=2):
+    """Step x of a call of n steps from global step step0 launches its selection alone (its event is applied inside the next
+    sweep launch) iff it is not the call's last step and the next step is no temperature-update step."""
+    return x + 1 < n and not (thermal_mode and (step0 + x + 1) % 20 == 0)
+
+
+def count_deferred(calls, thermal_mode=2):
+    """What cetkmc_counters.deferred_steps holds after these calls on the deferring path: launches the host issued, so every
+    step of every call counts, also behind an early stop."""
+    return sum(is_deferred(c[0], c[1], x, thermal_mode) for c in calls for x in range(c[1]))
+
+
+def oracle_lattice(oracle_mod, lat, impurity_c, tweak=None):
+    st, th, ph, T, df = lat
+    o = oracle_mod.Lattice(st.astype(np.int64), th, ph, T, df.astype(np.int64), impurity_c=impurity_c)
+    for k, v in (tweak or {}).items():
+        setattr(o.params, k, v)
+    return o
+
+
+def deferred_coverage(L, calls, logs, defect_fraction, thermal_mode=2):
+    """What the deferred steps of a run exercised, from the ORACLE's per-call results ``logs`` (never the engine's): events
+    of each kind, diffusions whose two sites lie in different rows / planes, events on the i and j faces (clipped patch),
+    defect injections."""
+    cov = dict(kinds=[0, 0, 0, 0], diff_rows=0, diff_planes=0, face_i=0, face_j=0, defects=0)
+    for (step0, n, _, u_def, _), ro in zip(calls, logs):
+        for x in range(ro["done"]):
+            if not is_deferred(step0, n, x, thermal_mode):
+                continue
+            ev = ro["events"][x]
+            t, pos, tgt = int(ev["type"]), ev["pos"], ev["target"]
+            cov["kinds"][t] += 1
+            if t == 1:
+                cov["diff_rows"] += int(pos[0] != tgt[0] or pos[1] != tgt[1])
+                cov["diff_planes"] += int(pos[0] != tgt[0])
+            cov["face_i"] += int(pos[0] in (0, L - 1))
+            cov["face_j"] += int(pos[1] in (0, L - 1))
+            cov["defects"] += int(defect_fraction > 0.0 and u_def[x] < defect_fraction)
+    return cov
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def assert_call_matches_oracle(e, lat, rg, ro, rate_rtol, tag=""):
+    """One run_steps call of the engine ``e`` (result rg) against the same call of the oracle lattice ``lat`` (result ro):
+    stop state, stream positions, event log, totals, the downloaded fields and the row sums of the lattice the call left."""
+    for f in ("done", "status"):
+        assert rg[f] == ro[f], (tag, f, rg[f], ro[f])
+    # the log before the stream positions: a wrong step is reported as that step, not as what it did to the counts
+    for f in ("type", "pos", "target", "atom", "dep_rank"):
+        if not np.array_equal(rg["events"][f], ro["events"][f]):
+            x = [x for x in range(rg["done"]) if not np.array_equal(rg["events"][f][x], ro["events"][f][x])][0]
+            raise AssertionError(f"{tag}: event field {f} differs first at step {x} of the call: "
+                                 f"engine {rg['events'][x]} oracle {ro['events'][x]} (oracle's previous event: "
+                                 f"{ro['events'][x - 1] if x else None})")
+    for f in ("np_used", "q_used"):
+        assert rg[f] == ro[f], (tag, f, rg[f], ro[f])
+    assert rg["nucleation_count"] == lat.nuc_count, (tag, rg["nucleation_count"], lat.nuc_count)
+    assert np.array_equal(rg["n_events"], ro["n_events"]), (tag, "n_events", np.flatnonzero(rg["n_events"] != ro["n_events"])[:4])
+    assert len(rg["totals"]) == len(ro["totals"])
+    if len(ro["totals"]):
+        err = relerr(rg["totals"], ro["totals"])
+        assert err.max() <= rate_rtol, (tag, "totals", int(err.argmax()), float(err.max()))
+    d = e.download(defects=True)
+    assert np.array_equal(d["state"], lat.state), (tag, "state", np.argwhere(d["state"] != lat.state)[:4])
+    assert np.array_equal(_bits(d["theta"]), _bits(lat.theta)), (tag, "theta")
+    assert np.array_equal(_bits(d["phi"]), _bits(lat.phi)), (tag, "phi")
+    assert np.array_equal(d["defects"], lat.defects), (tag, "defects")
+    assert np.array_equal(d["T"], lat.T, equal_nan=True), (tag, "T")
+    # sweep of the lattice the call left (state, rate table and interface sums as the batch's last apply kept them)
+    sw = lat.sweep()
+    total, n_events, n_dep = e.rate_sweep()
+    rsum, rcnt = e.row_sums()
+    assert (n_events, n_dep) == (sw["n_events"], sw["n_dep"]), (tag, n_events, n_dep, sw["n_events"], sw["n_dep"])
+    assert np.array_equal(rcnt, sw["rowcnt"]), (tag, "rowcnt", np.argwhere(rcnt != sw["rowcnt"])[:4])
+    fin = np.isfinite(sw["rowsum"])
+    assert np.array_equal(np.isfinite(rsum), fin), (tag, "row sum finiteness")
+    if fin.any():
+        err = relerr(rsum[fin], sw["rowsum"][fin])
+        assert err.max() <= rate_rtol, (tag, "rowsum", float(err.max()))
+    if np.isfinite(sw["total"]):
+        assert abs(total - sw["total"]) <= rate_rtol * abs(sw["total"]), (tag, total, sw["total"])

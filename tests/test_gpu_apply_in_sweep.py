@@ -4,29 +4,22 @@ equal the immediate select + apply path bit for bit: per-step logs, counters, ro
 import numpy as np
 import pytest
 
+from helpers import APPLY_IN_SWEEP_BATCHES, FOUR_KIND_PARAMS, batch_calls, count_deferred, is_deferred
+from helpers import face_lattice as _lattice
+from helpers import step_uniforms as _uniforms
+
 pytestmark = pytest.mark.gpu
 
 
-def _lattice(L, seed, n_atoms):
-    from cetkmc import synthetic
-    st, th, ph, T, df = synthetic.planes(L, 0, L, seed=seed)
-    rs = np.random.RandomState(seed)
-    idx = rs.randint(0, L, (n_atoms, 3))
-    st[idx[:, 0], idx[:, 1], idx[:, 2]] = rs.randint(1, 5, n_atoms)
-    # atoms on the lattice faces and in the top plane: events whose stale rows are clipped
-    for f in range(8):
-        st[0, rs.randint(L), rs.randint(L)] = 1 + f % 3
-        st[L - 1, rs.randint(L), rs.randint(L)] = 1 + f % 3
-        st[rs.randint(L), 0, rs.randint(L)] = 1 + f % 3
-        st[rs.randint(L), L - 1, rs.randint(L)] = 1 + f % 3
-    return st, th, ph, T, df
-
-
-def _run(L, lat, calls, on, rng_mode=1, defect_fraction=0.05):
-    """calls: (step0, n, u_pick, u_def, u_np); returns everything observable after each call."""
+def _run(L, lat, calls, on, rng_mode=1, defect_fraction=0.05, tweak=None):
+    """calls: (step0, n, u_pick, u_def, u_np); returns everything observable after each call.  The deferred-step counter
+    must say which path ran: every eligible step with the option on, none with it off."""
     import cetkmc
     from cetkmc import synthetic
-    e = cetkmc.Engine(L, impurity_c=0.2)
+    params = cetkmc.default_params(0.2)
+    for k, v in (tweak or {}).items():
+        setattr(params, k, v)
+    e = cetkmc.Engine(L, impurity_c=0.2, params=params)
     e.set_option("apply_in_sweep", int(on))
     e.upload_planes(0, L, *lat)
     e.set_prev_state(None)
@@ -40,7 +33,9 @@ def _run(L, lat, calls, on, rng_mode=1, defect_fraction=0.05):
         out.append((r["done"], r["status"], r["np_used"], r["q_used"], r["nucleation_count"], r["full_sweeps"],
                     r["totals"].tobytes(), r["events"].tobytes(), r["n_events"].tobytes(), info, rs.tobytes(), rc.tobytes())
                    + tuple(d[k].tobytes() for k in sorted(d)))
+    deferred = e.counters()["deferred_steps"]
     e.close()
+    assert deferred == (count_deferred(calls) if on else 0), (on, deferred, count_deferred(calls))
     return out
 
 
@@ -54,9 +49,22 @@ def _compare(L, lat, calls, **kw):
     return a
 
 
-def _uniforms(seed, n, n_np):
-    rs = np.random.RandomState(seed)
-    return rs.random_sample(n), rs.random_sample(n), rs.random_sample(n_np)
+def _events(out):
+    """the per-call event logs of _run's result (the executed steps of each call)"""
+    from cetkmc.engine import EVENT_DTYPE
+    return [np.frombuffer(o[7], dtype=EVENT_DTYPE) for o in out]
+
+
+def _deferred_kinds(calls, out):
+    """events of each kind on deferred steps and, of the diffusions among them, those whose sites lie in different rows"""
+    kinds, diff_rows = [0, 0, 0, 0], 0
+    for (step0, n, *_), ev in zip(calls, _events(out)):
+        for x in range(len(ev)):
+            if is_deferred(step0, n, x):
+                t = int(ev["type"][x])
+                kinds[t] += 1
+                diff_rows += int(t == 1 and tuple(ev["pos"][x][:2]) != tuple(ev["target"][x][:2]))
+    return kinds, diff_rows
 
 
 @pytest.mark.parametrize("L", [256, 200])
@@ -105,8 +113,10 @@ def test_apply_in_sweep_termination():
 
 
 def test_apply_in_sweep_diffusion_events():
-    """A lattice with many W/Re/C atoms beside empty voxels and a cool field: diffusion moves (two changed sites) are
-    among the chosen events."""
+    """A lattice with many W/Re/C atoms beside empty voxels, a cool field and I0 lowered to 1e11 (at the default 5e13 every
+    chosen event of this lattice is a nucleation): diffusion moves (two changed sites, stale rows around both) are among
+    the events applied inside a sweep.  The oracle gives 4 diffusions, 6 nucleations and 18 attachments for these inputs,
+    3 of the diffusions on deferred steps and between different rows."""
     L = 192
     st, th, ph, T, df = _lattice(L, 11, 40000)
     T[:] = np.minimum(T, 1500.0)
@@ -114,5 +124,23 @@ def test_apply_in_sweep_diffusion_events():
     for k, n in enumerate((19, 9)):
         u_pick, u_def, u_np = _uniforms(30 + k, n, 2 * n + 2)
         calls.append((0 if k == 0 else 19, n, u_pick, u_def, u_np))
-    out = _compare(L, (st, th, ph, T, df), calls)
-    assert out[0][0] == 19
+    out = _compare(L, (st, th, ph, T, df), calls, tweak=FOUR_KIND_PARAMS)
+    assert out[0][0] == 19 and out[1][0] == 9
+    ev = np.concatenate(_events(out))
+    moved = ev[(ev["type"] == 1) & ((ev["pos"][:, 0] != ev["target"][:, 0]) | (ev["pos"][:, 1] != ev["target"][:, 1]))]
+    assert len(moved) >= 2, ev["type"]
+    kinds, diff_rows = _deferred_kinds(calls, out)
+    assert diff_rows >= 2, (kinds, diff_rows)
+
+
+@pytest.mark.parametrize("L", [256, 200])
+def test_apply_in_sweep_four_event_kinds(L):
+    """The batches of the offsets test plus one of 37 steps with I0 = 1e11: depositions, diffusions, nucleations and
+    attachments are all applied inside a sweep (the same inputs run against the oracle in
+    test_gpu_deferred_apply_vs_oracle.py, where the oracle's log gives at least 7 of each kind on deferred steps)."""
+    lat = _lattice(L, 17 + L, 6000)
+    calls = batch_calls(APPLY_IN_SWEEP_BATCHES + (37,))
+    out = _compare(L, lat, calls, tweak=FOUR_KIND_PARAMS)
+    assert all(o[0] == c[1] and o[1] == 0 for o, c in zip(out, calls))
+    kinds, diff_rows = _deferred_kinds(calls, out)
+    assert min(kinds) >= 3 and diff_rows >= 2, (kinds, diff_rows)
