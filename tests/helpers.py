@@ -266,6 +266,31 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
+def assert_fields_match_oracle(e, lat, rate_rtol, tag=""):
+    """The lattice the engine (or ensemble replica) ``e`` holds against the oracle lattice ``lat``: all five fields (theta
+    and phi by their bits, T with NaN == NaN, the defect mask) and the sweep of that lattice (counts, row counts, row sums,
+    total)."""
+    d = e.download(defects=True)
+    assert np.array_equal(d["state"], lat.state), (tag, "state", np.argwhere(d["state"] != lat.state)[:4])
+    assert np.array_equal(_bits(d["theta"]), _bits(lat.theta)), (tag, "theta")
+    assert np.array_equal(_bits(d["phi"]), _bits(lat.phi)), (tag, "phi")
+    assert np.array_equal(d["defects"], lat.defects), (tag, "defects")
+    assert np.array_equal(d["T"], lat.T, equal_nan=True), (tag, "T")
+    # sweep of the lattice the call left (state, rate table and interface sums as the batch's last apply kept them)
+    sw = lat.sweep()
+    total, n_events, n_dep = e.rate_sweep()
+    rsum, rcnt = e.row_sums()
+    assert (n_events, n_dep) == (sw["n_events"], sw["n_dep"]), (tag, n_events, n_dep, sw["n_events"], sw["n_dep"])
+    assert np.array_equal(rcnt, sw["rowcnt"]), (tag, "rowcnt", np.argwhere(rcnt != sw["rowcnt"])[:4])
+    fin = np.isfinite(sw["rowsum"])
+    assert np.array_equal(np.isfinite(rsum), fin), (tag, "row sum finiteness")
+    if fin.any():
+        err = relerr(rsum[fin], sw["rowsum"][fin])
+        assert err.max() <= rate_rtol, (tag, "rowsum", float(err.max()))
+    if np.isfinite(sw["total"]):
+        assert abs(total - sw["total"]) <= rate_rtol * abs(sw["total"]), (tag, total, sw["total"])
+
+
 def assert_call_matches_oracle(e, lat, rg, ro, rate_rtol, tag=""):
     """One run_steps call of the engine ``e`` (result rg) against the same call of the oracle lattice ``lat`` (result ro):
     stop state, stream positions, event log, totals, the downloaded fields and the row sums of the lattice the call left."""
@@ -286,22 +311,35 @@ def assert_call_matches_oracle(e, lat, rg, ro, rate_rtol, tag=""):
     if len(ro["totals"]):
         err = relerr(rg["totals"], ro["totals"])
         assert err.max() <= rate_rtol, (tag, "totals", int(err.argmax()), float(err.max()))
-    d = e.download(defects=True)
-    assert np.array_equal(d["state"], lat.state), (tag, "state", np.argwhere(d["state"] != lat.state)[:4])
-    assert np.array_equal(_bits(d["theta"]), _bits(lat.theta)), (tag, "theta")
-    assert np.array_equal(_bits(d["phi"]), _bits(lat.phi)), (tag, "phi")
-    assert np.array_equal(d["defects"], lat.defects), (tag, "defects")
-    assert np.array_equal(d["T"], lat.T, equal_nan=True), (tag, "T")
-    # sweep of the lattice the call left (state, rate table and interface sums as the batch's last apply kept them)
-    sw = lat.sweep()
-    total, n_events, n_dep = e.rate_sweep()
-    rsum, rcnt = e.row_sums()
-    assert (n_events, n_dep) == (sw["n_events"], sw["n_dep"]), (tag, n_events, n_dep, sw["n_events"], sw["n_dep"])
-    assert np.array_equal(rcnt, sw["rowcnt"]), (tag, "rowcnt", np.argwhere(rcnt != sw["rowcnt"])[:4])
-    fin = np.isfinite(sw["rowsum"])
-    assert np.array_equal(np.isfinite(rsum), fin), (tag, "row sum finiteness")
-    if fin.any():
-        err = relerr(rsum[fin], sw["rowsum"][fin])
-        assert err.max() <= rate_rtol, (tag, "rowsum", float(err.max()))
-    if np.isfinite(sw["total"]):
-        assert abs(total - sw["total"]) <= rate_rtol * abs(sw["total"]), (tag, total, sw["total"])
+    assert_fields_match_oracle(e, lat, rate_rtol, tag)
+
+
+def assert_ensemble_call_matches_oracle(ens, lats, res, oracle_results, rate_rtol, tag=""):
+    """One cetkmc.Ensemble.run call (result ``res``) against the same call of every replica's own oracle lattice:
+    ``oracle_results[r]`` is what lats[r].run_steps (rng_mode 0) or lats[r].run_supersteps(box == L) (rng_mode 2) returned,
+    or None for a replica that was frozen when the call began (its oracle lattice was not stepped: status 1, no steps).
+    Per replica: stop state, stream position (rng_mode 0), nucleation count, totals, the terminating total, the time
+    increments (rng_mode 2), the selection margin, then the fields and the sweep of the lattice the call left."""
+    assert len(lats) == len(oracle_results) == ens.R
+    for r, (lat, ro) in enumerate(zip(lats, oracle_results)):
+        t = f"{tag} replica {r}"
+        done, status = (0, 1) if ro is None else (ro["done"], ro["status"])
+        assert (int(res["done"][r]), int(res["status"][r])) == (done, status), (t, "done, status", res["done"][r], res["status"][r],
+                                                                                done, status)
+        if ro is not None and "np_used" in ro:
+            assert int(res["np_used"][r]) == ro["np_used"], (t, "np_used", res["np_used"][r], ro["np_used"])
+        assert int(res["nucleation_count"][r]) == lat.nuc_count, (t, "nucleation_count", res["nucleation_count"][r], lat.nuc_count)
+        if done:
+            err = relerr(res["totals"][r][:done], ro["totals"][:done])
+            assert err.max() <= rate_rtol, (t, "totals", int(err.argmax()), float(err.max()))
+        if ro is not None and status == 1:         # the total the termination branch saw: 0, below 1e-25 or not finite
+            got, want = float(res["totals"][r][done]), float(ro["totals"][done])
+            if np.isfinite(want):
+                assert relerr([got], [want])[0] <= rate_rtol, (t, "terminating total", got, want)
+            else:
+                assert np.array_equal(got, want, equal_nan=True), (t, "terminating total", got, want)
+        if ro is not None and "dt_event" in ro and done:
+            err = relerr(res["dt"][r][:done], ro["dt_event"][:done])
+            assert err.max() <= rate_rtol, (t, "dt", int(err.argmax()), float(err.max()))
+        assert 0.0 < res["min_margin"][r] <= 1.0, (t, "min_margin", res["min_margin"][r])
+        assert_fields_match_oracle(ens.replica(r), lat, rate_rtol, t)
