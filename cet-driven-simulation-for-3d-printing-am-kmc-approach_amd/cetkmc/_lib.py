@@ -89,7 +89,8 @@ class EnsArgs(C.Structure):
         ("step0", C.c_int64), ("n_steps", C.c_int64), ("defect_fraction", C.POINTER(C.c_double)),
         ("u_pick", C.POINTER(C.c_double)), ("u_defect", C.POINTER(C.c_double)), ("u_np", C.POINTER(C.c_double)),
         ("np_stride", C.c_int64), ("seed", C.POINTER(C.c_uint64)), ("rng_mode", C.c_int32), ("thermal_mode", C.c_int32),
-        ("thermal_dt", C.c_double),
+        ("thermal_dt", C.c_double), ("q_planes", C.POINTER(C.c_double)), ("n_q", C.c_int64), ("n_sets", C.c_int32),
+        ("q_set", C.POINTER(C.c_int32)), ("use_latent", C.c_int32),
     ]
 
 

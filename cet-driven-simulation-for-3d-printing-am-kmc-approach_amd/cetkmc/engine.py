@@ -457,10 +457,13 @@ class Ensemble:
             pass
 
     def run(self, step0, n, defect_fraction, u_pick=None, u_defect=None, u_np=None, rng_mode=0, seeds=None, thermal_mode=1,
-            thermal_dt=1e-6):
+            thermal_dt=1e-6, q_planes=None, q_set=None, use_latent=True):
         """n lockstep steps of every live replica from global step step0.  rng_mode 0: u_pick / u_defect (R, n) and
-        u_np (R, np_stride >= n * (L*L + 2)) from each replica's own generators; rng_mode 2: ``seeds`` (R,).  Returns
-        dict(done, status, np_used, nucleation_count, min_margin (R,), totals (R, n + 1), dt (R, n) (rng_mode 2), wall_ms)."""
+        u_np (R, np_stride >= n * (L*L + 2)) from each replica's own generators; rng_mode 2: ``seeds`` (R,).
+        thermal_mode 2 (laser source + latent heat): ``q_planes`` (n_sets, n_q, L, L), plane u of a set feeding the u-th
+        temperature update of the call (None when the call holds no update); ``q_set`` (R,) names the set of each replica
+        (None: set r for replica r, n_sets == R).  Returns dict(done, status, np_used, q_used, nucleation_count,
+        min_margin (R,), totals (R, n + 1), dt (R, n) (rng_mode 2), wall_ms)."""
         R, n = self.R, int(n)
         df = np.ascontiguousarray(np.broadcast_to(np.asarray(defect_fraction, dtype=np.float64), (R,)))
         a = EnsArgs()
@@ -477,12 +480,23 @@ class Ensemble:
             a.seed = sd.ctypes.data_as(C.POINTER(C.c_uint64))
             keep.append(sd)
         a.rng_mode, a.thermal_mode, a.thermal_dt = int(rng_mode), int(thermal_mode), float(thermal_dt)
+        if int(thermal_mode) == 2:
+            qs = None if q_set is None else np.ascontiguousarray(np.asarray(q_set, dtype=np.int32).reshape(R))
+            if q_planes is None:
+                q, a.n_q, a.n_sets = None, 0, (R if qs is None else int(qs.max()) + 1)
+            else:
+                q = np.ascontiguousarray(q_planes, dtype=np.float64)
+                assert q.ndim == 4 and q.shape[2:] == (self.L, self.L), q.shape
+                a.n_sets, a.n_q = q.shape[0], q.shape[1]
+            a.q_planes, a.use_latent = _dptr(q), int(bool(use_latent))
+            a.q_set = None if qs is None else qs.ctypes.data_as(C.POINTER(C.c_int32))
+            keep += [q, qs]
         res = (RunResult * R)()
         totals = np.zeros((R, n + 1), np.float64)
         dt = np.zeros((R, max(n, 1)), np.float64)
         self._ck(self.lib.cetkmc_run_ensemble(self.h, C.byref(a), res, _ptr(totals), _ptr(dt) if rng_mode == 2 else None))
         return dict(done=np.array([x.steps_done for x in res], np.int64), status=np.array([x.status for x in res], np.int32),
-                    np_used=np.array([x.np_used for x in res], np.int64),
+                    np_used=np.array([x.np_used for x in res], np.int64), q_used=np.array([x.q_used for x in res], np.int64),
                     nucleation_count=np.array([x.nucleation_count for x in res], np.int64),
                     min_margin=np.array([x.min_margin for x in res], np.float64), totals=totals, dt=dt[:, :n],
                     wall_ms=float(res[0].wall_ms) if R else 0.0)

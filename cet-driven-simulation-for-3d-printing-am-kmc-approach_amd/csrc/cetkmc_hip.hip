@@ -1083,6 +1083,8 @@ struct Ens {
     cetkmc_event* d_log_event = nullptr;
     int64_t* d_log_nev = nullptr;
     size_t cap_pick = 0, cap_defect = 0, cap_np = 0, cap_total = 0, cap_event = 0, cap_nev = 0;
+    double* d_q = nullptr;               // thermal_mode 2: [n_sets][updates of the call][L*L] source planes of the call
+    size_t cap_q = 0;
     StepState* d_ss_out = nullptr;
     int* d_n_out = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1112,7 +1114,7 @@ void destroy_ens(Ens* e)
         (void)hipSetDevice(e->reps[0]->dev);
         (void)hipStreamSynchronize(e->reps[0]->stream);
     }
-    void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev,
+    void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
                     e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -2358,8 +2360,21 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (a->rng_mode != 0 && a->rng_mode != 2) return fail("ensembles run rng_mode 0 (reference streams) or 2 (all counter based)");
-    if (a->thermal_mode != 0 && a->thermal_mode != 1) return fail("ensembles run thermal_mode 0 or 1 (no laser source)");
+    if (a->thermal_mode < 0 || a->thermal_mode > 2) return fail("thermal_mode must be 0 (none), 1 (diffusion) or 2 (laser source)");
     if (!a->defect_fraction) return fail("defect_fraction[R] required");
+    // temperature updates of the call: the cadence is shared, so every replica's u-th update is the same global step
+    int64_t n_therm = 0;
+    if (a->thermal_mode) for (int64_t s = 0; s < n; ++s) n_therm += (a->step0 + s) % 20 == 0;
+    const bool laser = a->thermal_mode == 2;
+    if (laser) {       // everything about the plane sets is checked before anything is copied or launched
+        if (a->n_q < n_therm) return fail("thermal_mode 2 needs one q plane per temperature update of the call in every plane set (n_q too small)");
+        if (n_therm > 0 && !a->q_planes) return fail("thermal_mode 2: q_planes[n_sets][n_q][L*L] required (the call holds a temperature update)");
+        if (!a->q_set && a->n_sets != R) return fail("thermal_mode 2: q_set NULL means plane set r for replica r, so n_sets must equal R");
+        if (a->n_sets < 1) return fail("thermal_mode 2: n_sets must be >= 1");
+        if (a->q_set)
+            for (int r = 0; r < R; ++r)
+                if (a->q_set[r] < 0 || a->q_set[r] >= a->n_sets) return fail("thermal_mode 2: q_set[" + std::to_string(r) + "] is outside [0, n_sets)");
+    }
     bool any_defect = false;
     for (int r = 0; r < R; ++r) any_defect |= a->defect_fraction[r] > 0.0;
     const int64_t per_step = (int64_t)L * L + 2;         // at most L^2 deposition candidates + two orientation draws
@@ -2397,6 +2412,12 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
             HIPCHK(hipMemcpyAsync(e->d_u_defect, a->u_defect, (size_t)R * n * 8, hipMemcpyHostToDevice, st));
         }
     }
+    const size_t L2 = (size_t)L * L;
+    if (laser && n_therm > 0) {      // the first n_therm planes of every set, once per call: [n_sets][n_therm][L*L] on the device
+        CHK(grow(&e->d_q, &e->cap_q, (size_t)a->n_sets * (size_t)n_therm * L2));
+        HIPCHK(hipMemcpy2DAsync(e->d_q, (size_t)n_therm * L2 * 8, a->q_planes, (size_t)a->n_q * L2 * 8, (size_t)n_therm * L2 * 8,
+                                (size_t)a->n_sets, hipMemcpyHostToDevice, st));
+    }
     for (int r = 0; r < R; ++r)      // a new lattice uploaded into a terminated replica steps again
         if (e->reps[(size_t)r]->state_uploads != e->uploads_seen[(size_t)r]) {
             e->frozen[(size_t)r] = 0;
@@ -2421,6 +2442,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         t.u_np = streams ? e->d_u_np + (size_t)r * stride : nullptr;
         t.log_total = e->d_log_total + (size_t)r * nn; t.log_event = e->d_log_event + (size_t)r * nn; t.log_nev = e->d_log_nev + (size_t)r * nn;
         t.active = e->frozen[(size_t)r] ? 0 : 1;
+        t.q = (laser && n_therm > 0) ? e->d_q + (size_t)(a->q_set ? a->q_set[r] : r) * (size_t)n_therm * L2 : nullptr;
     }
     HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)R * sizeof(EnsRep), hipMemcpyHostToDevice, st));
     // launch shapes: those of the single-lattice path (launch_sweep / launch_table / launch_interface / launch_thermal)
@@ -2440,8 +2462,10 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const KParams kp0 = h0->kp;
     const double K0 = host_k_eff(h0->p, 0, 0);
     const SlabView v0{};
-    const ThermalCfg tc0 = thermal_cfg(h0, a->thermal_dt, 0, 0, 1);
+    const int latent = laser && a->use_latent ? 1 : 0;
+    const ThermalCfg tc0 = thermal_cfg(h0, a->thermal_dt, laser ? 1 : 0, latent, 1);
     const BatchCfg cfg0{};
+    const dim3 g_flags((unsigned)std::min<int64_t>(((int64_t)(L + 4) * L + 255) / 256, 64), (unsigned)R);
     EnsSel sel{e->d_table, 0, nz};
     auto table_and_interface = [&]() {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rate_table<EnsSel>), g_table, dim3(256), 0, st, kp0, v0, K0, (const StepState*)nullptr, sel);
@@ -2459,7 +2483,10 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_thermal_march<EnsSel>), g_therm, dim3(256), 0, st, v0, (const double*)nullptr,
                                (double*)nullptr, (uint8_t*)nullptr, (const double*)nullptr, tc0, (const StepState*)nullptr, sel);
+            // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
+            if (latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
             sel.rel ^= 1;
+            sel.q_off += laser ? (int64_t)L2 : 0;
             ++flips;
             table_and_interface();
         }
@@ -2477,6 +2504,8 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     HIPCHK(hipGetLastError());
     std::vector<StepState> ss((size_t)R);
     std::vector<int> list_len((size_t)R);
+    std::vector<uint8_t> t_active((size_t)R);           // stepped by this call (not frozen when it began)
+    for (int r = 0; r < R; ++r) t_active[(size_t)r] = e->frozen[(size_t)r] ? 0 : 1;
     std::vector<double> tot(n > 0 ? (size_t)R * n : 0);
     HIPCHK(hipMemcpyAsync(ss.data(), e->d_ss_out, (size_t)R * sizeof(StepState), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(list_len.data(), e->d_n_out, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2498,6 +2527,12 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         cetkmc_run_result& o = res[r];
         o = cetkmc_run_result{};
         o.steps_done = q.cur; o.status = q.status; o.np_used = a->rng_mode == 0 ? q.np_pos : 0;
+        if (laser && t_active[(size_t)r]) {
+            // planes consumed, as on a single handle: the updates of the executed steps and of the step the replica stopped
+            // in (its update precedes the selection that noticed the stop); later updates were pass-throughs
+            if (q.status == 0) o.q_used = n_therm;
+            else for (int64_t s = 0; s <= q.cur && s < n; ++s) o.q_used += (a->step0 + s) % 20 == 0;
+        }
         o.nucleation_count = q.nuc_count; o.min_margin = q.min_margin; o.wall_ms = ms; o.full_sweeps = q.cur;
         const int64_t done = q.cur;
         if (totals) {

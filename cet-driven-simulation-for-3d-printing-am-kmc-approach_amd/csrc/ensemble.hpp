@@ -1,7 +1,7 @@
 // ensemble.hpp -- replica ensembles: R independent lattices of the same L stepped by the same launches.
 //
 // Every kernel of a Mode A step at L <= 128 (k_batch_reset, k_thermal_march, k_rate_table, k_interface, k_sweep_plane,
-// k_select_apply) has an instantiation with a trailing EnsSel argument (kernels.hpp).  It takes the replica index from a
+// k_select_apply) has an instantiation with a trailing EnsSel argument (kernels.hpp); k_clear_row_flags has its twin here.  It takes the replica index from a
 // grid dimension the single-lattice kernel leaves free and reads everything that belongs to one lattice -- its slab view of
 // either temperature buffer, rate constants, step state, block sums, random streams and logs -- from the replica's EnsRep.
 // Replicas never interact: each keeps the trajectory a single handle would have produced.
@@ -27,6 +27,8 @@ struct EnsRep {
     cetkmc_event* log_event;
     int64_t* log_nev;
     int active;                 // 0: terminated in an earlier call -- the batch reset keeps it terminated (frozen)
+    const double* q;            // thermal_mode 2: the replica's set of source planes [updates of the call][L*L] (shared by the
+                                // replicas of one scan); null in the other modes, where no kernel reads a plane
 };
 
 struct EnsSel {
@@ -35,6 +37,7 @@ struct EnsSel {
     int nz;                     // k_thermal_march: plane groups per replica (the replica is folded into blockIdx.z)
     int64_t stride;             // analysis kernels (cluster.hpp): entries per replica of the label / parent arrays (L^3)
     const long long* offs;      // analysis kernels: per-replica offsets into a concatenated array (cluster stats, scatter list)
+    int64_t q_off;              // k_thermal_march, laser mode: offset of the current update's plane in every plane set (u * L*L)
 };
 
 // end of a call: every replica's step state and interface-list length into contiguous arrays (one copy to the host)
@@ -45,6 +48,17 @@ __global__ void k_ens_collect(const EnsRep* __restrict__ reps, int R, StepState*
         ss_out[r] = *reps[r].ss;
         ifc_n_out[r] = *reps[r].view[0].ifc_n;
     }
+}
+
+// k_clear_row_flags of every replica (y) behind a latent-heat temperature update: prev_state equals state again.  Not in a
+// replica that has terminated or is frozen -- its update was a pass-through that left prev_state and the flags alone.
+__global__ void k_ens_clear_row_flags(const EnsRep* __restrict__ reps)
+{
+    const EnsRep& e = reps[blockIdx.y];
+    if (e.ss->status) return;
+    const SlabView& S = e.view[0];
+    const int64_t n = (int64_t)(S.nloc + 4) * S.L;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) S.row_chg[q] = 0;
 }
 
 // Cluster numbering of every replica without a host sort: a component's root is its first voxel in row-major order

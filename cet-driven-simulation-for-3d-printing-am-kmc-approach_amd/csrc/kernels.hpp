@@ -42,6 +42,7 @@ template <class S> __device__ __forceinline__ int ens_rel(const S& sel) { return
 template <class S> __device__ __forceinline__ unsigned ens_nz(const S& sel) { return (unsigned)sel.nz; }
 template <class S> __device__ __forceinline__ int64_t ens_stride(const S& sel) { return sel.stride; }
 template <class S> __device__ __forceinline__ const long long* ens_offs(const S& sel) { return sel.offs; }
+template <class S> __device__ __forceinline__ int64_t ens_q_off(const S& sel) { return sel.q_off; }
 // the rate constants a kernel reads: its KParams argument, or (ensemble) replica r's copy in the device table -- by
 // reference, so that the atom-type-indexed E_b / E_diff stay plain loads (a modified by-value copy would go to scratch)
 struct KParams;
@@ -2298,6 +2299,7 @@ __global__ __launch_bounds__(256) void k_thermal_march(SlabView S, const double*
         const auto& e = ens_rep(r, ens...);
         const int rel = ens_rel(ens...);
         S = e.view[rel]; Tin = e.view[rel].T; Tout = e.view[rel ^ 1].T; prev_state = e.prev; ss = e.ss;
+        q_top = e.q + ens_q_off(ens...);        // laser mode: this update's plane of the replica's plane set
     }
     constexpr int TJ = THERM_TJ, KT = THERM_KT, LW = KT + 2;
     __shared__ double tile[(TJ + 2) * LW];

@@ -8,11 +8,18 @@ collects the CET classification of the last metrics row of every run into ``outp
 
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
                        [--mode B --box 8] [--seeds K] [--ensemble [--rng counter]]
+                       [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]]
 
 ``--seeds K`` runs every point with the seeds RANDOM_SEED .. RANDOM_SEED + K - 1 (one gv_map.csv row per point and seed, with
 a ``seed`` column when K > 1); ``--ensemble`` runs all of them as one replica ensemble (run_kmc_ensemble): with the default
 ``--rng reference`` it writes the files of the sequential run, ``--rng counter`` runs every point like ``--mode B --box L``
 with the super-step thermal cadence.
+
+``--laser-power`` and ``--scan-speed`` (both or neither) add two axes to the map: every point runs with run_kmc's ``laser``
+option (a Gaussian beam of that power [W] moving by that many voxels per temperature update from ``--laser-start``), the
+run directories carry ``_P<power>_S<speed>`` and gv_map.csv gains the columns ``power`` and ``speed``.  The seeds of one
+point share the beam, so in an ensemble they share its source planes on the device.  Without the two flags the files are
+what they were.
 """
 import argparse
 import os
@@ -23,8 +30,12 @@ from constants import ATOMIC_SPACING_W, DEFECT_PROB, N_SEEDS, RANDOM_SEED, T_MEL
 from kmc_simulation import run_kmc, run_kmc_ensemble
 
 
-def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw):
+def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers=None, scan_speeds=None):
     """Driver arguments, checked before any device call."""
+    if bool(laser_powers) != bool(scan_speeds):
+        raise ValueError("--laser-power and --scan-speed come together (at least one value each)")
+    if laser_powers and run_kw.get("mode", "A") != "A":
+        raise ValueError("the laser axes need mode A (run_kmc refuses laser with mode B)")
     if rng not in ("reference", "counter"):
         raise ValueError("rng must be 'reference' or 'counter'")
     if int(seeds) < 1:
@@ -42,31 +53,39 @@ def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw):
 
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
-             **run_kw):
+             laser_powers=None, scan_speeds=None, laser_start=0.0, **run_kw):
     """``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
     engine (same metrics.csv columns; n_steps stays the number of executed events).  ``seeds=K`` runs every point with the
-    seeds RANDOM_SEED .. RANDOM_SEED + K - 1; ``ensemble=True`` runs all runs of the map as one replica ensemble."""
-    check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw)
+    seeds RANDOM_SEED .. RANDOM_SEED + K - 1; ``ensemble=True`` runs all runs of the map as one replica ensemble.
+    ``laser_powers`` / ``scan_speeds`` (both or neither): two more axes, every point with run_kmc's ``laser`` option."""
+    check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers, scan_speeds)
     seeds = int(seeds)
+    beams = [(p, v) for p in laser_powers for v in scan_speeds] if laser_powers else [None]
     runs = []
     for T_sub in temps:
         for nu_dep in nu_deps:
-            for s in range(seeds):
-                prefix = f"gv_sweep/T{int(T_sub)}_V{nu_dep:.0e}_c_{int(carbon * 100)}" + (f"_seed{RANDOM_SEED + s}" if seeds > 1 else "")
-                runs.append((T_sub, nu_dep, RANDOM_SEED + s, prefix))
+            for beam in beams:
+                for s in range(seeds):
+                    prefix = f"gv_sweep/T{int(T_sub)}_V{nu_dep:.0e}" + (f"_P{beam[0]:g}_S{beam[1]:g}" if beam else "") + \
+                             f"_c_{int(carbon * 100)}" + (f"_seed{RANDOM_SEED + s}" if seeds > 1 else "")
+                    runs.append((T_sub, nu_dep, RANDOM_SEED + s, prefix, beam))
     cfg = [dict(temp=T_sub, defect_fraction=defect_fraction, n_seeds=n_seeds, impurity_c=carbon, output_prefix=prefix,
-                nu_dep=nu_dep, **({"seed": seed} if seeds > 1 else {})) for T_sub, nu_dep, seed, prefix in runs]
+                nu_dep=nu_dep, **({"seed": seed} if seeds > 1 else {}),
+                **({"laser": dict(power=float(beam[0]), start=float(laser_start), speed=float(beam[1]))} if beam else {}))
+           for T_sub, nu_dep, seed, prefix, beam in runs]
     if ensemble:
         run_kmc_ensemble(cfg, L, n_steps, rng=rng)
     else:
         for c in cfg:
             run_kmc(L=L, n_steps=n_steps, **c, **run_kw)
     rows = []
-    for T_sub, nu_dep, seed, prefix in runs:
+    for T_sub, nu_dep, seed, prefix, beam in runs:
         last = pd.read_csv(f"outputs/{prefix}/metrics.csv").iloc[-1]
         G = (T_MELT - T_sub) / (L * VOXEL_SIZE)                 # gradient of the initial ramp of this run
         V = nu_dep * ATOMIC_SPACING_W
         row = {"T_sub": T_sub, "nu_dep": nu_dep}
+        if beam:
+            row.update(power=beam[0], speed=beam[1])
         if seeds > 1:
             row["seed"] = seed
         row.update({"G_K_per_m": G, "V_m_per_s": V, "G_over_V": G / V,
@@ -93,7 +112,11 @@ if __name__ == "__main__":
     ap.add_argument("--ensemble", action="store_true", help="run the whole map as one replica ensemble")
     ap.add_argument("--rng", choices=("reference", "counter"), default="reference",
                     help="--ensemble: reference streams (= the sequential run's files) or counter uniforms (= --mode B --box L)")
+    floats = lambda s: tuple(float(x) for x in s.split(",") if x)       # noqa: E731
+    ap.add_argument("--laser-power", type=floats, default=None, help="P1,P2,... [W]: laser axis of the map (with --scan-speed)")
+    ap.add_argument("--scan-speed", type=floats, default=None, help="V1,V2,... [voxels per temperature update]")
+    ap.add_argument("--laser-start", type=float, default=0.0, help="beam centre at the first temperature update [voxels]")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
-                   **kw).to_string(index=False))
+                   laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, **kw).to_string(index=False))

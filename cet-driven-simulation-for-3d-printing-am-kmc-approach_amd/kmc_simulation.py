@@ -33,6 +33,7 @@ from lattice_init import initialize_lattice
 from metrics import (compute_CET, compute_metrics, compute_metrics_device, compute_metrics_from_clusters,  # noqa: F401
                      detect_CET_transition)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
+from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
 
 # What the last run_kmc call observed besides its return tuple (the reference's signature has no room for it):
@@ -48,9 +49,25 @@ THERMAL_DT = 1e-6           # kmc_simulation.py:250
 _MAX_STREAM_DOUBLES = 1 << 25   # host staging cap for the pre-drawn NumPy stream (256 MiB)
 
 
-def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, incremental=True, thermal_mode=1):
+LASER_KEYS = ("power", "start", "speed", "beam_radius", "absorptivity", "latent")
+
+
+def _check_laser(laser, where="laser"):
+    """A laser scan description (thermal_solver.laser_scan_planes): dict with power, start, speed and optionally
+    beam_radius, absorptivity, latent.  Returns a copy."""
+    if not isinstance(laser, dict):
+        raise ValueError(f"{where} must be a dict with keys power, start, speed[, beam_radius, absorptivity, latent]")
+    bad, missing = set(laser) - set(LASER_KEYS), {"power", "start", "speed"} - set(laser)
+    if bad or missing:
+        raise ValueError(f"{where}: unknown keys {sorted(bad)}, missing keys {sorted(missing)} (allowed: {', '.join(LASER_KEYS)})")
+    return dict(laser)
+
+
+def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, incremental=True, thermal_mode=1, laser=None):
     """Run steps first..last (inclusive) on the device.  Returns (steps_done, terminated,
-    last_total, dt_sum_increments) with both host generators left where the reference's would be."""
+    last_total, dt_sum_increments) with both host generators left where the reference's would be.
+    ``laser``: the temperature updates are thermal_mode 2 with the scan's source planes of each batch (a plane depends on
+    the global step only, so a batch continued from a status-2 stop is handed the plane of its first step again)."""
     dts = []
     _advance_to.min_margin = 1.0
     step = first
@@ -74,9 +91,11 @@ def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, inc
         draws = np.array([random.random() for _ in range(per * n)], dtype=np.float64).reshape(n, per)
         np_state = np.random.get_state()
         u_np = np.random.random(n * per_step)
+        q = laser_scan_planes(L, laser, step, n) if laser is not None else None
         res = engine.run_steps(step, n, defect_fraction, draws[:, 0], draws[:, 1] if per == 3 else None, u_np,
-                               rng_mode=rng_mode, seed=seed, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT,
-                               incremental=incremental)
+                               rng_mode=rng_mode, seed=seed, thermal_mode=2 if laser is not None else thermal_mode,
+                               thermal_dt=THERMAL_DT, incremental=incremental, q_planes=q if q is not None and len(q) else None,
+                               use_latent=bool(laser.get("latent", True)) if laser is not None else True)
         done = res["done"]
         _advance_to.min_margin = min(_advance_to.min_margin, res["min_margin"])
         # rewind both generators to what the executed steps consumed
@@ -201,6 +220,7 @@ def run_kmc(
     seed: int = None,
     metrics_every: int = METRIC_UPDATE_STEP,
     thermal_updates: bool = True,
+    laser: dict = None,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -229,10 +249,26 @@ def run_kmc(
     ``thermal_cadence="events"`` (default) keeps the reference's cadence of one temperature update per 20 executed events
     (kmc_simulation.py:248-250): before every super-step the field is brought to ``executed // 20 + 1`` updates;
     ``"supersteps"`` updates once per 20 super-steps inside the engine (throughput setting for large lattices: the
-    temperature history per executed event then differs from the reference's)."""
+    temperature history per executed event then differs from the reference's).
+
+    ``laser`` (mode "A"): every temperature update is the laser update of thermal_solver.update_temperature -- a moving
+    Gaussian source on plane L-1 and, with ``latent`` (default on), latent heat where a voxel solidified since the previous
+    update -- instead of update_temperature_cet.  A dict ``power``, ``start`` (beam centre at update 0, voxels), ``speed``
+    (voxels per update) and optionally ``beam_radius``, ``absorptivity``, ``latent`` (thermal_solver.laser_scan_planes).
+    prev_state lives on the device: the initial upload snapshots it and every update brings it level with state.
+    Refused with ValueError: ``laser`` with ``mode="B"``; with ``checkpoint_every`` / ``resume_from`` (a checkpoint does not
+    carry prev_state); with ``thermal_updates=False``."""
     import cetkmc
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
+    if laser is not None:
+        laser = _check_laser(laser)
+        if mode != "A":
+            raise ValueError("laser needs mode 'A' (the super-step engine has no laser option here)")
+        if checkpoint_every or resume_from:
+            raise ValueError("laser cannot be combined with checkpoint_every / resume_from (a checkpoint does not carry prev_state)")
+        if not thermal_updates:
+            raise ValueError("laser needs thermal_updates=True (the source acts through the temperature update)")
     if thermal_cadence not in ("events", "supersteps"):
         raise ValueError("thermal_cadence must be 'events' or 'supersteps'")
     run_seed = RANDOM_SEED if seed is None else int(seed)
@@ -300,7 +336,7 @@ def run_kmc(
         if checkpoint_every > 0:      # also stop right before every checkpoint boundary
             stop = min(stop, (next_step // checkpoint_every + 1) * checkpoint_every - 1)
         done, terminated, last_total, dts = _advance_to(engine, next_step, stop, L, defect_fraction, incremental=incremental,
-                                                         thermal_mode=1 if thermal_updates else 0)
+                                                         thermal_mode=1 if thermal_updates else 0, laser=laser)
         for dt in dts:
             total_time += dt
         min_margin = min(min_margin, _advance_to.min_margin)
@@ -402,14 +438,15 @@ def run_kmc(
 
 # ---- replica ensembles: many independent runs in the same launches -----------------------------
 _C_SITE = 3                 # carbon state (defects.py: only carbon sites can become defects)
-ENSEMBLE_KEYS = ("temp", "defect_fraction", "n_seeds", "impurity_c", "output_prefix", "nu_dep", "seed")
-_RUN_DEFAULTS = dict(temp=T_SUB, defect_fraction=0.0, n_seeds=5, impurity_c=0.0, output_prefix="cet_run", nu_dep=None, seed=None)
+ENSEMBLE_KEYS = ("temp", "defect_fraction", "n_seeds", "impurity_c", "output_prefix", "nu_dep", "seed", "laser")
+_RUN_DEFAULTS = dict(temp=T_SUB, defect_fraction=0.0, n_seeds=5, impurity_c=0.0, output_prefix="cet_run", nu_dep=None, seed=None,
+                     laser=None)
 # per-replica generators and counters of the last run_kmc_ensemble call (the return tuples have no room for them):
 # random_state / np_state (where run_kmc would have left the global generators), executed_events, min_margin
 last_ensemble_info = []
 
 
-def _ensemble_configs(configs, L, n_steps, rng, metrics_every):
+def _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates=True):
     """Argument validation of run_kmc_ensemble (before any device call); returns the completed per-replica configs."""
     if rng not in ("reference", "counter"):
         raise ValueError("rng must be 'reference' (run_kmc's exact loop) or 'counter' (run_kmc mode 'B', box = L)")
@@ -431,7 +468,18 @@ def _ensemble_configs(configs, L, n_steps, rng, metrics_every):
         d = dict(_RUN_DEFAULTS, **c)
         if not (float(d["defect_fraction"]) >= 0.0):
             raise ValueError(f"configs[{i}]: defect_fraction must be >= 0")
+        if d["laser"] is not None:
+            d["laser"] = _check_laser(d["laser"], f"configs[{i}]['laser']")
         out.append(d)
+    lasers = [d["laser"] is not None for d in out]
+    if any(lasers):
+        # the thermal mode belongs to the call, and a laser of zero power does not give the bits of the diffusion-only update
+        if not all(lasers):
+            raise ValueError("either every config has a laser or none has (the thermal mode is shared by the ensemble)")
+        if not thermal_updates:
+            raise ValueError("laser needs thermal_updates=True (the source acts through the temperature update)")
+        if len({bool(d["laser"].get("latent", True)) for d in out}) != 1:
+            raise ValueError("the lasers' 'latent' setting must be the same in every config (it is shared by the ensemble)")
     if rng == "reference" and len(out) * (int(L) * int(L) + 2) > _MAX_STREAM_DOUBLES:
         raise ValueError(f"rng='reference': R * (L*L + 2) must stay within {_MAX_STREAM_DOUBLES} pre-drawn doubles per step "
                          "(split the ensemble)")
@@ -475,7 +523,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
-    output_prefix, nu_dep, seed).  Returns one run_kmc return tuple per replica and writes each replica's
+    output_prefix, nu_dep, seed, laser).  ``laser`` (run_kmc's laser dict): either every config has one or none has, with
+    the same ``latent`` setting; configs with equal dicts share one set of source planes on the device.  Returns one run_kmc return tuple per replica and writes each replica's
     ``outputs/<prefix>/metrics.csv`` and ``metrics_<tag>.csv``.
 
     ``rng="reference"``: replica r equals ``run_kmc(L=L, n_steps=n_steps, **configs[r])`` bit for bit (arrays, total_time,
@@ -484,7 +533,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     **configs[r])`` -- all-counter uniforms, the host draws nothing per step.  The caller's global generator states are
     restored on return.  One completion line is printed per replica (no per-row progress)."""
     import cetkmc
-    cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every)
+    cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
     caller_py, caller_np = random.getstate(), np.random.get_state()
     ens = None
@@ -520,6 +569,21 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         metrics = [[] for _ in range(R)]
         cet = [False] * R
         thermal_mode = 1 if thermal_updates else 0
+        # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
+        scans, q_set, use_latent = [], None, True
+        if cfgs[0]["laser"] is not None:
+            thermal_mode, q_set = 2, np.zeros(R, np.int32)
+            use_latent = bool(cfgs[0]["laser"].get("latent", True))
+            for r, c in enumerate(cfgs):
+                if c["laser"] not in scans:
+                    scans.append(c["laser"])
+                q_set[r] = scans.index(c["laser"])
+
+        def laser_kw(s0, n):
+            if not scans:
+                return {}
+            q = np.stack([laser_scan_planes(L, z, s0, n) for z in scans])
+            return dict(q_planes=q if q.shape[1] else None, q_set=q_set, use_latent=use_latent)
         cap = _MAX_STREAM_DOUBLES // (R * per_step) if rng == "reference" else 4096
         next_step = 0
         while next_step < n_steps and any(alive):
@@ -547,9 +611,11 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                         u_pick[r] = draws[r][:, 0]
                         if per[r] == 3:
                             u_def[r] = draws[r][:, 1]
-                    res = ens.run(s0, n, df, u_pick, u_def, u_np, rng_mode=0, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT)
+                    res = ens.run(s0, n, df, u_pick, u_def, u_np, rng_mode=0, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT,
+                                  **laser_kw(s0, n))
                 else:
-                    res = ens.run(s0, n, df, rng_mode=2, seeds=seeds, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT)
+                    res = ens.run(s0, n, df, rng_mode=2, seeds=seeds, thermal_mode=thermal_mode, thermal_dt=THERMAL_DT,
+                                  **laser_kw(s0, n))
                 for r in range(R):
                     if not alive[r]:
                         continue

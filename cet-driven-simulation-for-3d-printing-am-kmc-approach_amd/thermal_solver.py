@@ -76,6 +76,28 @@ def laser_source_plane(L, laser_pos, laser_power, beam_radius=DEFAULT_BEAM_RADIU
     return surface / VOXEL_SIZE
 
 
+SCAN_EVERY = 20      # run_kmc's temperature update cadence (kmc_simulation.py:248)
+
+
+def laser_scan_planes(L, laser, first_step, n_steps):
+    """Source planes (n, L, L) of the temperature updates that fall in the global steps [first_step, first_step + n_steps):
+    one per step g with g % 20 == 0, in step order.  ``laser`` is a dict: ``power`` [W], ``start`` (beam centre at update
+    0, in voxels), ``speed`` (voxels per update), optional ``beam_radius`` / ``absorptivity`` (this module's defaults) and
+    ``latent`` (read by the stepping loops, not here).  The beam centre of update u = g // 20 is start + speed * u, so a
+    plane depends on the global step alone: adjacent ranges concatenate, and a batch that starts again at the same step
+    gets the same plane again."""
+    first_step, n_steps = int(first_step), int(n_steps)
+    u0 = -(-first_step // SCAN_EVERY)                               # first update at or after first_step
+    u1 = -(-(first_step + max(n_steps, 0)) // SCAN_EVERY)           # first update at or after the end
+    out = np.zeros((max(u1 - u0, 0), L, L), dtype=np.float64)
+    start, speed = float(laser["start"]), float(laser["speed"])
+    for x, u in enumerate(range(u0, u1)):
+        c = start + speed * u
+        out[x] = laser_source_plane(L, (c, c), laser["power"], laser.get("beam_radius", DEFAULT_BEAM_RADIUS),
+                                    laser.get("absorptivity", DEFAULT_ABSORPTIVITY))
+    return out
+
+
 def update_temperature(T, state, prev_state, dt, laser_pos, laser_power,
                        beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY):
     """Explicit Euler step with Laplacian + Gaussian surface source on i=L-1 + latent heat where

@@ -345,15 +345,24 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
 
 /* Replica ensembles: R independent lattices of the same edge L (1 <= L <= 128) on one GPU, each
  * with its own parameters, fields, defect mask, random streams and step state, advanced one Mode A step per launch
- * sequence.  Every replica follows exactly the trajectory a single handle would (full sweep every step; thermal_mode 0
- * or 1, the update every 20 global steps shared by all replicas).  A replica whose step ends in the termination branch
- * (status 1) freezes: later calls leave it as it is and report it with status 1 and no steps.
+ * sequence.  Every replica follows exactly the trajectory a single handle would (full sweep every step; thermal_mode 0,
+ * 1 or 2, the update every 20 global steps shared by all replicas).  A replica whose step ends in the termination branch
+ * (status 1) freezes: later calls leave it as it is (fields, prev_state) and report it with status 1 and no steps.
  * res[r].full_sweeps = the replica's executed steps.
+ *
+ * thermal_mode 2 (laser source on plane L-1, latent heat with use_latent, as in cetkmc_run_args): the source planes come
+ * in n_sets plane sets of n_q planes each, q_planes[n_sets][n_q][L*L] in host memory, copied to the device once per call.
+ * Replica r reads set q_set[r] (q_set NULL: set r, and n_sets must equal R); replicas that share a scan share a set.  The
+ * u-th temperature update of the call (the u-th global step g of the call with g % 20 == 0) reads plane u of every set.
+ * A call is refused before anything is launched when n_q is smaller than its number of updates, when q_planes is NULL
+ * with an update due, when q_set is NULL and n_sets != R, or when a q_set entry lies outside [0, n_sets).  res[r].q_used:
+ * as on a single handle, the planes consumed by the replica's executed steps including the step it stopped in; 0 for a
+ * replica that was frozen when the call began.
  *
  * cetkmc_create_ensemble: p[R] (one parameter set per replica).  The returned handle addresses replica 0 in the
  * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
  * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
- * thermal_cet, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*) except the
+ * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*) except the
  * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
  * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
  * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
@@ -371,8 +380,13 @@ typedef struct cetkmc_ens_args {
     int64_t np_stride;              /* rng_mode 0: >= n_steps * (L*L + 2), the worst case -- no replica can run short */
     const uint64_t* seed;           /* [R]            rng_mode 2 */
     int32_t rng_mode;               /* 0 (reference streams) or 2 (all counter based) */
-    int32_t thermal_mode;           /* 0 or 1 */
+    int32_t thermal_mode;           /* 0, 1 or 2 */
     double thermal_dt;
+    const double* q_planes;         /* [n_sets][n_q][L*L] thermal_mode 2, host memory */
+    int64_t n_q;                    /* planes per set */
+    int32_t n_sets;
+    const int32_t* q_set;           /* [R] plane set of each replica; NULL: set r for replica r (n_sets == R) */
+    int32_t use_latent;             /* thermal_mode 2 */
 } cetkmc_ens_args;
 
 int cetkmc_create_ensemble(const cetkmc_params* p, int L, int R, int device_id, void** handle);
