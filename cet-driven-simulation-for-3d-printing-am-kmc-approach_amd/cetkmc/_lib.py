@@ -101,9 +101,17 @@ class EnsAnalysis(C.Structure):
     ]
 
 
+class FrontStats(C.Structure):
+    _fields_ = [
+        ("n_front", C.c_int64), ("n_skipped", C.c_int64), ("pos_sum", C.c_int64 * 3), ("G_sum", C.c_double),
+        ("G_min", C.c_double), ("G_max", C.c_double), ("Gi_sum", C.c_double), ("T_sum", C.c_double), ("n_melt", C.c_int64),
+        ("melt_bbox", C.c_int32 * 6),
+    ]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
-                  "ens_analysis": EnsAnalysis}
+                  "ens_analysis": EnsAnalysis, "front_stats": FrontStats}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -157,6 +165,8 @@ PROTOTYPES = {
     "cetkmc_ensemble_analyze": (C.c_int, [C.c_void_p, _P(EnsAnalysis)]),
     "cetkmc_ensemble_analysis_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cetkmc_ensemble_set_defects_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_front_stats": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "cetkmc_ensemble_front_stats": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
 }
 
 

@@ -9,6 +9,10 @@ from ._lib import Counters, EnsAnalysis, EnsArgs, Event, Params, RunArgs, RunRes
 EVENT_DTYPE = np.dtype([("type", "<i4"), ("pos", "<i4", 3), ("target", "<i4", 3), ("atom", "<i4"),
                         ("rate", "<f8"), ("dep_rank", "<i8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
 assert EVENT_DTYPE.itemsize == C.sizeof(Event) == 64
+FRONT_DTYPE = np.dtype([("n_front", "<i8"), ("n_skipped", "<i8"), ("pos_sum", "<i8", 3), ("G_sum", "<f8"), ("G_min", "<f8"),
+                        ("G_max", "<f8"), ("Gi_sum", "<f8"), ("T_sum", "<f8"), ("n_melt", "<i8"), ("melt_bbox", "<i4", 6)],
+                       align=True)
+assert FRONT_DTYPE.itemsize == C.sizeof(_lib.FrontStats) == 112
 
 TYPE_BYTES = (b"dep", b"diff", b"nuc", b"att")   # kmc_event_rates.py:72,109,132,158
 
@@ -44,6 +48,11 @@ def _ptr(a):
 
 def _dptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _default_inv_dx():
+    import constants as K
+    return 1.0 / K.VOXEL_SIZE
 
 
 def device_count():
@@ -362,6 +371,15 @@ class Engine:
         a = np.ascontiguousarray(lin_idx, dtype=np.int64)
         self._ck(self.lib.cetkmc_set_defects_sparse(self.h, _ptr(a) if len(a) else None, len(a)))
 
+    def front_stats(self, inv_dx=None):
+        """cetkmc_front_stats (solidification-front diagnostics) of the resident lattice as a dict:
+        n_front, n_skipped, n_melt (int), pos_sum (3,) int64, G_sum, G_min, G_max, Gi_sum, T_sum (float), melt_bbox (6,)
+        int32.  ``inv_dx`` defaults to 1 / constants.VOXEL_SIZE.  metrics.front_metrics turns it into the row's columns."""
+        buf = np.zeros(1, dtype=FRONT_DTYPE)
+        self._ck(self.lib.cetkmc_front_stats(self.h, float(_default_inv_dx() if inv_dx is None else inv_dx), _ptr(buf)))
+        rec = buf[0]
+        return {n: (rec[n].copy() if rec[n].ndim else rec[n].item()) for n in FRONT_DTYPE.names}
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -536,6 +554,13 @@ class Ensemble:
             c0 += k
             out.append(d)
         return out
+
+    def front_stats(self, inv_dx=None):
+        """cetkmc_ensemble_front_stats: Engine.front_stats of every replica (frozen ones included) in launches that do not
+        depend on R.  A dict of arrays with leading dimension R; entry r has the bits of replica(r).front_stats()."""
+        buf = np.zeros(max(self.R, 1), dtype=FRONT_DTYPE)
+        self._ck(self.lib.cetkmc_ensemble_front_stats(self.h, float(_default_inv_dx() if inv_dx is None else inv_dx), _ptr(buf)))
+        return {n: buf[n][:self.R].copy() for n in FRONT_DTYPE.names}
 
     def set_defects_sparse(self, lists):
         """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""

@@ -25,6 +25,7 @@
 #include "cluster.hpp"
 #include "superstep.hpp"
 #include "ensemble.hpp"
+#include "front.hpp"
 
 using namespace cetkmc;
 
@@ -1095,6 +1096,8 @@ struct Ens {
     size_t cap_sc_idx = 0;
     double* d_g_T = nullptr;
     unsigned long long *d_counts = nullptr, *d_g_n = nullptr;
+    FrontPart* d_front_part = nullptr;   // cetkmc_ensemble_front_stats: [R][blocks of a lattice] partials, [R] results
+    FrontStats* d_front_out = nullptr;
     std::vector<int64_t> an_clusters, an_gathered;     // per replica, of the last analysis (-1: none yet)
     int an_species = -1;
 };
@@ -1116,7 +1119,7 @@ void destroy_ens(Ens* e)
     }
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
-                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n};
+                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_front_part, e->d_front_out};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1160,6 +1163,7 @@ int cetkmc_struct_size(const char* name)
     SZ("params", cetkmc_params); SZ("event", cetkmc_event); SZ("sweep_info", cetkmc_sweep_info);
     SZ("run_args", cetkmc_run_args); SZ("run_result", cetkmc_run_result); SZ("super_args", cetkmc_super_args);
     SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm); SZ("ens_args", cetkmc_ens_args); SZ("ens_analysis", cetkmc_ens_analysis);
+    SZ("front_stats", struct cetkmc_front_stats);
 #undef SZ
     return -1;
 }
@@ -2713,6 +2717,61 @@ int cetkmc_ensemble_set_defects_sparse(void* handle, const int64_t* counts, cons
     HIPCHK(hipStreamSynchronize(st));
     for (int r = 0; r < R; ++r)
         if (counts[r] >= 0) { e->reps[(size_t)r]->swept = false; e->reps[(size_t)r]->ifc_fresh = false; }
+    return 0;
+}
+
+// ---- solidification-front diagnostics (front.hpp) ----------------------------------------------
+static dim3 front_grid(int L, int R)
+{
+    return dim3((unsigned)(((L + FRONT_TJ - 1) / FRONT_TJ) * ((L + FRONT_TK - 1) / FRONT_TK)), (unsigned)((L + FRONT_NI - 1) / FRONT_NI),
+                (unsigned)R);
+}
+
+int cetkmc_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !out) return fail("null argument");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_front_stats needs the whole lattice in one slab");
+    HIPCHK(hipSetDevice(h->dev));
+    const dim3 g = front_grid(h->L, 1);
+    const int nb = (int)(g.x * g.y);
+    DevTmp<FrontPart> part;
+    DevTmp<FrontStats> d_out;
+    HIPCHK(part.alloc((size_t)nb));
+    HIPCHK(d_out.alloc(1));
+    hipLaunchKernelGGL(k_front_stats, g, dim3(256), 0, h->stream, view_of(h, 0), h->kp.T_melt, inv_dx, part.p);
+    hipLaunchKernelGGL(k_front_fold, dim3(1), dim3(256), 0, h->stream, (const FrontPart*)part.p, nb, h->L, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(FrontStats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cnt.bytes_d2h += (int64_t)sizeof(FrontStats);
+    return 0;
+}
+
+int cetkmc_ensemble_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out)
+{
+    if (!handle || !out) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    const int R = e->R, L = e->L;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    const dim3 g = front_grid(L, R);
+    const int nb = (int)(g.x * g.y);
+    if (!e->d_front_part) {
+        HIPCHK(hipMalloc((void**)&e->d_front_part, (size_t)R * nb * sizeof(FrontPart)));
+        HIPCHK(hipMalloc((void**)&e->d_front_out, (size_t)R * sizeof(FrontStats)));
+    }
+    for (int r = 0; r < R; ++r) e->table[(size_t)r].kp = e->reps[(size_t)r]->kp;      // T_melt of the replica's own parameters
+    CHK(ens_push_views(e));
+    EnsSel sel{e->d_table, 0, 0, 0, nullptr};
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_front_stats<EnsSel>), g, dim3(256), 0, st, SlabView{}, 0.0, inv_dx, e->d_front_part, sel);
+    hipLaunchKernelGGL(k_front_fold, dim3((unsigned)R), dim3(256), 0, st, (const FrontPart*)e->d_front_part, nb, L, e->d_front_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, e->d_front_out, (size_t)R * sizeof(FrontStats), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h0->cnt.bytes_d2h += (int64_t)R * (int64_t)sizeof(FrontStats);
     return 0;
 }
 

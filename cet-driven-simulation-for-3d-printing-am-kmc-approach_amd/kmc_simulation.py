@@ -31,7 +31,7 @@ from defects import draw_defect_sites, introduce_defects, refresh_defects_device
 from kmc_event_rates import get_event_rates  # noqa: F401  (re-exported like the reference)
 from lattice_init import initialize_lattice
 from metrics import (compute_CET, compute_metrics, compute_metrics_device, compute_metrics_from_clusters,  # noqa: F401
-                     detect_CET_transition)
+                     detect_CET_transition, front_metrics as _front_metrics, front_velocity as _front_velocity)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
@@ -155,6 +155,14 @@ def _metrics_row(cl, counts, nuc, L, step, total_time, n_flagged, nuc_offset, ce
     }
 
 
+def _add_front_columns(row, stats, L, prev):
+    """front_metrics=True: the measured front columns (metrics.front_metrics) and V_front behind the 18 columns of ``row``;
+    ``prev`` is the run's previous row (None on the first)."""
+    row.update(_front_metrics(stats, L, VOXEL_SIZE))
+    row["V_front"] = _front_velocity(row, prev, VOXEL_SIZE)
+    return row
+
+
 def _print_row(step, row):
     print(
         f"Step {step}: AR={row['AspectRatio']:.2f}, "
@@ -221,6 +229,7 @@ def run_kmc(
     metrics_every: int = METRIC_UPDATE_STEP,
     thermal_updates: bool = True,
     laser: dict = None,
+    front_metrics: bool = False,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -257,7 +266,13 @@ def run_kmc(
     (voxels per update) and optionally ``beam_radius``, ``absorptivity``, ``latent`` (thermal_solver.laser_scan_planes).
     prev_state lives on the device: the initial upload snapshots it and every update brings it level with state.
     Refused with ValueError: ``laser`` with ``mode="B"``; with ``checkpoint_every`` / ``resume_from`` (a checkpoint does not
-    carry prev_state); with ``thermal_updates=False``."""
+    carry prev_state); with ``thermal_updates=False``.
+
+    ``front_metrics=True`` (both modes, with and without ``laser``): every metrics row gains, behind its 18 columns, the
+    measured front columns of metrics.front_metrics -- temperature gradient at the growth front, front position, melt-pool
+    size, reduced on the device by cetkmc_front_stats (112 bytes cross PCIe per row) -- and ``V_front`` = (Front_i - the
+    previous row's) * VOXEL_SIZE / (Time - the previous row's) in m/s (0.0 on the first row, for a zero time difference or
+    when either row has no front; a resumed run takes the previous row from the checkpoint's rows)."""
     import cetkmc
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
@@ -324,6 +339,8 @@ def run_kmc(
         row = _metrics_row(engine.clusters(0.5, labels=True), engine.species_counts(), engine.nucleation_count(), L, step,
                            total_time, n_flagged, nuc_offset, cet_detected, G, R, R_phys, G_over_R_phys)
         cet_detected = row["CET_Detected"]
+        if front_metrics:
+            _add_front_columns(row, engine.front_stats(), L, metrics_data[-1] if metrics_data else None)
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -519,7 +536,8 @@ def _replica_prefix(cfg, L):
                 py_state=random.getstate(), np_state=np.random.get_state())
 
 
-def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True):
+def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
+                     front_metrics=False):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -531,7 +549,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     CSV; its private generators end where run_kmc leaves the global ones: ``last_ensemble_info``).
     ``rng="counter"``: replica r equals ``run_kmc(L=L, n_steps=n_steps, mode="B", box=L, thermal_cadence="supersteps",
     **configs[r])`` -- all-counter uniforms, the host draws nothing per step.  The caller's global generator states are
-    restored on return.  One completion line is printed per replica (no per-row progress)."""
+    restored on return.  One completion line is printed per replica (no per-row progress).
+    ``front_metrics=True``: run_kmc's option of that name, from ONE batched cetkmc_ensemble_front_stats call per metrics row."""
     import cetkmc
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
@@ -658,6 +677,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                             lists[r] = draw_defect_sites(*an[r]["gather"])
                         n_flagged[r] = int(len(lists[r]))
                 ens.set_defects_sparse(lists)
+            fs = ens.front_stats() if front_metrics else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -666,6 +686,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 row = _metrics_row(an[r]["clusters"], an[r]["counts"], an[r]["nucleation_count"], L, stop, total_time[r],
                                    n_flagged[r], 0, cet[r], G, Rg, R_phys, GoR)
                 cet[r] = row["CET_Detected"]
+                if fs is not None:
+                    _add_front_columns(row, {k: v[r] for k, v in fs.items()}, L, metrics[r][-1] if metrics[r] else None)
                 metrics[r].append(row)
             next_step = stop + 1
 

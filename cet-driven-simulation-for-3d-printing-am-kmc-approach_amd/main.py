@@ -7,6 +7,7 @@ outside the accelerated path and are not part of this package.
 
     python main.py [--L 30] [--steps 20000] [--levels 0.0 0.1 0.2] [--plots] [--mode B --box 8]
     python main.py --ensemble [--rng counter]     # all carbon levels as one replica ensemble (run_kmc_ensemble)
+    python main.py --front                        # every metrics.csv with the measured front columns (run_kmc front_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
 every level like ``--mode B --box L`` with the super-step thermal cadence.
@@ -42,12 +43,14 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
         raise ValueError("need n_steps >= 0 and at least one carbon level")
 
 
-def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", **run_kw):
+def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
+         **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
     summary = {"carbon_levels": [], "grain_sizes": [], "defect_densities": [], "aspect_ratios": []}
     ens_out, ens_t = None, 0.0
+    fm = {"front_metrics": True} if front else {}     # --front: measured front columns in every metrics.csv (run_kmc)
     if ensemble:                  # every level in one replica ensemble; the per-level epilogue below reads its results
         for c in carbon_levels:
             prefix = f"impurity_c_{int(c * 100)}"
@@ -56,7 +59,8 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
             save_lattice(*init[:4], init[4], prefix=f"outputs/{prefix}/init")
         t0 = time.time()
         ens_out = run_kmc_ensemble([dict(temp=T_SUB, defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, impurity_c=c,
-                                         output_prefix=f"impurity_c_{int(c * 100)}") for c in carbon_levels], L, n_steps, rng=rng)
+                                         output_prefix=f"impurity_c_{int(c * 100)}") for c in carbon_levels], L, n_steps, rng=rng,
+                                   **fm)
         ens_t = time.time() - t0
     for q, c in enumerate(carbon_levels):
         prefix = f"impurity_c_{int(c * 100)}"
@@ -70,7 +74,7 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
             save_lattice(*init[:4], init[4], prefix=f"{out_dir}/init")
             t0 = time.time()
             state, atom_type, total_time, theta, phi = run_kmc(L=L, n_steps=n_steps, temp=T_SUB, defect_fraction=DEFECT_PROB,
-                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw)
+                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw, **fm)
         else:
             state, atom_type, total_time, theta, phi = ens_out[q]
             t0 -= ens_t / len(carbon_levels)
@@ -108,6 +112,7 @@ if __name__ == "__main__":
     ap.add_argument("--ensemble", action="store_true", help="run all carbon levels as one replica ensemble")
     ap.add_argument("--rng", choices=("reference", "counter"), default="reference",
                     help="--ensemble: reference streams (= the sequential run's files) or counter uniforms (= --mode B --box L)")
+    ap.add_argument("--front", action="store_true", help="measured front columns (G, V, melt pool) in every metrics.csv")
     a = ap.parse_args()
-    main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng,
+    main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front,
          **(dict(mode="B", box=a.box) if a.mode == "B" else {}))

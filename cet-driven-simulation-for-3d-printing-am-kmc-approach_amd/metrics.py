@@ -6,7 +6,7 @@ quirk that the grain-diameter percentiles are taken over the LABEL volume return
 """
 import numpy as np
 
-from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD, VOXEL_SIZE
+from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD, T_MELT, VOXEL_SIZE
 from utils import calculate_aspect_ratio, get_clusters
 
 
@@ -146,6 +146,40 @@ def compute_metrics_from_clusters(cl, n_voxels, defects_count=0, voxel_size=VOXE
         "Grain_d50_um": d50, "Grain_d90_um": d90,
         "VOXEL_SIZE_m": voxel_size, "RANDOM_SEED": rng_seed,
     }
+
+
+FRONT_COLUMNS = ("G_front", "G_front_max", "Gi_front", "T_front", "Undercooling_front", "Front_i", "FrontVoxels",
+                 "MeltVoxels", "MeltDepth", "MeltLength", "MeltWidth")
+
+
+def front_metrics(stats, L, voxel_size=VOXEL_SIZE):
+    """Columns of a metrics row from one lattice's front statistics (Engine.front_stats, or entry r of every array of
+    Ensemble.front_stats; taken with inv_dx = 1 / voxel_size, so gradients are in K/m): G_front (mean |grad T| over the
+    front voxels), G_front_max, Gi_front (mean component along the build direction), T_front (mean), Undercooling_front
+    (T_MELT - T_front), Front_i (mean plane index of the front), FrontVoxels (n_front: 0 marks a row without a front),
+    MeltVoxels and MeltDepth / MeltLength / MeltWidth (extents of the melt voxels' bounding box along i, j, k in voxels).
+    Everything that is a mean over an empty front (Undercooling_front included) is 0.0; the extents of an empty pool are 0."""
+    n = int(stats["n_front"])
+    bb = [int(x) for x in stats["melt_bbox"]]
+    n_melt = int(stats["n_melt"])
+    mean = (lambda x: float(x) / n) if n else (lambda x: 0.0)
+    T_front = mean(stats["T_sum"])
+    ext = [(bb[3 + a] - bb[a] + 1) if n_melt else 0 for a in range(3)]
+    return {
+        "G_front": mean(stats["G_sum"]), "G_front_max": float(stats["G_max"]) if n else 0.0, "Gi_front": mean(stats["Gi_sum"]),
+        "T_front": T_front, "Undercooling_front": (float(T_MELT) - T_front) if n else 0.0,
+        "Front_i": mean(int(stats["pos_sum"][0])), "FrontVoxels": n,
+        "MeltVoxels": n_melt, "MeltDepth": ext[0], "MeltLength": ext[1], "MeltWidth": ext[2],
+    }
+
+
+def front_velocity(row, prev, voxel_size=VOXEL_SIZE):
+    """V_front of a metrics row: (Front_i - the previous row's) * voxel_size / (Time - the previous row's) in m/s; 0.0 on
+    the first row (``prev`` None), when the time difference is 0 or when either row has no front."""
+    if prev is None or not row["FrontVoxels"] or not prev.get("FrontVoxels"):
+        return 0.0
+    dt = float(row["Time"]) - float(prev["Time"])
+    return (float(row["Front_i"]) - float(prev["Front_i"])) * voxel_size / dt if dt != 0.0 else 0.0
 
 
 def compute_CET(state, theta, phi, voxel_size=VOXEL_SIZE):

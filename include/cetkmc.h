@@ -187,7 +187,7 @@ int cetkmc_abi_version(void);
  * hand build): the binding compares it with the sources beside it and rebuilds / refuses a stale library */
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
- * "host_comm"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "host_comm", "ens_args", "ens_analysis", "front_stats"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the apply-in-sweep row patch are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -362,7 +362,8 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
  * cetkmc_create_ensemble: p[R] (one parameter set per replica).  The returned handle addresses replica 0 in the
  * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
  * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
- * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*) except the
+ * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*,
+ * front_stats) except the
  * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
  * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
  * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
@@ -415,6 +416,33 @@ int cetkmc_ensemble_analyze(void* handle, cetkmc_ens_analysis* a);
 int cetkmc_ensemble_analysis_data(void* handle, int32_t* first_voxel, int64_t* size, int32_t* bbox, int32_t* labels,
                                   int64_t* lin_idx, double* T_vals);
 int cetkmc_ensemble_set_defects_sparse(void* handle, const int64_t* counts, const int64_t* lin_idx);
+
+/* Solidification-front diagnostics (NOT in the reference): one streaming pass over T and state on the
+ * device, nothing written to the lattice.  With inv_dx = 1 / voxel edge (computed by the host, like inv_dx2):
+ *   front voxel: state != 0 and at least one of its six face neighbours INSIDE the lattice has state == 0;
+ *   gradient component along an axis at index x: (T[x+1] - T[x-1]) * (0.5 * inv_dx) inside, (T[1] - T[0]) * inv_dx at
+ *     x == 0, (T[L-1] - T[L-2]) * inv_dx at x == L-1, 0.0 when L == 1; G = sqrt(gi*gi + gj*gj + gk*gk), left to right;
+ *   a front voxel whose G or own T is not finite is counted in n_skipped and in nothing else;
+ *   melt voxel: any voxel, whatever its state, with T >= T_melt of the lattice's parameters (NaN is none, +inf is one).
+ * The three sums are formed in a fixed order (no floating-point atomics): two calls on an unchanged lattice return the same
+ * bits, and a replica's entry of the batched call has the bits of the same lattice on a single handle.
+ * (A struct tag without a typedef: the per-lattice call carries the same name.) */
+struct cetkmc_front_stats {
+    int64_t n_front;        /* front voxels not skipped                                             */
+    int64_t n_skipped;      /* front voxels skipped                                                 */
+    int64_t pos_sum[3];     /* sum of i, j, k over the n_front voxels                               */
+    double  G_sum, G_min, G_max;   /* over the n_front voxels; G_min = G_max = 0 when n_front == 0  */
+    double  Gi_sum;         /* signed sum of gi, the component along the build direction (axis 0)   */
+    double  T_sum;          /* sum of the front voxels' own T                                       */
+    int64_t n_melt;         /* melt voxels                                                          */
+    int32_t melt_bbox[6];   /* imin, jmin, kmin, imax, jmax, kmax of the melt voxels; {L, L, L, -1, -1, -1} when none */
+};
+/* One lattice: a single-slab, single-process handle or a replica handle (multi-slab and multi-rank handles are refused).
+ * Ordered on the handle's stream behind pending stepping work; copies sizeof(struct cetkmc_front_stats) to the host. */
+int cetkmc_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out);
+/* Every replica of an ensemble, frozen ones included, in a launch sequence that does not depend on R; out[R].  A
+ * single-lattice handle is refused. */
+int cetkmc_ensemble_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out);
 
 #ifdef __cplusplus
 }
