@@ -19,6 +19,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -45,6 +46,34 @@ int fail(const std::string& m) { g_err = m; return 1; }
 
 int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 int round_up(int n, int m) { return (n + m - 1) / m * m; }
+
+// ---- kernel launches ------------------------------------------------------------------
+// One launch.  With ev_a and ev_b the two hipEvents ride on the dispatch itself (hipExtLaunchKernelGGL start / stop events =
+// the dispatch's own begin / end timestamps: no barrier packets in the stream, so a timed launch runs like an untimed
+// one); without them it is a plain launch.  The arguments are converted to the kernel's own parameter types.
+template <class T> struct arg_of { using type = T; };
+template <class... P>
+void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t shmem, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b,
+            typename arg_of<P>::type... args)
+{
+    if (ev_a && ev_b) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)shmem, st, ev_a, ev_b, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, shmem, st, args...);
+}
+
+// Run-time flags -> template arguments: f is called once, with std::true_type / std::false_type values, for exactly the
+// combinations the kernels are built for.  with_source: (LASER, LATENT) of the temperature tiles.
+using Yes = std::true_type;
+using No = std::false_type;
+template <class F> void with_flag(bool on, F&& f) { if (on) f(Yes{}); else f(No{}); }
+template <class F> void with_source(int laser, int latent, F&& f) { if (laser && latent) f(Yes{}, Yes{}); else if (laser) f(Yes{}, No{}); else f(No{}, No{}); }
+
+// 20-step temperature updates (kmc_simulation.py:248) among the global steps [step0, step0 + n): multiples of 20 below
+// step0 + n less those below step0
+int64_t updates_in(int64_t step0, int64_t n)
+{
+    auto below = [](int64_t x) { return (x > 0 ? x + 19 : x) / 20; };       // ceil(x / 20)
+    return n > 0 ? below(step0 + n) - below(step0) : 0;
+}
 
 // ---- RCCL, loaded on demand -----------------------------------------------------------
 struct Rccl {
@@ -377,6 +406,35 @@ SlabView view_of(Handle* h, int s, int par = -1)
     return v;
 }
 
+// ---- launch shapes: the single-lattice path and the replica ensembles (R lattices per launch) take them from here ----
+// Rows of Pk <= 256 columns are half-wave rows (hw); longer ones are swept in one chunk or, past 512 columns, in two
+// (ch2).  npf: 16-B chunks of a class slab per thread of the streaming sweep (L > 512: pitchC >= 544, so npf >= 2).
+struct RowShape { bool hw, ch2; int npf; };
+RowShape row_shape(const Handle* h) { return {h->Pk <= 256, h->Pk > 512, ((SWEEP_TJ + 4) * h->pitchC / 16 + 255) / 256}; }
+// (HW, CH2) of the row kernels
+template <class F> void with_rows(const RowShape& rs, F&& f) { if (rs.hw) f(Yes{}, No{}); else if (!rs.ch2) f(No{}, No{}); else f(No{}, Yes{}); }
+// the five (HW, NPF, CH2) shapes of k_sweep_stream
+template <bool TAB, class F> void with_stream_kernel(const RowShape& rs, F&& f)
+{
+    if (rs.hw) f(k_sweep_stream<TAB, true, 1, false>);
+    else if (rs.npf == 1) f(k_sweep_stream<TAB, false, 1, false>);
+    else if (rs.npf == 2 && !rs.ch2) f(k_sweep_stream<TAB, false, 2, false>);
+    else if (rs.npf == 2) f(k_sweep_stream<TAB, false, 2, true>);
+    else f(k_sweep_stream<TAB, false, 3, true>);
+}
+// plane-marching temperature kernels: column tiles x row tiles x groups of ni planes (of every replica)
+dim3 thermal_grid(int L, int nloc, int ni, int R = 1) { return dim3((L + THERM_KT - 1) / THERM_KT, (L + THERM_TJ - 1) / THERM_TJ, (nloc + ni - 1) / ni * R); }
+// k_rate_table: one thread per pair of entries, grid-stride past 8192 blocks
+dim3 table_grid(const SlabView& v, int R = 1)
+{
+    const int64_t pairs = (int64_t)v.nloc * v.L * (v.pitchT / 2);
+    return dim3((unsigned)std::min<int64_t>((pairs + 255) / 256, 8192), (unsigned)R);
+}
+// k_sweep_plane: the 3L row sums and row counts of its plane
+uint32_t plane_shmem(int L) { return (uint32_t)(3 * L * (sizeof(double) + sizeof(int))); }
+// the interface lists grow while stepping: keep the interface kernel's grid at one entry per thread
+void grow_ifc_grid(Handle* h, int n_list) { h->ifc_blocks = std::max(h->ifc_blocks, std::min(8192, (n_list + 255) / 256 + 64)); }
+
 // per-call device allocation released on every return path
 template <class T>
 struct DevTmp {
@@ -499,7 +557,7 @@ int upload_impl(Handle* h, int i_begin, int i_end, const I* state, const double*
             int n = 0;
             HIPCHK(hipMemcpyAsync(&n, s.v.ifc_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
-            h->ifc_blocks = std::max(h->ifc_blocks, std::min(8192, (n + 255) / 256 + 64));
+            grow_ifc_grid(h, n);
         }
     }
     HIPCHK(hipGetLastError());
@@ -549,8 +607,7 @@ int launch_table(Handle* h, hipStream_t st, const StepState* ss, int par)
     const double K0 = host_k_eff(h->p, 0, 0);
     for (size_t s = 0; s < h->slabs.size(); ++s) {
         SlabView v = view_of(h, (int)s, par);
-        const int64_t pairs = (int64_t)v.nloc * v.L * (v.pitchT / 2);
-        hipLaunchKernelGGL(k_rate_table, dim3((unsigned)std::min<int64_t>((pairs + 255) / 256, 8192)), dim3(256), 0, st, h->kp, v, K0, ss);
+        hipLaunchKernelGGL(k_rate_table, table_grid(v), dim3(256), 0, st, h->kp, v, K0, ss);
         h->cnt.alg_bytes_table += (int64_t)16 * v.nloc * v.L * v.L;     // T read, table entry written
     }
     HIPCHK(hipGetLastError());
@@ -577,14 +634,23 @@ StreamArgs stream_args(Handle* h, const SlabView& v)
     return sa;
 }
 
-// the interface lists grow while stepping: keep the interface kernel's grid at one entry per thread (called where the
-// host has just synchronised anyway)
+// the rate table's inputs and the table of buffer pair `par`, for the temperature tiles that write it (k_thermal_tiles16<.., TABLE>)
+TableCfg table_cfg(Handle* h, const Slab& s, int par)
+{
+    TableCfg tb{};
+    tb.T_melt = h->kp.T_melt; tb.delta_T_c = h->kp.delta_T_c; tb.kT = h->kp.kT; tb.I0 = h->kp.I0;
+    tb.rate_threshold = h->kp.rate_threshold; tb.K0 = host_k_eff(h->p, 0, 0); tb.nu_dep = h->kp.nu_dep;
+    tb.vval = s.vvalbuf[par]; tb.dep_val = s.depbuf[par];
+    return tb;
+}
+
+// interface-kernel grid from the lists' lengths as they stand (called where the host has just synchronised anyway)
 int refresh_ifc_grid(Handle* h)
 {
     for (auto& sl : h->slabs) {
         int n_list = 0;
         HIPCHK(hipMemcpy(&n_list, sl.v.ifc_n, sizeof(int), hipMemcpyDeviceToHost));
-        h->ifc_blocks = std::max(h->ifc_blocks, std::min(8192, (n_list + 255) / 256 + 64));
+        grow_ifc_grid(h, n_list);
     }
     return 0;
 }
@@ -638,13 +704,11 @@ int launch_dirty_rows(Handle* h, hipEvent_t ev_a, hipEvent_t ev_b)
         const int* dl = h->d_dirty;
         int* pc = h->d_dirty + 1 + DIRTY_MAX;
         const StepState* ss = h->d_ss;
-        const bool tab = h->sweep_variant == 1 || h->sweep_variant >= 3, hw = h->Pk <= 256, ch2 = h->Pk > 512;
-#define CETKMC_LAUNCH_ROWS(TAB, HW, CH2) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rows_eval<TAB, HW, CH2>), dim3(24), dim3(256), 0, h->stream, sa, dl, ss, h->d_blocks, pc)
-        if (hw) { if (tab) CETKMC_LAUNCH_ROWS(true, true, false); else CETKMC_LAUNCH_ROWS(false, true, false); }
-        else if (!ch2) { if (tab) CETKMC_LAUNCH_ROWS(true, false, false); else CETKMC_LAUNCH_ROWS(false, false, false); }
-        else { if (tab) CETKMC_LAUNCH_ROWS(true, false, true); else CETKMC_LAUNCH_ROWS(false, false, true); }
-#undef CETKMC_LAUNCH_ROWS
+        with_rows(row_shape(h), [&](auto hw, auto ch2) {
+            with_flag(h->sweep_variant == 1 || h->sweep_variant >= 3, [&](auto tab) {
+                launch(k_rows_eval<tab.value, hw.value, ch2.value>, dim3(24), dim3(256), 0, h->stream, nullptr, nullptr, sa, dl, ss, h->d_blocks, pc);
+            });
+        });
     }
     if (ev_b) HIPCHK(hipEventRecord(ev_b, h->stream));
     HIPCHK(hipGetLastError());
@@ -678,76 +742,37 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
         }
     }
     // sweep timing of a batch (profile 1 / 3: ev_a, ev_b without the phase events): the two hipEvents ride on the launch itself
-    // (hipExtLaunchKernelGGL start / stop events = the dispatch's own begin / end timestamps) -- no barrier packets in the
-    // stream, so the timed steps run like untimed ones.  Several slabs in one process / the phase table: plain records.
+    // (launch()).  Several slabs in one process / the phase table: plain records.
     const bool ext = ev_a && ev_b && !ev_pre && h->slabs.size() == 1 && h->sweep_variant >= 1;
+    const hipEvent_t xa = ext ? ev_a : nullptr, xb = ext ? ev_b : nullptr;
     if (ev_a && !ext) HIPCHK(hipEventRecord(ev_a, h->stream));
     const int sv = (h->sweep_auto && h->sweep_variant == 1 && h->L <= 128) ? 4 : h->sweep_variant;      // effective sweep kernel
+    const RowShape rs = row_shape(h);
     for (size_t s = 0; s < h->slabs.size(); ++s) {
         SlabView v = view_of(h, (int)s);
+        const StreamArgs sa = stream_args(h, v);
         if (sv == 4) {
             // census-free table sweep, one 16-wave block per owned plane, block sums folded in the same launch
-            const StreamArgs sa = stream_args(h, v);
-            const bool hw = h->Pk <= 256, ch2 = h->Pk > 512;
-            const dim3 g((unsigned)v.nloc);
-            const uint32_t shm = (uint32_t)(3 * h->L * (sizeof(double) + sizeof(int)));
-#define CETKMC_LAUNCH_PLANE(HW, CH2)                                                                                             \
-    do {                                                                                                                         \
-        if (ext) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_plane<HW, CH2>), g, dim3(1024), shm, h->stream, ev_a, ev_b, 0, sa, ss, h->d_blocks); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_plane<HW, CH2>), g, dim3(1024), shm, h->stream, sa, ss, h->d_blocks);     \
-    } while (0)
-            if (hw) CETKMC_LAUNCH_PLANE(true, false);
-            else if (!ch2) CETKMC_LAUNCH_PLANE(false, false);
-            else CETKMC_LAUNCH_PLANE(false, true);
-#undef CETKMC_LAUNCH_PLANE
+            with_rows(rs, [&](auto hw, auto ch2) {
+                launch(k_sweep_plane<hw.value, ch2.value>, dim3((unsigned)v.nloc), dim3(1024), plane_shmem(h->L), h->stream, xa, xb, sa, ss, h->d_blocks);
+            });
         } else if (sv == 3) {
             // census-free table sweep: class bytes + rate table streamed once, no LDS
-            const StreamArgs sa = stream_args(h, v);
-            const bool hw = h->Pk <= 256, ch2 = h->Pk > 512;
-            const int ipp = hw ? (h->L + 1) / 2 : h->L;
+            const int ipp = rs.hw ? (h->L + 1) / 2 : h->L;
             const int64_t n_items = (int64_t)ipp * v.nloc;
             const dim3 g((unsigned)((n_items + 4 * TABLE_IPW - 1) / (4 * TABLE_IPW)));
-#define CETKMC_LAUNCH_TABLE(HW, CH2)                                                                                             \
-    do {                                                                                                                         \
-        if (ext) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_table<HW, CH2>), g, dim3(256), 0, h->stream, ev_a, ev_b, 0, sa, ss); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_table<HW, CH2>), g, dim3(256), 0, h->stream, sa, ss);                     \
-    } while (0)
-            if (hw) CETKMC_LAUNCH_TABLE(true, false);
-            else if (!ch2) CETKMC_LAUNCH_TABLE(false, false);
-            else CETKMC_LAUNCH_TABLE(false, true);
-#undef CETKMC_LAUNCH_TABLE
+            with_rows(rs, [&](auto hw, auto ch2) {
+                launch(k_sweep_table<hw.value, ch2.value>, g, dim3(256), 0, h->stream, xa, xb, sa, ss);
+            });
+        } else if (h->sweep_variant >= 1 && h->pend_live) {
+            // the previous step's event is applied by one extra workgroup (blockIdx 0) of this launch (run_steps defers
+            // only under the streaming sweep with the rate table, and only where rows are half-wave rows)
+            ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_patch, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
+                        (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
+            launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X);
         } else if (h->sweep_variant >= 1) {
-            const StreamArgs sa = stream_args(h, v);
-            const dim3 g(sa.group_count * njt);
-            const bool tab = h->sweep_variant == 1, hw = h->Pk <= 256;
-            const int npf = ((SWEEP_TJ + 4) * h->pitchC / 16 + 255) / 256;       // 16-B chunks of a class slab per thread
-#define CETKMC_LAUNCH_STREAM(TAB, HW, NPF, CH2)                                                                                   \
-    do {                                                                                                                         \
-        if (ext) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream<TAB, HW, NPF, CH2>), g, dim3(256), (uint32_t)h->shmem_stream, \
-                                       h->stream, ev_a, ev_b, 0, sa, ss);                                                        \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream<TAB, HW, NPF, CH2>), g, dim3(256), h->shmem_stream, h->stream, sa, ss); \
-    } while (0)
-            const bool ch2 = h->Pk > 512;       // L > 512: pitchC >= 544, so npf >= 2
-            if (h->pend_live) {
-                // the previous step's event is applied by one extra workgroup (blockIdx 0) of this launch
-                ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_patch, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
-                            (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
-                const dim3 ga(g.x + 1);
-#define CETKMC_LAUNCH_STREAM_APPLY(HW, NPF, CH2)                                                                                  \
-    do {                                                                                                                         \
-        if (ext) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream_apply<HW, NPF, CH2>), ga, dim3(256), (uint32_t)h->shmem_stream, \
-                                       h->stream, ev_a, ev_b, 0, sa, (const StepState*)h->d_ss, X);                              \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_stream_apply<HW, NPF, CH2>), ga, dim3(256), h->shmem_stream, h->stream, sa, \
-                                (const StepState*)h->d_ss, X);                                                                   \
-    } while (0)
-                CETKMC_LAUNCH_STREAM_APPLY(true, 1, false);      // (run_steps defers only where rows are half-wave rows)
-#undef CETKMC_LAUNCH_STREAM_APPLY
-            } else if (hw) { if (tab) CETKMC_LAUNCH_STREAM(true, true, 1, false); else CETKMC_LAUNCH_STREAM(false, true, 1, false); }
-            else if (npf == 1) { if (tab) CETKMC_LAUNCH_STREAM(true, false, 1, false); else CETKMC_LAUNCH_STREAM(false, false, 1, false); }
-            else if (npf == 2 && !ch2) { if (tab) CETKMC_LAUNCH_STREAM(true, false, 2, false); else CETKMC_LAUNCH_STREAM(false, false, 2, false); }
-            else if (npf == 2) { if (tab) CETKMC_LAUNCH_STREAM(true, false, 2, true); else CETKMC_LAUNCH_STREAM(false, false, 2, true); }
-            else { if (tab) CETKMC_LAUNCH_STREAM(true, false, 3, true); else CETKMC_LAUNCH_STREAM(false, false, 3, true); }
-#undef CETKMC_LAUNCH_STREAM
+            auto go = [&](auto k) { launch(k, dim3(sa.group_count * njt), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, ss); };
+            if (h->sweep_variant == 1) with_stream_kernel<true>(rs, go); else with_stream_kernel<false>(rs, go);
         } else {
             hipLaunchKernelGGL(k_sweep_simple, dim3(v.nloc * njt), dim3(256), shmem0, h->stream, h->kp, v, h->d_ktab, ss);
         }
@@ -782,14 +807,11 @@ int launch_select(Handle* h, const BatchCfg& cfg, double r_direct, int info_only
 int launch_select_apply(Handle* h, const BatchCfg& cfg, int eval_touched, int* dirty, int64_t cur_hint)
 {
     if (!multi_rank(h)) {
-#define CETKMC_LAUNCH_SELAPPLY(IFC)                                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_apply<IFC>), dim3(1), dim3(256), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur], \
-                       (int)h->slabs.size(), h->L, h->PB, (const BlockEnt*)h->d_blocks, h->d_ss, cfg,                               \
-                       (const double*)h->d_u_pick, (const double*)h->d_ktab, h->d_events_all + h->my_first,                         \
-                       IFC ? 1 : 0, (const double*)h->d_u_defect, (const double*)h->d_u_np,                                         \
-                       h->d_log_total, h->d_log_event, h->d_log_nev, eval_touched, dirty, (long long)cur_hint)
-        if (h->sweep_variant >= 1) CETKMC_LAUNCH_SELAPPLY(true); else CETKMC_LAUNCH_SELAPPLY(false);
-#undef CETKMC_LAUNCH_SELAPPLY
+        with_flag(h->sweep_variant >= 1, [&](auto ifc) {
+            launch(k_select_apply<ifc.value>, dim3(1), dim3(256), 0, h->stream, nullptr, nullptr, h->kp, h->d_views[h->cur], (int)h->slabs.size(),
+                   h->L, h->PB, h->d_blocks, h->d_ss, cfg, h->d_u_pick, h->d_ktab, h->d_events_all + h->my_first, ifc.value ? 1 : 0,
+                   h->d_u_defect, h->d_u_np, h->d_log_total, h->d_log_event, h->d_log_nev, eval_touched, dirty, (long long)cur_hint);
+        });
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -874,58 +896,56 @@ int exchange_T_halo(Handle* h, int buf, hipStream_t st = nullptr)
     return 0;
 }
 
-int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+ThermalCfg thermal_cfg(Handle* h, double dt, int laser, int use_latent, int scrub)
 {
     ThermalCfg C{};
     C.dt = dt; C.alpha = h->p.alpha; C.inv_dx2 = h->p.inv_dx2; C.clip_lo = h->p.T_clip_lo; C.clip_hi = h->p.T_clip_hi;
     C.T_nan = h->p.T_nan; C.rho_cp = h->p.rho_cp; C.latent_coef = h->p.latent_coef;
     C.laser = laser; C.use_latent = use_latent; C.scrub = scrub; C.ni = h->therm_ni;
+    return C;
+}
+
+int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+{
+    const ThermalCfg C = thermal_cfg(h, dt, laser, use_latent, scrub);
     ++h->cnt.thermal_updates;
     for (auto& sl : h->slabs) h->cnt.alg_bytes_thermal += (int64_t)16 * sl.v.nloc * h->L * h->L;   // T read + written
     const int nxt = h->cur ^ 1;
     size_t n_fused = 0;
+    const StepState* ssp = batch ? h->d_ss : nullptr;
     for (size_t s = 0; s < h->slabs.size(); ++s) {
         SlabView v = view_of(h, (int)s);
+        const double* Tin = h->slabs[s].Tbuf[h->cur];
+        double* Tout = h->slabs[s].Tbuf[nxt];
+        uint8_t* prev = h->slabs[s].prev;
         if (h->thermal_variant == 1) {
-            dim3 grid((h->L + THERM_KT - 1) / THERM_KT, (h->L + THERM_TJ - 1) / THERM_TJ, (v.nloc + h->therm_ni - 1) / h->therm_ni);
-            const StepState* ssp = batch ? (const StepState*)h->d_ss : nullptr;
-            const double* Tin = h->slabs[s].Tbuf[h->cur];
-            double* Tout = h->slabs[s].Tbuf[nxt];
-            uint8_t* prev = h->slabs[s].prev;
+            const dim3 grid = thermal_grid(h->L, v.nloc, h->therm_ni);
             if (h->L % THERM_KT == 0 && h->L % THERM16_TJ == 0 && !h->thermal_general && h->thermal_tiles16) {   // 16-row tiles (option), covering the lattice exactly
                 ThermalCfg C16 = C;
                 C16.ni = h->therm_ni16;
-                dim3 g16(h->L / h->thermal_kt, h->L / THERM16_TJ, (v.nloc + C16.ni - 1) / C16.ni);
+                const dim3 g16(h->L / h->thermal_kt, h->L / THERM16_TJ, (v.nloc + C16.ni - 1) / C16.ni);
                 // the default tiles also write the new field's rate table (k_rate_table's work, without reading T again)
                 const bool fuse = h->thermal_table && h->thermal_rpt == 2 && h->thermal_kt == 256 && h->sweep_variant >= 1;
-                TableCfg TB{};
-                TB.T_melt = h->kp.T_melt; TB.delta_T_c = h->kp.delta_T_c; TB.kT = h->kp.kT; TB.I0 = h->kp.I0;
-                TB.rate_threshold = h->kp.rate_threshold; TB.K0 = host_k_eff(h->p, 0, 0); TB.nu_dep = h->kp.nu_dep;
-                TB.vval = h->slabs[s].vvalbuf[nxt]; TB.dep_val = h->slabs[s].depbuf[nxt];
                 if (fuse) { ++n_fused; h->cnt.alg_bytes_table += (int64_t)8 * v.nloc * v.L * v.L; }      // table entry written (T not re-read)
-#define CETKMC_LAUNCH_T16(LA, LT)                                                                                                 \
-    do {                                                                                                                          \
-        if (fuse) hipLaunchKernelGGL((k_thermal_tiles16<LA, LT, 2, 256, true>), g16, dim3(1024), 0, h->stream, v, Tin, Tout, prev, d_q, C16, ssp, TB); \
-        else if (h->thermal_rpt == 2 && h->thermal_kt == 128) hipLaunchKernelGGL((k_thermal_tiles16<LA, LT, 2, 128>), g16, dim3(512), 0, h->stream, v, Tin, Tout, prev, d_q, C16, ssp, TableCfg{}); \
-        else if (h->thermal_rpt == 2) hipLaunchKernelGGL((k_thermal_tiles16<LA, LT, 2, 256>), g16, dim3(1024), 0, h->stream, v, Tin, Tout, prev, d_q, C16, ssp, TableCfg{}); \
-        else hipLaunchKernelGGL((k_thermal_tiles16<LA, LT, 4, 256>), g16, dim3(512), 0, h->stream, v, Tin, Tout, prev, d_q, C16, ssp, TableCfg{});   \
-    } while (0)
-                if (laser && use_latent) CETKMC_LAUNCH_T16(true, true);
-                else if (laser) CETKMC_LAUNCH_T16(true, false);
-                else CETKMC_LAUNCH_T16(false, false);
-#undef CETKMC_LAUNCH_T16
+                with_source(laser, use_latent, [&](auto la, auto lt) {
+                    auto go = [&](auto k, unsigned threads, const TableCfg& tb) {
+                        launch(k, g16, dim3(threads), 0, h->stream, nullptr, nullptr, v, Tin, Tout, prev, d_q, C16, ssp, tb);
+                    };
+                    if (fuse) go(k_thermal_tiles16<la.value, lt.value, 2, 256, true>, 1024, table_cfg(h, h->slabs[s], nxt));
+                    else if (h->thermal_rpt == 2 && h->thermal_kt == 128) go(k_thermal_tiles16<la.value, lt.value, 2, 128>, 512, TableCfg{});
+                    else if (h->thermal_rpt == 2) go(k_thermal_tiles16<la.value, lt.value, 2, 256>, 1024, TableCfg{});
+                    else go(k_thermal_tiles16<la.value, lt.value, 4, 256>, 512, TableCfg{});
+                });
             } else if (h->L % THERM_KT == 0 && h->L % THERM_TJ == 0 && !h->thermal_general) {      // the 8-row tiles cover the lattice exactly
-                if (laser && use_latent) hipLaunchKernelGGL((k_thermal_tiles<true, true>), grid, dim3(256), 0, h->stream, v, Tin, Tout, prev, d_q, C, ssp);
-                else if (laser) hipLaunchKernelGGL((k_thermal_tiles<true, false>), grid, dim3(256), 0, h->stream, v, Tin, Tout, prev, d_q, C, ssp);
-                else hipLaunchKernelGGL((k_thermal_tiles<false, false>), grid, dim3(256), 0, h->stream, v, Tin, Tout, prev, d_q, C, ssp);
+                with_source(laser, use_latent, [&](auto la, auto lt) {
+                    launch(k_thermal_tiles<la.value, lt.value>, grid, dim3(256), 0, h->stream, nullptr, nullptr, v, Tin, Tout, prev, d_q, C, ssp);
+                });
             } else {
                 hipLaunchKernelGGL(k_thermal_march, grid, dim3(256), 0, h->stream, v, Tin, Tout, prev, d_q, C, ssp);
             }
         } else {
-            dim3 grid((h->L + 255) / 256, h->L, v.nloc);
-            hipLaunchKernelGGL(k_thermal, grid, dim3(256), 0, h->stream, v, (const double*)h->slabs[s].Tbuf[h->cur],
-                               h->slabs[s].Tbuf[nxt], (const uint8_t*)h->slabs[s].prev, d_q, C,
-                               batch ? (const StepState*)h->d_ss : nullptr);
+            hipLaunchKernelGGL(k_thermal, dim3((h->L + 255) / 256, h->L, v.nloc), dim3(256), 0, h->stream, v, Tin, Tout,
+                               (const uint8_t*)prev, d_q, C, ssp);
         }
     }
     HIPCHK(hipGetLastError());
@@ -946,15 +966,6 @@ int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_l
     return 0;
 }
 
-ThermalCfg thermal_cfg(Handle* h, double dt, int laser, int use_latent, int scrub)
-{
-    ThermalCfg C{};
-    C.dt = dt; C.alpha = h->p.alpha; C.inv_dx2 = h->p.inv_dx2; C.clip_lo = h->p.T_clip_lo; C.clip_hi = h->p.T_clip_hi;
-    C.T_nan = h->p.T_nan; C.rho_cp = h->p.rho_cp; C.latent_coef = h->p.latent_coef;
-    C.laser = laser; C.use_latent = use_latent; C.scrub = scrub; C.ni = h->therm_ni;
-    return C;
-}
-
 // Look-ahead: the temperature update that global step g will perform, and the rate table of its result, computed NOW on
 // stream2 from the current field into the other buffer pair -- without the latent-heat term (k_thermal_fix adds it at
 // the update, for the few voxels it concerns).  The current field does not change until then, so this is the update's
@@ -970,8 +981,7 @@ int launch_thermal_ahead(Handle* h, int64_t g, double dt, int laser, const doubl
     HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_main, 0));
     for (size_t s = 0; s < h->slabs.size(); ++s) {
         SlabView v = view_of(h, (int)s);
-        dim3 grid((h->L + THERM_KT - 1) / THERM_KT, (h->L + THERM_TJ - 1) / THERM_TJ, (v.nloc + h->therm_ni - 1) / h->therm_ni);
-        hipLaunchKernelGGL(k_thermal_march, grid, dim3(256), 0, h->stream2, v, (const double*)h->slabs[s].Tbuf[h->cur],
+        hipLaunchKernelGGL(k_thermal_march, thermal_grid(h->L, v.nloc, h->therm_ni), dim3(256), 0, h->stream2, v, (const double*)h->slabs[s].Tbuf[h->cur],
                            h->slabs[s].Tbuf[nxt], h->slabs[s].prev, d_q, C, (const StepState*)h->d_ss);
     }
     HIPCHK(hipGetLastError());
@@ -1017,6 +1027,18 @@ int thermal_step(Handle* h, int64_t g, double dt, int laser, const double* d_q, 
     return 0;
 }
 
+// the update of global step g in a batch that ends before global step `end`; thermal_mode 2: from source plane *q_idx of h->d_q
+int batch_thermal(Handle* h, int64_t g, int64_t end, int thermal_mode, double dt, int use_latent, int64_t* q_idx)
+{
+    const size_t L2 = (size_t)h->L * h->L;
+    const int laser = thermal_mode == 2 ? 1 : 0, latent = laser ? use_latent : 0;
+    CHK(thermal_step(h, g, dt, laser, laser ? h->d_q + (size_t)*q_idx * L2 : nullptr, latent, 1));
+    *q_idx += laser;
+    if (g + 20 < end)      // the next update lies inside this batch (its source plane is on the device): look ahead
+        CHK(launch_thermal_ahead(h, g + 20, dt, laser, laser ? h->d_q + (size_t)*q_idx * L2 : nullptr, latent, 1));
+    return 0;
+}
+
 template <class T>
 int grow(T** p, size_t* cap, size_t need)
 {
@@ -1036,6 +1058,31 @@ int grow_pinned(char** p, size_t* cap, size_t need)
     const size_t c = std::max<size_t>(need + need / 2, 1 << 16);
     HIPCHK(hipHostMalloc((void**)p, c, hipHostMallocDefault));
     *cap = c;
+    return 0;
+}
+// the five per-step device buffers of a batch (pick / defect uniforms, the three per-step logs) for n steps
+int reserve_steps(Handle* h, size_t n)
+{
+    size_t c1 = h->cap_steps, c2 = h->cap_steps, c3 = h->cap_steps, c4 = h->cap_steps, c5 = h->cap_steps;
+    CHK(grow(&h->d_u_pick, &c1, n));
+    CHK(grow(&h->d_u_defect, &c2, n));
+    CHK(grow(&h->d_log_total, &c3, n));
+    CHK(grow(&h->d_log_event, &c4, n));
+    CHK(grow(&h->d_log_nev, &c5, n));
+    h->cap_steps = std::min({c1, c2, c3, c4, c5});
+    return 0;
+}
+// the handle's pool of timing events / the milliseconds between two of them, added to *acc
+int reserve_events(Handle* h, int64_t need)
+{
+    while ((int64_t)h->prof.size() < need) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->prof.push_back(e); }
+    return 0;
+}
+int add_elapsed(hipEvent_t ea, hipEvent_t eb, double* acc)
+{
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, ea, eb));
+    *acc += t;
     return 0;
 }
 constexpr size_t PIN_SMALL_MAX = 1 << 20;      // larger arrays (long u_np streams, many source planes) are copied directly
@@ -1101,6 +1148,13 @@ struct Ens {
     std::vector<int64_t> an_clusters, an_gathered;     // per replica, of the last analysis (-1: none yet)
     int an_species = -1;
 };
+// every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
+bool shared_params_equal(cetkmc_params a, cetkmc_params b)
+{
+    a.impurity_c = b.impurity_c = 0.0; a.nu_dep = b.nu_dep = 0.0;
+    return !memcmp(&a, &b, sizeof a);
+}
+const char* const SHARED_PARAMS_MSG = "ensemble replicas may differ in impurity_c and nu_dep only (cetkmc_params)";
 std::mutex g_ens_mu;
 std::map<const void*, Ens*> g_ens;        // ensemble handle (= replica 0's handle) -> ensemble
 
@@ -1297,21 +1351,13 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         HIPCHK(hipSetDevice(h->dev));
         h->staged.valid = false;           // growing a buffer moves it: a batch staged before this call is gone
         const size_t n = (size_t)value;
-        size_t c1 = h->cap_steps, c2 = h->cap_steps, c3 = h->cap_steps, c4 = h->cap_steps, c5 = h->cap_steps;
-        CHK(grow(&h->d_u_pick, &c1, n));
-        CHK(grow(&h->d_u_defect, &c2, n));
-        CHK(grow(&h->d_log_total, &c3, n));
-        CHK(grow(&h->d_log_event, &c4, n));
-        CHK(grow(&h->d_log_nev, &c5, n));
-        h->cap_steps = std::min({c1, c2, c3, c4, c5});
+        CHK(reserve_steps(h, n));
         CHK(grow(&h->d_u_np, &h->cap_np, 2 * n + 2 + (size_t)h->L * h->L));
         CHK(grow(&h->d_q, &h->cap_q, (n / 20 + 2) * (size_t)h->L * h->L));
         CHK(grow_pinned(&h->pin_in, &h->pin_in_cap, 2 * n * 8 + (2 * n + 2) * 8 + std::min<size_t>(PIN_SMALL_MAX, (n / 20 + 2) * (size_t)h->L * h->L * 8)));
         CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, 64 + n * (16 + sizeof(cetkmc_event)) + h->slabs.size() * sizeof(int)));
         // events: the per-phase mode (7 per step) is used on short batches only; the sampled modes need 2 per (8th) step
-        const int64_t need = std::max<int64_t>(7 * std::min<int64_t>(value, 256), value <= 64 ? 2 * value : 2 * (value / 8 + 1));
-        while ((int64_t)h->prof.size() < need) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->prof.push_back(e); }
-        return 0;
+        return reserve_events(h, std::max<int64_t>(7 * std::min<int64_t>(value, 256), value <= 64 ? 2 * value : 2 * (value / 8 + 1)));
     }
     if (!strcmp(key, "thermal_variant")) {
         // 0: one thread per voxel; 1 (default): plane marching -- k_thermal_tiles16 (16 x 256 tiles, 1024 threads, 2 rows per
@@ -1541,8 +1587,9 @@ int cetkmc_enumerate_events(void* handle, cetkmc_event* buf, int64_t cap, int64_
     return 0;
 }
 
-// host inputs of a batch -> the handle's device buffers (grown as needed); shared by cetkmc_stage_inputs / cetkmc_run_steps
-static int check_run_args(Handle* h, const cetkmc_run_args* a, bool need_ptrs, int64_t* n_therm_out)
+// argument checks / host inputs of a batch -> the handle's device buffers (grown as needed); shared by cetkmc_stage_inputs /
+// cetkmc_run_steps
+static int check_run_args(const cetkmc_run_args* a, bool need_ptrs)
 {
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
@@ -1551,26 +1598,17 @@ static int check_run_args(Handle* h, const cetkmc_run_args* a, bool need_ptrs, i
     if (need_ptrs && streams && n > 0 && !a->u_pick) return fail("u_pick required");
     if (need_ptrs && streams && a->defect_fraction > 0.0 && n > 0 && !a->u_defect) return fail("u_defect required when defect_fraction > 0");
     if (need_ptrs && streams && a->np_cap > 0 && !a->u_np) return fail("u_np required");
-    int64_t n_therm = 0;
-    if (a->thermal_mode) for (int64_t s = 0; s < n; ++s) if ((a->step0 + s) % 20 == 0) ++n_therm;
+    const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     if (a->thermal_mode == 2 && (n_therm > a->n_q || (need_ptrs && n_therm > 0 && !a->q_planes)))
         return fail("thermal_mode 2 needs one q plane per thermal update in the batch");
-    *n_therm_out = n_therm;
-    (void)h;
     return 0;
 }
 
-static int upload_run_inputs(Handle* h, const cetkmc_run_args* a, int64_t n_therm)
+static int upload_run_inputs(Handle* h, const cetkmc_run_args* a)
 {
-    const int64_t n = a->n_steps;
+    const int64_t n = a->n_steps, n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     const size_t L2 = (size_t)h->L * h->L;
-    size_t c1 = h->cap_steps, c2 = h->cap_steps, c3 = h->cap_steps, c4 = h->cap_steps, c5 = h->cap_steps;
-    CHK(grow(&h->d_u_pick, &c1, (size_t)n));
-    CHK(grow(&h->d_u_defect, &c2, (size_t)n));
-    CHK(grow(&h->d_log_total, &c3, (size_t)n));
-    CHK(grow(&h->d_log_event, &c4, (size_t)n));
-    CHK(grow(&h->d_log_nev, &c5, (size_t)n));
-    h->cap_steps = std::min({c1, c2, c3, c4, c5});
+    CHK(reserve_steps(h, (size_t)n));
     CHK(grow(&h->d_u_np, &h->cap_np, (size_t)std::max<int64_t>(a->np_cap, 2)));
     if (a->thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
     // the small arrays travel through the page-locked staging buffer (queued copies); a large one goes directly
@@ -1606,11 +1644,10 @@ int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* a)
     Handle* h = (Handle*)handle;
     if (!h || !a) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
-    int64_t n_therm = 0;
     h->staged.valid = false;
-    CHK(check_run_args(h, a, true, &n_therm));
+    CHK(check_run_args(a, true));
     HIPCHK(hipSetDevice(h->dev));
-    CHK(upload_run_inputs(h, a, n_therm));
+    CHK(upload_run_inputs(h, a));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->staged.valid = true;
     h->staged.step0 = a->step0; h->staged.n_steps = a->n_steps; h->staged.np_cap = a->np_cap; h->staged.n_q = a->n_q;
@@ -1618,17 +1655,51 @@ int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* a)
     return 0;
 }
 
-int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* res, double* totals,
-                     cetkmc_event* events, int64_t* n_events)
+// hipEvents of a profiled batch (cetkmc_run_args.profile; Handle::prof).  1: two events per step around the rate-sweep
+// kernel (bench roofline); 3: like 1 but only every 8th step (every 4th in batches of <= 64 steps) carries the two events (a
+// pair costs ~4 us of stream time); 2: seven per step (thermal | interface | sweep | reduce(+all-gather) | select+apply
+// boundaries) for cetkmc_get_counters.  An event a mode does not have is nullptr.
+struct ProfEvents {
+    static constexpr int EPS = 7;      // events per step of profile 2
+    Handle* h;
+    int mode;
+    int64_t n, stride;
+    std::vector<char> was_thermal, was_full;      // profile 2: what each step ran
+    ProfEvents(Handle* h_, int mode_, int64_t n_)
+        : h(h_), mode(mode_), n(n_), stride(mode_ == 3 ? (n_ <= 64 ? 4 : 8) : 1), was_thermal(mode_ == 2 ? (size_t)n_ : 0, 0), was_full(was_thermal) {}
+    int64_t needed() const { return mode == 2 ? EPS * n : mode ? 2 * ((n + stride - 1) / stride) : 0; }     // sampled steps only
+    bool sampled(int64_t s) const { return mode == 1 || (mode == 3 && s % stride == 0); }
+    hipEvent_t phase(int64_t s, int q) const { return mode == 2 ? h->prof[EPS * s + q] : nullptr; }
+    hipEvent_t pair(int64_t s, int q) const { return sampled(s) ? h->prof[2 * (s / stride) + q] : nullptr; }
+    hipEvent_t sweep(int64_t s, int q) const { return mode == 2 ? phase(s, 2 + q) : pair(s, q); }      // around the step's sweep / dirty-row kernel
+    int record(int64_t s, int q) const { if (mode == 2) HIPCHK(hipEventRecord(phase(s, q), h->stream)); return 0; }
+    // after the batch's synchronisation: the sweep time of the call, and (profile 2) the phase times of the counters
+    int collect(cetkmc_run_result* res) const
+    {
+        cetkmc_counters& c = h->cnt;
+        for (int64_t s = 0; s < n && mode; ++s) {
+            const bool full = mode != 2 || was_full[s];
+            if (full && sweep(s, 0)) { CHK(add_elapsed(sweep(s, 0), sweep(s, 1), &res->sweep_ms_total)); ++res->sweep_launches; }
+            if (mode != 2) continue;
+            auto ph = [&](int q, double* acc) { return add_elapsed(phase(s, q), phase(s, q + 1), acc); };
+            if (full && was_thermal[s]) CHK(ph(0, &c.ms_thermal));
+            if (full) CHK(ph(1, &c.ms_interface));
+            CHK(ph(2, full ? &c.ms_sweep : &c.ms_dirty_rows));
+            CHK(ph(3, &c.ms_reduce));
+            CHK(ph(4, &c.ms_select_apply));
+        }
+        if (mode == 2) c.profiled_steps += n;
+        return 0;
+    }
+};
+
+// cetkmc_run_steps, part 1: argument checks, the staged batch (consumed or dropped), the inputs' upload
+static int stage_run(Handle* h, const cetkmc_run_args* a)
 {
-    Handle* h = (Handle*)handle;
-    if (!h || !a || !res) return fail("null argument");
-    if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     const int64_t n = a->n_steps;
     // all input pointers NULL: the batch's inputs were put on the device by cetkmc_stage_inputs (same batch shape)
     const bool staged = n > 0 && a->rng_mode != 2 && !a->u_pick && !a->u_defect && !a->u_np && !a->q_planes;
-    int64_t n_therm = 0;
-    CHK(check_run_args(h, a, !staged, &n_therm));
+    CHK(check_run_args(a, !staged));
     const auto g = h->staged;
     h->staged.valid = false;           // a staged batch is consumed (or dropped) by the next stepping call
     if (staged) {
@@ -1638,34 +1709,15 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
             return fail("the staged batch (cetkmc_stage_inputs) does not match this call's step0 / n_steps / np_cap / n_q / thermal_mode");
     }
     HIPCHK(hipSetDevice(h->dev));
-    const size_t L2 = (size_t)h->L * h->L;
-    if (!staged) CHK(upload_run_inputs(h, a, n_therm));
-    // reset the batch part of the step state (nucleation_count persists): a one-thread kernel, no host round trip
-    StepState ss;
-    hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
+    return staged ? 0 : upload_run_inputs(h, a);
+}
 
-    BatchCfg cfg{};
-    cfg.step0 = a->step0; cfg.np_cap = a->np_cap; cfg.defect_fraction = a->defect_fraction; cfg.seed = a->seed;
-    cfg.rng_mode = a->rng_mode; cfg.batch = 1;
-    if (a->rng_mode == 2) cfg.np_cap = INT64_MAX / 2;       // no stream to run out of
-    // profile 1: two events per step around the rate-sweep kernel (bench roofline); profile 2: seven per step
-    // (thermal | interface | sweep | reduce(+all-gather) | select+apply boundaries) for cetkmc_get_counters
-    const int EPS = a->profile == 2 ? 7 : 2;
-    // profile 3: like 1 but only every 8th step (every 4th in batches of <= 64 steps) carries the two events (a pair costs
-    // ~4 us of stream time)
-    const int64_t pstride = a->profile == 3 ? (n <= 64 ? 4 : 8) : 1;
-    auto sampled = [&](int64_t s) { return a->profile == 1 || (a->profile == 3 && s % pstride == 0); };
-    if (a->profile) {
-        const int64_t need = a->profile == 2 ? EPS * n : 2 * ((n + pstride - 1) / pstride);     // sampled steps only
-        while ((int64_t)h->prof.size() < need) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->prof.push_back(e); }
-    }
-    auto pev = [&](int64_t s, int q) -> hipEvent_t { return a->profile == 2 ? h->prof[EPS * s + q] : nullptr; };
-    std::vector<char> was_thermal, was_full;
-    if (a->profile == 2) { was_thermal.assign((size_t)n, 0); was_full.assign((size_t)n, 0); }
-    h->time_comm = a->profile == 2 && multi_rank(h);
-    h->comm_ev_used = 0;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    int64_t q_idx = 0;
+// cetkmc_run_steps, part 2: the n steps queued on the stream.  therm_skip_g: the global step whose temperature update the
+// previous (stopped) batch has already applied, or -1.  *q_idx: source planes handed to updates.
+static int enqueue_steps(Handle* h, const cetkmc_run_args* a, const BatchCfg& cfg, ProfEvents& pe, int64_t therm_skip_g,
+                         cetkmc_run_result* res, int64_t* q_idx)
+{
+    const int64_t n = a->n_steps;
     const bool incr = a->incremental && h->sweep_variant >= 1;
     // the apply kernel re-evaluates the <= 30 listed voxels an event touches, which keeps every listed voxel's sum
     // current between temperature updates (the interface kernel then runs only after one); off: the interface kernel
@@ -1675,48 +1727,33 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     // sweep launch (the streaming kernel with the rate table, one slab, one process) applies the event.  The last step of the
     // call stays immediate, so no event is pending when the call returns.
     const bool pend_ok = h->apply_in_sweep && !incr && eval_touched && !multi_rank(h) && h->slabs.size() == 1 &&
-                         h->sweep_variant == 1 && !(h->sweep_auto && h->L <= 128) && h->Pk <= 256;
+                         h->sweep_variant == 1 && !(h->sweep_auto && h->L <= 128) && row_shape(h).hw;
     h->pend_live = false;
     h->pend_cfg = cfg;
-    res->full_sweeps = 0;
-    // continuation of a batch that ran out of stream on a temperature-update step: that update is already in the field
-    const int64_t therm_skip_g = h->therm_applied_g;
-    h->therm_applied_g = -1;
     for (int64_t s = 0; s < n; ++s) {
         const int64_t g = a->step0 + s;
         const bool therm_due = a->thermal_mode && g % 20 == 0;
         const bool therm = therm_due && !(s == 0 && g == therm_skip_g);
-        if (therm_due && !therm && a->thermal_mode == 2) ++q_idx;      // its source plane was consumed by the stopped batch
+        if (therm_due && !therm && a->thermal_mode == 2) ++*q_idx;      // its source plane was consumed by the stopped batch
         if (incr && s > 0 && !therm) {
             // exact incremental step: rates can only have changed in the rows recorded by the last apply
             ++h->cnt.incremental_steps;
-            if (a->profile == 2) {
-                HIPCHK(hipEventRecord(pev(s, 2), h->stream));
-                CHK(launch_dirty_rows(h, nullptr, pev(s, 3)));
-                HIPCHK(hipEventRecord(pev(s, 4), h->stream));
-                CHK(launch_select_apply(h, cfg, 1, h->d_dirty, s));
-                HIPCHK(hipEventRecord(pev(s, 5), h->stream));
-            } else {
-                CHK(launch_dirty_rows(h, sampled(s) ? h->prof[2 * (s / pstride)] : nullptr, sampled(s) ? h->prof[2 * (s / pstride) + 1] : nullptr));
-                CHK(launch_select_apply(h, cfg, 1, h->d_dirty, s));
-            }
+            CHK(pe.record(s, 2));
+            CHK(launch_dirty_rows(h, pe.pair(s, 0), pe.sweep(s, 1)));
+            CHK(pe.record(s, 4));
+            CHK(launch_select_apply(h, cfg, 1, h->d_dirty, s));
+            CHK(pe.record(s, 5));
             h->swept = false;
             continue;
         }
         ++res->full_sweeps;
-        if (a->profile == 2) { was_full[s] = 1; HIPCHK(hipEventRecord(pev(s, 0), h->stream)); }
+        if (pe.mode == 2) pe.was_full[s] = 1;
+        CHK(pe.record(s, 0));
         if (therm) {
-            const int laser = a->thermal_mode == 2 ? 1 : 0, latent = laser ? a->use_latent : 0;
-            CHK(thermal_step(h, g, a->thermal_dt, laser, laser ? h->d_q + (size_t)q_idx * L2 : nullptr, latent, 1));
-            q_idx += laser;
-            if (g + 20 < a->step0 + n)      // the next update lies inside this batch (its source plane is on the device): look ahead
-                CHK(launch_thermal_ahead(h, g + 20, a->thermal_dt, laser, laser ? h->d_q + (size_t)q_idx * L2 : nullptr, latent, 1));
-            if (a->profile == 2) was_thermal[s] = 1;
+            CHK(batch_thermal(h, g, a->step0 + n, a->thermal_mode, a->thermal_dt, a->use_latent, q_idx));
+            if (pe.mode == 2) pe.was_thermal[s] = 1;
         }
-        int rc_sw;
-        if (a->profile == 2) rc_sw = launch_sweep(h, true, pev(s, 2), pev(s, 3), false, pev(s, 1), pev(s, 4));
-        else if (sampled(s)) rc_sw = launch_sweep(h, true, h->prof[2 * (s / pstride)], h->prof[2 * (s / pstride) + 1]);
-        else rc_sw = launch_sweep(h, true);
+        const int rc_sw = launch_sweep(h, true, pe.sweep(s, 0), pe.sweep(s, 1), false, pe.phase(s, 1), pe.phase(s, 4));
         h->pend_live = false;
         CHK(rc_sw);
         if (pend_ok && s + 1 < n && !(a->thermal_mode && (g + 1) % 20 == 0)) {
@@ -1727,91 +1764,88 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
             CHK(launch_select_apply(h, cfg, (incr || eval_touched) ? 1 : 0, incr ? h->d_dirty : nullptr, s));
         }
         if (!(incr || eval_touched)) h->ifc_fresh = false;
-        if (a->profile == 2) HIPCHK(hipEventRecord(pev(s, 5), h->stream));
+        CHK(pe.record(s, 5));
         h->swept = false;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    // everything the host wants back travels behind ONE synchronisation: step state, the per-step logs (all n entries;
-    // only the first steps_done are meaningful) and the interface lists' lengths
+    return 0;
+}
+
+// cetkmc_run_steps, part 3: everything the host wants back travels behind ONE synchronisation -- step state, the per-step
+// logs (all n entries; only the first steps_done are meaningful) and the interface lists' lengths
+static int download_run(Handle* h, int64_t n, StepState* ss, double* totals, cetkmc_event* events, int64_t* n_events)
+{
     const size_t nsl = h->slabs.size();
     const size_t o_tot = 64, o_ev = o_tot + (size_t)n * 8, o_nev = o_ev + (size_t)n * sizeof(cetkmc_event), o_len = o_nev + (size_t)n * 8;
     static_assert(sizeof(StepState) <= 64, "StepState grew: move the log offsets");
     CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, o_len + nsl * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(h->pin_out, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->pin_out, h->d_ss, sizeof *ss, hipMemcpyDeviceToHost, h->stream));
     if (totals && n > 0) HIPCHK(hipMemcpyAsync(h->pin_out + o_tot, h->d_log_total, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
     if (events && n > 0) HIPCHK(hipMemcpyAsync(h->pin_out + o_ev, h->d_log_event, (size_t)n * sizeof(cetkmc_event), hipMemcpyDeviceToHost, h->stream));
     if (n_events && n > 0) HIPCHK(hipMemcpyAsync(h->pin_out + o_nev, h->d_log_nev, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    std::vector<int> list_len(nsl, 0);
     for (size_t sl = 0; sl < nsl; ++sl)
         HIPCHK(hipMemcpyAsync(h->pin_out + o_len + sl * sizeof(int), h->slabs[sl].v.ifc_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    memcpy(&ss, h->pin_out, sizeof ss);
+    memcpy(ss, h->pin_out, sizeof *ss);
     if (totals && n > 0) memcpy(totals, h->pin_out + o_tot, (size_t)n * 8);
     if (events && n > 0) memcpy(events, h->pin_out + o_ev, (size_t)n * sizeof(cetkmc_event));
     if (n_events && n > 0) memcpy(n_events, h->pin_out + o_nev, (size_t)n * 8);
-    if (nsl) memcpy(list_len.data(), h->pin_out + o_len, nsl * sizeof(int));
+    for (size_t sl = 0; sl < nsl; ++sl) {
+        int n_list = 0;
+        memcpy(&n_list, h->pin_out + o_len + sl * sizeof(int), sizeof(int));
+        grow_ifc_grid(h, n_list);
+    }
+    h->cnt.bytes_d2h += (totals ? n * 8 : 0) + (events ? n * (int64_t)sizeof(cetkmc_event) : 0) + (n_events ? n * 8 : 0);
+    return 0;
+}
+
+int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* res, double* totals,
+                     cetkmc_event* events, int64_t* n_events)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !a || !res) return fail("null argument");
+    if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
+    const int64_t n = a->n_steps;
+    CHK(stage_run(h, a));
+    // reset the batch part of the step state (nucleation_count persists): a one-thread kernel, no host round trip
+    hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
+    BatchCfg cfg{};
+    cfg.step0 = a->step0; cfg.np_cap = a->np_cap; cfg.defect_fraction = a->defect_fraction; cfg.seed = a->seed;
+    cfg.rng_mode = a->rng_mode; cfg.batch = 1;
+    if (a->rng_mode == 2) cfg.np_cap = INT64_MAX / 2;       // no stream to run out of
+    ProfEvents pe(h, a->profile, n);
+    CHK(reserve_events(h, pe.needed()));
+    h->time_comm = a->profile == 2 && multi_rank(h);
+    h->comm_ev_used = 0;
+    // continuation of a batch that ran out of stream on a temperature-update step: that update is already in the field
+    const int64_t therm_skip_g = h->therm_applied_g;
+    h->therm_applied_g = -1;
+    int64_t q_idx = 0;
+    res->full_sweeps = 0;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    CHK(enqueue_steps(h, a, cfg, pe, therm_skip_g, res, &q_idx));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    StepState ss;
+    CHK(download_run(h, n, &ss, totals, events, n_events));
     if (h->spec.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); h->spec.valid = false; }      // never outlives its batch
     if (h->time_comm) {
         for (size_t q = 0; q + 1 < h->comm_ev_used; q += 2) {
-            float t = 0.f;
-            HIPCHK(hipEventElapsedTime(&t, h->comm_ev[q], h->comm_ev[q + 1]));
-            h->cnt.ms_comm += t;
+            CHK(add_elapsed(h->comm_ev[q], h->comm_ev[q + 1], &h->cnt.ms_comm));
             ++h->cnt.comm_calls;
         }
         h->time_comm = false; h->comm_ev_used = 0;
     }
-    res->steps_done = ss.cur; res->status = ss.status; res->np_used = ss.np_pos; res->q_used = q_idx;
-    if (ss.status != 0 && a->thermal_mode == 2) {
-        // q_idx counts the planes of every update the host queued; behind an early stop those updates ran as pass-throughs
-        // and read no plane.  Consumed: the updates of the executed steps and of the step the batch stopped in (its update
-        // precedes the selection that noticed the stop).
-        int64_t q = 0;
-        for (int64_t s = 0; s <= ss.cur && s < n; ++s) q += (a->step0 + s) % 20 == 0;
-        res->q_used = q;
-    }
-    res->nucleation_count = ss.nuc_count;
-    res->min_margin = ss.min_margin;
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    res->wall_ms = ms;
-    res->sweep_ms_total = 0.0; res->sweep_launches = 0;
-    if (a->profile == 2) {
-        auto el = [&](int64_t s, int qa, int qb, double* acc) -> int {
-            float t = 0.f;
-            HIPCHK(hipEventElapsedTime(&t, h->prof[EPS * s + qa], h->prof[EPS * s + qb]));
-            *acc += t;
-            return 0;
-        };
-        for (int64_t s = 0; s < n; ++s) {
-            if (was_full[s]) {
-                if (was_thermal[s]) CHK(el(s, 0, 1, &h->cnt.ms_thermal));
-                CHK(el(s, 1, 2, &h->cnt.ms_interface));
-                CHK(el(s, 2, 3, &h->cnt.ms_sweep));
-                CHK(el(s, 3, 4, &h->cnt.ms_reduce));
-                CHK(el(s, 4, 5, &h->cnt.ms_select_apply));
-                double t = 0.0;
-                CHK(el(s, 2, 3, &t));
-                res->sweep_ms_total += t;
-                ++res->sweep_launches;
-            } else {
-                CHK(el(s, 2, 3, &h->cnt.ms_dirty_rows));
-                CHK(el(s, 3, 4, &h->cnt.ms_reduce));
-                CHK(el(s, 4, 5, &h->cnt.ms_select_apply));
-            }
-        }
-        h->cnt.profiled_steps += n;
-    } else if (a->profile) {
-        for (int64_t s = 0; s < n; ++s) {
-            if (!sampled(s)) continue;
-            float t = 0.f;
-            HIPCHK(hipEventElapsedTime(&t, h->prof[2 * (s / pstride)], h->prof[2 * (s / pstride) + 1]));
-            res->sweep_ms_total += t;
-            ++res->sweep_launches;
-        }
-    }
-    h->cnt.steps += ss.cur;
     const int64_t done = ss.cur;
+    res->steps_done = done; res->status = ss.status; res->np_used = ss.np_pos; res->q_used = q_idx;
+    // q_idx counts the planes of every update the host queued; behind an early stop those updates ran as pass-throughs
+    // and read no plane.  Consumed: the updates of the executed steps and of the step the batch stopped in (its update
+    // precedes the selection that noticed the stop).
+    if (ss.status != 0 && a->thermal_mode == 2) res->q_used = updates_in(a->step0, std::min(done + 1, n));
+    res->nucleation_count = ss.nuc_count; res->min_margin = ss.min_margin;
+    res->wall_ms = 0.0; res->sweep_ms_total = 0.0; res->sweep_launches = 0;
+    CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
+    CHK(pe.collect(res));
+    h->cnt.steps += done;
     if (ss.status != 0) {
         // the batch stopped early: the steps still queued behind the stop ran as pass-throughs (temperature copied through,
         // buffer pair flipped, rate table / interface kernels returning at once), so the host's freshness flags describe
@@ -1823,11 +1857,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
         else if (ss.status == 2 && done == 0 && a->step0 == therm_skip_g)
             h->therm_applied_g = therm_skip_g;             // still the same pending step (nothing executed, nothing updated)
     }
-    const int64_t nt = done + (ss.status == 1 ? 1 : 0);
-    if (totals && ss.status == 1 && nt <= n) totals[done] = ss.total;
-    h->cnt.bytes_d2h += (totals ? n * 8 : 0) + (events ? n * (int64_t)sizeof(cetkmc_event) : 0) + (n_events ? n * 8 : 0);
-    // the interface lists grow while stepping: keep the interface kernel's grid at one entry per thread
-    for (int n_list : list_len) h->ifc_blocks = std::max(h->ifc_blocks, std::min(8192, (n_list + 255) / 256 + 64));
+    if (totals && ss.status == 1 && done < n) totals[done] = ss.total;
     return 0;
 }
 
@@ -1883,8 +1913,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     const bool ranks = multi_rank(h) && h->nranks > 1;
     if (ranks && h->nranks > 64) return fail("Mode B supports up to 64 ranks");
     if (ranks && (h->L / h->nranks) % a->box) return fail("across ranks the boxes must be aligned to the slabs: (L / nranks) % box == 0");
-    int64_t n_therm = 0;
-    if (a->thermal_mode) for (int64_t s = 0; s < n; ++s) if ((a->step0 + s) % 20 == 0) ++n_therm;
+    const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     if (a->thermal_mode == 2 && (n_therm > a->n_q || (n_therm > 0 && !a->q_planes)))
         return fail("thermal_mode 2 needs one q plane per thermal update in the batch");
     HIPCHK(hipSetDevice(h->dev));
@@ -1905,16 +1934,8 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     const int NE = D + 2 * nb2;                               // own events | lower neighbour's top layer | upper neighbour's bottom layer
     const size_t shmem = (size_t)C.PT * C.PH * C.PH * 19;     // heap: 2*NL doubles + 2*NL flags, NL leaf codes
     h->staged.valid = false;            // the batch buffers are reused below
-    {
-        size_t c1 = h->cap_steps, c2 = h->cap_steps, c3 = h->cap_steps, c4 = h->cap_steps, c5 = h->cap_steps;
-        CHK(grow(&h->d_u_pick, &c1, (size_t)n));
-        CHK(grow(&h->d_u_defect, &c2, (size_t)n));
-        CHK(grow(&h->d_log_total, &c3, (size_t)n));
-        CHK(grow(&h->d_log_event, &c4, (size_t)n));
-        CHK(grow(&h->d_log_nev, &c5, (size_t)n));
-        h->cap_steps = std::min({c1, c2, c3, c4, c5});
-        if (a->thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
-    }
+    CHK(reserve_steps(h, (size_t)n));
+    if (a->thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
     // working buffers of the handle (grow-only; the previous call ended with a synchronisation, nothing still reads them)
     CHK(grow(&h->d_sup_rmax, &h->cap_sup_rmax, (size_t)std::max(C.nranks, 1)));
     CHK(grow(&h->d_sup_dom, &h->cap_sup_dom, (size_t)NE));
@@ -1943,11 +1964,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
         const int64_t g = a->step0 + s;
         const bool therm = a->thermal_mode && g % 20 == 0;
         if (therm) {
-            const int laser = a->thermal_mode == 2 ? 1 : 0, latent = laser ? a->use_latent : 0;
-            CHK(thermal_step(h, g, a->thermal_dt, laser, laser ? h->d_q + (size_t)q_idx * L2 : nullptr, latent, 1));
-            q_idx += laser;
-            if (g + 20 < a->step0 + n)      // the next update lies inside this batch (its source plane is on the device): look ahead
-                CHK(launch_thermal_ahead(h, g + 20, a->thermal_dt, laser, laser ? h->d_q + (size_t)q_idx * L2 : nullptr, latent, 1));
+            CHK(batch_thermal(h, g, a->step0 + n, a->thermal_mode, a->thermal_dt, a->use_latent, &q_idx));
         }
         // interface sums: the list kernel after a temperature update / when something else made them stale (list
         // rebuilt in address order first: k_domain_touch flags new interface voxels without appending them); otherwise
@@ -1992,9 +2009,9 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     if (h->spec.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); h->spec.valid = false; }
     res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = q_idx;
     res->nucleation_count = ss.nuc_count;
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    res->wall_ms = ms; res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = n; res->min_margin = 1.0;
+    res->wall_ms = 0.0;
+    CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
+    res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = n; res->min_margin = 1.0;
     h->cnt.supersteps += ss.cur;
     if (ss.status != 0) { h->table_fresh = false; h->ifc_fresh = false; h->swept = false; }     // as in cetkmc_run_steps
     CHK(refresh_ifc_grid(h));
@@ -2196,10 +2213,8 @@ int cetkmc_time_sweeps(void* handle, int n, double* ms_total)
     for (int s = 0; s < n; ++s) CHK(launch_sweep(h, false));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    *ms_total = ms;
-    return 0;
+    *ms_total = 0.0;
+    return add_elapsed(h->ev0, h->ev1, ms_total);
 }
 
 int cetkmc_event_overhead(void* handle, int n, double* ms_avg)
@@ -2207,7 +2222,7 @@ int cetkmc_event_overhead(void* handle, int n, double* ms_avg)
     Handle* h = (Handle*)handle;
     if (!h || !ms_avg || n < 1) return fail("bad argument");
     HIPCHK(hipSetDevice(h->dev));
-    while ((int)h->prof.size() < 2 * n) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->prof.push_back(e); }
+    CHK(reserve_events(h, 2 * n));
     for (int q = 0; q < n; ++q) {
         // a kernel before the pair as well: the bracketed launches of a batch follow other kernels back to back
         hipLaunchKernelGGL(k_empty, dim3(1), dim3(64), 0, h->stream);
@@ -2218,7 +2233,7 @@ int cetkmc_event_overhead(void* handle, int n, double* ms_avg)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     double tot = 0.0;
-    for (int q = 0; q < n; ++q) { float t = 0.f; HIPCHK(hipEventElapsedTime(&t, h->prof[2 * q], h->prof[2 * q + 1])); tot += t; }
+    for (int q = 0; q < n; ++q) CHK(add_elapsed(h->prof[2 * q], h->prof[2 * q + 1], &tot));
     *ms_avg = tot / n;
     return 0;
 }
@@ -2315,11 +2330,8 @@ int cetkmc_create_ensemble(const cetkmc_params* p, int L, int R, int device_id, 
     Ens* e = new Ens();
     e->L = L; e->R = R;
     auto bail = [&](int rc) { destroy_ens(e); return rc; };
-    for (int r = 1; r < R; ++r) {      // every field but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
-        cetkmc_params a = p[0], b = p[r];
-        a.impurity_c = b.impurity_c = 0.0; a.nu_dep = b.nu_dep = 0.0;
-        if (memcmp(&a, &b, sizeof a)) return bail(fail("ensemble replicas may differ in impurity_c and nu_dep only (cetkmc_params)"));
-    }
+    for (int r = 1; r < R; ++r)
+        if (!shared_params_equal(p[0], p[r])) return bail(fail(SHARED_PARAMS_MSG));
     const std::vector<std::pair<int, int>> ranges{{0, L}};
     for (int r = 0; r < R; ++r) {
         void* hv = nullptr;
@@ -2367,8 +2379,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     if (a->thermal_mode < 0 || a->thermal_mode > 2) return fail("thermal_mode must be 0 (none), 1 (diffusion) or 2 (laser source)");
     if (!a->defect_fraction) return fail("defect_fraction[R] required");
     // temperature updates of the call: the cadence is shared, so every replica's u-th update is the same global step
-    int64_t n_therm = 0;
-    if (a->thermal_mode) for (int64_t s = 0; s < n; ++s) n_therm += (a->step0 + s) % 20 == 0;
+    const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     const bool laser = a->thermal_mode == 2;
     if (laser) {       // everything about the plane sets is checked before anything is copied or launched
         if (a->n_q < n_therm) return fail("thermal_mode 2 needs one q plane per temperature update of the call in every plane set (n_q too small)");
@@ -2392,11 +2403,8 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         if (h->sweep_variant != 1 || !h->sweep_auto || h->thermal_variant != 1 || h->ifc_every_step || h->thermal_ahead)
             return fail("ensembles run the default kernel variants only (sweep_variant / thermal_variant / interface options untouched)");
     Handle* h0 = e->reps[0];
-    for (Handle* h : e->reps) {        // cetkmc_set_params on a replica must keep the shared fields shared
-        cetkmc_params x = h0->p, y = h->p;
-        x.impurity_c = y.impurity_c = 0.0; x.nu_dep = y.nu_dep = 0.0;
-        if (memcmp(&x, &y, sizeof x)) return fail("ensemble replicas may differ in impurity_c and nu_dep only (cetkmc_params)");
-    }
+    for (Handle* h : e->reps)          // cetkmc_set_params on a replica must keep the shared fields shared
+        if (!shared_params_equal(h0->p, h->p)) return fail(SHARED_PARAMS_MSG);
     HIPCHK(hipSetDevice(h0->dev));
     HIPCHK(hipStreamSynchronize(h0->stream));
     hipStream_t st = h0->stream;
@@ -2449,18 +2457,11 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         t.q = (laser && n_therm > 0) ? e->d_q + (size_t)(a->q_set ? a->q_set[r] : r) * (size_t)n_therm * L2 : nullptr;
     }
     HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)R * sizeof(EnsRep), hipMemcpyHostToDevice, st));
-    // launch shapes: those of the single-lattice path (launch_sweep / launch_table / launch_interface / launch_thermal)
-    // with the replica in y (z for the temperature kernel)
-    const Handle* hs = h0;
+    // the replica rides in y (in z, times the plane groups, for the temperature kernel)
     int ifc_blocks = 0;
     for (Handle* h : e->reps) ifc_blocks = std::max(ifc_blocks, h->ifc_blocks);
-    const int ni = hs->therm_ni, nz = (L + ni - 1) / ni;
-    const dim3 g_therm((L + THERM_KT - 1) / THERM_KT, (L + THERM_TJ - 1) / THERM_TJ, (unsigned)(nz * R));
-    const int64_t pairs = (int64_t)L * L * (hs->pitchT / 2);
-    const dim3 g_table((unsigned)std::min<int64_t>((pairs + 255) / 256, 8192), (unsigned)R);
-    const dim3 g_ifc((unsigned)ifc_blocks, (unsigned)R);
-    const dim3 g_sweep((unsigned)L, (unsigned)R);
-    const uint32_t shm_sweep = (uint32_t)(3 * L * (sizeof(double) + sizeof(int)));
+    const dim3 g_therm = thermal_grid(L, L, h0->therm_ni, R), g_table = table_grid(e->table[0].view[0], R);
+    const dim3 g_ifc((unsigned)ifc_blocks, (unsigned)R), g_sweep((unsigned)L, (unsigned)R);
     // shared arguments: rate constants / thermal settings of replica 0 (equal in every replica but impurity_c, nu_dep)
     const StreamArgs sa0{};
     const KParams kp0 = h0->kp;
@@ -2470,11 +2471,10 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const ThermalCfg tc0 = thermal_cfg(h0, a->thermal_dt, laser ? 1 : 0, latent, 1);
     const BatchCfg cfg0{};
     const dim3 g_flags((unsigned)std::min<int64_t>(((int64_t)(L + 4) * L + 255) / 256, 64), (unsigned)R);
-    EnsSel sel{e->d_table, 0, nz};
+    EnsSel sel{e->d_table, 0, (int)g_therm.z / R};
     auto table_and_interface = [&]() {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rate_table<EnsSel>), g_table, dim3(256), 0, st, kp0, v0, K0, (const StepState*)nullptr, sel);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_interface<EnsSel>), g_ifc, dim3(256), 0, st, kp0, v0, (const double*)nullptr,
-                           (const StepState*)nullptr, sel);
+        launch(k_rate_table<EnsSel>, g_table, dim3(256), 0, st, nullptr, nullptr, kp0, v0, K0, nullptr, sel);
+        launch(k_interface<EnsSel>, g_ifc, dim3(256), 0, st, nullptr, nullptr, kp0, v0, nullptr, nullptr, sel);
     };
     HIPCHK(hipEventRecord(e->ev0, st));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_reset<EnsSel>), dim3((unsigned)R), dim3(1), 0, st, (StepState*)nullptr, sel);
@@ -2485,8 +2485,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     for (int64_t s = 0; s < n; ++s) {
         const int64_t g = a->step0 + s;
         if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_thermal_march<EnsSel>), g_therm, dim3(256), 0, st, v0, (const double*)nullptr,
-                               (double*)nullptr, (uint8_t*)nullptr, (const double*)nullptr, tc0, (const StepState*)nullptr, sel);
+            launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc0, nullptr, sel);
             // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
             if (latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
             sel.rel ^= 1;
@@ -2494,13 +2493,9 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
             ++flips;
             table_and_interface();
         }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_plane<true, false, EnsSel>), g_sweep, dim3(1024), shm_sweep, st, sa0,
-                           (const StepState*)nullptr, (BlockEnt*)nullptr, sel);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_apply<true, EnsSel>), dim3((unsigned)R), dim3(256), 0, st, kp0,
-                           (const SlabView*)nullptr, 1, L, hs->PB, (const BlockEnt*)nullptr, (StepState*)nullptr, cfg0,
-                           (const double*)nullptr, (const double*)nullptr, (cetkmc_event*)nullptr, 1, (const double*)nullptr,
-                           (const double*)nullptr, (double*)nullptr, (cetkmc_event*)nullptr, (int64_t*)nullptr, 1, (int*)nullptr,
-                           (long long)s, sel);
+        launch(k_sweep_plane<true, false, EnsSel>, g_sweep, dim3(1024), plane_shmem(L), st, nullptr, nullptr, sa0, nullptr, nullptr, sel);
+        launch(k_select_apply<true, EnsSel>, dim3((unsigned)R), dim3(256), 0, st, nullptr, nullptr, kp0, nullptr, 1, L, h0->PB, nullptr,
+               nullptr, cfg0, nullptr, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, (long long)s, sel);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev1, st));
@@ -2525,7 +2520,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         h->cur ^= flips & 1;
         // the replica's freshness flags describe nothing the ensemble kernels maintained: recompute on demand
         h->table_fresh = false; h->ifc_fresh = false; h->swept = false; h->therm_applied_g = -1;
-        h->ifc_blocks = std::max(h->ifc_blocks, std::min(8192, (list_len[(size_t)r] + 255) / 256 + 64));
+        grow_ifc_grid(h, list_len[(size_t)r]);
         h->cnt.steps += q.cur;
         if (q.status == 1) e->frozen[(size_t)r] = 1;
         cetkmc_run_result& o = res[r];
@@ -2534,8 +2529,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         if (laser && t_active[(size_t)r]) {
             // planes consumed, as on a single handle: the updates of the executed steps and of the step the replica stopped
             // in (its update precedes the selection that noticed the stop); later updates were pass-throughs
-            if (q.status == 0) o.q_used = n_therm;
-            else for (int64_t s = 0; s <= q.cur && s < n; ++s) o.q_used += (a->step0 + s) % 20 == 0;
+            o.q_used = q.status == 0 ? n_therm : updates_in(a->step0, std::min(q.cur + 1, n));
         }
         o.nucleation_count = q.nuc_count; o.min_margin = q.min_margin; o.wall_ms = ms; o.full_sweeps = q.cur;
         const int64_t done = q.cur;

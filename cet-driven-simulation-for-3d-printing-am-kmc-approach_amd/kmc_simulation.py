@@ -63,13 +63,51 @@ def _check_laser(laser, where="laser"):
     return dict(laser)
 
 
+def _draw_uniforms(per, n, per_step):
+    """The host streams of n steps from the global generators: ``per`` CPython uniforms per step (pick[, defect], time) and
+    ``per_step`` NumPy uniforms per step.  Returns (generator states before the draws, draws[n, per], u_np)."""
+    py_state = random.getstate()
+    draws = np.array([random.random() for _ in range(per * n)], dtype=np.float64).reshape(n, per)
+    np_state = np.random.get_state()
+    return (py_state, np_state), draws, np.random.random(n * per_step)
+
+
+def _rewind_uniforms(saved, per, n, done, np_used):
+    """Both global generators back to what the ``done`` executed steps of ``n`` consumed (``np_used`` NumPy uniforms)."""
+    py_state, np_state = saved
+    np.random.set_state(np_state)
+    if np_used:
+        np.random.random(np_used)
+    if done < n:
+        random.setstate(py_state)
+        for _ in range(per * done):
+            random.random()
+
+
+def _nominal_gr(L, nu_dep):
+    """Nominal (G, R, R_phys, G_over_R_phys) of a run: kmc_simulation.py:229-232."""
+    G = (T_MELT - T_SUB) / (L * VOXEL_SIZE)
+    R_phys = nu_dep * ATOMIC_SPACING_W
+    return G, nu_dep * 2.74e-10 / VOXEL_SIZE, R_phys, G / R_phys
+
+
+def _write_metrics(output_prefix, rows):
+    """outputs/<prefix>/metrics.csv, and metrics_<tag>.csv beside it: plot_cet.py globs outputs/impurity_c_*/metrics_*.csv
+    (plot_cet.py:26).  Returns the first path."""
+    df = pd.DataFrame(rows)
+    output_path = os.path.join(f"outputs/{output_prefix}", "metrics.csv")
+    df.to_csv(output_path, index=False)
+    df.to_csv(os.path.join(f"outputs/{output_prefix}", f"metrics_{output_prefix.split('_')[-1]}.csv"), index=False)
+    return output_path
+
+
 def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, incremental=True, thermal_mode=1, laser=None):
     """Run steps first..last (inclusive) on the device.  Returns (steps_done, terminated,
-    last_total, dt_sum_increments) with both host generators left where the reference's would be.
+    last_total, dt_sum_increments, min_margin) with both host generators left where the reference's would be.
     ``laser``: the temperature updates are thermal_mode 2 with the scan's source planes of each batch (a plane depends on
     the global step only, so a batch continued from a status-2 stop is handed the plane of its first step again)."""
     dts = []
-    _advance_to.min_margin = 1.0
+    min_margin = 1.0
     step = first
     terminated = False
     last_total = 0.0
@@ -87,25 +125,15 @@ def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, inc
         else:
             per_step = 2
         n = max(1, min(n, _MAX_STREAM_DOUBLES // per_step))
-        py_state = random.getstate()
-        draws = np.array([random.random() for _ in range(per * n)], dtype=np.float64).reshape(n, per)
-        np_state = np.random.get_state()
-        u_np = np.random.random(n * per_step)
+        saved, draws, u_np = _draw_uniforms(per, n, per_step)
         q = laser_scan_planes(L, laser, step, n) if laser is not None else None
         res = engine.run_steps(step, n, defect_fraction, draws[:, 0], draws[:, 1] if per == 3 else None, u_np,
                                rng_mode=rng_mode, seed=seed, thermal_mode=2 if laser is not None else thermal_mode,
                                thermal_dt=THERMAL_DT, incremental=incremental, q_planes=q if q is not None and len(q) else None,
                                use_latent=bool(laser.get("latent", True)) if laser is not None else True)
         done = res["done"]
-        _advance_to.min_margin = min(_advance_to.min_margin, res["min_margin"])
-        # rewind both generators to what the executed steps consumed
-        np.random.set_state(np_state)
-        if res["np_used"]:
-            np.random.random(res["np_used"])
-        if done < n:
-            random.setstate(py_state)
-            for _ in range(per * done):
-                random.random()
+        min_margin = min(min_margin, res["min_margin"])
+        _rewind_uniforms(saved, per, n, done, res["np_used"])
         for s in range(done):
             total = res["totals"][s]
             dts.append(max(-np.log(max(1e-12, draws[s, per - 1])) / total, 1e-12))   # kmc_simulation.py:331
@@ -118,8 +146,7 @@ def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, inc
             if slack >= L * L:
                 raise RuntimeError("pre-drawn NumPy stream too small for a single step")
             slack = min(L * L, 4 * slack + 64)       # the estimate was short (candidates appeared): widen and retry
-    return step - first, terminated, last_total, dts
-
+    return step - first, terminated, last_total, dts, min_margin
 
 
 def _metrics_row(cl, counts, nuc, L, step, total_time, n_flagged, nuc_offset, cet_detected, G, R, R_phys, G_over_R_phys):
@@ -305,10 +332,7 @@ def run_kmc(
         defects_mask, defect_density = introduce_defects(state, atom_type, T, apply_to_state=False)
 
     nu_dep_eff = NU_DEP if nu_dep is None else float(nu_dep)
-    G = (T_MELT - T_SUB) / (L * VOXEL_SIZE)
-    R = nu_dep_eff * 2.74e-10 / VOXEL_SIZE
-    R_phys = nu_dep_eff * ATOMIC_SPACING_W
-    G_over_R_phys = G / R_phys
+    G, R, R_phys, G_over_R_phys = _nominal_gr(L, nu_dep_eff)
 
     params = cetkmc.default_params(impurity_c)
     params.nu_dep = nu_dep_eff
@@ -344,6 +368,11 @@ def run_kmc(
         metrics_data.append(row)
         _print_row(step, row)
 
+    def checkpoint(at, extra=None):
+        save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
+                        engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
+                        at, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected, extra=extra)
+
     while mode == "A" and next_step < n_steps:
         # next step after which the host has work: metrics (and, on multiples of
         # metrics_every, the defect-mask refresh) -- kmc_simulation.py:335-341
@@ -352,11 +381,11 @@ def run_kmc(
         stop = min(stop, n_steps - 1)
         if checkpoint_every > 0:      # also stop right before every checkpoint boundary
             stop = min(stop, (next_step // checkpoint_every + 1) * checkpoint_every - 1)
-        done, terminated, last_total, dts = _advance_to(engine, next_step, stop, L, defect_fraction, incremental=incremental,
-                                                         thermal_mode=1 if thermal_updates else 0, laser=laser)
+        done, terminated, last_total, dts, margin = _advance_to(engine, next_step, stop, L, defect_fraction, incremental=incremental,
+                                                                 thermal_mode=1 if thermal_updates else 0, laser=laser)
         for dt in dts:
             total_time += dt
-        min_margin = min(min_margin, _advance_to.min_margin)
+        min_margin = min(min_margin, margin)
         if terminated:
             step = next_step + done
             print(f"Terminating at step {step}: no valid events (rate={last_total:.2e})")
@@ -366,16 +395,11 @@ def run_kmc(
 
         is_metric_step = (step % metrics_every == 0) or (step == n_steps - 1)
         if not is_metric_step:        # a pure checkpoint stop
-            fields = engine.download()
-            save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), fields, engine.download(state=False, theta=False,
-                            phi=False, T=False, defects=True)["defects"], next_step, total_time,
-                            nuc_offset + engine.nucleation_count(), metrics_data, cet_detected)
+            checkpoint(next_step)
             continue
         metrics_row(step, step % metrics_every == 0)
         if checkpoint_every > 0 and next_step % checkpoint_every == 0:
-            save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
-                            engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
-                            next_step, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected)
+            checkpoint(next_step)
 
     if mode == "B":
         # Super-step loop.  executed = events executed so far = index of the next event; g = super-step index (octant
@@ -392,12 +416,6 @@ def run_kmc(
                 raise ValueError(f"checkpoint was written by a run with {ex}, this call asks for {mb_cfg}")
             executed, g, thermal_done = next_step, int(ex["superstep"]), int(ex["thermal_done"])
         by_events = thermal_cadence == "events" and thermal_updates
-
-        def checkpoint_b():
-            save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
-                            engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
-                            executed, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected,
-                            extra=dict(mb_cfg, superstep=g, thermal_done=thermal_done))
         while executed < n_steps:
             # super-steps until (at the earliest) the next metrics / checkpoint boundary or the end: a super-step executes
             # <= d_max events (a row is due once executed - 1 reaches the next multiple of metrics_every)
@@ -428,17 +446,12 @@ def run_kmc(
             if crossed or executed >= n_steps:
                 metrics_row(step, crossed)
             if checkpoint_every > 0 and executed // checkpoint_every > before // checkpoint_every:
-                checkpoint_b()          # after the row of this super-step: a resumed run continues with the next super-step
+                # after the row of this super-step: a resumed run continues with the next super-step
+                checkpoint(executed, dict(mb_cfg, superstep=g, thermal_done=thermal_done))
         next_step = executed
 
     if metrics_data:
-        df = pd.DataFrame(metrics_data)
-        output_path = os.path.join(output_dir, "metrics.csv")
-        df.to_csv(output_path, index=False)
-        # plot_cet.py globs outputs/impurity_c_*/metrics_*.csv (plot_cet.py:26): also emit that name
-        tag = output_prefix.split("_")[-1]
-        df.to_csv(os.path.join(output_dir, f"metrics_{tag}.csv"), index=False)
-        print(f"Metrics saved to {output_path}")
+        print(f"Metrics saved to {_write_metrics(output_prefix, metrics_data)}")
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -559,22 +572,16 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     try:
         pre = [_replica_prefix(c, L) for c in cfgs]
         gens = [_GlobalRNG(p["py_state"], p["np_state"]) for p in pre]
-        params = []
+        params, geo = [], []
         for c in cfgs:
             p = cetkmc.default_params(c["impurity_c"])
             p.nu_dep = NU_DEP if c["nu_dep"] is None else float(c["nu_dep"])
             params.append(p)
+            geo.append(_nominal_gr(L, p.nu_dep))
         ens = cetkmc.Ensemble(L, params)
         for r, p in enumerate(pre):
             ens.replica(r).upload(p["state"], p["theta"], p["phi"], p["T"], p["defects"])
         n_flagged = [int(np.sum(p["defects"])) for p in pre]
-        geo = []
-        for c in cfgs:
-            nu = NU_DEP if c["nu_dep"] is None else float(c["nu_dep"])
-            G = (T_MELT - T_SUB) / (L * VOXEL_SIZE)
-            Rg = nu * 2.74e-10 / VOXEL_SIZE
-            R_phys = nu * ATOMIC_SPACING_W
-            geo.append((G, Rg, R_phys, G / R_phys))
         for c in cfgs:
             os.makedirs(f"outputs/{c['output_prefix']}", exist_ok=True)
         df = np.array([float(c["defect_fraction"]) for c in cfgs])
@@ -620,13 +627,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                     for r in range(R):
                         if not alive[r]:
                             continue
-                        g = gens[r]
-                        with g:          # the same draws _advance_to takes, from the replica's generators
-                            py_state = random.getstate()
-                            draws[r] = np.array([random.random() for _ in range(per[r] * n)], dtype=np.float64).reshape(n, per[r])
-                            np_state = np.random.get_state()
-                            u_np[r] = np.random.random(n * per_step)
-                        saved[r] = (py_state, np_state)
+                        with gens[r]:          # from the replica's generators
+                            saved[r], draws[r], u_np[r] = _draw_uniforms(per[r], n, per_step)
                         u_pick[r] = draws[r][:, 0]
                         if per[r] == 3:
                             u_def[r] = draws[r][:, 1]
@@ -641,16 +643,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                     done = int(res["done"][r])
                     min_margin[r] = min(min_margin[r], float(res["min_margin"][r]))
                     if rng == "reference":
-                        g = gens[r]
-                        py_state, np_state = saved[r]
-                        with g:          # rewind both generators to what the executed steps consumed (as _advance_to)
-                            np.random.set_state(np_state)
-                            if res["np_used"][r]:
-                                np.random.random(int(res["np_used"][r]))
-                            if done < n:
-                                random.setstate(py_state)
-                                for _ in range(per[r] * done):
-                                    random.random()
+                        with gens[r]:
+                            _rewind_uniforms(saved[r], per[r], n, done, int(res["np_used"][r]))
                         for s in range(done):
                             total_time[r] += max(-np.log(max(1e-12, draws[r][s, per[r] - 1])) / res["totals"][r, s], 1e-12)
                     else:
@@ -694,12 +688,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         out = []
         last_ensemble_info.clear()
         for r, c in enumerate(cfgs):
-            output_dir = f"outputs/{c['output_prefix']}"
             if metrics[r]:
-                frame = pd.DataFrame(metrics[r])
-                frame.to_csv(os.path.join(output_dir, "metrics.csv"), index=False)
-                tag = c["output_prefix"].split("_")[-1]
-                frame.to_csv(os.path.join(output_dir, f"metrics_{tag}.csv"), index=False)
+                _write_metrics(c["output_prefix"], metrics[r])
             fields = ens.replica(r).download()
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))
