@@ -109,9 +109,16 @@ class FrontStats(C.Structure):
     ]
 
 
+class LayerRec(C.Structure):
+    _fields_ = [
+        ("n_occ", C.c_int64), ("n_start", C.c_int64), ("n_eq", C.c_int64), ("seg", C.c_int64 * 3), ("cut", C.c_int64 * 3),
+        ("occ_state", C.c_int64 * 4), ("gb_state", C.c_int64 * 4), ("pad", C.c_int64),
+    ]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
-                  "ens_analysis": EnsAnalysis, "front_stats": FrontStats}
+                  "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -167,6 +174,8 @@ PROTOTYPES = {
     "cetkmc_ensemble_set_defects_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cetkmc_front_stats": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "cetkmc_ensemble_front_stats": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "cetkmc_layer_profile": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "cetkmc_ensemble_layer_profile": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
 }
 
 

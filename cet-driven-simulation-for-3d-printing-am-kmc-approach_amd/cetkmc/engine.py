@@ -13,6 +13,9 @@ FRONT_DTYPE = np.dtype([("n_front", "<i8"), ("n_skipped", "<i8"), ("pos_sum", "<
                         ("G_max", "<f8"), ("Gi_sum", "<f8"), ("T_sum", "<f8"), ("n_melt", "<i8"), ("melt_bbox", "<i4", 6)],
                        align=True)
 assert FRONT_DTYPE.itemsize == C.sizeof(_lib.FrontStats) == 112
+LAYER_DTYPE = np.dtype([("n_occ", "<i8"), ("n_start", "<i8"), ("n_eq", "<i8"), ("seg", "<i8", 3), ("cut", "<i8", 3),
+                        ("occ_state", "<i8", 4), ("gb_state", "<i8", 4), ("pad", "<i8")])
+assert LAYER_DTYPE.itemsize == C.sizeof(_lib.LayerRec) == 144
 
 TYPE_BYTES = (b"dep", b"diff", b"nuc", b"att")   # kmc_event_rates.py:72,109,132,158
 
@@ -48,6 +51,11 @@ def _ptr(a):
 
 def _dptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _default_ar_threshold():
+    import constants as K
+    return K.CET_AR_THRESHOLD
 
 
 def _default_inv_dx():
@@ -380,6 +388,21 @@ class Engine:
         rec = buf[0]
         return {n: (rec[n].copy() if rec[n].ndim else rec[n].item()) for n in FRONT_DTYPE.names}
 
+    def layer_profile(self, threshold=0.5, ar_threshold=None, recluster=True):
+        """cetkmc_layer_profile (layer-resolved grain structure) of the resident lattice: a dict of
+        int64 arrays with leading dimension L (plane i of the build direction) -- n_occ, n_start, n_eq (L,), seg, cut (L, 3),
+        occ_state, gb_state (L, 4).  Clusters first with ``threshold`` unless ``recluster`` is False, which reuses the
+        handle's last clustering (Engine.clusters; the lattice must not have changed since).  ``ar_threshold`` defaults to
+        constants.CET_AR_THRESHOLD.  metrics.layer_metrics turns it into the row's columns.  The ensemble's own handle
+        (replica 0) is refused: Ensemble.layer_profile covers every replica."""
+        if recluster:
+            n = C.c_int64(0)
+            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+        buf = np.zeros(max(self.L, 1), dtype=LAYER_DTYPE)
+        self._ck(self.lib.cetkmc_layer_profile(self.h, float(_default_ar_threshold() if ar_threshold is None else ar_threshold),
+                                               _ptr(buf)))
+        return {n: buf[n].copy() for n in LAYER_DTYPE.names if n != "pad"}
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -561,6 +584,17 @@ class Ensemble:
         buf = np.zeros(max(self.R, 1), dtype=FRONT_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_front_stats(self.h, float(_default_inv_dx() if inv_dx is None else inv_dx), _ptr(buf)))
         return {n: buf[n][:self.R].copy() for n in FRONT_DTYPE.names}
+
+    def layer_profile(self, threshold=0.5, ar_threshold=None, recluster=True):
+        """cetkmc_ensemble_layer_profile: Engine.layer_profile of every replica (frozen ones included) in launches that do
+        not depend on R.  A dict of int64 arrays with leading dimensions (R, L).  Runs :meth:`analyze` first (without
+        downloading labels) unless ``recluster`` is False, which reuses the last analysis."""
+        if recluster:
+            self.analyze(threshold, labels=False)
+        buf = np.zeros((max(self.R, 1), self.L), dtype=LAYER_DTYPE)
+        self._ck(self.lib.cetkmc_ensemble_layer_profile(
+            self.h, float(_default_ar_threshold() if ar_threshold is None else ar_threshold), _ptr(buf)))
+        return {n: buf[n][:self.R].copy() for n in LAYER_DTYPE.names if n != "pad"}
 
     def set_defects_sparse(self, lists):
         """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""

@@ -27,6 +27,7 @@
 #include "superstep.hpp"
 #include "ensemble.hpp"
 #include "front.hpp"
+#include "layer.hpp"
 
 using namespace cetkmc;
 
@@ -1145,6 +1146,9 @@ struct Ens {
     unsigned long long *d_counts = nullptr, *d_g_n = nullptr;
     FrontPart* d_front_part = nullptr;   // cetkmc_ensemble_front_stats: [R][blocks of a lattice] partials, [R] results
     FrontStats* d_front_out = nullptr;
+    LayerRec *d_layer_part = nullptr, *d_layer_out = nullptr;   // cetkmc_ensemble_layer_profile: [R][L][tiles] partials, [R][L] records
+    uint8_t* d_layer_eq = nullptr;       // class byte of every replica's grains (offs[r] + r + id)
+    size_t cap_layer_eq = 0;
     std::vector<int64_t> an_clusters, an_gathered;     // per replica, of the last analysis (-1: none yet)
     int an_species = -1;
 };
@@ -1173,7 +1177,8 @@ void destroy_ens(Ens* e)
     }
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
-                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_front_part, e->d_front_out};
+                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_front_part, e->d_front_out,
+                    e->d_layer_part, e->d_layer_out, e->d_layer_eq};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1217,7 +1222,7 @@ int cetkmc_struct_size(const char* name)
     SZ("params", cetkmc_params); SZ("event", cetkmc_event); SZ("sweep_info", cetkmc_sweep_info);
     SZ("run_args", cetkmc_run_args); SZ("run_result", cetkmc_run_result); SZ("super_args", cetkmc_super_args);
     SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm); SZ("ens_args", cetkmc_ens_args); SZ("ens_analysis", cetkmc_ens_analysis);
-    SZ("front_stats", struct cetkmc_front_stats);
+    SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec);
 #undef SZ
     return -1;
 }
@@ -2551,6 +2556,7 @@ static int ens_push_views(Ens* e)
         Handle* h = e->reps[(size_t)r];
         e->table[(size_t)r].view[0] = view_of(h, 0, h->cur);
         e->table[(size_t)r].view[1] = view_of(h, 0, h->cur ^ 1);
+        e->table[(size_t)r].ss = h->d_ss;      // k_ens_collect reads it: an analysis may precede the ensemble's first run
     }
     HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)e->R * sizeof(EnsRep), hipMemcpyHostToDevice, e->reps[0]->stream));
     return 0;
@@ -2766,6 +2772,71 @@ int cetkmc_ensemble_front_stats(void* handle, double inv_dx, struct cetkmc_front
     HIPCHK(hipMemcpyAsync(out, e->d_front_out, (size_t)R * sizeof(FrontStats), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     h0->cnt.bytes_d2h += (int64_t)R * (int64_t)sizeof(FrontStats);
+    return 0;
+}
+
+// ---- layer-resolved grain structure (layer.hpp) ------------------------------------------------
+static dim3 layer_grid(int L, int R)
+{
+    return dim3((unsigned)(((L + LAYER_TJ - 1) / LAYER_TJ) * ((L + LAYER_TK - 1) / LAYER_TK)), (unsigned)((L + LAYER_NI - 1) / LAYER_NI),
+                (unsigned)R);
+}
+
+int cetkmc_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !out) return fail("null argument");
+    if (ens_of(handle)) return fail("cetkmc_layer_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_layer_profile");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_layer_profile needs the whole lattice in one slab");
+    if (h->cc_n_clusters < 0) return fail("cetkmc_layer_profile needs a preceding cetkmc_cluster");
+    HIPCHK(hipSetDevice(h->dev));
+    const int L = h->L, nc = (int)h->cc_n_clusters;
+    const dim3 g = layer_grid(L, 1);
+    DevTmp<uint8_t> eq;
+    DevTmp<LayerRec> part, d_out;
+    HIPCHK(eq.alloc((size_t)nc + 1));
+    HIPCHK(part.alloc((size_t)L * g.x));
+    HIPCHK(d_out.alloc((size_t)L));
+    hipLaunchKernelGGL(k_layer_class, dim3((unsigned)(nc / 256 + 1)), dim3(256), 0, h->stream, (const int*)h->d_cc_stats, nc, ar_threshold, eq.p);
+    hipLaunchKernelGGL(k_layer_profile, g, dim3(256), 0, h->stream, view_of(h, 0), (const int*)h->d_cc_labels, (const int*)h->d_cc_roots,
+                       (const uint8_t*)eq.p, part.p);
+    hipLaunchKernelGGL(k_layer_fold, dim3((unsigned)L, 1), dim3(64), 0, h->stream, (const LayerRec*)part.p, (int)g.x, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)L * sizeof(LayerRec), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cnt.bytes_d2h += (int64_t)L * (int64_t)sizeof(LayerRec);
+    return 0;
+}
+
+int cetkmc_ensemble_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out)
+{
+    if (!handle || !out) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_layer_profile needs a preceding cetkmc_ensemble_analyze");
+    const int R = e->R, L = e->L;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    const dim3 g = layer_grid(L, R);
+    int64_t total = 0, maxc = 0;
+    for (int r = 0; r < R; ++r) { total += e->an_clusters[(size_t)r]; maxc = std::max(maxc, e->an_clusters[(size_t)r]); }
+    if (!e->d_layer_part) {
+        HIPCHK(hipMalloc((void**)&e->d_layer_part, (size_t)R * L * g.x * sizeof(LayerRec)));
+        HIPCHK(hipMalloc((void**)&e->d_layer_out, (size_t)R * L * sizeof(LayerRec)));
+    }
+    CHK(grow(&e->d_layer_eq, &e->cap_layer_eq, (size_t)(total + R)));
+    CHK(ens_push_views(e));
+    EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer_class<EnsSel>), dim3((unsigned)std::min<int64_t>(maxc / 256 + 1, 4096), (unsigned)R), dim3(256), 0, st,
+                       (const int*)e->d_cc_stats, 0, ar_threshold, e->d_layer_eq, sel);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer_profile<EnsSel>), g, dim3(256), 0, st, SlabView{}, (const int*)e->d_cc_labels,
+                       (const int*)e->d_cc_roots, (const uint8_t*)e->d_layer_eq, e->d_layer_part, sel);
+    hipLaunchKernelGGL(k_layer_fold, dim3((unsigned)L, (unsigned)R), dim3(64), 0, st, (const LayerRec*)e->d_layer_part, (int)g.x, e->d_layer_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, e->d_layer_out, (size_t)R * L * sizeof(LayerRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h0->cnt.bytes_d2h += (int64_t)R * L * (int64_t)sizeof(LayerRec);
     return 0;
 }
 

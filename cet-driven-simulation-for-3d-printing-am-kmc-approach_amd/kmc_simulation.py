@@ -31,7 +31,8 @@ from defects import draw_defect_sites, introduce_defects, refresh_defects_device
 from kmc_event_rates import get_event_rates  # noqa: F401  (re-exported like the reference)
 from lattice_init import initialize_lattice
 from metrics import (compute_CET, compute_metrics, compute_metrics_device, compute_metrics_from_clusters,  # noqa: F401
-                     detect_CET_transition, front_metrics as _front_metrics, front_velocity as _front_velocity)
+                     detect_CET_transition, front_metrics as _front_metrics, front_velocity as _front_velocity,
+                     layer_metrics as _layer_metrics, write_layers_csv as _write_layers_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
@@ -190,6 +191,15 @@ def _add_front_columns(row, stats, L, prev):
     return row
 
 
+def _add_layer_columns(row, profile, L):
+    """layer_metrics=True: the layer columns (metrics.LAYER_COLUMNS) behind every other column of ``row``, in place;
+    returns the per-plane table of the row (the rows of layers.csv)."""
+    m = _layer_metrics(profile, L, VOXEL_SIZE)
+    planes = m.pop("planes")
+    row.update(m)
+    return planes
+
+
 def _print_row(step, row):
     print(
         f"Step {step}: AR={row['AspectRatio']:.2f}, "
@@ -257,6 +267,7 @@ def run_kmc(
     thermal_updates: bool = True,
     laser: dict = None,
     front_metrics: bool = False,
+    layer_metrics: bool = False,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -299,7 +310,13 @@ def run_kmc(
     measured front columns of metrics.front_metrics -- temperature gradient at the growth front, front position, melt-pool
     size, reduced on the device by cetkmc_front_stats (112 bytes cross PCIe per row) -- and ``V_front`` = (Front_i - the
     previous row's) * VOXEL_SIZE / (Time - the previous row's) in m/s (0.0 on the first row, for a zero time difference or
-    when either row has no front; a resumed run takes the previous row from the checkpoint's rows)."""
+    when either row has no front; a resumed run takes the previous row from the checkpoint's rows).
+
+    ``layer_metrics=True`` (both modes, with and without ``laser``): every metrics row gains, behind its 18 columns (and
+    behind the front columns), the layer columns of metrics.layer_metrics -- the CET height, the equiaxed area fraction,
+    the mean intercept lengths along and across the build direction and the species-resolved grain-boundary fractions --
+    from the row's own clustering, reduced on the device by cetkmc_layer_profile (L * 144 bytes cross PCIe per row); the
+    per-plane table of the last row is written to ``outputs/<prefix>/layers.csv``."""
     import cetkmc
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
@@ -350,6 +367,7 @@ def run_kmc(
     step = -1
     next_step = 0
     nuc_offset = 0
+    layer_planes = None
     if ckpt:
         total_time, metrics_data, cet_detected = ckpt["total_time"], ckpt["metrics_data"], ckpt["cet_detected"]
         next_step, nuc_offset = ckpt["next_step"], ckpt["nucleation_count"]
@@ -357,7 +375,7 @@ def run_kmc(
     def metrics_row(step, refresh_defects):
         """kmc_simulation.py:335-389 for the lattice as it stands after event index `step` -- WITHOUT moving the lattice: the
         defect mask is refreshed from the carbon sites only, grains are clustered and species counted on the GPU."""
-        nonlocal n_flagged, cet_detected
+        nonlocal n_flagged, cet_detected, layer_planes
         if refresh_defects:
             n_flagged, _ = refresh_defects_device(engine)       # kmc_simulation.py:335-338
         row = _metrics_row(engine.clusters(0.5, labels=True), engine.species_counts(), engine.nucleation_count(), L, step,
@@ -365,6 +383,8 @@ def run_kmc(
         cet_detected = row["CET_Detected"]
         if front_metrics:
             _add_front_columns(row, engine.front_stats(), L, metrics_data[-1] if metrics_data else None)
+        if layer_metrics:               # from the clustering of this row: no second clustering, no label download
+            layer_planes = _add_layer_columns(row, engine.layer_profile(recluster=False), L)
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -452,6 +472,8 @@ def run_kmc(
 
     if metrics_data:
         print(f"Metrics saved to {_write_metrics(output_prefix, metrics_data)}")
+    if layer_planes is not None:
+        _write_layers_csv(os.path.join(output_dir, "layers.csv"), layer_planes)
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -550,7 +572,7 @@ def _replica_prefix(cfg, L):
 
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
-                     front_metrics=False):
+                     front_metrics=False, layer_metrics=False):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -563,7 +585,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     ``rng="counter"``: replica r equals ``run_kmc(L=L, n_steps=n_steps, mode="B", box=L, thermal_cadence="supersteps",
     **configs[r])`` -- all-counter uniforms, the host draws nothing per step.  The caller's global generator states are
     restored on return.  One completion line is printed per replica (no per-row progress).
-    ``front_metrics=True``: run_kmc's option of that name, from ONE batched cetkmc_ensemble_front_stats call per metrics row."""
+    ``front_metrics=True``: run_kmc's option of that name, from ONE batched cetkmc_ensemble_front_stats call per metrics row.
+    ``layer_metrics=True``: run_kmc's option of that name (columns and ``layers.csv`` of every replica), from ONE batched
+    cetkmc_ensemble_layer_profile call per metrics row on the row's own analysis."""
     import cetkmc
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
@@ -594,6 +618,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         min_margin = [1.0] * R
         metrics = [[] for _ in range(R)]
         cet = [False] * R
+        layer_planes = [None] * R
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -672,6 +697,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                         n_flagged[r] = int(len(lists[r]))
                 ens.set_defects_sparse(lists)
             fs = ens.front_stats() if front_metrics else None
+            lp = ens.layer_profile(recluster=False) if layer_metrics else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -682,6 +708,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 cet[r] = row["CET_Detected"]
                 if fs is not None:
                     _add_front_columns(row, {k: v[r] for k, v in fs.items()}, L, metrics[r][-1] if metrics[r] else None)
+                if lp is not None:
+                    layer_planes[r] = _add_layer_columns(row, {k: v[r] for k, v in lp.items()}, L)
                 metrics[r].append(row)
             next_step = stop + 1
 
@@ -690,6 +718,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         for r, c in enumerate(cfgs):
             if metrics[r]:
                 _write_metrics(c["output_prefix"], metrics[r])
+            if layer_planes[r] is not None:
+                _write_layers_csv(os.path.join(f"outputs/{c['output_prefix']}", "layers.csv"), layer_planes[r])
             fields = ens.replica(r).download()
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))

@@ -8,6 +8,7 @@ outside the accelerated path and are not part of this package.
     python main.py [--L 30] [--steps 20000] [--levels 0.0 0.1 0.2] [--plots] [--mode B --box 8]
     python main.py --ensemble [--rng counter]     # all carbon levels as one replica ensemble (run_kmc_ensemble)
     python main.py --front                        # every metrics.csv with the measured front columns (run_kmc front_metrics)
+    python main.py --layers                       # layer columns in every metrics.csv and a layers.csv per level (run_kmc layer_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
 every level like ``--mode B --box L`` with the super-step thermal cadence.
@@ -44,13 +45,15 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
-         **run_kw):
+         layers=False, **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
     summary = {"carbon_levels": [], "grain_sizes": [], "defect_densities": [], "aspect_ratios": []}
     ens_out, ens_t = None, 0.0
     fm = {"front_metrics": True} if front else {}     # --front: measured front columns in every metrics.csv (run_kmc)
+    if layers:                                        # --layers: layer columns and layers.csv (run_kmc layer_metrics)
+        fm["layer_metrics"] = True
     if ensemble:                  # every level in one replica ensemble; the per-level epilogue below reads its results
         for c in carbon_levels:
             prefix = f"impurity_c_{int(c * 100)}"
@@ -113,6 +116,7 @@ if __name__ == "__main__":
     ap.add_argument("--rng", choices=("reference", "counter"), default="reference",
                     help="--ensemble: reference streams (= the sequential run's files) or counter uniforms (= --mode B --box L)")
     ap.add_argument("--front", action="store_true", help="measured front columns (G, V, melt pool) in every metrics.csv")
+    ap.add_argument("--layers", action="store_true", help="layer columns (CET height, intercepts, GB fractions) and layers.csv")
     a = ap.parse_args()
-    main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front,
+    main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers,
          **(dict(mode="B", box=a.box) if a.mode == "B" else {}))

@@ -173,6 +173,74 @@ def front_metrics(stats, L, voxel_size=VOXEL_SIZE):
     }
 
 
+LAYER_COLUMNS = ("CET_plane", "CET_height_um", "EqAreaFrac", "Intercept_build_um", "Intercept_plane_um", "InterceptRatio",
+                 "GB_frac_W", "GB_frac_Re", "GB_frac_C")
+
+
+def layer_metrics(profile, L, voxel_size=VOXEL_SIZE):
+    """Columns of a metrics row (LAYER_COLUMNS) from one lattice's layer profile (Engine.layer_profile, or entry r of every
+    array of Ensemble.layer_profile), plus the per-plane arrays under "planes" (the rows of layers.csv).
+
+    EqAreaFrac: voxels of equiaxed grains over occupied voxels.  CET_plane: the lowest occupied plane from which on every
+    occupied plane has more than CET_EQ_THRESHOLD of its occupied voxels in equiaxed grains (-1: none); CET_height_um its
+    height (-1.0: none).  Intercept_build_um / Intercept_plane_um: mean intercept length (occupied voxels per grain
+    segment of the test lines) along the build direction / averaged over the two in-plane axes; InterceptRatio build over
+    plane (> 1: elongated along the build direction).  GB_frac_W / _Re / _C: of the voxels of that species, the fraction
+    with a face neighbour in another grain or empty (metrics.compute_boundary_fraction with grain_ids = labels).  Every
+    ratio with a zero denominator is 0.0."""
+    n_occ = np.asarray(profile["n_occ"], dtype=np.int64).reshape(L)
+    n_eq = np.asarray(profile["n_eq"], dtype=np.int64).reshape(L)
+    seg = np.asarray(profile["seg"], dtype=np.int64).reshape(L, 3)
+    occ_state = np.asarray(profile["occ_state"], dtype=np.int64).reshape(L, 4)
+    gb_state = np.asarray(profile["gb_state"], dtype=np.int64).reshape(L, 4)
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else 0.0
+
+    tot = int(n_occ.sum())
+    cet = -1
+    for i in range(L - 1, -1, -1):              # downwards from the top: the run of equiaxed planes that reaches it
+        if n_occ[i] == 0:
+            continue
+        if ratio(n_eq[i], n_occ[i]) > CET_EQ_THRESHOLD:
+            cet = i
+        else:
+            break
+    build = ratio(tot, int(seg[:, 0].sum())) * voxel_size * 1e6
+    plane = ratio(2 * tot, int(seg[:, 1].sum() + seg[:, 2].sum())) * voxel_size * 1e6
+    occ_t, gb_t = occ_state.sum(axis=0), gb_state.sum(axis=0)
+    out = {
+        "CET_plane": cet, "CET_height_um": cet * voxel_size * 1e6 if cet >= 0 else -1.0,
+        "EqAreaFrac": ratio(int(n_eq.sum()), tot),
+        "Intercept_build_um": build, "Intercept_plane_um": plane, "InterceptRatio": ratio(build, plane),
+        "GB_frac_W": ratio(gb_t[0], occ_t[0]), "GB_frac_Re": ratio(gb_t[1], occ_t[1]), "GB_frac_C": ratio(gb_t[2], occ_t[2]),
+    }
+    planes = {"plane": np.arange(L, dtype=np.int64), "n_occ": n_occ,
+              "n_start": np.asarray(profile["n_start"], dtype=np.int64).reshape(L), "n_eq": n_eq,
+              "EqAreaFrac_i": np.array([ratio(a, b) for a, b in zip(n_eq.tolist(), n_occ.tolist())], dtype=np.float64)}
+    cut = np.asarray(profile["cut"], dtype=np.int64).reshape(L, 3)
+    for a in range(3):
+        planes[f"seg{a}"] = seg[:, a]
+    for a in range(3):
+        planes[f"cut{a}"] = cut[:, a]
+    for t, name in enumerate(("W", "Re", "C", "defect")):
+        planes[f"occ_{name}"] = occ_state[:, t]
+        planes[f"gb_{name}"] = gb_state[:, t]
+    out["planes"] = planes
+    return out
+
+
+def write_layers_csv(path, planes):
+    """The per-plane table of :func:`layer_metrics` (its "planes" entry) as a CSV with one row per plane."""
+    import csv
+    names = list(planes)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(names)
+        for i in range(len(planes["plane"])):
+            w.writerow([planes[n][i].item() for n in names])
+
+
 def front_velocity(row, prev, voxel_size=VOXEL_SIZE):
     """V_front of a metrics row: (Front_i - the previous row's) * voxel_size / (Time - the previous row's) in m/s; 0.0 on
     the first row (``prev`` None), when the time difference is 0 or when either row has no front."""

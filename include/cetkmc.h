@@ -187,7 +187,7 @@ int cetkmc_abi_version(void);
  * hand build): the binding compares it with the sources beside it and rebuilds / refuses a stale library */
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
- * "host_comm", "ens_args", "ens_analysis", "front_stats"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the apply-in-sweep row patch are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -363,7 +363,7 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
  * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
  * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
  * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*,
- * front_stats) except the
+ * front_stats, layer_profile) except the
  * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
  * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
  * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
@@ -443,6 +443,41 @@ int cetkmc_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* o
 /* Every replica of an ensemble, frozen ones included, in a launch sequence that does not depend on R; out[R].  A
  * single-lattice handle is refused. */
 int cetkmc_ensemble_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out);
+
+/* Layer-resolved grain structure (not in the reference): one record of integer counters per plane i
+ * of the build direction (axis 0), from the label volume and the per-grain table of the handle's LAST clustering and the
+ * lattice's state, in one streaming pass on the device.  g(v) is the label of voxel v = (i, j, k) (0 = empty, ids 1..n as
+ * cetkmc_cluster_stats / _labels number them), s(v) its state.  Only voxels with g(v) != 0 count, each in the record of its
+ * own plane:
+ *   n_occ        +1;
+ *   n_start      +1 if v is its grain's first voxel in row-major order;
+ *   n_eq         +1 if its grain is equiaxed: (double)max(d) / (double)max(min(d), 1) < ar_threshold over the extents
+ *                d = max - min + 1 of the grain's bounding box (the expression of metrics.compute_metrics_from_clusters);
+ *   seg[a]       +1 if the predecessor u of v along axis a (that coordinate minus 1) is outside the lattice or
+ *                g(u) != g(v): a grain segment of a line along axis a starts here;
+ *   cut[a]       +1 if u is inside, g(u) != 0 and g(u) != g(v): a grain-grain boundary crossed by that line;
+ *   occ_state[t-1]  +1 for t = s(v) in 1..4;
+ *   gb_state[t-1]   +1 if in addition one of the six face neighbours of v inside the lattice has a label other than g(v)
+ *                (label 0 counts as other): metrics.compute_boundary_fraction's rule with grain_ids = labels.
+ * Everything is integer counting: the result is defined to the bit.  pad is 0.
+ * The profile describes the lattice as it was clustered: for a lattice changed since that clustering (stepping, uploads)
+ * the result is unspecified (the call stays inside its arrays).
+ * (A struct tag without a typedef, as cetkmc_front_stats.) */
+struct cetkmc_layer_rec {
+    int64_t n_occ, n_start, n_eq;
+    int64_t seg[3], cut[3];
+    int64_t occ_state[4], gb_state[4];
+    int64_t pad;
+};
+/* One lattice: a single-slab, single-process handle or a replica handle, after cetkmc_cluster on that handle (without
+ * one the call fails as cetkmc_cluster_labels does; multi-slab and multi-rank handles are refused).  The handle
+ * cetkmc_create_ensemble returned is refused here although it addresses replica 0 elsewhere: replica 0's profile is entry 0
+ * of the batched call.  out[L].  Ordered on the handle's stream behind pending stepping work; copies
+ * L * sizeof(struct cetkmc_layer_rec) to the host (counted in bytes_d2h); writes no lattice field. */
+int cetkmc_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out);
+/* Every replica of an ensemble, frozen ones included, from the clustering of the last cetkmc_ensemble_analyze (required),
+ * in a launch sequence that does not depend on R; out[R][L].  A single-lattice handle is refused. */
+int cetkmc_ensemble_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out);
 
 #ifdef __cplusplus
 }
