@@ -176,6 +176,8 @@ PROTOTYPES = {
     "cetkmc_ensemble_front_stats": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "cetkmc_layer_profile": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "cetkmc_ensemble_layer_profile": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "cetkmc_cluster_import": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int64)]),
+    "cetkmc_ensemble_cluster_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -357,6 +357,23 @@ class Engine:
             out["labels"] = lab
         return out
 
+    def import_clusters(self, labels):
+        """cetkmc_cluster_import: install ``labels`` (L, L, L) -- 0 = empty, ids 1..n numbered by first occurrence in
+        row-major order; anything else is refused with the offending voxel named -- as the handle's last clustering, for
+        ``layer_profile(recluster=False)`` and the table calls.  Labels are not checked against the state.  Returns the
+        table as ``clusters(labels=False)`` does: dict(first, size, bbox)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        assert lab.shape == (self.L,) * 3, lab.shape
+        n = C.c_int64(0)
+        self._ck(self.lib.cetkmc_cluster_import(self.h, _ptr(lab), C.byref(n)))
+        k = n.value
+        first = np.zeros((max(k, 1), 3), np.int32)
+        size = np.zeros(max(k, 1), np.int64)
+        bbox = np.zeros((max(k, 1), 6), np.int32)
+        if k:
+            self._ck(self.lib.cetkmc_cluster_stats(self.h, k, _ptr(first), _ptr(size), _ptr(bbox)))
+        return dict(first=first[:k], size=size[:k], bbox=bbox[:k])
+
     # -- sparse site queries (defect model / species counts without full-lattice transfers) -------
     def species_counts(self):
         c = np.zeros(6, np.int64)
@@ -577,6 +594,23 @@ class Ensemble:
             c0 += k
             out.append(d)
         return out
+
+    def import_clusters(self, labels):
+        """cetkmc_ensemble_cluster_import: Engine.import_clusters for every replica at once, ``labels`` (R, L, L, L), in
+        place of the clustering of the last :meth:`analyze` (required; its counts and gather stay).  One bad replica
+        refuses the call and leaves the analysis as it was.  Returns one dict(first, size, bbox) per replica."""
+        R = self.R
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        assert lab.shape == (R,) + (self.L,) * 3, lab.shape
+        nc = np.zeros(max(R, 1), np.int64)
+        self._ck(self.lib.cetkmc_ensemble_cluster_import(self.h, _ptr(lab), _ptr(nc)))
+        tot = int(nc[:R].sum())
+        first = np.zeros((max(tot, 1), 3), np.int32)
+        size = np.zeros(max(tot, 1), np.int64)
+        bbox = np.zeros((max(tot, 1), 6), np.int32)
+        self._ck(self.lib.cetkmc_ensemble_analysis_data(self.h, _ptr(first), _ptr(size), _ptr(bbox), None, None, None))
+        at = np.concatenate(([0], np.cumsum(nc[:R])))
+        return [dict(first=first[at[r]:at[r + 1]], size=size[at[r]:at[r + 1]], bbox=bbox[at[r]:at[r + 1]]) for r in range(R)]
 
     def front_stats(self, inv_dx=None):
         """cetkmc_ensemble_front_stats: Engine.front_stats of every replica (frozen ones included) in launches that do not

@@ -2034,6 +2034,19 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
 }
 
 // ---- grain clustering (utils.get_clusters / dfs_cluster, utils.py:28-84) ---------------------------
+// the per-voxel arrays of a handle's clustering (all at once: d_cc_parent stands for the five)
+static int cc_alloc(Handle* h)
+{
+    if (h->d_cc_parent) return 0;
+    const int64_t n = (int64_t)h->L * h->L * h->L;
+    HIPCHK(hipMalloc((void**)&h->d_cc_parent, n * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&h->d_cc_roots, n * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&h->d_cc_cid, n * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&h->d_cc_labels, n * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&h->d_cc_n, sizeof(int)));
+    return 0;
+}
+
 int cetkmc_cluster(void* handle, double threshold, int64_t* n_clusters)
 {
     Handle* h = (Handle*)handle;
@@ -2042,13 +2055,7 @@ int cetkmc_cluster(void* handle, double threshold, int64_t* n_clusters)
     HIPCHK(hipSetDevice(h->dev));
     const SlabView v = view_of(h, 0);
     const int64_t n = (int64_t)h->L * h->L * h->L;
-    if (!h->d_cc_parent) {
-        HIPCHK(hipMalloc((void**)&h->d_cc_parent, n * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->d_cc_roots, n * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->d_cc_cid, n * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->d_cc_labels, n * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->d_cc_n, sizeof(int)));
-    }
+    CHK(cc_alloc(h));
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
     HIPCHK(hipMemsetAsync(h->d_cc_n, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_cc_init, dim3(grid), dim3(256), 0, h->stream, v, h->d_cc_parent);
@@ -2103,6 +2110,67 @@ int cetkmc_cluster_labels(void* handle, int32_t* labels)
     if (!h || !labels) return fail("null argument");
     if (h->cc_n_clusters < 0) return fail("cetkmc_cluster_labels needs a preceding cetkmc_cluster");
     HIPCHK(hipMemcpy(labels, h->d_cc_labels, (size_t)h->L * h->L * h->L * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- imported labellings -----------------------------------------------------------------------
+// One host pass over a label volume of L^3 voxels: refuses anything but ids numbered 1, 2, .. by first occurrence in row-major
+// order (0 = empty) -- so no label is negative or beyond n, every id 1..n is present and the roots come out ascending, which
+// is what k_layer_profile's roots[g - 1] / eq[g] lookups and its n_start shortcut rely on -- and derives what cetkmc_cluster
+// leaves behind: roots[id - 1] = linear index of the grain's first voxel, and k_cc_stats' table {size, min3, max3, 0}.
+// `rep` < 0: a single lattice; otherwise the replica named in the message.
+static int cc_import_scan(const char* who, const int32_t* lab, int L, int rep, std::vector<int>& roots, std::vector<int>& stats)
+{
+    const int64_t n = (int64_t)L * L * L;
+    roots.clear(); stats.clear();
+    for (int64_t x = 0; x < n; ++x) {
+        const int g = lab[x];
+        if (g == 0) continue;
+        const int c[3] = {(int)(x / ((int64_t)L * L)), (int)((x / L) % L), (int)(x % L)};
+        const int64_t seen = (int64_t)roots.size();
+        if (g < 0 || g > seen + 1) {
+            const std::string at = "label " + std::to_string(g) + " at voxel (" + std::to_string(c[0]) + ", " + std::to_string(c[1]) + ", " +
+                                   std::to_string(c[2]) + ")" + (rep >= 0 ? " of replica " + std::to_string(rep) : std::string());
+            return fail(std::string(who) + ": " + at + (g < 0 ? ": labels are 0 (empty) or ids 1..n"
+                        : ": ids are numbered 1..n by first occurrence in row-major order, the next new id here is " + std::to_string(seen + 1)));
+        }
+        if (g == seen + 1) {
+            roots.push_back((int)x);
+            const int fresh[8] = {0, c[0], c[1], c[2], c[0], c[1], c[2], 0};
+            stats.insert(stats.end(), fresh, fresh + 8);
+        }
+        int* s = &stats[(size_t)8 * (size_t)(g - 1)];
+        s[0] += 1;
+        for (int a = 0; a < 3; ++a) { s[1 + a] = std::min(s[1 + a], c[a]); s[4 + a] = std::max(s[4 + a], c[a]); }
+    }
+    return 0;
+}
+
+int cetkmc_cluster_import(void* handle, const int32_t* labels, int64_t* n_clusters)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !labels || !n_clusters) return fail("null argument");
+    if (ens_of(handle)) return fail("cetkmc_cluster_import takes one lattice: an ensemble handle goes to cetkmc_ensemble_cluster_import");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_cluster_import needs the whole lattice in one slab");
+    std::vector<int> roots, stats;
+    CHK(cc_import_scan("cetkmc_cluster_import", labels, h->L, -1, roots, stats));
+    HIPCHK(hipSetDevice(h->dev));
+    const int64_t n = (int64_t)h->L * h->L * h->L;
+    const size_t nr = roots.size();
+    CHK(cc_alloc(h));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (nr > 0) {
+        if (h->d_cc_stats) { HIPCHK(hipFree(h->d_cc_stats)); h->d_cc_stats = nullptr; }
+        HIPCHK(hipMalloc((void**)&h->d_cc_stats, nr * 8 * sizeof(int)));
+        HIPCHK(hipMemcpyAsync(h->d_cc_roots, roots.data(), nr * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_cc_stats, stats.data(), nr * 8 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipMemcpyAsync(h->d_cc_labels, labels, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cnt.bytes_h2d += (int64_t)(((size_t)n + nr * 9) * sizeof(int));
+    h->cc_roots_sorted.swap(roots);
+    h->cc_n_clusters = (int64_t)nr;
+    *n_clusters = (int64_t)nr;
     return 0;
 }
 
@@ -2680,6 +2748,42 @@ int cetkmc_ensemble_analysis_data(void* handle, int32_t* first_voxel, int64_t* s
             if (T_vals) T_vals[p] = gT[(size_t)r * maxg + c];
         }
     }
+    return 0;
+}
+
+int cetkmc_ensemble_cluster_import(void* handle, const int32_t* labels, int64_t* n_clusters)
+{
+    if (!handle || !labels || !n_clusters) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_cluster_import needs a preceding cetkmc_ensemble_analyze");
+    const int R = e->R, L = e->L;
+    const int64_t n = (int64_t)L * L * L;
+    // every replica is checked before anything is uploaded: one bad replica leaves the previous analysis as it is
+    std::vector<int> roots, stats, r1, s1;
+    std::vector<long long> offs((size_t)R + 1, 0);
+    for (int r = 0; r < R; ++r) {
+        CHK(cc_import_scan("cetkmc_ensemble_cluster_import", labels + (int64_t)r * n, L, r, r1, s1));
+        roots.insert(roots.end(), r1.begin(), r1.end());
+        stats.insert(stats.end(), s1.begin(), s1.end());
+        offs[(size_t)r + 1] = offs[(size_t)r] + (long long)r1.size();
+    }
+    const int64_t total = offs[(size_t)R];
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    HIPCHK(hipStreamSynchronize(st));
+    CHK(grow(&e->d_cc_stats, &e->cap_cc_stats, (size_t)std::max<int64_t>(total, 1) * 8));
+    HIPCHK(hipMemcpyAsync(e->d_cc_offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    for (int r = 0; r < R; ++r) {        // a replica's roots at r * L^3, as k_cc_compress leaves them
+        const long long a = offs[(size_t)r], k = offs[(size_t)r + 1] - a;
+        if (k > 0) HIPCHK(hipMemcpyAsync(e->d_cc_roots + (int64_t)r * n, roots.data() + a, (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    if (total > 0) HIPCHK(hipMemcpyAsync(e->d_cc_stats, stats.data(), (size_t)total * 8 * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->d_cc_labels, labels, (size_t)R * n * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h0->cnt.bytes_h2d += (int64_t)(((size_t)R * n + (size_t)total * 9) * sizeof(int) + offs.size() * sizeof(long long));
+    for (int r = 0; r < R; ++r) e->an_clusters[(size_t)r] = n_clusters[r] = offs[(size_t)r + 1] - offs[(size_t)r];
     return 0;
 }
 

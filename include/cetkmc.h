@@ -479,6 +479,22 @@ int cetkmc_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_
  * in a launch sequence that does not depend on R; out[R][L].  A single-lattice handle is refused. */
 int cetkmc_ensemble_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out);
 
+/* Imported labellings: install a labelling of the caller's as the handle's last clustering, exactly
+ * as cetkmc_cluster would have left it (labels, first voxels ascending, size / bounding-box table, cluster count), so that
+ * cetkmc_cluster_stats, cetkmc_cluster_labels and cetkmc_layer_profile read it; a later cetkmc_cluster replaces it
+ * completely.  labels[L^3], row-major: 0 = empty, ids 1..n numbered by first occurrence in row-major order (so every id
+ * 1..n is present); a grain need not be connected.  Anything else is refused on the host with a message that names the
+ * offending voxel, before anything is allocated, uploaded or launched: the profile kernel indexes its tables with the
+ * label.  Labels are not checked against the lattice's state: the counters follow their definition, occupancy from the
+ * labels and species from the state.  A single-slab, single-process handle or a replica handle; multi-slab and multi-rank
+ * handles and the handle cetkmc_create_ensemble returned are refused. */
+int cetkmc_cluster_import(void* handle, const int32_t* labels, int64_t* n_clusters);
+/* The same for every replica of an ensemble, in place of the clustering of the last cetkmc_ensemble_analyze (required: its
+ * species counts and gather results stay as they are): labels[R][L^3], n_clusters[R] out.  Every replica is checked before
+ * anything is uploaded; one bad replica refuses the call and leaves the previous analysis intact.
+ * cetkmc_ensemble_analysis_data and cetkmc_ensemble_layer_profile then read the import.  A single-lattice handle is refused. */
+int cetkmc_ensemble_cluster_import(void* handle, const int32_t* labels, int64_t* n_clusters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,12 +98,9 @@ def constructed(L, h=None, species=None):
     return state, np.ascontiguousarray(th[colour]), np.ascontiguousarray(ph[colour]), h
 
 
-def random_blocks(L, seed, fill=0.7):
-    """Random block lattice: boxes of random edge 1..4 per axis tile the lattice (cut positions drawn per axis), a block is
-    filled with probability ``fill``, its orientation random; the states 1..4 drawn per voxel, all four present for
-    L >= 2.  Returns state (int64), theta, phi."""
-    rs = np.random.RandomState(seed)
-
+def _boxes(rs, L, fill):
+    """the box partition of :func:`random_blocks`: per axis the box index of every coordinate (boxes of random edge 1..4),
+    and which boxes are filled."""
     def ids(n):
         out, q = [], 0
         while len(out) < n:
@@ -111,8 +108,17 @@ def random_blocks(L, seed, fill=0.7):
             q += 1
         return np.array(out[:n])
     a, b, c = ids(L), ids(L), ids(L)
-    na, nb, nc = a.max() + 1, b.max() + 1, c.max() + 1
-    filled = rs.random_sample((na, nb, nc)) < fill
+    filled = rs.random_sample((a.max() + 1, b.max() + 1, c.max() + 1)) < fill
+    return a, b, c, filled
+
+
+def random_blocks(L, seed, fill=0.7):
+    """Random block lattice: boxes of random edge 1..4 per axis tile the lattice (cut positions drawn per axis), a block is
+    filled with probability ``fill``, its orientation random; the states 1..4 drawn per voxel, all four present for
+    L >= 2.  Returns state (int64), theta, phi."""
+    rs = np.random.RandomState(seed)
+    a, b, c, filled = _boxes(rs, L, fill)
+    na, nb, nc = filled.shape
     bt = np.arccos(rs.uniform(-1.0, 1.0, (na, nb, nc)))
     bp = rs.uniform(-np.pi, np.pi, (na, nb, nc))
     ix = np.ix_(a, b, c)
@@ -129,13 +135,18 @@ STENCIL = ((1, 1, 0), (1, -1, 0), (-1, 1, 0), (-1, -1, 0), (0, 1, 1), (0, 1, -1)
            (2, 0, 0), (-2, 0, 0), (0, 2, 0), (0, -2, 0), (0, 0, 2), (0, 0, -2))
 
 
-def block_labels(L, h):
-    """The grains of :func:`constructed` when every block is ONE grain (an idealised, face-connected labelling): labels
-    numbered by first voxel in row-major order, first (n, 3), bbox (n, 6)."""
+def _block_key(L, h):
+    """the block of every voxel of :func:`constructed` (any order of numbering); -1 in the empty plane h."""
     i, j, k = np.meshgrid(np.arange(L), np.arange(L), np.arange(L), indexing="ij")
     bi = np.where(i < h, 0, (i - (h + 1)) // 2 + 1)
     nb = (L + 1) // 2
-    key = np.where(i == h, -1, (bi * nb + j // 2) * nb + k // 2)
+    return np.where(i == h, -1, (bi * nb + j // 2) * nb + k // 2)
+
+
+def block_labels(L, h):
+    """The grains of :func:`constructed` when every block is ONE grain (an idealised, face-connected labelling): labels
+    numbered by first voxel in row-major order, first (n, 3), bbox (n, 6)."""
+    key = _block_key(L, h)
     labels = np.zeros((L, L, L), np.int64)
     first, bbox, seen = [], [], {}
     for x in range(L ** 3):
@@ -197,3 +208,147 @@ def host_clusters(state, theta, phi, threshold=0.5):
         size[q - 1] = len(at)
         bbox[q - 1] = list(at.min(axis=0)) + list(at.max(axis=0))
     return labels, np.array(first, np.int64).reshape(n, 3), size, bbox
+
+
+# ---- labellings of the caller's (cetkmc_cluster_import) --------------------------------------------------------------------
+def from_raw(raw):
+    """Any non-negative integer volume (0 = empty; equal values = one grain, connected or not) as an importable labelling:
+    labels renumbered 1..n by first occurrence in row-major order, first (n, 3), size (n,), bbox (n, 6).  Whole-array
+    operations only."""
+    raw = np.asarray(raw)
+    assert raw.ndim == 3 and (raw >= 0).all()
+    flat = raw.reshape(-1)
+    vals, at, inv = np.unique(flat, return_index=True, return_inverse=True)
+    keep = vals != 0
+    n = int(keep.sum())
+    lut = np.zeros(len(vals), np.int64)
+    lut[np.flatnonzero(keep)[np.argsort(at[keep])]] = np.arange(1, n + 1)
+    lab = lut[inv.reshape(-1)]
+    first = np.stack(np.unravel_index(np.sort(at[keep]), raw.shape), axis=1).astype(np.int64).reshape(n, 3)
+    size = np.bincount(lab, minlength=n + 1)[1:].astype(np.int64)
+    bbox = np.zeros((n, 6), np.int64)
+    if n:
+        order = np.argsort(lab, kind="stable")
+        order = order[len(lab) - int(size.sum()):]                    # the occupied voxels, grain by grain
+        begin = np.concatenate(([0], np.cumsum(size)[:-1]))
+        for a, c in enumerate(np.unravel_index(order, raw.shape)):
+            bbox[:, a] = np.minimum.reduceat(c, begin)
+            bbox[:, 3 + a] = np.maximum.reduceat(c, begin)
+    return lab.reshape(raw.shape), first, size, bbox
+
+
+KINDS = ("one", "stripes0", "stripes1", "stripes2", "blocks", "scattered", "constructed_blocks")
+
+
+def _species(rs, occ):
+    """states 1..4 drawn per occupied voxel, all four present when four voxels are occupied."""
+    state = np.where(occ, rs.randint(1, 5, occ.shape), 0).astype(np.int64)
+    if occ.sum() >= 4:
+        state.reshape(-1)[rs.choice(np.flatnonzero(occ.reshape(-1)), 4, replace=False)] = np.arange(1, 5)
+    return state
+
+
+def one(L, seed=0):
+    """the full lattice as one grain.  Returns raw, state."""
+    raw = np.ones((L, L, L), np.int64)
+    return raw, _species(np.random.RandomState(seed), raw != 0)
+
+
+def stripes(L, a, w=3, seed=0):
+    """grains are slabs of thickness w perpendicular to axis a, every 5th slab empty (3 and 5 share no factor with the
+    kernel's tile edges 8, 32, 16: slab faces and tile faces meet in every relative position).  Returns raw, state."""
+    slab = np.arange(L) // w
+    line = np.where(slab % 5 == 4, 0, slab + 1)
+    shape = [1, 1, 1]
+    shape[a] = L
+    raw = np.ascontiguousarray(np.broadcast_to(line.reshape(shape), (L, L, L))).astype(np.int64)
+    return raw, _species(np.random.RandomState(seed), raw != 0)
+
+
+def blocks(L, seed=0, fill=0.7):
+    """the box partition of :func:`random_blocks` (edges 1..4 at random cuts) with ONE grain per filled box.  Returns raw,
+    state."""
+    rs = np.random.RandomState(seed)
+    a, b, c, filled = _boxes(rs, L, fill)
+    _, nb, nc = filled.shape
+    box = (a[:, None, None] * nb + b[None, :, None]) * nc + c[None, None, :]
+    raw = np.where(filled[np.ix_(a, b, c)], box + 1, 0).astype(np.int64)
+    return raw, _species(rs, raw != 0)
+
+
+def scattered(L, seed=0, fill=0.7, n_ids=3):
+    """every voxel occupied with probability ``fill`` draws one of n_ids raw ids: the grains are disconnected, and the same,
+    another and no label occur among the face neighbours in every combination.  Returns raw, state."""
+    rs = np.random.RandomState(seed)
+    occ = rs.random_sample((L, L, L)) < fill
+    raw = np.where(occ, rs.randint(1, n_ids + 1, (L, L, L)), 0).astype(np.int64)
+    return raw, _species(rs, occ)
+
+
+def constructed_blocks(L, seed=0):
+    """:func:`constructed` with every block one grain (:func:`block_labels`' labelling, as a raw volume): the only maker
+    with both columnar and equiaxed grains.  Returns raw, state."""
+    state, _, _, h = constructed(L, species=np.random.RandomState(seed))
+    return (_block_key(L, h) + 1).astype(np.int64), state
+
+
+# the shapes of the device comparison on imported labellings: every tile edge (8 rows, 32 columns, 16 planes) from both
+# sides; 65 = two full column tiles and a remainder, five plane groups, a ragged last row tile
+SHAPES = (1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 32, 33, 34, 64, 65)
+
+
+def case_seed(kind, L):
+    """the fixed seed of the (kind, L) case: check_not_vacuous holds with it at every L of SHAPES (pinned on the host)."""
+    return {"scattered": 196}.get(kind, 0) + L
+
+
+def labelling(kind, L, seed=0):
+    """raw, state of one of KINDS."""
+    if kind.startswith("stripes"):
+        return stripes(L, int(kind[-1]), seed=seed)
+    return {"one": one, "blocks": blocks, "scattered": scattered, "constructed_blocks": constructed_blocks}[kind](L, seed)
+
+
+# the kernel's block edges (csrc/layer.hpp: LAYER_TJ rows, LAYER_TK columns, LAYER_NI planes): (axis, last index before the edge)
+EDGES = ((1, 7), (2, 31), (0, 15))
+
+
+def straddles(labels, axis, at):
+    """(same, other): is there a pair of occupied face neighbours across the edge between the indices at and at + 1 of
+    ``axis`` with the same label / with two different labels."""
+    lo = np.take(labels, at, axis=axis)
+    hi = np.take(labels, at + 1, axis=axis)
+    both = (lo != 0) & (hi != 0)
+    return bool((both & (lo == hi)).any()), bool((both & (lo != hi)).any())
+
+
+def check_not_vacuous(kind, L, labels, want):
+    """Guards against a vacuous pass of a comparison on an imported labelling of KINDS (all but constructed_blocks, L >= 4),
+    evaluated on the reference's inputs and result: the same-label side of every predicate is there, and same-label pairs
+    lie across the kernel's tile, rim and plane-group edges.
+
+    ``blocks`` is a product partition: across one edge its occupied pairs are ALL of one box or ALL of two, so it cannot
+    have both sorts of pair at the same edge; there an occupied pair of either sort is asked for (test_layer_ref_host.py
+    pins that over the shapes of the device test both sorts occur at every edge), while ``scattered`` has both at every
+    edge of every shape."""
+    if kind == "constructed_blocks" or L < 4:
+        return
+    n_occ, occ_s, gb_s = want["n_occ"].sum(), want["occ_state"].sum(), want["gb_state"].sum()
+    assert n_occ > 0
+    for a in range(3):
+        assert want["seg"][:, a].sum() < n_occ, (kind, L, a)
+    if kind in ("blocks", "scattered"):
+        assert all(want["cut"][:, a].sum() > 0 for a in range(3)), (kind, L)
+        assert 0 < gb_s < occ_s, (kind, L)
+    if kind == "one":
+        assert all(want["seg"][:, a].sum() == L * L for a in range(3))
+        assert not want["cut"].any() and not want["gb_state"].any() and want["n_start"].sum() == 1
+    for axis, at in EDGES:
+        if L > at + 1:
+            same, other = straddles(labels, axis, at)
+            if kind == "blocks":
+                assert same or other, (kind, L, axis)
+            else:
+                assert same, (kind, L, axis)
+                if kind == "scattered":
+                    assert other, (kind, L, axis)

@@ -8,8 +8,9 @@ Replica 0's handle IS the ensemble handle, which the single call refuses by defi
 the replicas r >= 1.
 
 What the device clustering cannot produce: two face neighbours in one grain (its 14-stencil keeps the parity of i + j + k),
-so with its labels seg[a] == n_occ and the "predecessor has my label" side of the segment predicates is exercised on the
-host only (test_layer_ref_host.py pins the comparator there)."""
+so with its labels seg[a] == n_occ and the "neighbour has my label" side of the predicates is not reached in this file:
+test_gpu_layer_imported.py reaches it on the device through imported labellings (cetkmc_cluster_import), and
+test_layer_ref_host.py pins the comparator on the host."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,7 @@
 """The NumPy comparator of the layer profile (layer_ref.py) and metrics.layer_metrics, pinned without a GPU: lattices whose
 every counter is written out by hand, identities on random lattices, a constructed columnar / equiaxed lattice whose CET
-plane is known, and the empty and single-voxel lattices."""
+plane is known, the empty and single-voxel lattices, and the labellings the device test imports (from_raw against the loop-based
+block_labels, the makers, and the guards against a vacuous pass at every shape of that test)."""
 import numpy as np
 import pytest
 
@@ -191,3 +192,76 @@ def test_empty_and_single_voxel():
     m = metrics.layer_metrics(r, 1, 5e-6)
     assert m["CET_plane"] == 0 and m["CET_height_um"] == 0.0 and m["InterceptRatio"] == 1.0 and m["GB_frac_C"] == 0.0
     assert list(m)[:9] == list(metrics.LAYER_COLUMNS)
+
+
+# ---- imported labellings: from_raw, the makers, the guards of tests/test_gpu_layer_imported.py ------------------------------
+def test_from_raw_by_hand():
+    raw = np.array([[[7, 7], [0, 2]], [[2, 9], [7, 0]]])
+    lab, first, size, bbox = LR.from_raw(raw)
+    assert lab.tolist() == [[[1, 1], [0, 2]], [[2, 3], [1, 0]]]
+    assert first.tolist() == [[0, 0, 0], [0, 1, 1], [1, 0, 1]] and size.tolist() == [3, 2, 1]
+    assert bbox.tolist() == [[0, 0, 0, 1, 1, 1], [0, 0, 0, 1, 1, 1], [1, 0, 1, 1, 0, 1]]
+    lab, first, size, bbox = LR.from_raw(np.zeros((3, 3, 3), np.int64))
+    assert not lab.any() and first.shape == (0, 3) and size.shape == (0,) and bbox.shape == (0, 6)
+
+
+@pytest.mark.parametrize("L", (5, 8, 9))
+def test_from_raw_against_block_labels(L):
+    state, _, _, h = LR.constructed(L)
+    labels, first, bbox = LR.block_labels(L, h)
+    raw, _ = LR.constructed_blocks(L)
+    lab, f, size, b = LR.from_raw(raw * 3 + 11 * (raw != 0))             # any other raw ids of the same partition
+    assert np.array_equal(lab, labels) and np.array_equal(f, first) and np.array_equal(b, bbox)
+    assert np.array_equal(size, np.bincount(labels.reshape(-1))[1:]) and np.array_equal(lab != 0, state != 0)
+    t_first, t_bbox = _tables(labels)
+    assert np.array_equal(f, t_first) and np.array_equal(b, t_bbox)
+
+
+@pytest.mark.parametrize("kind", LR.KINDS)
+def test_makers_and_guards(kind):
+    """every (kind, L) case of the device test: an importable labelling (ids 1..n by first occurrence), all four species,
+    and the guards against a vacuous pass hold with the fixed seeds."""
+    sorts = {}
+    for L in LR.SHAPES:
+        raw, state = LR.labelling(kind, L, LR.case_seed(kind, L))
+        assert raw.shape == state.shape == (L, L, L) and np.array_equal(raw != 0, state != 0)
+        lab, first, size, bbox = LR.from_raw(raw)
+        n = len(size)
+        seen = lab.reshape(-1)[np.sort(np.unique(lab.reshape(-1), return_index=True)[1])]
+        assert seen[seen != 0].tolist() == list(range(1, n + 1))
+        assert np.array_equal(lab != 0, raw != 0) and size.sum() == np.count_nonzero(raw)
+        for q in [q for q in {1, (n + 1) // 2, n} if 1 <= q <= n]:       # spot checks against the plain definition
+            at = np.argwhere(lab == q)
+            assert len(at) == size[q - 1] and at[0].tolist() == first[q - 1].tolist() and len(np.unique(raw[lab == q])) == 1
+            assert bbox[q - 1].tolist() == list(at.min(axis=0)) + list(at.max(axis=0))
+        if L >= 3:
+            assert set(np.unique(state)) - {0} == {1, 2, 3, 4}, (kind, L)
+        want = LR.layer_ref(lab, state, bbox, first, AR)
+        LR.check_not_vacuous(kind, L, lab, want)
+        for axis, at in LR.EDGES:
+            if L > at + 1:
+                same, other = LR.straddles(lab, axis, at)
+                sorts.setdefault(axis, set()).update({"same"} if same else set(), {"other"} if other else set())
+    if kind in ("blocks", "scattered"):
+        assert all(sorts[a] == {"same", "other"} for a in range(3)), sorts
+    if kind == "scattered":
+        assert np.unique(raw).tolist() == [0, 1, 2, 3]                  # of the last, largest shape
+
+
+def test_makers_by_hand():
+    raw, _ = LR.stripes(17, 1)
+    assert raw[0, :, 0].tolist() == [1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4, 0, 0, 0, 6, 6] and (raw == raw[:1, :, :1]).all()
+    assert (LR.one(4)[0] == 1).all()
+    lab, _, size, bbox = LR.from_raw(LR.blocks(12, 3)[0])
+    ext = bbox[:, 3:] - bbox[:, :3] + 1
+    assert np.array_equal(size, ext.prod(axis=1)) and ext.max() <= 4          # one filled box = one grain
+
+
+def test_guards_catch_a_parity_labelling():
+    """the device clustering's own kind of labelling (no two face neighbours in one grain) fails the guards."""
+    L = 9
+    i, j, k = np.meshgrid(np.arange(L), np.arange(L), np.arange(L), indexing="ij")
+    lab, first, size, bbox = LR.from_raw(1 + (i + j + k) % 2)
+    want = LR.layer_ref(lab, np.where(lab != 0, 1, 0), bbox, first, AR)
+    with pytest.raises(AssertionError):
+        LR.check_not_vacuous("scattered", L, lab, want)
