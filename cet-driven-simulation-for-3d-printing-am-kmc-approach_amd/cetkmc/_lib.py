@@ -128,6 +128,8 @@ PROTOTYPES = {
     "cetkmc_source_hash": (C.c_char_p, []),
     "cetkmc_struct_size": (C.c_int, [C.c_char_p]),
     "cetkmc_dirty_offset": (C.c_int, [C.c_int, C.c_int]),
+    "cetkmc_stale_row": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_int, C.c_int]),
+    "cetkmc_stale_rows": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_int, C.c_void_p]),
     "cetkmc_device_count": (C.c_int, [_P(C.c_int)]),
     "cetkmc_create": (C.c_int, [_P(Params), C.c_int, C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "cetkmc_get_unique_id": (C.c_int, [C.c_char_p]),

@@ -146,7 +146,6 @@ struct Handle {
     StepState* d_ss = nullptr;
     int* d_dirty = nullptr;      // [1 + DIRTY_MAX] rows made stale by the last applied event (incremental mode)
     PendRec* d_pend = nullptr;   // the event of a deferred step, applied by the next sweep launch (k_select_pend -> k_sweep_stream_apply)
-    RowPatch* d_patch = nullptr; // that launch's re-evaluated stale rows (k_sweep_stream_apply -> k_plane_reduce)
     int apply_in_sweep = 1;      // option "apply_in_sweep": defer the application of eligible batched steps into the next sweep
     bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
     BatchCfg pend_cfg{};         // ... with this batch configuration
@@ -384,8 +383,6 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
     HIPCHK(hipMemsetAsync(h->d_dirty, 0, (1 + 2 * DIRTY_MAX) * sizeof(int), h->stream));
     HIPCHK(hipMalloc((void**)&h->d_pend, sizeof(PendRec)));
     HIPCHK(hipMemsetAsync(h->d_pend, 0, sizeof(PendRec), h->stream));
-    HIPCHK(hipMalloc((void**)&h->d_patch, sizeof(RowPatch)));
-    HIPCHK(hipMemsetAsync(h->d_patch, 0, sizeof(RowPatch), h->stream));
     HIPCHK(hipMalloc((void**)&h->d_ktab, 225 * sizeof(double)));
     HIPCHK(hipMalloc((void**)&h->d_kp, sizeof(KParams)));
     HIPCHK(hipMalloc((void**)&h->d_flag, sizeof(int)));
@@ -768,7 +765,7 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
         } else if (h->sweep_variant >= 1 && h->pend_live) {
             // the previous step's event is applied by one extra workgroup (blockIdx 0) of this launch (run_steps defers
             // only under the streaming sweep with the rate table, and only where rows are half-wave rows)
-            ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_patch, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
+            ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
                         (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
             launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X);
         } else if (h->sweep_variant >= 1) {
@@ -782,8 +779,7 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
     if (sv != 4)          // (variant 4 folds the block sums in the sweep launch)
         for (size_t s = 0; s < h->slabs.size(); ++s) {
             SlabView v = view_of(h, (int)s);
-            hipLaunchKernelGGL(k_plane_reduce, dim3(3 * v.nloc), dim3(64), 0, h->stream, v, h->d_blocks, ss,
-                               (const RowPatch*)(h->pend_live ? h->d_patch : nullptr));
+            hipLaunchKernelGGL(k_plane_reduce, dim3(3 * v.nloc), dim3(64), 0, h->stream, v, h->d_blocks, ss);
         }
     HIPCHK(hipGetLastError());
     if (multi_rank(h)) CHK(comm_allgather(h, h->d_blocks, (size_t)3 * (h->L / h->nranks) * sizeof(BlockEnt)));
@@ -1103,7 +1099,7 @@ void destroy_impl(Handle* h)
     }
     void* ccp[] = {h->d_cc_parent, h->d_cc_roots, h->d_cc_cid, h->d_cc_labels, h->d_cc_stats, h->d_cc_n};
     for (void* p : ccp) if (p) (void)hipFree(p);
-    void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_patch, h->d_ktab, h->d_kp, h->d_scratch,
+    void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1229,6 +1225,28 @@ int cetkmc_struct_size(const char* name)
 
 // the kernels' own stale-row rule (kernels.hpp), for host-side checks of its footprint
 int cetkmc_dirty_offset(int di, int dj) { return dirty_offset(di, dj) ? 1 : 0; }
+static StaleEv stale_ev_host(int type, const int pos[2], const int target[2])
+{
+    StaleEv se;
+    se.type = type; se.pi = pos[0]; se.pj = pos[1]; se.ti = target[0]; se.tj = target[1];
+    return se;
+}
+int cetkmc_stale_row(int type, const int pos[2], const int target[2], int gi, int j)
+{
+    return stale_row(stale_ev_host(type, pos, target), gi, j) ? 1 : 0;
+}
+int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, int rows[][2])
+{
+    const StaleEv se = stale_ev_host(type, pos, target);
+    int n = 0;
+    for (int c = 0; c < STALE_CAND; ++c) {          // the apply block: lane c tests candidate c
+        int gi, j;
+        if (!stale_candidate(se, L, c, gi, j)) continue;
+        if (n < PATCH_MAX) { rows[n][0] = gi; rows[n][1] = j; }
+        ++n;
+    }
+    return n;
+}
 
 int cetkmc_device_count(int* n)
 {

@@ -236,22 +236,15 @@ constexpr int STREAM_MAXPF = 3;   // 16-B chunks of a class slab per thread (L <
 
 // Block sum of (owned plane lp, category c) by one wave: balanced tree over j of the row sums.  COH: some row sums
 // were written by other blocks of the SAME launch (k_rows_eval's in-launch reduction) -> agent-scope loads.
-struct RowPatch;
-__device__ __forceinline__ unsigned long long patch_plane(const RowPatch* patch, int gi, int lane, int& pe);
-__device__ __forceinline__ void patch_rows(const RowPatch* patch, unsigned long long pm, int pe, int j, int c, double& v, int& cv,
-                                           double* rowsum_w, int32_t* rowcnt_w);
 template <bool COH>
 __device__ __forceinline__ void plane_reduce_wave(const double* rowsum, const int32_t* rowcnt, BlockEnt* blocks,
-                                                  int L, int Pk, int gi0, int lp, int c, int lane,
-                                                  const RowPatch* patch = nullptr, double* rowsum_w = nullptr, int32_t* rowcnt_w = nullptr)
+                                                  int L, int Pk, int gi0, int lp, int c, int lane)
 {
     const int b = lp * 3 + c;
     const int nch = Pk > 64 ? (Pk >> 6) : 1;
     double stk[5];
     double tot = 0.0;
     int64_t cnt = 0;
-    int pe = 0;                                                  // patch: this plane's entries (lane q = entry q)
-    const unsigned long long pm = patch ? patch_plane(patch, gi0 + lp, lane, pe) : 0ull;
     for (int m = 0; m < nch; ++m) {
         const int j = (m << 6) + lane;
         double v = 0.0;
@@ -264,12 +257,76 @@ __device__ __forceinline__ void plane_reduce_wave(const double* rowsum, const in
                 v = rowsum[(int64_t)b * L + j]; cv = rowcnt[(int64_t)b * L + j];
             }
         }
-        if (pm) patch_rows(patch, pm, pe, j, c, v, cv, rowsum_w + (int64_t)b * L, rowcnt_w + (int64_t)b * L);
         v = wave_tree_sum(v);
         cnt += wave_sum_i(cv);
         tot = stack_push(stk, v, m);
     }
     if (lane == 0) { blocks[3 * (gi0 + lp) + c].sum = tot; blocks[3 * (gi0 + lp) + c].cnt = cnt; }
+}
+
+// (di, dj) of a row whose sums change when voxel (i, j, k) changes: the rows of the voxel and of its 14 neighbours (11 rows).
+// The one definition of "dirty" for the incremental mode's list and for the rows the sweep leaves to its apply block.
+__host__ __device__ constexpr bool dirty_offset(int di, int dj)
+{
+    const int a = di < 0 ? -di : di, c = dj < 0 ? -dj : dj;
+    return a + c <= 2 && !(a == 1 && c == 0);
+}
+// The stale rows of a pending event (the record k_select_pend leaves to the next sweep launch, k_sweep_stream_apply): the
+// rows whose sums may depend on whether a tile read the lattice before or after the launch's apply block wrote the event.
+// A function of the record alone -- type, site, diffusion target -- not of whether the application succeeds: the tiles
+// that can hold such a row do not store it, the apply block stores every one of them, once, after the event.
+struct StaleEv {
+    int type = -1;                 // cetkmc_event::type; < 0: no event
+    int pi = 0, pj = 0;            // pos[0], pos[1]
+    int ti = 0, tj = 0;            // target[0], target[1] (EV_DIFF)
+};
+// the sites of a record that names an event, (plane << 16) | row each: two scalars for the tiles that test rows against them
+// (a record without a second site holds the first one twice)
+struct StaleWin {
+    unsigned a = ~0u, b = ~0u;     // no event: plane and row 65535, further than 2 from every row of a lattice
+};
+__host__ __device__ __forceinline__ StaleWin stale_win(const StaleEv& e)
+{
+    StaleWin w;
+    if (e.type < 0) return w;
+    w.a = ((unsigned)e.pi << 16) | (unsigned)e.pj;
+    w.b = e.type == EV_DIFF ? (((unsigned)e.ti << 16) | (unsigned)e.tj) : w.a;
+    return w;
+}
+__host__ __device__ __forceinline__ bool stale_row(const StaleWin& w, int gi, int j)
+{
+    return dirty_offset(gi - (int)(w.a >> 16), j - (int)(w.a & 0xFFFFu)) || dirty_offset(gi - (int)(w.b >> 16), j - (int)(w.b & 0xFFFFu));
+}
+__host__ __device__ __forceinline__ bool stale_row(const StaleEv& e, int gi, int j)
+{
+    return stale_row(stale_win(e), gi, j);
+}
+// The apply block's enumeration of those rows: candidate c = 25 v + 5 (di + 2) + (dj + 2) is offset (di, dj) from site v
+// (0: pos, 1: the diffusion target); it names a row iff the offset is dirty, the row lies in the lattice and, for the second
+// site, is not a row of the first site as well.  Every stale row in the lattice is named by exactly one candidate.
+constexpr int STALE_CAND = 50;
+constexpr int PATCH_MAX = 22;      // 11 rows around each of <= 2 changed sites
+constexpr int stale_offsets()
+{
+    int n = 0;
+    for (int di = -2; di <= 2; ++di)
+        for (int dj = -2; dj <= 2; ++dj) n += dirty_offset(di, dj) ? 1 : 0;
+    return n;
+}
+static_assert(2 * stale_offsets() <= PATCH_MAX && STALE_CAND <= 64, "stale rows of one event: at most PATCH_MAX, one candidate per lane");
+__host__ __device__ __forceinline__ void stale_candidate_row(const StaleEv& e, int c, int& gi, int& j)
+{
+    const int v = c >= 25 ? 1 : 0, o = c - 25 * v, a = o / 5;
+    gi = (v ? e.ti : e.pi) + a - 2;
+    j = (v ? e.tj : e.pj) + (o - 5 * a) - 2;
+}
+__host__ __device__ __forceinline__ bool stale_candidate(const StaleEv& e, int L, int c, int& gi, int& j)
+{
+    stale_candidate_row(e, c, gi, j);
+    const int v = c >= 25 ? 1 : 0;
+    if (e.type < 0 || c < 0 || c >= (e.type == EV_DIFF ? 50 : 25)) return false;
+    if (!dirty_offset(gi - (v ? e.ti : e.pi), j - (v ? e.tj : e.pj)) || gi < 0 || gi >= L || j < 0 || j >= L) return false;
+    return !(v && dirty_offset(gi - e.pi, j - e.pj));
 }
 
 struct StreamArgs {
@@ -375,9 +432,10 @@ __device__ __forceinline__ void load_vals(const StreamArgs& A, int li, int jrow,
 // li+d, row jrow+dj -- an LDS ring slot in the streaming kernel, the global class array in the dirty-row kernel;
 // everything else is shared, so both produce bit-identical row sums.  v0 = load_vals() of chunk 0.
 // CH2: rows of 513..1024 voxels (two 512-voxel chunks per row; only without HW).
-template <bool TAB, bool HW, bool CH2, class ROWP>
+// SK (the tiles of k_sweep_stream_apply that can hold a stale row of the pending event, sites `sw`): such a row is not stored.
+template <bool TAB, bool HW, bool CH2, bool SK = false, class ROWP>
 __device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li, int lp, int jrow, bool top, int lane,
-                                          const double (&v0)[8])
+                                          const double (&v0)[8], const StaleWin& sw = StaleWin{})
 {
     static_assert(!(HW && CH2), "half-wave rows have one chunk");
     const int L = A.L;
@@ -527,41 +585,34 @@ __device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li
         n2 += packed & 0xFFFF;
         n1 = packed >> 16;
     }
-    if (sl == 0 && jrow < L) {
-        const int64_t o = (int64_t)lp * 3 * L + jrow;
+    // SK: the test and the store offsets are worked out here, from a copy of the row index the compiler cannot see through,
+    // so nothing of them is hoisted out of the plane loop into vector registers that would live across it
+    int jst = jrow;
+    if (SK) asm volatile("" : "+v"(jst));
+    if (sl == 0 && jrow < L && !(SK && stale_row(sw, A.gi0 + lp, jst))) {
+        const int64_t o = (int64_t)lp * 3 * L + jst;
         A.rowsum[o] = r0; A.rowsum[o + L] = r1; A.rowsum[o + 2 * (int64_t)L] = r2;
         A.rowcnt[o] = n0; A.rowcnt[o + L] = n1; A.rowcnt[o + 2 * (int64_t)L] = n2;
     }
 }
 
-// (di, dj) of a row whose sums change when voxel (i, j, k) changes: the rows of the voxel and of its 14 neighbours (11 rows).
-// The one definition of "dirty" for the incremental mode's list and for the rows the sweep leaves to its apply block.
-__host__ __device__ __forceinline__ bool dirty_offset(int di, int dj)
+// Tile b of a launch (its index among the launch's tiles): plane group ibr of the launch's groups, row tile jt
+__device__ __forceinline__ void stream_tile_of(const StreamArgs& A, int b, int& ibr, int& jt)
 {
-    const int a = di < 0 ? -di : di, c = dj < 0 ? -dj : dj;
-    return a + c <= 2 && !(a == 1 && c == 0);
+    const int njt = (A.L + SWEEP_TJ - 1) / SWEEP_TJ;
+    const int nblk = njt * A.group_count;
+    if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);   // contiguous block ranges per XCD
+    ibr = b / njt; jt = b - ibr * njt;
 }
-// The stale rows of an event applied inside a sweep launch (k_sweep_stream_apply), re-evaluated by its apply block after
-// the event: k_plane_reduce folds these sums instead of what the launch's tiles stored for those rows, and stores them
-constexpr int PATCH_MAX = 22;      // 11 rows around each of <= 2 changed sites
-struct RowPatch {
-    int n;
-    int row[PATCH_MAX];            // (global plane << 16) | row
-    double sum[PATCH_MAX][3];      // by category
-    int cnt[PATCH_MAX][3];
-};
-// NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682).  One tile (b = its index among the
-// launch's tiles)
-template <bool TAB, bool HW, int NPF, bool CH2>
-__device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, unsigned char* smem)
+// NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682).  One tile.  SK: sweep_row()
+template <bool TAB, bool HW, int NPF, bool CH2, bool SK = false>
+__device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, unsigned char* smem, const StaleWin& sw = StaleWin{})
 {
     constexpr int TJ = SWEEP_TJ, TR = TJ + 4;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int L = A.L;
-    const int njt = (L + TJ - 1) / TJ;
-    const int nblk = njt * A.group_count;
-    if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);   // contiguous block ranges per XCD
-    const int ibr = b / njt, jt = b - ibr * njt;
+    int ibr, jt;
+    stream_tile_of(A, b, ibr, jt);
     const int j0 = jt * TJ;
     const int lp0 = (A.group_first + ibr) * STREAM_NI, lp1 = min(lp0 + STREAM_NI, A.nloc);
     const int pitchC = A.pitchC;
@@ -631,13 +682,13 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
             load_vals<TAB, HW>(A, min(li + 1, lp1 + 1), j0 + row_of(0), lane, 0, nxt);
             const int r = row_of(0);
             auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-            sweep_row<TAB, HW, CH2>(A, rowp, li, lp, j0 + r, top, lane, cur);
+            sweep_row<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
         } else {
             {
                 load_vals<TAB, HW>(A, li, j0 + row_of(1), lane, 0, nxt);
                 const int r = row_of(0);
                 auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-                sweep_row<TAB, HW, CH2>(A, rowp, li, lp, j0 + r, top, lane, cur);
+                sweep_row<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
             }
             {
 #ifdef CETKMC_NO_TAIL_PREFETCH
@@ -646,7 +697,7 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
                 load_vals<TAB, HW>(A, min(li + 1, lp1 + 1), j0 + row_of(0), lane, 0, cur);
                 const int r = row_of(1);
                 auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-                sweep_row<TAB, HW, CH2>(A, rowp, li, lp, j0 + r, top, lane, nxt);
+                sweep_row<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, nxt, sw);
             }
         }
 #ifdef CETKMC_NO_TAIL_PREFETCH
@@ -702,8 +753,7 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
 }
 template <bool HW, bool CH2>
 __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, int jrow, bool top, int lane, const double (&v0)[8],
-                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */,
-                                          RowPatch* patch = nullptr, int pq = 0 /* patch: slot pq instead of rowsum / rowcnt */)
+                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */)
 {
     static_assert(!(HW && CH2), "half-wave rows have one chunk");
     const int L = A.L;
@@ -792,13 +842,7 @@ __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, i
         n2 += packed & 0xFFFF;
         n1 = packed >> 16;
     }
-    if (patch) {
-        if (sl == 0 && jrow < L) {
-            patch->row[pq] = ((A.gi0 + lp) << 16) | jrow;
-            patch->sum[pq][0] = r0; patch->sum[pq][1] = r1; patch->sum[pq][2] = r2;
-            patch->cnt[pq][0] = n0; patch->cnt[pq][1] = n1; patch->cnt[pq][2] = n2;
-        }
-    } else if (sl == 0 && jrow < L) {
+    if (sl == 0 && jrow < L) {
         const int64_t o = (int64_t)lp * 3 * L + jrow;
         A.rowsum[o] = r0; A.rowsum[o + L] = r1; A.rowsum[o + 2 * (int64_t)L] = r2;
         A.rowcnt[o] = n0; A.rowcnt[o + L] = n1; A.rowcnt[o + 2 * (int64_t)L] = n2;
@@ -1039,32 +1083,12 @@ __global__ __launch_bounds__(256) void k_rate_table(KParams P, SlabView S, doubl
 }
 
 // k_plane_reduce: one wave per (owned plane, category): balanced tree over j of the row sums.
-// patch (after k_sweep_stream_apply): the apply block's sums of the rows its event made stale replace the tiles' ones
-__device__ __forceinline__ unsigned long long patch_plane(const RowPatch* patch, int gi, int lane, int& pe)
-{
-    const int n = patch->n;                                      // <= PATCH_MAX < 64
-    pe = lane < n ? patch->row[lane] : -1;
-    return __ballot(lane < n && (pe >> 16) == gi);
-}
-// (called by the whole wave; pm: the patch entries of this plane) row j's sums replaced by and stored from the patch
-__device__ __forceinline__ void patch_rows(const RowPatch* patch, unsigned long long pm, int pe, int j, int c, double& v, int& cv,
-                                           double* rowsum_w, int32_t* rowcnt_w)
-{
-    while (pm) {
-        const int q = __builtin_ctzll(pm);
-        pm &= pm - 1;
-        if (j == (__builtin_amdgcn_readlane(pe, q) & 0xFFFF)) {
-            v = patch->sum[q][c]; cv = patch->cnt[q][c];
-            rowsum_w[j] = v; rowcnt_w[j] = cv;
-        }
-    }
-}
 __global__ __launch_bounds__(64) void k_plane_reduce(SlabView S, BlockEnt* __restrict__ blocks,
-                                                     const StepState* __restrict__ ss, const RowPatch* __restrict__ patch)
+                                                     const StepState* __restrict__ ss)
 {
     if (ss && ss->status) return;
     const int b = blockIdx.x;
-    plane_reduce_wave<false>(S.rowsum, S.rowcnt, blocks, S.L, S.Pk, S.gi0, b / 3, b % 3, (int)threadIdx.x, patch, S.rowsum, S.rowcnt);
+    plane_reduce_wave<false>(S.rowsum, S.rowcnt, blocks, S.L, S.Pk, S.gi0, b / 3, b % 3, (int)threadIdx.x);
 }
 
 // ---- counter-based uniforms (DESIGN.md "RNG"): u(seed, step, key) in [0, 1); the oracle's orc_counter_uniform ----------
@@ -1997,10 +2021,12 @@ __global__ __launch_bounds__(256) void k_select_apply(KParams P, const SlabView*
 // ---- apply inside the next sweep (single process, one slab, streaming sweep with the rate table, full sweeps) ---------------
 // A deferred step launches the selection alone (k_select_pend): the event and what k_select_apply carries in LDS go to a
 // device record.  The next sweep launch (k_sweep_stream_apply) carries one extra workgroup, blockIdx 0, that applies that
-// event exactly as k_select_apply would have and then re-evaluates the rows the event made stale (dirty_offset() around
-// the changed sites) into a RowPatch.  The tiles are those of k_sweep_stream: every row that is not stale does not depend on
-// whether a tile read the lattice before or after the event; k_plane_reduce replaces the stale rows' sums by the patch.
-// Stream order between the launches is unchanged.
+// event exactly as k_select_apply would have and then re-evaluates and stores the rows the event makes stale (stale_row():
+// dirty_offset() around the record's sites).  The tiles are those of k_sweep_stream: every row that is not stale does not
+// depend on whether a tile read the lattice before or after the event.  A stale row is stored once, by the apply block: the
+// <= 8 tiles whose planes and rows meet the 5 x 5 window of a site run the same tile code with that row's store predicated
+// off (decided from the record's scalars; every other tile runs exactly k_sweep_stream's code).  k_plane_reduce is the plain
+// reduce.  Stream order between the launches is unchanged.
 struct PendRec {
     cetkmc_event ev;
     SelCarry carry;
@@ -2009,7 +2035,6 @@ struct ApplyArgs {
     KParams P;
     const SlabView* slabs;      // the handle's device views (one slab)
     const PendRec* pend;
-    RowPatch* patch;
     StepState* ss;
     BatchCfg cfg;
     const double* u_defect;
@@ -2041,11 +2066,21 @@ __global__ __launch_bounds__(256) void k_select_pend(KParams P, const SlabView* 
                       u_defect, u_np);
 }
 
-// The apply block: apply_batch_body of the fused launch (carry from the record instead of LDS), then the stale rows, one
-// per wave (HW: the first half-wave), with the census-free row reduction of the incremental mode's k_rows_eval.  It is
-// latency-bound beside the tiles, so an empty voxel's neighbour gathers go one at a time: the kernel keeps the tiles'
+// The apply block: apply_batch_body of the fused launch (carry from the record instead of LDS), then the stale rows with
+// the census-free row reduction of the incremental mode's k_rows_eval, stored into rowsum / rowcnt.  Which rows follows from
+// the record alone, as for the tiles that left them out (a record that names an event is always applied: select_body sets
+// carry->ready exactly when it names one; were an application ever refused, the unchanged lattice would give these rows
+// the sums they had).  One row per wave (HW: the first half-wave), the rows dealt round-robin to the four waves; two rows per
+// wave was measured and not every run was faster.
+// It is latency-bound beside the tiles, so an empty voxel's neighbour gathers go one at a time: the kernel keeps the tiles'
 // register budget (5 waves per SIMD).
 constexpr int PEND_EB = 1;
+__device__ __forceinline__ StaleEv stale_ev_of(const cetkmc_event& ev)
+{
+    StaleEv se;
+    se.type = ev.type; se.pi = ev.pos[0]; se.pj = ev.pos[1]; se.ti = ev.target[0]; se.tj = ev.target[1];
+    return se;
+}
 template <bool HW, bool CH2>
 __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const ApplyArgs& X, unsigned char* smem)
 {
@@ -2060,8 +2095,8 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
     for (int q = threadIdx.x; q < (int)(sizeof(SlabView) / 8); q += blockDim.x)
         reinterpret_cast<uint64_t*>(Sl)[q] = reinterpret_cast<const uint64_t*>(X.slabs)[q];
     __syncthreads();
-    const int ok = apply_batch_body<PEND_EB>(*Pl, Sl, 1, A.L, &X.pend->ev, 1, X.ss, X.cfg, X.u_defect, X.u_np, X.log_total,
-                                             X.log_event, X.log_nev, X.ktab_g, 1, nullptr, &X.pend->carry);
+    apply_batch_body<PEND_EB>(*Pl, Sl, 1, A.L, &X.pend->ev, 1, X.ss, X.cfg, X.u_defect, X.u_np, X.log_total, X.log_event, X.log_nev,
+                              X.ktab_g, 1, nullptr, &X.pend->carry);
 #ifdef CETKMC_SEL_STAMPS
     if (threadIdx.x == 0) g_pend_stamps[1] = g_sel_stamps[10];
 #endif
@@ -2071,29 +2106,22 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     PEND_STAMP(2);
-    const cetkmc_event& ev = X.pend->ev;
-    const int nsite = ok ? (ev.type == EV_DIFF ? 2 : 1) : 0;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, L = A.L;
-    const int i0 = ev.pos[0], j0 = ev.pos[1];
-    int q = 0;
-    for (int v = 0; v < nsite; ++v) {
-        const int ci = v ? ev.target[0] : i0, cj = v ? ev.target[1] : j0;
-        for (int di = -2; di <= 2; ++di)
-            for (int dj = -2; dj <= 2; ++dj) {
-                const int gi = ci + di, j = cj + dj;
-                if (!dirty_offset(di, dj) || gi < 0 || gi >= L || j < 0 || j >= L) continue;
-                if (v && dirty_offset(gi - i0, j - j0)) continue;       // a row of the first site as well
-                const int pq = q++;
-                if ((pq & 3) != w) continue;
-                const int lp = gi - A.gi0, li = lp + 2;
-                const int jrow = (HW && lane >= 32) ? L_INACTIVE : j;
-                double v0[8];
-                load_vals<true, HW>(A, li, jrow, lane, 0, v0);
-                table_row<HW, CH2>(A, li, lp, jrow, gi == L - 1, lane, v0, load_cls8(A, li, jrow, HW ? (lane & 31) : lane, 0),
-                                   nullptr, nullptr, X.patch, pq);
-            }
+    const StaleEv se = stale_ev_of(X.pend->ev);
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), L = A.L;
+    // lane c = candidate c: every wave finds the same set of rows; wave w takes the rows of rank w, w + 4, ...
+    int cgi = 0, cj = 0;
+    unsigned long long m = __ballot(lane < STALE_CAND && stale_candidate(se, L, lane, cgi, cj));
+    for (int k = w; k > 0; --k) m &= m - 1;
+    while (m) {
+        int gi, j;
+        stale_candidate_row(se, __builtin_ctzll(m), gi, j);
+        const int lp = gi - A.gi0, li = lp + 2;
+        const int jrow = (HW && lane >= 32) ? L_INACTIVE : j;
+        double v0[8];
+        load_vals<true, HW>(A, li, jrow, lane, 0, v0);
+        table_row<HW, CH2>(A, li, lp, jrow, gi == L - 1, lane, v0, load_cls8(A, li, jrow, HW ? (lane & 31) : lane, 0));
+        for (int k = 4; k > 0; --k) m &= m - 1;
     }
-    if (threadIdx.x == 0) X.patch->n = q;
 #ifdef CETKMC_SEL_STAMPS
     __syncthreads();
     PEND_STAMP(3);
@@ -2108,7 +2136,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     if (ss->status) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (blockIdx.x != 0) {
-        sweep_stream_tile<true, HW, NPF, CH2>(A, (int)blockIdx.x - 1, smem);
+        // the pending record was written by the previous launch and is only read in this one: uniform (scalar) loads
+        const int b = (int)blockIdx.x - 1;
+        const StaleEv se = stale_ev_of(X.pend->ev);
+        int ibr, jt;
+        stream_tile_of(A, b, ibr, jt);
+        const int g0 = A.gi0 + (A.group_first + ibr) * STREAM_NI, j0 = jt * SWEEP_TJ;
+        auto meets = [&](int ci, int cj) {          // the tile's planes x rows against the 5 x 5 window of a site
+            return ci + 2 >= g0 && ci - 2 < g0 + STREAM_NI && cj + 2 >= j0 && cj - 2 < j0 + SWEEP_TJ;
+        };
+        if (se.type >= 0 && (meets(se.pi, se.pj) || (se.type == EV_DIFF && meets(se.ti, se.tj))))
+            sweep_stream_tile<true, HW, NPF, CH2, true>(A, b, smem, stale_win(se));
+        else
+            sweep_stream_tile<true, HW, NPF, CH2>(A, b, smem);
 #ifdef CETKMC_SEL_STAMPS
         if (threadIdx.x == 0) atomicMax(&g_pend_stamps[4], (unsigned long long)wall_clock64());
 #endif

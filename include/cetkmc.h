@@ -190,9 +190,16 @@ const char* cetkmc_source_hash(void);
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
- * list and the apply-in-sweep row patch are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
+ * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
  * device. */
 int cetkmc_dirty_offset(int di, int dj);
+/* The stale rows of a deferred step's pending event -- type (cetkmc_event::type, < 0: none), pos[0..1] and, for a diffusion,
+ * target[0..1]: the rows the sweep launch that applies the event leaves to its apply block.  cetkmc_stale_row: 1 when row j
+ * of global plane gi is one (a function of the record alone; lattice bounds are the caller's), else 0.  cetkmc_stale_rows:
+ * the apply block's own enumeration for an L^3 lattice, (plane, row) pairs into rows[22][2]; returns their number (never more
+ * than 22; entries beyond 22 would not be written).  Host functions; need no device. */
+int cetkmc_stale_row(int type, const int pos[2], const int target[2], int gi, int j);
+int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, int rows[][2]);
 int cetkmc_device_count(int* n);
 
 /* Lifetime.  n_slabs > 1 with all device_ids equal splits the lattice into axis-0 slabs
