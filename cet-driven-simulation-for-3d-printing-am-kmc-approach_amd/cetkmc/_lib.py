@@ -116,9 +116,17 @@ class LayerRec(C.Structure):
     ]
 
 
+class TextureArgs(C.Structure):
+    _fields_ = [
+        ("n_bins", C.c_int32), ("pad", C.c_int32), ("gb_edges", C.POINTER(C.c_double)), ("pole_edges", C.POINTER(C.c_double)),
+        ("axis", C.c_double * 3),
+    ]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
-                  "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec}
+                  "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
+                  "texture_args": TextureArgs}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -180,6 +188,8 @@ PROTOTYPES = {
     "cetkmc_ensemble_layer_profile": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "cetkmc_cluster_import": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int64)]),
     "cetkmc_ensemble_cluster_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_texture_profile": (C.c_int, [C.c_void_p, _P(TextureArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_ensemble_texture_profile": (C.c_int, [C.c_void_p, _P(TextureArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -53,6 +53,27 @@ def _dptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def texture_edges_deg(n_bins, span_deg):
+    """The n_bins - 1 interior edges of n_bins equal steps over 0..span_deg, in degrees (ascending)."""
+    return np.arange(1, int(n_bins), dtype=np.float64) * (float(span_deg) / int(n_bins))
+
+
+def _texture_args(n_bins, gb_edges_deg, pole_edges_deg, axis):
+    """(TextureArgs, the arrays it points into, gb edge angles, pole edge angles): the edges go to the library as
+    np.cos(np.deg2rad(angles)), cosines of ascending angles = strictly decreasing values; it does the checking."""
+    gb_deg = texture_edges_deg(n_bins, 180.0) if gb_edges_deg is None else np.asarray(gb_edges_deg, np.float64).ravel()
+    pole_deg = texture_edges_deg(n_bins, 90.0) if pole_edges_deg is None else np.asarray(pole_edges_deg, np.float64).ravel()
+    n_edges = max(int(n_bins) - 1, 0)
+    if len(gb_deg) != n_edges or len(pole_deg) != n_edges:
+        raise ValueError(f"n_bins = {n_bins} takes {n_edges} interior edges, got {len(gb_deg)} and {len(pole_deg)}")
+    keep = (np.ascontiguousarray(np.cos(np.deg2rad(gb_deg))), np.ascontiguousarray(np.cos(np.deg2rad(pole_deg))))
+    a = _lib.TextureArgs()
+    a.n_bins = int(n_bins)
+    a.gb_edges, a.pole_edges = (_dptr(keep[0]), _dptr(keep[1])) if n_edges else (None, None)
+    a.axis[:] = [float(x) for x in axis]
+    return a, keep, gb_deg, pole_deg
+
+
 def _default_ar_threshold():
     import constants as K
     return K.CET_AR_THRESHOLD
@@ -420,6 +441,29 @@ class Engine:
                                                _ptr(buf)))
         return {n: buf[n].copy() for n in LAYER_DTYPE.names if n != "pad"}
 
+    def texture_profile(self, n_bins=36, gb_edges_deg=None, pole_edges_deg=None, axis=(1.0, 0.0, 0.0), threshold=0.5,
+                        recluster=True):
+        """cetkmc_texture_profile (grain-boundary misorientation and pole histograms) of the resident
+        lattice: a dict of int64 arrays with leading dimension L (plane i of the build direction) -- gb_hist (L, 3, n_bins):
+        the grain-grain faces of the plane across each lattice axis by misorientation bin; pole_hist (L, n_bins): its
+        occupied voxels by the angle between their orientation vector (or its opposite) and ``axis``; bad (L, 4): faces per
+        axis / voxels whose value is not finite -- plus the interior edge angles used, ``gb_edges_deg`` and
+        ``pole_edges_deg`` (n_bins - 1 ascending degrees each; bin b lies between edge b - 1 and edge b, a value exactly on
+        an edge belongs to the bin above it).  The defaults are equal steps over 0..180 degrees (boundaries) and 0..90
+        degrees (pole).  ``axis`` is used as given, not normalised.  The model attaches no crystal frame to the lattice:
+        reading component 0 of the orientation vectors against lattice axis 0, the build direction, is this project's
+        convention for the default axis.  Clusters first with ``threshold`` unless ``recluster`` is False, which reuses the
+        handle's last clustering or import (the lattice must not have changed since).  metrics.texture_metrics turns the
+        profile into columns.  The ensemble's own handle is refused: Ensemble.texture_profile covers every replica."""
+        if recluster:
+            n = C.c_int64(0)
+            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+        a, _keep, gb_deg, pole_deg = _texture_args(n_bins, gb_edges_deg, pole_edges_deg, axis)
+        nb, L = max(int(n_bins), 1), max(self.L, 1)
+        gb, pole, bad = np.zeros((L, 3, nb), np.int64), np.zeros((L, nb), np.int64), np.zeros((L, 4), np.int64)
+        self._ck(self.lib.cetkmc_texture_profile(self.h, C.byref(a), _ptr(gb), _ptr(pole), _ptr(bad)))
+        return dict(gb_hist=gb, pole_hist=pole, bad=bad, gb_edges_deg=gb_deg, pole_edges_deg=pole_deg)
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -629,6 +673,20 @@ class Ensemble:
         self._ck(self.lib.cetkmc_ensemble_layer_profile(
             self.h, float(_default_ar_threshold() if ar_threshold is None else ar_threshold), _ptr(buf)))
         return {n: buf[n][:self.R].copy() for n in LAYER_DTYPE.names if n != "pad"}
+
+    def texture_profile(self, n_bins=36, gb_edges_deg=None, pole_edges_deg=None, axis=(1.0, 0.0, 0.0), threshold=0.5,
+                        recluster=True):
+        """cetkmc_ensemble_texture_profile: Engine.texture_profile of every replica (frozen ones included) in one launch
+        whatever R.  The int64 arrays gain the leading dimension R: gb_hist (R, L, 3, n_bins), pole_hist (R, L, n_bins), bad
+        (R, L, 4).  Runs :meth:`analyze` first (without downloading labels) unless ``recluster`` is False, which reuses the
+        last analysis or import."""
+        if recluster:
+            self.analyze(threshold, labels=False)
+        a, _keep, gb_deg, pole_deg = _texture_args(n_bins, gb_edges_deg, pole_edges_deg, axis)
+        nb, L, R = max(int(n_bins), 1), self.L, max(self.R, 1)
+        gb, pole, bad = np.zeros((R, L, 3, nb), np.int64), np.zeros((R, L, nb), np.int64), np.zeros((R, L, 4), np.int64)
+        self._ck(self.lib.cetkmc_ensemble_texture_profile(self.h, C.byref(a), _ptr(gb), _ptr(pole), _ptr(bad)))
+        return dict(gb_hist=gb[:self.R], pole_hist=pole[:self.R], bad=bad[:self.R], gb_edges_deg=gb_deg, pole_edges_deg=pole_deg)
 
     def set_defects_sparse(self, lists):
         """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""

@@ -28,6 +28,7 @@
 #include "ensemble.hpp"
 #include "front.hpp"
 #include "layer.hpp"
+#include "texture.hpp"
 
 using namespace cetkmc;
 
@@ -1218,7 +1219,7 @@ int cetkmc_struct_size(const char* name)
     SZ("params", cetkmc_params); SZ("event", cetkmc_event); SZ("sweep_info", cetkmc_sweep_info);
     SZ("run_args", cetkmc_run_args); SZ("run_result", cetkmc_run_result); SZ("super_args", cetkmc_super_args);
     SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm); SZ("ens_args", cetkmc_ens_args); SZ("ens_analysis", cetkmc_ens_analysis);
-    SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec);
+    SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec); SZ("texture_args", struct cetkmc_texture_args);
 #undef SZ
     return -1;
 }
@@ -2960,6 +2961,94 @@ int cetkmc_ensemble_layer_profile(void* handle, double ar_threshold, struct cetk
     HIPCHK(hipStreamSynchronize(st));
     h0->cnt.bytes_d2h += (int64_t)R * L * (int64_t)sizeof(LayerRec);
     return 0;
+}
+
+// ---- grain-boundary misorientation and pole histograms (texture.hpp) ---------------------------
+// the caller's arguments checked and turned into the kernel's: everything a refusal needs is known here, on the host
+static int texture_args(const char* fn, const struct cetkmc_texture_args* a, TexArgs* A)
+{
+    const std::string f(fn);
+    if (a->n_bins < 1 || a->n_bins > TEX_MAX_BINS) return fail(f + ": n_bins " + std::to_string(a->n_bins) + " outside 1.." + std::to_string(TEX_MAX_BINS));
+    const double* src[2] = {a->gb_edges, a->pole_edges};
+    const char* const name[2] = {"gb_edges", "pole_edges"};
+    A->n_bins = a->n_bins; A->pad = 0;
+    for (int w = 0; w < 2; ++w) {
+        if (a->n_bins > 1 && !src[w]) return fail(f + ": " + name[w] + " is NULL with n_bins > 1");
+        for (int q = 0; q < TEX_NE; ++q) {
+            if (q >= a->n_bins - 1) { A->edges[w][q] = -HUGE_VAL; continue; }
+            const double e = src[w][q];
+            if (!std::isfinite(e)) return fail(f + ": " + name[w] + "[" + std::to_string(q) + "] is not finite");
+            if (q > 0 && !(e < src[w][q - 1])) return fail(f + ": " + name[w] + "[" + std::to_string(q) + "] is not below its predecessor (strictly decreasing edges)");
+            A->edges[w][q] = e;
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(a->axis[c])) return fail(f + ": axis[" + std::to_string(c) + "] is not finite");
+        A->axis[c] = a->axis[c];
+    }
+    return 0;
+}
+static dim3 texture_grid(int L, int R)
+{
+    return dim3((unsigned)(((L + TEX_TJ - 1) / TEX_TJ) * ((L + TEX_TK - 1) / TEX_TK)), (unsigned)((L + TEX_NI - 1) / TEX_NI), (unsigned)R);
+}
+// zero the rows on the stream, count into them (go = the launch), bring them to the host and split the `rows` device rows
+// of 4 n_bins + 4 counters into the caller's three arrays (any of them may be NULL)
+extern "C++" template <class Go>
+static int texture_rows(Handle* h, hipStream_t st, int64_t rows, int nb, int64_t* gb_hist, int64_t* pole_hist, int64_t* bad, Go&& go)
+{
+    const int nc = 4 * nb + 4;
+    DevTmp<unsigned long long> d_rows;
+    HIPCHK(d_rows.alloc((size_t)rows * nc));
+    HIPCHK(hipMemsetAsync(d_rows.p, 0, (size_t)rows * nc * sizeof(unsigned long long), st));
+    go(d_rows.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> host((size_t)rows * nc);
+    HIPCHK(hipMemcpyAsync(host.data(), d_rows.p, host.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h->cnt.bytes_d2h += (int64_t)(host.size() * sizeof(int64_t));
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t* s = host.data() + r * nc;
+        if (gb_hist) std::copy(s, s + 3 * nb, gb_hist + r * 3 * nb);
+        if (pole_hist) std::copy(s + 3 * nb, s + 4 * nb, pole_hist + r * nb);
+        if (bad) std::copy(s + 4 * nb, s + nc, bad + r * 4);
+    }
+    return 0;
+}
+
+int cetkmc_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist, int64_t* bad)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !args) return fail("null argument");
+    if (ens_of(handle)) return fail("cetkmc_texture_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_texture_profile");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_texture_profile needs the whole lattice in one slab");
+    if (h->cc_n_clusters < 0) return fail("cetkmc_texture_profile needs a preceding cetkmc_cluster");
+    TexArgs A;
+    CHK(texture_args("cetkmc_texture_profile", args, &A));
+    HIPCHK(hipSetDevice(h->dev));
+    return texture_rows(h, h->stream, h->L, A.n_bins, gb_hist, pole_hist, bad, [&](unsigned long long* d_rows) {
+        launch(k_texture_profile<>, texture_grid(h->L, 1), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), (const int*)h->d_cc_labels, A, d_rows);
+    });
+}
+
+int cetkmc_ensemble_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist,
+                                    int64_t* bad)
+{
+    if (!handle || !args) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_texture_profile needs a preceding cetkmc_ensemble_analyze");
+    TexArgs A;
+    CHK(texture_args("cetkmc_ensemble_texture_profile", args, &A));
+    const int R = e->R, L = e->L;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    CHK(ens_push_views(e));
+    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, nullptr};
+    return texture_rows(h0, st, (int64_t)R * L, A.n_bins, gb_hist, pole_hist, bad, [&](unsigned long long* d_rows) {
+        launch(k_texture_profile<EnsSel>, texture_grid(L, R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, (const int*)e->d_cc_labels, A, d_rows, sel);
+    });
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ collects the CET classification of the last metrics row of every run into ``outp
 
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
                        [--mode B --box 8] [--seeds K] [--ensemble [--rng counter]]
-                       [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]] [--front] [--layers]
+                       [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]] [--front] [--layers] [--texture]
 
 ``--seeds K`` runs every point with the seeds RANDOM_SEED .. RANDOM_SEED + K - 1 (one gv_map.csv row per point and seed, with
 a ``seed`` column when K > 1); ``--ensemble`` runs all of them as one replica ensemble (run_kmc_ensemble): with the default
@@ -29,6 +29,11 @@ what they were.
 ``--layers`` measures the layer-resolved grain structure of every run on the device (run_kmc's ``layer_metrics``): every
 metrics.csv gains the layer columns, every run directory a layers.csv, and gv_map.csv the columns ``CET_height_um`` and
 ``InterceptRatio`` from each run's last row (behind the front columns).  Without the flag the files are what they were.
+
+``--texture`` measures the grain-boundary misorientation and pole histograms of every run on the device (run_kmc's
+``texture_metrics``): every metrics.csv gains the texture columns, every run directory a texture.csv, and gv_map.csv the
+columns ``GB_low_angle_frac`` and ``Pole_aligned_frac`` from each run's last row (behind the layer columns).  Without the
+flag the files are what they were.
 """
 import argparse
 import os
@@ -62,7 +67,8 @@ def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_p
 
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
-             laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, **run_kw):
+             laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, texture=False,
+             **run_kw):
     """``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
     engine (same metrics.csv columns; n_steps stays the number of executed events).  ``seeds=K`` runs every point with the
     seeds RANDOM_SEED .. RANDOM_SEED + K - 1; ``ensemble=True`` runs all runs of the map as one replica ensemble.
@@ -70,7 +76,8 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
     ``front=True``: every run with ``front_metrics=True``; gv_map.csv gains the measured ``G_front_K_per_m``,
     ``V_front_m_per_s`` and ``G_over_V_front`` (inf when V is 0) of each run's last row behind the nominal columns.
     ``layers=True``: every run with ``layer_metrics=True``; gv_map.csv gains ``CET_height_um`` (-1.0: no transition) and
-    ``InterceptRatio`` of each run's last row behind those."""
+    ``InterceptRatio`` of each run's last row behind those.  ``texture=True``: every run with ``texture_metrics=True``;
+    gv_map.csv gains ``GB_low_angle_frac`` and ``Pole_aligned_frac`` of each run's last row behind those."""
     check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers, scan_speeds)
     seeds = int(seeds)
     beams = [(p, v) for p in laser_powers for v in scan_speeds] if laser_powers else [None]
@@ -86,7 +93,8 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
                 nu_dep=nu_dep, **({"seed": seed} if seeds > 1 else {}),
                 **({"laser": dict(power=float(beam[0]), start=float(laser_start), speed=float(beam[1]))} if beam else {}))
            for T_sub, nu_dep, seed, prefix, beam in runs]
-    opt = dict(**({"front_metrics": True} if front else {}), **({"layer_metrics": True} if layers else {}))
+    opt = dict(**({"front_metrics": True} if front else {}), **({"layer_metrics": True} if layers else {}),
+               **({"texture_metrics": True} if texture else {}))
     if ensemble:
         run_kmc_ensemble(cfg, L, n_steps, rng=rng, **opt)
     else:
@@ -111,6 +119,8 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
             row.update({"G_front_K_per_m": Gf, "V_front_m_per_s": Vf, "G_over_V_front": Gf / Vf if Vf != 0.0 else float("inf")})
         if layers:
             row.update({"CET_height_um": float(last["CET_height_um"]), "InterceptRatio": float(last["InterceptRatio"])})
+        if texture:
+            row.update({"GB_low_angle_frac": float(last["GB_low_angle_frac"]), "Pole_aligned_frac": float(last["Pole_aligned_frac"])})
         rows.append(row)
     os.makedirs(out_dir, exist_ok=True)
     df = pd.DataFrame(rows)
@@ -139,8 +149,11 @@ if __name__ == "__main__":
                     help="measure G and V at the growth front on the device: front columns in every metrics.csv and gv_map.csv")
     ap.add_argument("--layers", action="store_true",
                     help="layer-resolved grain structure on the device: layer columns in every metrics.csv, layers.csv, gv_map.csv")
+    ap.add_argument("--texture", action="store_true",
+                    help="boundary misorientation and pole histograms on the device: texture columns in every metrics.csv, "
+                         "texture.csv, gv_map.csv")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
-                   layers=a.layers, **kw).to_string(index=False))
+                   layers=a.layers, texture=a.texture, **kw).to_string(index=False))

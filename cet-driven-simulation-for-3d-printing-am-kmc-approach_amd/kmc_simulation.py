@@ -32,7 +32,8 @@ from kmc_event_rates import get_event_rates  # noqa: F401  (re-exported like the
 from lattice_init import initialize_lattice
 from metrics import (compute_CET, compute_metrics, compute_metrics_device, compute_metrics_from_clusters,  # noqa: F401
                      detect_CET_transition, front_metrics as _front_metrics, front_velocity as _front_velocity,
-                     layer_metrics as _layer_metrics, write_layers_csv as _write_layers_csv)
+                     layer_metrics as _layer_metrics, texture_metrics as _texture_metrics,
+                     write_layers_csv as _write_layers_csv, write_texture_csv as _write_texture_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
@@ -200,6 +201,15 @@ def _add_layer_columns(row, profile, L):
     return planes
 
 
+def _add_texture_columns(row, profile):
+    """texture_metrics=True: the texture columns (metrics.TEXTURE_COLUMNS) behind every other column of ``row``, in place;
+    returns the per-plane table of the row (the rows of texture.csv)."""
+    m = _texture_metrics(profile)
+    planes = m.pop("planes")
+    row.update(m)
+    return planes
+
+
 def _print_row(step, row):
     print(
         f"Step {step}: AR={row['AspectRatio']:.2f}, "
@@ -268,6 +278,7 @@ def run_kmc(
     laser: dict = None,
     front_metrics: bool = False,
     layer_metrics: bool = False,
+    texture_metrics: bool = False,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -316,7 +327,13 @@ def run_kmc(
     behind the front columns), the layer columns of metrics.layer_metrics -- the CET height, the equiaxed area fraction,
     the mean intercept lengths along and across the build direction and the species-resolved grain-boundary fractions --
     from the row's own clustering, reduced on the device by cetkmc_layer_profile (L * 144 bytes cross PCIe per row); the
-    per-plane table of the last row is written to ``outputs/<prefix>/layers.csv``."""
+    per-plane table of the last row is written to ``outputs/<prefix>/layers.csv``.
+
+    ``texture_metrics=True`` (both modes, with and without ``laser``): every metrics row gains, behind the layer columns,
+    the texture columns of metrics.texture_metrics -- grain-grain faces, their mean misorientation, the low-angle and
+    lateral shares and the share of voxels aligned with the build axis -- from the row's own clustering, binned on the
+    device by cetkmc_texture_profile (Engine.texture_profile's defaults: 36 bins, axis (1, 0, 0); L * 148 * 8 bytes cross
+    PCIe per row); the per-plane table of the last row is written to ``outputs/<prefix>/texture.csv``."""
     import cetkmc
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
@@ -367,7 +384,7 @@ def run_kmc(
     step = -1
     next_step = 0
     nuc_offset = 0
-    layer_planes = None
+    layer_planes = texture_planes = None
     if ckpt:
         total_time, metrics_data, cet_detected = ckpt["total_time"], ckpt["metrics_data"], ckpt["cet_detected"]
         next_step, nuc_offset = ckpt["next_step"], ckpt["nucleation_count"]
@@ -375,7 +392,7 @@ def run_kmc(
     def metrics_row(step, refresh_defects):
         """kmc_simulation.py:335-389 for the lattice as it stands after event index `step` -- WITHOUT moving the lattice: the
         defect mask is refreshed from the carbon sites only, grains are clustered and species counted on the GPU."""
-        nonlocal n_flagged, cet_detected, layer_planes
+        nonlocal n_flagged, cet_detected, layer_planes, texture_planes
         if refresh_defects:
             n_flagged, _ = refresh_defects_device(engine)       # kmc_simulation.py:335-338
         row = _metrics_row(engine.clusters(0.5, labels=True), engine.species_counts(), engine.nucleation_count(), L, step,
@@ -385,6 +402,8 @@ def run_kmc(
             _add_front_columns(row, engine.front_stats(), L, metrics_data[-1] if metrics_data else None)
         if layer_metrics:               # from the clustering of this row: no second clustering, no label download
             layer_planes = _add_layer_columns(row, engine.layer_profile(recluster=False), L)
+        if texture_metrics:
+            texture_planes = _add_texture_columns(row, engine.texture_profile(recluster=False))
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -474,6 +493,8 @@ def run_kmc(
         print(f"Metrics saved to {_write_metrics(output_prefix, metrics_data)}")
     if layer_planes is not None:
         _write_layers_csv(os.path.join(output_dir, "layers.csv"), layer_planes)
+    if texture_planes is not None:
+        _write_texture_csv(os.path.join(output_dir, "texture.csv"), texture_planes)
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -572,7 +593,7 @@ def _replica_prefix(cfg, L):
 
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
-                     front_metrics=False, layer_metrics=False):
+                     front_metrics=False, layer_metrics=False, texture_metrics=False):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -587,7 +608,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     restored on return.  One completion line is printed per replica (no per-row progress).
     ``front_metrics=True``: run_kmc's option of that name, from ONE batched cetkmc_ensemble_front_stats call per metrics row.
     ``layer_metrics=True``: run_kmc's option of that name (columns and ``layers.csv`` of every replica), from ONE batched
-    cetkmc_ensemble_layer_profile call per metrics row on the row's own analysis."""
+    cetkmc_ensemble_layer_profile call per metrics row on the row's own analysis.
+    ``texture_metrics=True``: run_kmc's option of that name (columns and ``texture.csv`` of every replica), from ONE batched
+    cetkmc_ensemble_texture_profile call per metrics row on the row's own analysis."""
     import cetkmc
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
@@ -619,6 +642,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         metrics = [[] for _ in range(R)]
         cet = [False] * R
         layer_planes = [None] * R
+        texture_planes = [None] * R
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -698,6 +722,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 ens.set_defects_sparse(lists)
             fs = ens.front_stats() if front_metrics else None
             lp = ens.layer_profile(recluster=False) if layer_metrics else None
+            tp = ens.texture_profile(recluster=False) if texture_metrics else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -710,6 +735,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                     _add_front_columns(row, {k: v[r] for k, v in fs.items()}, L, metrics[r][-1] if metrics[r] else None)
                 if lp is not None:
                     layer_planes[r] = _add_layer_columns(row, {k: v[r] for k, v in lp.items()}, L)
+                if tp is not None:
+                    texture_planes[r] = _add_texture_columns(
+                        row, {k: (v[r] if k in ("gb_hist", "pole_hist", "bad") else v) for k, v in tp.items()})
                 metrics[r].append(row)
             next_step = stop + 1
 
@@ -720,6 +748,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 _write_metrics(c["output_prefix"], metrics[r])
             if layer_planes[r] is not None:
                 _write_layers_csv(os.path.join(f"outputs/{c['output_prefix']}", "layers.csv"), layer_planes[r])
+            if texture_planes[r] is not None:
+                _write_texture_csv(os.path.join(f"outputs/{c['output_prefix']}", "texture.csv"), texture_planes[r])
             fields = ens.replica(r).download()
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))

@@ -241,6 +241,69 @@ def write_layers_csv(path, planes):
             w.writerow([planes[n][i].item() for n in names])
 
 
+TEXTURE_COLUMNS = ("GB_faces", "GB_misorientation_mean_deg", "GB_low_angle_frac", "GB_lateral_frac", "Pole_aligned_frac",
+                   "Texture_bad")
+TEXTURE_LOW_ANGLE_DEG = 15.0
+
+
+def texture_metrics(profile, low_angle_deg=TEXTURE_LOW_ANGLE_DEG):
+    """Columns of a metrics row (TEXTURE_COLUMNS) from one lattice's texture profile (Engine.texture_profile, or entry r of
+    the three count arrays of Ensemble.texture_profile with the edge angles beside them), plus the per-plane table under
+    "planes" (the rows of texture.csv).  Everything is computed here, on the host, from the integer bins.
+
+    GB_faces: grain-grain faces that fell into a bin.  GB_misorientation_mean_deg: their mean misorientation with every
+    face at the centre of its bin (the bins span 0..180 degrees between the interior edges).  GB_low_angle_frac: the share
+    of them in bins that end at or below ``low_angle_deg`` (the default 5-degree edges contain 15 degrees; with other edges
+    a bin that straddles the angle is not counted).  GB_lateral_frac: the share across lattice axes 1 and 2, i.e. of
+    boundaries that run along the build direction.  Pole_aligned_frac: of the binned voxels, the share within
+    ``low_angle_deg`` of the axis (bins span 0..90 degrees).  Texture_bad: faces and voxels whose value was not finite
+    (they are in no bin and in none of the ratios).  Every ratio with a zero denominator is 0.0."""
+    gb = np.asarray(profile["gb_hist"], dtype=np.int64)
+    pole = np.asarray(profile["pole_hist"], dtype=np.int64)
+    bad = np.asarray(profile["bad"], dtype=np.int64)
+    L, nb = pole.shape
+    gb = gb.reshape(L, 3, nb)
+    bad = bad.reshape(L, 4)
+    gb_full = np.concatenate(([0.0], np.asarray(profile["gb_edges_deg"], dtype=np.float64), [180.0]))
+    pole_full = np.concatenate(([0.0], np.asarray(profile["pole_edges_deg"], dtype=np.float64), [90.0]))
+    gb_centre = 0.5 * (gb_full[:-1] + gb_full[1:])
+    gb_low = gb_full[1:] <= low_angle_deg + 1e-9
+    pole_low = pole_full[1:] <= low_angle_deg + 1e-9
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else 0.0
+
+    def columns(g, p):            # g (3, nb), p (nb,): one plane or the sum over the planes
+        faces, by_bin = int(g.sum()), g.sum(axis=0)
+        return (faces, ratio(float(np.dot(by_bin, gb_centre)), faces), ratio(int(by_bin[gb_low].sum()), faces),
+                ratio(int(g[1].sum() + g[2].sum()), faces), ratio(int(p[pole_low].sum()), int(p.sum())))
+
+    tot = columns(gb.sum(axis=0), pole.sum(axis=0))
+    out = dict(zip(TEXTURE_COLUMNS[:5], tot))
+    out["Texture_bad"] = int(bad.sum())
+    per = [columns(gb[i], pole[i]) for i in range(L)]
+    planes = {"plane": np.arange(L, dtype=np.int64)}
+    for c, name in enumerate(TEXTURE_COLUMNS[:5]):
+        planes[name] = np.array([x[c] for x in per], dtype=np.int64 if c == 0 else np.float64)
+    for a in range(3):
+        planes[f"GB_faces{a}"] = gb[:, a, :].sum(axis=1)
+    for a in range(4):
+        planes[f"bad{a}"] = bad[:, a]
+    for a in range(3):
+        for b in range(nb):
+            planes[f"gb{a}_bin{b}"] = gb[:, a, b]
+    for b in range(nb):
+        planes[f"pole_bin{b}"] = pole[:, b]
+    out["planes"] = planes
+    return out
+
+
+def write_texture_csv(path, planes):
+    """The per-plane table of :func:`texture_metrics` (its "planes" entry) as a CSV with one row per plane: the summary
+    columns of the plane, its faces per axis, the non-finite counts and the raw bins."""
+    write_layers_csv(path, planes)
+
+
 def front_velocity(row, prev, voxel_size=VOXEL_SIZE):
     """V_front of a metrics row: (Front_i - the previous row's) * voxel_size / (Time - the previous row's) in m/s; 0.0 on
     the first row (``prev`` None), when the time difference is 0 or when either row has no front."""

@@ -187,7 +187,7 @@ int cetkmc_abi_version(void);
  * hand build): the binding compares it with the sources beside it and rebuilds / refuses a stale library */
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
- * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -501,6 +501,43 @@ int cetkmc_cluster_import(void* handle, const int32_t* labels, int64_t* n_cluste
  * anything is uploaded; one bad replica refuses the call and leaves the previous analysis intact.
  * cetkmc_ensemble_analysis_data and cetkmc_ensemble_layer_profile then read the import.  A single-lattice handle is refused. */
 int cetkmc_ensemble_cluster_import(void* handle, const int32_t* labels, int64_t* n_clusters);
+
+/* Grain-boundary misorientation and texture profiles (not in the reference): integer histograms per
+ * plane i of the build direction (axis 0), from the label volume of the handle's LAST clustering (cetkmc_cluster or
+ * cetkmc_cluster_import) and the per-voxel orientation unit vectors the device keeps (sin t cos p, sin t sin p, cos t), in
+ * one streaming pass.  g(v) is the label of voxel v = (i, j, k) (0 = empty), o(v) its three doubles.
+ * One binning rule serves both histograms: over n_bins - 1 interior edges e[0] > e[1] > ... (strictly decreasing, finite:
+ * cosines of ascending angles, computed by the caller) bin(x) is the number of edges with x <= e[q], so bin 0 holds the
+ * values above e[0] and bin n_bins - 1 those at or below the last edge.  The device applies no acos and no clamp (a value
+ * above 1 by rounding lands in bin 0); a value that is not finite is counted in bad and in no bin.
+ *   gb_hist[i][a][b]   for every v of plane i with g(v) != 0 and every axis a whose predecessor u (that coordinate minus 1)
+ *                      is inside the lattice with g(u) != 0 and g(u) != g(v) -- the faces cut[a] of cetkmc_layer_rec counts:
+ *                      +1 at b = bin(d), d = o(u)[0]*o(v)[0] + o(u)[1]*o(v)[1] + o(u)[2]*o(v)[2] summed left to right
+ *                      without fused multiply-add, against gb_edges; bad[i][a] +1 instead if d is not finite;
+ *   pole_hist[i][b]    for every v of plane i with g(v) != 0: +1 at b = bin(c), c = fabs(axis[0]*o(v)[0] + axis[1]*o(v)[1]
+ *                      + axis[2]*o(v)[2]) against pole_edges; bad[i][3] +1 instead if c is not finite.
+ * axis is used as given (not normalised) and must be finite.  So sum_b gb_hist[i][a][b] + bad[i][a] == cut[a] and
+ * sum_b pole_hist[i][b] + bad[i][3] == n_occ of plane i's cetkmc_layer_rec.  Everything is integer counting: the result is
+ * defined to the bit given the vectors, and two calls return the same bits.  For a lattice changed since its clustering the
+ * result is unspecified (the call stays inside its arrays). */
+struct cetkmc_texture_args {
+    int32_t n_bins;               /* 1..64, of both histograms                                             */
+    int32_t pad;
+    const double* gb_edges;       /* [n_bins - 1] host, strictly decreasing; may be NULL when n_bins == 1  */
+    const double* pole_edges;     /* [n_bins - 1] likewise                                                 */
+    double axis[3];
+};
+/* One lattice, under the handle rules of cetkmc_layer_profile.  gb_hist[L][3][n_bins], pole_hist[L][n_bins], bad[L][4]; any
+ * of the three may be NULL.  n_bins outside 1..64, a NULL edge array with n_bins > 1, an edge that is not finite or not
+ * below its predecessor and a non-finite axis are refused on the host before anything is allocated or launched.  Ordered on
+ * the handle's stream behind pending stepping work; copies L * (4 * n_bins + 4) * 8 bytes to the host (counted in
+ * bytes_d2h); writes no lattice field. */
+int cetkmc_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist, int64_t* bad);
+/* Every replica of an ensemble, frozen ones included, from the clustering of the last cetkmc_ensemble_analyze (required) or
+ * an import on top of it, in one launch whatever R; gb_hist[R][L][3][n_bins], pole_hist[R][L][n_bins], bad[R][L][4].  A
+ * single-lattice handle is refused. */
+int cetkmc_ensemble_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist,
+                                    int64_t* bad);
 
 #ifdef __cplusplus
 }
