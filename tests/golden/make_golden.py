@@ -469,8 +469,33 @@ def gen_metrics():
     print("  wrote metrics_meta.json")
 
 
+def gen_clusters_general():
+    """get_clusters on continuous random orientations (every voxel its own), where "misorientation below the threshold" is
+    no equivalence relation: voxels end up in one grain through chains of neighbours although their own misorientation is
+    above the threshold.  The palette lattices of gen_metrics never have that.  Thresholds from nearly nothing joins (0.1)
+    to everything joins (4.0 > pi)."""
+    out = {}
+    for L, seed, fill in ((8, 41, 0.9), (10, 42, 0.8), (12, 43, 0.7)):
+        rs = np.random.RandomState(seed)
+        state = np.zeros((L, L, L), dtype=np.int64)
+        occ = rs.random_sample((L, L, L)) < fill
+        state[occ] = rs.choice([1, 2, 3, 4], size=int(occ.sum()), p=[0.6, 0.15, 0.2, 0.05])
+        theta = np.where(state != 0, rs.uniform(0, np.pi, (L, L, L)), 0.0)
+        phi = np.where(state != 0, rs.uniform(0, 2 * np.pi, (L, L, L)), 0.0)
+        out[f"c_L{L}_state"] = state.astype(np.int8)
+        out[f"c_L{L}_theta"] = theta
+        out[f"c_L{L}_phi"] = phi
+        for thr in (0.1, 0.5, 1.2, 4.0):
+            clusters, visited = ref_utils.get_clusters(state, theta, phi, theta_threshold=thr)
+            key = f"c_L{L}_t{thr}"
+            out[key + "_visited"] = np.asarray(visited, dtype=np.int32)
+            out[key + "_cluster_sizes"] = np.array([len(c) for c in clusters], np.int32)
+            out[key + "_cluster_first"] = np.array([c[0] for c in clusters], np.int32).reshape(-1, 3)
+    save("clusters_general", **out)
+
+
 GENS = dict(events=gen_events, events_odd=gen_events_odd, events_init=gen_events_initlattice, traj=gen_traj, thermal=gen_thermal,
-            init_defects=gen_init_defects, metrics=gen_metrics)
+            init_defects=gen_init_defects, metrics=gen_metrics, clusters_general=gen_clusters_general)
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
