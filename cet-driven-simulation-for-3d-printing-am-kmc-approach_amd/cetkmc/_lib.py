@@ -116,6 +116,13 @@ class LayerRec(C.Structure):
     ]
 
 
+class GrainRec(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64), ("sum", C.c_int64 * 3), ("sq", C.c_int64 * 6), ("n_state", C.c_int64 * 4), ("nb", C.c_int64 * 4),
+        ("first_theta", C.c_double), ("first_phi", C.c_double),
+    ]
+
+
 class TextureArgs(C.Structure):
     _fields_ = [
         ("n_bins", C.c_int32), ("pad", C.c_int32), ("gb_edges", C.POINTER(C.c_double)), ("pole_edges", C.POINTER(C.c_double)),
@@ -126,7 +133,7 @@ class TextureArgs(C.Structure):
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
-                  "texture_args": TextureArgs}
+                  "texture_args": TextureArgs, "grain_rec": GrainRec}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -190,6 +197,8 @@ PROTOTYPES = {
     "cetkmc_ensemble_cluster_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cetkmc_texture_profile": (C.c_int, [C.c_void_p, _P(TextureArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cetkmc_ensemble_texture_profile": (C.c_int, [C.c_void_p, _P(TextureArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_grain_table": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "cetkmc_ensemble_grain_table": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 

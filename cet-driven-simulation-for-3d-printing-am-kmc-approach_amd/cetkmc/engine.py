@@ -16,6 +16,9 @@ assert FRONT_DTYPE.itemsize == C.sizeof(_lib.FrontStats) == 112
 LAYER_DTYPE = np.dtype([("n_occ", "<i8"), ("n_start", "<i8"), ("n_eq", "<i8"), ("seg", "<i8", 3), ("cut", "<i8", 3),
                         ("occ_state", "<i8", 4), ("gb_state", "<i8", 4), ("pad", "<i8")])
 assert LAYER_DTYPE.itemsize == C.sizeof(_lib.LayerRec) == 144
+GRAIN_DTYPE = np.dtype([("n", "<i8"), ("sum", "<i8", 3), ("sq", "<i8", 6), ("n_state", "<i8", 4), ("nb", "<i8", 4),
+                        ("first_theta", "<f8"), ("first_phi", "<f8")])
+assert GRAIN_DTYPE.itemsize == C.sizeof(_lib.GrainRec) == 160
 
 TYPE_BYTES = (b"dep", b"diff", b"nuc", b"att")   # kmc_event_rates.py:72,109,132,158
 
@@ -365,7 +368,7 @@ class Engine:
         numbered in the reference's order (first voxel, row-major)."""
         n = C.c_int64(0)
         self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-        k = n.value
+        k = self._cc_n = n.value
         first = np.zeros((max(k, 1), 3), np.int32)
         size = np.zeros(max(k, 1), np.int64)
         bbox = np.zeros((max(k, 1), 6), np.int32)
@@ -387,7 +390,7 @@ class Engine:
         assert lab.shape == (self.L,) * 3, lab.shape
         n = C.c_int64(0)
         self._ck(self.lib.cetkmc_cluster_import(self.h, _ptr(lab), C.byref(n)))
-        k = n.value
+        k = self._cc_n = n.value
         first = np.zeros((max(k, 1), 3), np.int32)
         size = np.zeros(max(k, 1), np.int64)
         bbox = np.zeros((max(k, 1), 6), np.int32)
@@ -436,6 +439,7 @@ class Engine:
         if recluster:
             n = C.c_int64(0)
             self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+            self._cc_n = n.value
         buf = np.zeros(max(self.L, 1), dtype=LAYER_DTYPE)
         self._ck(self.lib.cetkmc_layer_profile(self.h, float(_default_ar_threshold() if ar_threshold is None else ar_threshold),
                                                _ptr(buf)))
@@ -458,11 +462,43 @@ class Engine:
         if recluster:
             n = C.c_int64(0)
             self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+            self._cc_n = n.value
         a, _keep, gb_deg, pole_deg = _texture_args(n_bins, gb_edges_deg, pole_edges_deg, axis)
         nb, L = max(int(n_bins), 1), max(self.L, 1)
         gb, pole, bad = np.zeros((L, 3, nb), np.int64), np.zeros((L, nb), np.int64), np.zeros((L, 4), np.int64)
         self._ck(self.lib.cetkmc_texture_profile(self.h, C.byref(a), _ptr(gb), _ptr(pole), _ptr(bad)))
         return dict(gb_hist=gb, pole_hist=pole, bad=bad, gb_edges_deg=gb_deg, pole_edges_deg=pole_deg)
+
+    _cc_n = None        # grains of the handle's last clustering, when it was made through this object
+
+    def grain_table(self, threshold=0.5, recluster=True):
+        """cetkmc_grain_table (per-grain table) of the resident lattice: a dict of arrays with leading
+        dimension n, entry id - 1 for grain id -- n (n,), sum (n, 3), sq (n, 6: ii, jj, kk, ij, ik, jk), n_state (n, 4), nb
+        (n, 4: same, other, empty, outside over the clustering's 14-offset stencil), all int64, and first_theta, first_phi
+        (n,) float64, the stored angles of the grain's first voxel bit for bit.  Clusters first with ``threshold`` unless
+        ``recluster`` is False, which reuses the handle's last clustering or import (the lattice must not have changed
+        since).  metrics.grain_metrics turns it into columns.  The ensemble's own handle is refused: Ensemble.grain_table
+        covers every replica."""
+        if recluster:
+            n = C.c_int64(0)
+            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+            self._cc_n = n.value
+        k = self._cc_n
+        if k is None:
+            # a clustering this object did not make (or none: then the call fails in the library's words): every grain
+            # has n >= 1, so the first record left at zero ends the table
+            cap = 1024
+            while True:
+                buf = np.zeros(cap, dtype=GRAIN_DTYPE)
+                self._ck(self.lib.cetkmc_grain_table(self.h, cap, _ptr(buf)))
+                k = int(np.count_nonzero(buf["n"]))
+                if k < cap or cap >= self.L ** 3:
+                    break
+                cap *= 4
+        else:
+            buf = np.zeros(max(k, 1), dtype=GRAIN_DTYPE)
+            self._ck(self.lib.cetkmc_grain_table(self.h, k, _ptr(buf)))
+        return {f: buf[f][:k].copy() for f in GRAIN_DTYPE.names}
 
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
@@ -614,6 +650,7 @@ class Ensemble:
         a.n_clusters, a.species_counts = nc.ctypes.data_as(C.POINTER(C.c_int64)), cnt.ctypes.data_as(C.POINTER(C.c_int64))
         a.nucleation_count, a.n_gathered = nuc.ctypes.data_as(C.POINTER(C.c_int64)), ng.ctypes.data_as(C.POINTER(C.c_int64))
         self._ck(self.lib.cetkmc_ensemble_analyze(self.h, C.byref(a)))
+        self._an_nc = nc.copy()
         tot, gt = int(nc.sum()), int(ng.sum())
         first = np.zeros((max(tot, 1), 3), np.int32)
         size = np.zeros(max(tot, 1), np.int64)
@@ -648,6 +685,7 @@ class Ensemble:
         assert lab.shape == (R,) + (self.L,) * 3, lab.shape
         nc = np.zeros(max(R, 1), np.int64)
         self._ck(self.lib.cetkmc_ensemble_cluster_import(self.h, _ptr(lab), _ptr(nc)))
+        self._an_nc = nc[:R].copy()
         tot = int(nc[:R].sum())
         first = np.zeros((max(tot, 1), 3), np.int32)
         size = np.zeros(max(tot, 1), np.int64)
@@ -687,6 +725,23 @@ class Ensemble:
         gb, pole, bad = np.zeros((R, L, 3, nb), np.int64), np.zeros((R, L, nb), np.int64), np.zeros((R, L, 4), np.int64)
         self._ck(self.lib.cetkmc_ensemble_texture_profile(self.h, C.byref(a), _ptr(gb), _ptr(pole), _ptr(bad)))
         return dict(gb_hist=gb[:self.R], pole_hist=pole[:self.R], bad=bad[:self.R], gb_edges_deg=gb_deg, pole_edges_deg=pole_deg)
+
+    _an_nc = None       # grains per replica of the last analysis or import
+
+    def grain_table(self, threshold=0.5, recluster=True):
+        """cetkmc_ensemble_grain_table: Engine.grain_table of every replica (frozen ones included) in launches that do not
+        depend on R.  Returns one dict per replica, as :meth:`analyze` lays out its per-cluster data; entry r has the bits
+        of replica(r).grain_table().  Runs :meth:`analyze` first (without downloading labels) unless ``recluster`` is
+        False, which reuses the last analysis or import."""
+        if recluster:
+            self.analyze(threshold, labels=False)
+        if self._an_nc is None:            # no analysis yet: fails in the library's words
+            self._ck(self.lib.cetkmc_ensemble_grain_table(self.h, None))
+            raise RuntimeError("cetkmc: Ensemble.grain_table needs a preceding Ensemble.analyze")
+        at = np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
+        buf = np.zeros(max(int(at[-1]), 1), dtype=GRAIN_DTYPE)
+        self._ck(self.lib.cetkmc_ensemble_grain_table(self.h, _ptr(buf)))
+        return [{f: buf[f][at[r]:at[r + 1]].copy() for f in GRAIN_DTYPE.names} for r in range(self.R)]
 
     def set_defects_sparse(self, lists):
         """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""

@@ -29,6 +29,7 @@
 #include "front.hpp"
 #include "layer.hpp"
 #include "texture.hpp"
+#include "grain.hpp"
 
 using namespace cetkmc;
 
@@ -1220,6 +1221,7 @@ int cetkmc_struct_size(const char* name)
     SZ("run_args", cetkmc_run_args); SZ("run_result", cetkmc_run_result); SZ("super_args", cetkmc_super_args);
     SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm); SZ("ens_args", cetkmc_ens_args); SZ("ens_analysis", cetkmc_ens_analysis);
     SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec); SZ("texture_args", struct cetkmc_texture_args);
+    SZ("grain_rec", struct cetkmc_grain_rec);
 #undef SZ
     return -1;
 }
@@ -3048,6 +3050,68 @@ int cetkmc_ensemble_texture_profile(void* handle, const struct cetkmc_texture_ar
     const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, nullptr};
     return texture_rows(h0, st, (int64_t)R * L, A.n_bins, gb_hist, pole_hist, bad, [&](unsigned long long* d_rows) {
         launch(k_texture_profile<EnsSel>, texture_grid(L, R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, (const int*)e->d_cc_labels, A, d_rows, sel);
+    });
+}
+
+// ---- per-grain table (grain.hpp) ----------------------------------------------------------------
+// zero `total` records on the stream, fill them (go = the two launches) and copy the first `n` to the caller
+extern "C++" template <class Go>
+static int grain_records(Handle* h, hipStream_t st, int64_t total, int64_t n, struct cetkmc_grain_rec* out, Go&& go)
+{
+    DevTmp<unsigned long long> d_rec;
+    if (d_rec.alloc((size_t)total * GRAIN_NW) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("per-grain table: no device memory for " + std::to_string(total) + " records of " + std::to_string(sizeof(GrainRec)) + " bytes");
+    }
+    HIPCHK(hipMemsetAsync(d_rec.p, 0, (size_t)total * sizeof(GrainRec), st));
+    go(d_rec.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_rec.p, (size_t)n * sizeof(GrainRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h->cnt.bytes_d2h += n * (int64_t)sizeof(GrainRec);
+    return 0;
+}
+static unsigned grain_blocks(int L) { return (unsigned)(((int64_t)L * L * L + GRAIN_VPB - 1) / GRAIN_VPB); }
+
+int cetkmc_grain_table(void* handle, int64_t cap, struct cetkmc_grain_rec* out)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return fail("null handle");
+    if (ens_of(handle)) return fail("cetkmc_grain_table takes one lattice: an ensemble handle goes to cetkmc_ensemble_grain_table");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_grain_table needs the whole lattice in one slab");
+    if (h->cc_n_clusters < 0) return fail("cetkmc_grain_table needs a preceding cetkmc_cluster");
+    const int64_t nc = h->cc_n_clusters, n = std::min<int64_t>(cap, nc);
+    if (n <= 0) return 0;
+    if (!out) return fail("null argument");
+    HIPCHK(hipSetDevice(h->dev));
+    // the device table holds every grain (the pass adds by label); the first n records are the caller's
+    return grain_records(h, h->stream, nc, n, out, [&](unsigned long long* d_rec) {
+        launch(k_grain_table<>, dim3(grain_blocks(h->L)), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), (const int*)h->d_cc_labels, (int)nc, d_rec);
+        launch(k_grain_first<>, dim3((unsigned)std::min<int64_t>((nc + 255) / 256, 4096)), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0),
+               (const int*)h->d_cc_roots, (int)nc, d_rec);
+    });
+}
+
+int cetkmc_ensemble_grain_table(void* handle, struct cetkmc_grain_rec* out)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_grain_table needs a preceding cetkmc_ensemble_analyze");
+    const int R = e->R, L = e->L;
+    int64_t total = 0, maxc = 0;
+    for (int r = 0; r < R; ++r) { total += e->an_clusters[(size_t)r]; maxc = std::max(maxc, e->an_clusters[(size_t)r]); }
+    if (total <= 0) return 0;
+    if (!out) return fail("null argument");
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    CHK(ens_push_views(e));
+    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
+    return grain_records(h0, st, total, total, out, [&](unsigned long long* d_rec) {
+        launch(k_grain_table<EnsSel>, dim3(grain_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, (const int*)e->d_cc_labels, 0, d_rec, sel);
+        launch(k_grain_first<EnsSel>, dim3((unsigned)std::min<int64_t>((maxc + 255) / 256, 4096), (unsigned)R), dim3(256), 0, st, nullptr, nullptr,
+               SlabView{}, (const int*)e->d_cc_roots, 0, d_rec, sel);
     });
 }
 

@@ -9,6 +9,7 @@ collects the CET classification of the last metrics row of every run into ``outp
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
                        [--mode B --box 8] [--seeds K] [--ensemble [--rng counter]]
                        [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]] [--front] [--layers] [--texture]
+                       [--grains]
 
 ``--seeds K`` runs every point with the seeds RANDOM_SEED .. RANDOM_SEED + K - 1 (one gv_map.csv row per point and seed, with
 a ``seed`` column when K > 1); ``--ensemble`` runs all of them as one replica ensemble (run_kmc_ensemble): with the default
@@ -34,6 +35,10 @@ metrics.csv gains the layer columns, every run directory a layers.csv, and gv_ma
 ``texture_metrics``): every metrics.csv gains the texture columns, every run directory a texture.csv, and gv_map.csv the
 columns ``GB_low_angle_frac`` and ``Pole_aligned_frac`` from each run's last row (behind the layer columns).  Without the
 flag the files are what they were.
+
+``--grains`` measures the per-grain table of every run on the device (run_kmc's ``grain_metrics``): every metrics.csv gains
+the grain columns, every run directory a grains.csv, and gv_map.csv the columns ``Columnar_vol_frac`` and
+``Grain_elong_mean`` from each run's last row (behind the texture columns).  Without the flag the files are what they were.
 """
 import argparse
 import os
@@ -68,7 +73,7 @@ def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_p
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
              laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, texture=False,
-             **run_kw):
+             grains=False, **run_kw):
     """``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
     engine (same metrics.csv columns; n_steps stays the number of executed events).  ``seeds=K`` runs every point with the
     seeds RANDOM_SEED .. RANDOM_SEED + K - 1; ``ensemble=True`` runs all runs of the map as one replica ensemble.
@@ -77,7 +82,9 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
     ``V_front_m_per_s`` and ``G_over_V_front`` (inf when V is 0) of each run's last row behind the nominal columns.
     ``layers=True``: every run with ``layer_metrics=True``; gv_map.csv gains ``CET_height_um`` (-1.0: no transition) and
     ``InterceptRatio`` of each run's last row behind those.  ``texture=True``: every run with ``texture_metrics=True``;
-    gv_map.csv gains ``GB_low_angle_frac`` and ``Pole_aligned_frac`` of each run's last row behind those."""
+    gv_map.csv gains ``GB_low_angle_frac`` and ``Pole_aligned_frac`` of each run's last row behind those.  ``grains=True``:
+    every run with ``grain_metrics=True``; gv_map.csv gains ``Columnar_vol_frac`` and ``Grain_elong_mean`` of each run's last
+    row behind those."""
     check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers, scan_speeds)
     seeds = int(seeds)
     beams = [(p, v) for p in laser_powers for v in scan_speeds] if laser_powers else [None]
@@ -94,7 +101,7 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
                 **({"laser": dict(power=float(beam[0]), start=float(laser_start), speed=float(beam[1]))} if beam else {}))
            for T_sub, nu_dep, seed, prefix, beam in runs]
     opt = dict(**({"front_metrics": True} if front else {}), **({"layer_metrics": True} if layers else {}),
-               **({"texture_metrics": True} if texture else {}))
+               **({"texture_metrics": True} if texture else {}), **({"grain_metrics": True} if grains else {}))
     if ensemble:
         run_kmc_ensemble(cfg, L, n_steps, rng=rng, **opt)
     else:
@@ -121,6 +128,8 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
             row.update({"CET_height_um": float(last["CET_height_um"]), "InterceptRatio": float(last["InterceptRatio"])})
         if texture:
             row.update({"GB_low_angle_frac": float(last["GB_low_angle_frac"]), "Pole_aligned_frac": float(last["Pole_aligned_frac"])})
+        if grains:
+            row.update({"Columnar_vol_frac": float(last["Columnar_vol_frac"]), "Grain_elong_mean": float(last["Grain_elong_mean"])})
         rows.append(row)
     os.makedirs(out_dir, exist_ok=True)
     df = pd.DataFrame(rows)
@@ -152,8 +161,10 @@ if __name__ == "__main__":
     ap.add_argument("--texture", action="store_true",
                     help="boundary misorientation and pole histograms on the device: texture columns in every metrics.csv, "
                          "texture.csv, gv_map.csv")
+    ap.add_argument("--grains", action="store_true",
+                    help="per-grain table on the device: grain columns in every metrics.csv, grains.csv, gv_map.csv")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
-                   layers=a.layers, texture=a.texture, **kw).to_string(index=False))
+                   layers=a.layers, texture=a.texture, grains=a.grains, **kw).to_string(index=False))

@@ -33,7 +33,8 @@ from lattice_init import initialize_lattice
 from metrics import (compute_CET, compute_metrics, compute_metrics_device, compute_metrics_from_clusters,  # noqa: F401
                      detect_CET_transition, front_metrics as _front_metrics, front_velocity as _front_velocity,
                      layer_metrics as _layer_metrics, texture_metrics as _texture_metrics,
-                     write_layers_csv as _write_layers_csv, write_texture_csv as _write_texture_csv)
+                     write_layers_csv as _write_layers_csv, write_texture_csv as _write_texture_csv,
+                     grain_metrics as _grain_metrics, write_grains_csv as _write_grains_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
@@ -210,6 +211,15 @@ def _add_texture_columns(row, profile):
     return planes
 
 
+def _add_grain_columns(row, table):
+    """grain_metrics=True: the grain columns (metrics.GRAIN_COLUMNS) behind every other column of ``row``, in place; returns
+    the per-grain table of the row (the rows of grains.csv)."""
+    m = _grain_metrics(table, VOXEL_SIZE)
+    grains = m.pop("grains")
+    row.update(m)
+    return grains
+
+
 def _print_row(step, row):
     print(
         f"Step {step}: AR={row['AspectRatio']:.2f}, "
@@ -279,6 +289,7 @@ def run_kmc(
     front_metrics: bool = False,
     layer_metrics: bool = False,
     texture_metrics: bool = False,
+    grain_metrics: bool = False,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -333,7 +344,13 @@ def run_kmc(
     the texture columns of metrics.texture_metrics -- grain-grain faces, their mean misorientation, the low-angle and
     lateral shares and the share of voxels aligned with the build axis -- from the row's own clustering, binned on the
     device by cetkmc_texture_profile (Engine.texture_profile's defaults: 36 bins, axis (1, 0, 0); L * 148 * 8 bytes cross
-    PCIe per row); the per-plane table of the last row is written to ``outputs/<prefix>/texture.csv``."""
+    PCIe per row); the per-plane table of the last row is written to ``outputs/<prefix>/texture.csv``.
+
+    ``grain_metrics=True`` (both modes, with and without ``laser``): every metrics row gains, behind every other column, the
+    grain columns of metrics.grain_metrics -- moment-based elongation and inclination of the grains, the columnar volume
+    fraction, the largest grain's share, the same-grain share of the stencil contacts and the aligned volume fraction --
+    from the row's own clustering, reduced on the device by cetkmc_grain_table (160 bytes per grain cross PCIe per row); the
+    per-grain table of the last row is written to ``outputs/<prefix>/grains.csv``."""
     import cetkmc
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
@@ -384,7 +401,7 @@ def run_kmc(
     step = -1
     next_step = 0
     nuc_offset = 0
-    layer_planes = texture_planes = None
+    layer_planes = texture_planes = grain_rows = None
     if ckpt:
         total_time, metrics_data, cet_detected = ckpt["total_time"], ckpt["metrics_data"], ckpt["cet_detected"]
         next_step, nuc_offset = ckpt["next_step"], ckpt["nucleation_count"]
@@ -392,7 +409,7 @@ def run_kmc(
     def metrics_row(step, refresh_defects):
         """kmc_simulation.py:335-389 for the lattice as it stands after event index `step` -- WITHOUT moving the lattice: the
         defect mask is refreshed from the carbon sites only, grains are clustered and species counted on the GPU."""
-        nonlocal n_flagged, cet_detected, layer_planes, texture_planes
+        nonlocal n_flagged, cet_detected, layer_planes, texture_planes, grain_rows
         if refresh_defects:
             n_flagged, _ = refresh_defects_device(engine)       # kmc_simulation.py:335-338
         row = _metrics_row(engine.clusters(0.5, labels=True), engine.species_counts(), engine.nucleation_count(), L, step,
@@ -404,6 +421,8 @@ def run_kmc(
             layer_planes = _add_layer_columns(row, engine.layer_profile(recluster=False), L)
         if texture_metrics:
             texture_planes = _add_texture_columns(row, engine.texture_profile(recluster=False))
+        if grain_metrics:
+            grain_rows = _add_grain_columns(row, engine.grain_table(recluster=False))
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -495,6 +514,8 @@ def run_kmc(
         _write_layers_csv(os.path.join(output_dir, "layers.csv"), layer_planes)
     if texture_planes is not None:
         _write_texture_csv(os.path.join(output_dir, "texture.csv"), texture_planes)
+    if grain_rows is not None:
+        _write_grains_csv(os.path.join(output_dir, "grains.csv"), grain_rows)
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -593,7 +614,7 @@ def _replica_prefix(cfg, L):
 
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
-                     front_metrics=False, layer_metrics=False, texture_metrics=False):
+                     front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -610,7 +631,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     ``layer_metrics=True``: run_kmc's option of that name (columns and ``layers.csv`` of every replica), from ONE batched
     cetkmc_ensemble_layer_profile call per metrics row on the row's own analysis.
     ``texture_metrics=True``: run_kmc's option of that name (columns and ``texture.csv`` of every replica), from ONE batched
-    cetkmc_ensemble_texture_profile call per metrics row on the row's own analysis."""
+    cetkmc_ensemble_texture_profile call per metrics row on the row's own analysis.
+    ``grain_metrics=True``: run_kmc's option of that name (columns and ``grains.csv`` of every replica), from ONE batched
+    cetkmc_ensemble_grain_table call per metrics row on the row's own analysis."""
     import cetkmc
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
@@ -643,6 +666,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         cet = [False] * R
         layer_planes = [None] * R
         texture_planes = [None] * R
+        grain_rows = [None] * R
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -723,6 +747,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             fs = ens.front_stats() if front_metrics else None
             lp = ens.layer_profile(recluster=False) if layer_metrics else None
             tp = ens.texture_profile(recluster=False) if texture_metrics else None
+            gt = ens.grain_table(recluster=False) if grain_metrics else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -738,6 +763,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 if tp is not None:
                     texture_planes[r] = _add_texture_columns(
                         row, {k: (v[r] if k in ("gb_hist", "pole_hist", "bad") else v) for k, v in tp.items()})
+                if gt is not None:
+                    grain_rows[r] = _add_grain_columns(row, gt[r])
                 metrics[r].append(row)
             next_step = stop + 1
 
@@ -750,6 +777,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 _write_layers_csv(os.path.join(f"outputs/{c['output_prefix']}", "layers.csv"), layer_planes[r])
             if texture_planes[r] is not None:
                 _write_texture_csv(os.path.join(f"outputs/{c['output_prefix']}", "texture.csv"), texture_planes[r])
+            if grain_rows[r] is not None:
+                _write_grains_csv(os.path.join(f"outputs/{c['output_prefix']}", "grains.csv"), grain_rows[r])
             fields = ens.replica(r).download()
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))

@@ -304,6 +304,95 @@ def write_texture_csv(path, planes):
     write_layers_csv(path, planes)
 
 
+GRAIN_COLUMNS = ("Grain_elong_mean", "Columnar_vol_frac", "Grain_incl_mean_deg", "Largest_grain_frac", "Contact_same_frac",
+                 "Aligned_vol_frac")
+
+
+def grain_metrics(table, voxel_size=VOXEL_SIZE):
+    """Columns of a metrics row (GRAIN_COLUMNS) from one lattice's per-grain table (Engine.grain_table, or one entry of
+    Ensemble.grain_table), plus the per-grain table under "grains" (the rows of grains.csv).  Everything is computed here,
+    on the host, in double, from the integer sums.
+
+    Per grain: centroid c = sum / n; covariance C_ab = sq_ab / n - c_a c_b plus 1/12 on the diagonal for the voxel's own
+    extent (a single voxel is isotropic, an a x b x c box has a^2/12, b^2/12, c^2/12); its eigenvalues (np.linalg.eigh) give
+    the principal lengths sqrt(12 lambda) in voxels, elong = sqrt(lambda_max / lambda_min) and incl_deg, the angle between
+    the major axis and the build direction (axis 0), 0..90.
+
+    Grain_elong_mean: volume-weighted mean of elong.  Columnar_vol_frac: share of the occupied voxels in grains with elong >=
+    CET_AR_THRESHOLD and incl_deg <= 45.  Grain_incl_mean_deg: volume-weighted mean of incl_deg over the grains with elong
+    >= CET_AR_THRESHOLD (the inclination is read only where the major axis is well defined).  Largest_grain_frac: max n /
+    sum n.  Contact_same_frac: same-grain stencil contacts over same-grain plus other-grain ones.  Aligned_vol_frac: share
+    of the occupied voxels in grains whose first-voxel orientation vector lies within TEXTURE_LOW_ANGLE_DEG of the build
+    axis or its opposite (a non-finite angle is not aligned).  Every ratio with a zero denominator is 0.0.  ``voxel_size``
+    scales nothing here (lengths are in voxels); it is accepted like its siblings' for a uniform call."""
+    n = np.asarray(table["n"], dtype=np.int64).reshape(-1)
+    k = len(n)
+    nf = n.astype(np.float64)
+    s = np.asarray(table["sum"], dtype=np.int64).reshape(k, 3).astype(np.float64)
+    q = np.asarray(table["sq"], dtype=np.int64).reshape(k, 6).astype(np.float64)
+    nb = np.asarray(table["nb"], dtype=np.int64).reshape(k, 4)
+    n_state = np.asarray(table["n_state"], dtype=np.int64).reshape(k, 4)
+    th = np.asarray(table["first_theta"], dtype=np.float64).reshape(-1)
+    ph = np.asarray(table["first_phi"], dtype=np.float64).reshape(-1)
+    safe = np.maximum(nf, 1.0)[:, None]
+    c = s / safe
+    m = q / safe
+    cov = np.zeros((k, 3, 3))
+    for a, b, col in ((0, 0, 0), (1, 1, 1), (2, 2, 2), (0, 1, 3), (0, 2, 4), (1, 2, 5)):
+        cov[:, a, b] = cov[:, b, a] = m[:, col] - c[:, a] * c[:, b]
+    cov[:, (0, 1, 2), (0, 1, 2)] += 1.0 / 12.0
+    if k:
+        lam, vec = np.linalg.eigh(cov)                  # ascending eigenvalues, eigenvectors in columns
+    else:
+        lam, vec = np.zeros((0, 3)), np.zeros((0, 3, 3))
+    lam = np.maximum(lam, 1e-300)
+    elong = np.sqrt(lam[:, 2] / lam[:, 0])
+    incl = np.degrees(np.arccos(np.clip(np.abs(vec[:, 0, 2]), 0.0, 1.0)))
+    with np.errstate(invalid="ignore"):
+        pole = np.abs(np.sin(th) * np.cos(ph))           # |component 0| of the orientation vector: the texture profile's axis
+        aligned = np.isfinite(pole) & (pole >= np.cos(np.radians(TEXTURE_LOW_ANGLE_DEG)))
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else 0.0
+
+    tot = float(nf.sum())
+    col = elong >= CET_AR_THRESHOLD
+    same, other = int(nb[:, 0].sum()), int(nb[:, 1].sum())
+    out = {
+        "Grain_elong_mean": ratio(float((nf * elong).sum()), tot),
+        "Columnar_vol_frac": ratio(float(nf[col & (incl <= 45.0)].sum()), tot),
+        "Grain_incl_mean_deg": ratio(float((nf * incl)[col].sum()), float(nf[col].sum())),
+        "Largest_grain_frac": ratio(float(nf.max()) if k else 0.0, tot),
+        "Contact_same_frac": ratio(same, same + other),
+        "Aligned_vol_frac": ratio(float(nf[aligned].sum()), tot),
+    }
+    length = np.sqrt(12.0 * lam)
+    grains = {"id": np.arange(1, k + 1, dtype=np.int64), "n": n}
+    for a, name in enumerate(("ci", "cj", "ck")):
+        grains[name] = c[:, a]
+    for a, name in enumerate(("len_major", "len_mid", "len_minor")):
+        grains[name] = length[:, 2 - a]
+    grains["elong"], grains["incl_deg"] = elong, incl
+    for t, name in enumerate(("W", "Re", "C", "defect")):
+        grains[f"n_{name}"] = n_state[:, t]
+    for t, name in enumerate(("nb_same", "nb_other", "nb_empty", "nb_out")):
+        grains[name] = nb[:, t]
+    grains["first_theta"], grains["first_phi"] = th, ph
+    out["grains"] = grains
+    return out
+
+
+def write_grains_csv(path, grains):
+    """The per-grain table of :func:`grain_metrics` (its "grains" entry) as a CSV with one row per grain."""
+    import csv
+    names = list(grains)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(names)
+        for i in range(len(grains["id"])):
+            w.writerow([grains[n][i].item() for n in names])
+
+
 def front_velocity(row, prev, voxel_size=VOXEL_SIZE):
     """V_front of a metrics row: (Front_i - the previous row's) * voxel_size / (Time - the previous row's) in m/s; 0.0 on
     the first row (``prev`` None), when the time difference is 0 or when either row has no front."""

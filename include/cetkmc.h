@@ -187,7 +187,7 @@ int cetkmc_abi_version(void);
  * hand build): the binding compares it with the sources beside it and rebuilds / refuses a stale library */
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
- * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -370,7 +370,7 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
  * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
  * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
  * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*,
- * front_stats, layer_profile) except the
+ * front_stats, layer_profile, grain_table) except the
  * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
  * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
  * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
@@ -538,6 +538,40 @@ int cetkmc_texture_profile(void* handle, const struct cetkmc_texture_args* args,
  * single-lattice handle is refused. */
 int cetkmc_ensemble_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist,
                                     int64_t* bad);
+
+/* Per-grain table (not in the reference): one record per grain id 1..n of the handle's LAST clustering
+ * (cetkmc_cluster or cetkmc_cluster_import), from the label volume g, the lattice's state s and the stored angles, in one
+ * streaming pass on the device.  Entry id - 1 is fed by every voxel v = (i, j, k) with g(v) == id:
+ *   n            +1 (equals the size cetkmc_cluster_stats reports);
+ *   sum[a]       + the coordinate a of v (i, j, k);
+ *   sq[..]       + i*i, j*j, k*k, i*j, i*k, j*k;
+ *   n_state[t-1] +1 for t = s(v) in 1..4 (a labelled voxel with another state is in none);
+ *   nb_*         for each of the 14 stencil offsets d of the clustering (kmc_event_rates.py:29-35), u = v + d:
+ *                u outside the lattice -> nb_out; g(u) == 0 -> nb_empty; g(u) == g(v) -> nb_same; otherwise -> nb_other.
+ * So nb_same + nb_other + nb_empty + nb_out == 14 * n, and the sum of nb_same over the grains is even.  first_theta and
+ * first_phi are the stored angles of the grain's first voxel in row-major order, copied bit for bit.  The 18 counters are
+ * integer sums (no floating point in the voxel pass, no floating-point atomics): the record is defined to the bit and two
+ * calls return the same bits.  For a lattice changed since its clustering the result is unspecified (the call stays inside
+ * its arrays).  (A struct tag without a typedef, as cetkmc_layer_rec.) */
+struct cetkmc_grain_rec {
+    int64_t n;
+    int64_t sum[3];
+    int64_t sq[6];
+    int64_t n_state[4];
+    int64_t nb_same, nb_other, nb_empty, nb_out;
+    double  first_theta, first_phi;
+};
+/* One lattice, under the handle rules of cetkmc_layer_profile (the handle cetkmc_create_ensemble returned, multi-slab and
+ * multi-rank handles are refused; without a clustering the call fails as cetkmc_cluster_labels does).  out[min(cap, n)]: the
+ * first min(cap, n) records, as cetkmc_cluster_stats treats cap.  Every refusal happens before anything is allocated or
+ * launched; a device allocation that fails is reported through cetkmc_last_error and leaves the handle usable.  Ordered on
+ * the handle's stream behind pending stepping work; copies min(cap, n) * sizeof(struct cetkmc_grain_rec) to the host
+ * (counted in bytes_d2h); writes no lattice field. */
+int cetkmc_grain_table(void* handle, int64_t cap, struct cetkmc_grain_rec* out);
+/* Every replica of an ensemble, frozen ones included, from the clustering of the last cetkmc_ensemble_analyze (required) or
+ * an import on top of it, in a launch sequence that does not depend on R: out[sum of n_clusters], the replicas' records one
+ * behind the other in replica order.  A single-lattice handle is refused. */
+int cetkmc_ensemble_grain_table(void* handle, struct cetkmc_grain_rec* out);
 
 #ifdef __cplusplus
 }
