@@ -158,6 +158,13 @@ class Engine:
         self.params.impurity_c = float(c)
         self._ck(self.lib.cetkmc_set_params(self.h, C.byref(self.params)))
 
+    def set_params(self, params=None):
+        """cetkmc_set_params: ``params`` (a cetkmc_params; None: ``self.params`` as the caller has edited it) replaces the
+        handle's model constants; the next sweep evaluates every rate with them."""
+        if params is not None:
+            self.params = params
+        self._ck(self.lib.cetkmc_set_params(self.h, C.byref(self.params)))
+
     # -- transfers --------------------------------------------------------------------
     def upload(self, state=None, theta=None, phi=None, T=None, defects=None):
         L = self.L

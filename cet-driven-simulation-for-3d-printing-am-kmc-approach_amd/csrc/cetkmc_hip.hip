@@ -563,7 +563,8 @@ int upload_impl(Handle* h, int i_begin, int i_end, const I* state, const double*
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->swept = false;
-    if (T) h->table_fresh = false;
+    // a new state changes the interface list: a voxel that leaves it keeps its interface sum in vval until the table is rewritten
+    if (T || state) h->table_fresh = false;
     h->ifc_fresh = false;
     h->therm_applied_g = -1;
     return 0;
@@ -1476,7 +1477,9 @@ int cetkmc_set_prev_state(void* handle, const int64_t* prev_state)
         } else {
             HIPCHK(hipMemcpyAsync(s.prev, s.v.state, s.nS, hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(hipMemsetAsync(s.v.row_chg, 0, (size_t)(s.v.nloc + 4) * h->L, h->stream));
-            HIPCHK(hipMemsetAsync(s.v.ifc_in, 0, s.nT, h->stream));
+            // the membership flags stay: a voxel that has left the interface since its last evaluation (steps under
+            // interface_every_step or sweep_variant 0 do not re-evaluate what they touch) still holds that evaluation's count
+            // in its class byte and its sum in the table, and only the list's next evaluation brings both up to date
             hipLaunchKernelGGL(k_ifc_rebuild, dim3(2048), dim3(256), 0, h->stream, s.v);
             CHK(relist_slab(h, (int)(&s - h->slabs.data())));
             h->ifc_fresh = false;

@@ -298,7 +298,12 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* args, cetkmc_run_resul
 /* Puts the host inputs of ONE coming batch (u_pick, u_defect, u_np, q_planes of `args`) into the handle's device
  * buffers and waits for the copies.  The next cetkmc_run_steps() call may then pass the same args with all four input
  * pointers NULL: it checks step0 / n_steps / np_cap / n_q / thermal_mode against the staged batch and copies nothing
- * (bench.py: inputs resident in HBM before the timed region).  Any other stepping call drops the staged batch. */
+ * (bench.py: inputs resident in HBM before the timed region).  Any other stepping call drops the staged batch, and so do
+ * cetkmc_run_supersteps and cetkmc_set_option("reserve_batch") (they reuse or move the buffers); a second
+ * cetkmc_stage_inputs replaces it.  The staged batch holds inputs only, nothing derived from the lattice: every other call
+ * between the two -- uploads, cetkmc_set_params, the defect masks, cetkmc_set_prev_state, the direct temperature updates,
+ * cetkmc_apply, the remaining options, the read-only calls -- leaves it valid, and the cetkmc_run_steps that consumes it
+ * steps the lattice and parameters as they stand when IT is called (tests/test_gpu_live_handle_vs_oracle.py). */
 int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* args);
 
 /* totals[n] (Mode A total of every super-step's sweep), events[n][D] or NULL (type -1: idle box, -2: null event),
@@ -335,6 +340,11 @@ int cetkmc_species_counts(void* handle, int64_t counts[6]);
 int cetkmc_gather_species(void* handle, int species, int64_t* lin_idx, double* T_vals, int64_t cap, int64_t* n);
 int cetkmc_set_defects_sparse(void* handle, const int64_t* lin_idx, int64_t n);
 
+/* The nucleation count is the handle's running total over every stepping call and cetkmc_apply since creation.  It belongs
+ * to the handle, not to the lattice: cetkmc_upload -- a whole new lattice included -- leaves it and cetkmc_counters as they
+ * are.  cetkmc_reset_counters zeroes the step state, the nucleation count with it, and leaves cetkmc_counters alone;
+ * cetkmc_get_counters(reset = 1) zeroes cetkmc_counters and leaves the nucleation count alone.  Neither touches the
+ * lattice or any cached rate (tests/test_gpu_live_handle_vs_oracle.py pins all of this). */
 int64_t cetkmc_nucleation_count(void* handle);
 int cetkmc_reset_counters(void* handle);
 
