@@ -130,10 +130,24 @@ class TextureArgs(C.Structure):
     ]
 
 
+class SolidInfo(C.Structure):
+    _fields_ = [("n_new", C.c_int64), ("n_cleared", C.c_int64), ("n_recorded", C.c_int64)]
+
+
+class SolidArgs(C.Structure):
+    _fields_ = [("qscale", C.c_double * 4)]
+
+
+class SolidRec(C.Structure):
+    _fields_ = [("n_rec", C.c_int64), ("n_bad", C.c_int64), ("n_cooling", C.c_int64), ("stamp_sum", C.c_int64),
+                ("stamp_min", C.c_int64), ("stamp_max", C.c_int64), ("q", C.c_int64 * 4)]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
-                  "texture_args": TextureArgs, "grain_rec": GrainRec}
+                  "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
+                  "solid_rec": SolidRec}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -199,6 +213,15 @@ PROTOTYPES = {
     "cetkmc_ensemble_texture_profile": (C.c_int, [C.c_void_p, _P(TextureArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cetkmc_grain_table": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "cetkmc_ensemble_grain_table": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cetkmc_solid_begin": (C.c_int, [C.c_void_p]),
+    "cetkmc_solid_end": (C.c_int, [C.c_void_p]),
+    "cetkmc_solid_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
+    "cetkmc_solid_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_solid_profile": (C.c_int, [C.c_void_p, _P(SolidArgs), C.c_void_p, C.c_int64, C.c_void_p]),
+    "cetkmc_ensemble_solid_begin": (C.c_int, [C.c_void_p]),
+    "cetkmc_ensemble_solid_end": (C.c_int, [C.c_void_p]),
+    "cetkmc_ensemble_solid_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
+    "cetkmc_ensemble_solid_profile": (C.c_int, [C.c_void_p, _P(SolidArgs), C.c_void_p, C.c_void_p]),
 }
 
 

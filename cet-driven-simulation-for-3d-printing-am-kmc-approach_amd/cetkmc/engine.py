@@ -19,6 +19,11 @@ assert LAYER_DTYPE.itemsize == C.sizeof(_lib.LayerRec) == 144
 GRAIN_DTYPE = np.dtype([("n", "<i8"), ("sum", "<i8", 3), ("sq", "<i8", 6), ("n_state", "<i8", 4), ("nb", "<i8", 4),
                         ("first_theta", "<f8"), ("first_phi", "<f8")])
 assert GRAIN_DTYPE.itemsize == C.sizeof(_lib.GrainRec) == 160
+SOLID_DTYPE = np.dtype([("n_rec", "<i8"), ("n_bad", "<i8"), ("n_cooling", "<i8"), ("stamp_sum", "<i8"), ("stamp_min", "<i8"),
+                        ("stamp_max", "<i8"), ("q", "<i8", 4)])
+assert SOLID_DTYPE.itemsize == C.sizeof(_lib.SolidRec) == 80
+SOLID_INFO_DTYPE = np.dtype([("n_new", "<i8"), ("n_cleared", "<i8"), ("n_recorded", "<i8")])
+assert SOLID_INFO_DTYPE.itemsize == C.sizeof(_lib.SolidInfo) == 24
 
 TYPE_BYTES = (b"dep", b"diff", b"nuc", b"att")   # kmc_event_rates.py:72,109,132,158
 
@@ -85,6 +90,26 @@ def _default_ar_threshold():
 def _default_inv_dx():
     import constants as K
     return 1.0 / K.VOXEL_SIZE
+
+
+def default_solid_scales():
+    """The quantisation scales (G, gi, cool, T_s) of the solidification profile (cetkmc_solid_args.qscale) when the caller
+    gives none: the quantities are counted in steps of 2^-24 of a natural unit -- T_MELT per voxel edge for the two
+    gradients (K/m), T_MELT per microsecond for the cooling rate (K/s), T_MELT for the temperature (K).  A value saturates
+    (the voxel counts as bad) at 2^14 of these units, far outside the clip range of the temperature update."""
+    import constants as K
+    u = 2.0 ** 24 / float(K.T_MELT)
+    return (u * K.VOXEL_SIZE, u * K.VOXEL_SIZE, u * 1e-6, u)
+
+
+def _solid_args(scales):
+    a = _lib.SolidArgs()
+    a.qscale[:] = [float(x) for x in (default_solid_scales() if scales is None else scales)]
+    return a
+
+
+def _solid_fields(buf):
+    return {f: buf[f].copy() for f in SOLID_DTYPE.names}
 
 
 def device_count():
@@ -507,6 +532,54 @@ class Engine:
             self._ck(self.lib.cetkmc_grain_table(self.h, k, _ptr(buf)))
         return {f: buf[f][:k].copy() for f in GRAIN_DTYPE.names}
 
+    # -- solidification map ----------------------------------------------------
+    def solid_begin(self):
+        """cetkmc_solid_begin: start (or reset) the handle's solidification map -- no voxel has a record, the voxels
+        occupied now are substrate, the snapshots hold the current state and T."""
+        self._ck(self.lib.cetkmc_solid_begin(self.h))
+
+    def solid_end(self):
+        """cetkmc_solid_end: free the map."""
+        self._ck(self.lib.cetkmc_solid_end(self.h))
+
+    def solid_update(self, stamp, dt, inv_dx=None):
+        """cetkmc_solid_update: record every voxel that solidified since the last update (stamp, its T, the gradient of
+        front_stats, cool = (T - T at the last update) / dt), clear those that emptied, refresh the snapshots.  Returns
+        dict(n_new, n_cleared, n_recorded).  ``inv_dx`` defaults to 1 / constants.VOXEL_SIZE."""
+        info = np.zeros(1, SOLID_INFO_DTYPE)
+        self._ck(self.lib.cetkmc_solid_update(self.h, int(stamp), float(_default_inv_dx() if inv_dx is None else inv_dx), float(dt),
+                                              _ptr(info)))
+        return {f: int(info[f][0]) for f in SOLID_INFO_DTYPE.names}
+
+    def solid_read(self):
+        """cetkmc_solid_read: the map as dict(stamp (L,L,L) int64, T_s (L,L,L), g (L,L,L,3), cool (L,L,L) float64)."""
+        L = self.L
+        out = dict(stamp=np.zeros((L,) * 3, np.int64), T_s=np.zeros((L,) * 3), g=np.zeros((L, L, L, 3)), cool=np.zeros((L,) * 3))
+        self._ck(self.lib.cetkmc_solid_read(self.h, _ptr(out["stamp"]), _ptr(out["T_s"]), _ptr(out["g"]), _ptr(out["cool"])))
+        return out
+
+    def solid_profile(self, scales=None, grains=False, threshold=0.5, recluster=True):
+        """cetkmc_solid_profile: dict(layers=..., grains=...) of int64 field arrays (n_rec, n_bad, n_cooling, stamp_sum,
+        stamp_min, stamp_max, q (.., 4): the quantised sums of G, gi, cool, T_s) with leading dimension L (plane i of the
+        build direction) and, with ``grains``, n (grain id - 1 of the handle's last clustering; None otherwise).
+        ``scales`` defaults to :func:`default_solid_scales`; a mean is q / (n_rec * scale).  With ``grains`` the call
+        clusters first with ``threshold`` unless ``recluster`` is False, which reuses the last clustering or import."""
+        a = _solid_args(scales)
+        lay = np.zeros(max(self.L, 1), SOLID_DTYPE)
+        if not grains:
+            self._ck(self.lib.cetkmc_solid_profile(self.h, C.byref(a), _ptr(lay), 0, None))
+            return dict(layers=_solid_fields(lay), grains=None)
+        if recluster:
+            n = C.c_int64(0)
+            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+            self._cc_n = n.value
+        k = self._cc_n
+        if k is None:       # a clustering this object did not make: its size from the stats call (fails without one)
+            k = len(self.grain_table(recluster=False)["n"])
+        gr = np.zeros(max(k, 1), SOLID_DTYPE)
+        self._ck(self.lib.cetkmc_solid_profile(self.h, C.byref(a), _ptr(lay), k, _ptr(gr)))
+        return dict(layers=_solid_fields(lay), grains=_solid_fields(gr[:k]))
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -749,6 +822,44 @@ class Ensemble:
         buf = np.zeros(max(int(at[-1]), 1), dtype=GRAIN_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_grain_table(self.h, _ptr(buf)))
         return [{f: buf[f][at[r]:at[r + 1]].copy() for f in GRAIN_DTYPE.names} for r in range(self.R)]
+
+    # -- solidification maps of every replica ----------------------------------
+    def solid_begin(self):
+        """cetkmc_ensemble_solid_begin: Engine.solid_begin for every replica."""
+        self._ck(self.lib.cetkmc_ensemble_solid_begin(self.h))
+
+    def solid_end(self):
+        self._ck(self.lib.cetkmc_ensemble_solid_end(self.h))
+
+    def solid_update(self, stamp, dt, inv_dx=None):
+        """cetkmc_ensemble_solid_update: Engine.solid_update of every replica (frozen ones included) in one launch whatever
+        R; stamp, dt and inv_dx are shared.  dict(n_new, n_cleared, n_recorded) of (R,) int64 arrays."""
+        info = np.zeros(max(self.R, 1), SOLID_INFO_DTYPE)
+        self._ck(self.lib.cetkmc_ensemble_solid_update(self.h, int(stamp), float(_default_inv_dx() if inv_dx is None else inv_dx),
+                                                       float(dt), _ptr(info)))
+        return {f: info[f][:self.R].copy() for f in SOLID_INFO_DTYPE.names}
+
+    def solid_read(self, r):
+        """The map of replica r (Engine.solid_read on its handle)."""
+        return self._reps[r].solid_read()
+
+    def solid_profile(self, scales=None, grains=False, threshold=0.5, recluster=True):
+        """cetkmc_ensemble_solid_profile: Engine.solid_profile of every replica in launches that do not depend on R.
+        dict(layers=field arrays with leading dimensions (R, L), grains=one dict per replica or None).  With ``grains``
+        runs :meth:`analyze` first (without downloading labels) unless ``recluster`` is False."""
+        a = _solid_args(scales)
+        lay = np.zeros((max(self.R, 1), self.L), SOLID_DTYPE)
+        if not grains:
+            self._ck(self.lib.cetkmc_ensemble_solid_profile(self.h, C.byref(a), _ptr(lay), None))
+            return dict(layers=_solid_fields(lay[:self.R]), grains=None)
+        if recluster:
+            self.analyze(threshold, labels=False)
+        if self._an_nc is None:
+            raise RuntimeError("cetkmc: Ensemble.solid_profile(grains=True) needs a preceding Ensemble.analyze")
+        at = np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
+        gr = np.zeros(max(int(at[-1]), 1), SOLID_DTYPE)
+        self._ck(self.lib.cetkmc_ensemble_solid_profile(self.h, C.byref(a), _ptr(lay), _ptr(gr)))
+        return dict(layers=_solid_fields(lay[:self.R]), grains=[_solid_fields(gr[at[r]:at[r + 1]]) for r in range(self.R)])
 
     def set_defects_sparse(self, lists):
         """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""

@@ -30,6 +30,7 @@
 #include "layer.hpp"
 #include "texture.hpp"
 #include "grain.hpp"
+#include "solid.hpp"
 
 using namespace cetkmc;
 
@@ -232,6 +233,12 @@ struct Handle {
     bool ens_member = false;     // replica r >= 1 of an ensemble (released with it)
     bool in_ensemble = false;    // any replica: stepped by cetkmc_run_ensemble only
     int64_t state_uploads = 0;   // lattice (state) uploads so far: a new lattice in a replica unfreezes it
+    // solidification map (cetkmc_solid_begin .. _end, solid.hpp): the arrays of this lattice; d_solid_block owns them on a
+    // single handle (a replica's lie in its ensemble's block)
+    SolidMap solid{};
+    void* d_solid_block = nullptr;
+    bool solid_on = false;
+    int64_t solid_recorded = 0;  // voxels with stamp >= 0
 };
 
 KParams make_kparams(const cetkmc_params& p)
@@ -1100,6 +1107,7 @@ void destroy_impl(Handle* h)
         (void)hipFree(s.v.rowsum); (void)hipFree(s.v.rowcnt);
         (void)hipFree(s.vvalbuf[0]); (void)hipFree(s.vvalbuf[1]); (void)hipFree(s.depbuf[0]); (void)hipFree(s.depbuf[1]); (void)hipFree(s.v.ifc_in); (void)hipFree(s.v.ifc_code); (void)hipFree(s.v.ifc_list); (void)hipFree(s.v.ifc_n);
     }
+    if (h->d_solid_block) (void)hipFree(h->d_solid_block);
     void* ccp[] = {h->d_cc_parent, h->d_cc_roots, h->d_cc_cid, h->d_cc_labels, h->d_cc_stats, h->d_cc_n};
     for (void* p : ccp) if (p) (void)hipFree(p);
     void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
@@ -1150,6 +1158,8 @@ struct Ens {
     size_t cap_layer_eq = 0;
     std::vector<int64_t> an_clusters, an_gathered;     // per replica, of the last analysis (-1: none yet)
     int an_species = -1;
+    void* d_solid_block = nullptr;       // cetkmc_ensemble_solid_begin: every replica's map, the counters [R][3], the map table [R]
+    SolidMap* d_solid_maps = nullptr;    // (inside the block)
 };
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
 bool shared_params_equal(cetkmc_params a, cetkmc_params b)
@@ -1177,7 +1187,7 @@ void destroy_ens(Ens* e)
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
                     e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_front_part, e->d_front_out,
-                    e->d_layer_part, e->d_layer_out, e->d_layer_eq};
+                    e->d_layer_part, e->d_layer_out, e->d_layer_eq, e->d_solid_block};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1223,6 +1233,7 @@ int cetkmc_struct_size(const char* name)
     SZ("counters", cetkmc_counters); SZ("host_comm", cetkmc_host_comm); SZ("ens_args", cetkmc_ens_args); SZ("ens_analysis", cetkmc_ens_analysis);
     SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec); SZ("texture_args", struct cetkmc_texture_args);
     SZ("grain_rec", struct cetkmc_grain_rec);
+    SZ("solid_info", struct cetkmc_solid_info); SZ("solid_args", struct cetkmc_solid_args); SZ("solid_rec", struct cetkmc_solid_rec);
 #undef SZ
     return -1;
 }
@@ -3115,6 +3126,286 @@ int cetkmc_ensemble_grain_table(void* handle, struct cetkmc_grain_rec* out)
         launch(k_grain_table<EnsSel>, dim3(grain_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, (const int*)e->d_cc_labels, 0, d_rec, sel);
         launch(k_grain_first<EnsSel>, dim3((unsigned)std::min<int64_t>((maxc + 255) / 256, 4096), (unsigned)R), dim3(256), 0, st, nullptr, nullptr,
                SlabView{}, (const int*)e->d_cc_roots, 0, d_rec, sel);
+    });
+}
+
+// ---- solidification map (solid.hpp) -------------------------------------------------------------
+// One device block for the maps of hs (one handle, or every replica of an ensemble): all stamps, then all doubles, the two
+// snapshots, the counters [n][3] and the map table [n] -- so that begin sets the block with two memsets whatever n.
+struct SolidLayout { size_t n, nsnap, o_dbl, o_snap, o_tsnap, o_cnt, o_tab, bytes; };
+static SolidLayout solid_layout(int L, int pitchT, size_t R)
+{
+    SolidLayout y{};
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    y.n = (size_t)L * L * L; y.nsnap = (size_t)L * L * pitchT;
+    y.o_dbl = up(R * y.n * 8);
+    y.o_snap = y.o_dbl + up(R * y.n * 5 * 8);
+    y.o_tsnap = y.o_snap + R * up(y.nsnap);
+    y.o_cnt = y.o_tsnap + R * up(y.nsnap * 8);
+    y.o_tab = y.o_cnt + up(R * 3 * 8);
+    y.bytes = y.o_tab + up(R * sizeof(SolidMap));
+    return y;
+}
+static dim3 solid_update_grid(int L, int pitchT, int R, int pairs_per_block)
+{
+    const int64_t npair = (int64_t)L * L * (pitchT / 2);
+    return dim3((unsigned)((npair + pairs_per_block - 1) / pairs_per_block), (unsigned)R);
+}
+static unsigned solid_blocks(int L) { return (unsigned)(((int64_t)L * L * L + SOLID_VPB - 1) / SOLID_VPB); }
+
+// (re)start the maps of hs in *block (allocated here if null); go = the snapshot launch
+extern "C++" template <class Go>
+static int solid_begin(std::vector<Handle*>& hs, void** block, SolidMap** d_maps, hipStream_t st, Go&& go)
+{
+    Handle* h0 = hs[0];
+    const size_t R = hs.size();
+    const SolidLayout y = solid_layout(h0->L, h0->pitchT, R);
+    if (!*block) {
+        if (hipMalloc(block, y.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *block = nullptr;
+            return fail("solidification map: no device memory for " + std::to_string(y.bytes) + " bytes");
+        }
+    }
+    // no handle has a map until everything below has completed: an error on the way leaves none (a second begin included)
+    for (Handle* h : hs) { h->solid_on = false; h->solid_recorded = 0; }
+    char* b = (char*)*block;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    std::vector<SolidMap> tab(R);
+    for (size_t r = 0; r < R; ++r) {
+        SolidMap& m = tab[r];
+        m.stamp = (long long*)b + r * y.n;
+        double* d = (double*)(b + y.o_dbl) + r * 5 * y.n;
+        m.Ts = d; m.g = d + y.n; m.cool = d + 4 * y.n;
+        m.snap = (uint8_t*)(b + y.o_snap + r * up(y.nsnap));
+        m.Tsnap = (double*)(b + y.o_tsnap + r * up(y.nsnap * 8));
+        m.cnt = (unsigned long long*)(b + y.o_cnt) + 3 * r;
+        hs[r]->solid = m;
+    }
+    if (d_maps) *d_maps = (SolidMap*)(b + y.o_tab);
+    auto issue = [&]() -> int {
+        HIPCHK(hipMemsetAsync(b, 0xff, R * y.n * 8, st));                           // stamp = -1
+        HIPCHK(hipMemsetAsync(b + y.o_dbl, 0, y.bytes - y.o_dbl, st));               // +0.0, snapshots, counters, table
+        HIPCHK(hipMemcpyAsync(b + y.o_tab, tab.data(), R * sizeof(SolidMap), hipMemcpyHostToDevice, st));
+        go();
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    const int rc = issue();
+    const hipError_t synced = hipStreamSynchronize(st);         // also after an error: the table is copied from this frame
+    if (rc) return rc;
+    HIPCHK(synced);
+    for (Handle* h : hs) h->solid_on = true;
+    return 0;
+}
+static int solid_update_args(const char* fn, int64_t stamp, double inv_dx, double dt)
+{
+    const std::string f(fn);
+    if (stamp < 0) return fail(f + ": stamp " + std::to_string(stamp) + " is negative");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(f + ": dt must be finite and > 0");
+    if (!std::isfinite(inv_dx)) return fail(f + ": inv_dx is not finite");
+    return 0;
+}
+static int solid_scales(const char* fn, const struct cetkmc_solid_args* a)
+{
+    for (int c = 0; c < 4; ++c)
+        if (!std::isfinite(a->qscale[c]) || !(a->qscale[c] > 0.0)) return fail(std::string(fn) + ": qscale[" + std::to_string(c) + "] must be finite and > 0");
+    return 0;
+}
+// the single-lattice handle of begin / update / end, or a refusal
+static int solid_single(const char* fn, Handle* h, bool need_map)
+{
+    const std::string f(fn);
+    if (!h) return fail("null handle");
+    if (h->in_ensemble) return fail(f + " takes a single-lattice handle: an ensemble's maps are kept by cetkmc_ensemble_solid_*");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
+    if (need_map && !h->solid_on) return fail(f + " needs a map (cetkmc_solid_begin)");
+    return 0;
+}
+// the counters of n lattices behind an update -> info, and each handle's running record count
+static int solid_collect(std::vector<Handle*>& hs, const unsigned long long* d_cnt, hipStream_t st, struct cetkmc_solid_info* info)
+{
+    std::vector<unsigned long long> c(3 * hs.size());
+    HIPCHK(hipMemcpyAsync(c.data(), d_cnt, c.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    hs[0]->cnt.bytes_d2h += (int64_t)c.size() * 8;
+    for (size_t r = 0; r < hs.size(); ++r) {
+        hs[r]->solid_recorded += (int64_t)c[3 * r] - (int64_t)c[3 * r + 2];
+        if (info) { info[r].n_new = (int64_t)c[3 * r]; info[r].n_cleared = (int64_t)c[3 * r + 1]; info[r].n_recorded = hs[r]->solid_recorded; }
+    }
+    return 0;
+}
+
+int cetkmc_solid_begin(void* handle)
+{
+    Handle* h = (Handle*)handle;
+    CHK(solid_single("cetkmc_solid_begin", h, false));
+    HIPCHK(hipSetDevice(h->dev));
+    std::vector<Handle*> hs{h};
+    return solid_begin(hs, &h->d_solid_block, nullptr, h->stream, [&] {
+        launch(k_solid_snapshot<>, solid_update_grid(h->L, h->pitchT, 1, 256), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), h->solid, nullptr);
+    });
+}
+
+int cetkmc_solid_end(void* handle)
+{
+    Handle* h = (Handle*)handle;
+    CHK(solid_single("cetkmc_solid_end", h, false));
+    if (!h->d_solid_block) return fail("cetkmc_solid_end needs a map (cetkmc_solid_begin)");      // (a begin that failed half way keeps its block)
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipFree(h->d_solid_block));
+    h->d_solid_block = nullptr; h->solid = SolidMap{}; h->solid_on = false; h->solid_recorded = 0;
+    return 0;
+}
+
+int cetkmc_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info)
+{
+    Handle* h = (Handle*)handle;
+    CHK(solid_single("cetkmc_solid_update", h, true));
+    CHK(solid_update_args("cetkmc_solid_update", stamp, inv_dx, dt));
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipMemsetAsync(h->solid.cnt, 0, 3 * 8, h->stream));
+    launch(k_solid_update<>, solid_update_grid(h->L, h->pitchT, 1, SOLID_PPB), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), h->solid, nullptr,
+           (long long)stamp, inv_dx, dt);
+    HIPCHK(hipGetLastError());
+    std::vector<Handle*> hs{h};
+    return solid_collect(hs, h->solid.cnt, h->stream, info);
+}
+
+int cetkmc_solid_read(void* handle, int64_t* stamp, double* T_s, double* g, double* cool)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return fail("null handle");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_solid_read needs the whole lattice in one slab");
+    if (!h->solid_on) return fail("cetkmc_solid_read needs a map (cetkmc_solid_begin)");
+    HIPCHK(hipSetDevice(h->dev));
+    const size_t n = (size_t)h->L * h->L * h->L;
+    int64_t bytes = 0;
+    if (stamp) { HIPCHK(hipMemcpyAsync(stamp, h->solid.stamp, n * 8, hipMemcpyDeviceToHost, h->stream)); bytes += (int64_t)n * 8; }
+    if (T_s) { HIPCHK(hipMemcpyAsync(T_s, h->solid.Ts, n * 8, hipMemcpyDeviceToHost, h->stream)); bytes += (int64_t)n * 8; }
+    if (g) { HIPCHK(hipMemcpyAsync(g, h->solid.g, n * 24, hipMemcpyDeviceToHost, h->stream)); bytes += (int64_t)n * 24; }
+    if (cool) { HIPCHK(hipMemcpyAsync(cool, h->solid.cool, n * 8, hipMemcpyDeviceToHost, h->stream)); bytes += (int64_t)n * 8; }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cnt.bytes_d2h += bytes;
+    return 0;
+}
+
+// initialise n_lay + n_gr records on the stream, fill them (go = the launch) and copy n_lay layer and n_copy grain records out
+extern "C++" template <class Go>
+static int solid_records(Handle* h, hipStream_t st, int64_t n_lay, int64_t n_gr, int64_t n_copy, struct cetkmc_solid_rec* layers,
+                         struct cetkmc_solid_rec* grains, Go&& go)
+{
+    DevTmp<long long> d_rec;
+    const int64_t words = (n_lay + n_gr) * SOLID_NW;
+    if (d_rec.alloc((size_t)words) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("solidification profile: no device memory for " + std::to_string(n_lay + n_gr) + " records of " + std::to_string(sizeof(SolidRec)) + " bytes");
+    }
+    launch(k_solid_rec_init, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, st, nullptr, nullptr, d_rec.p, words);
+    go(d_rec.p, d_rec.p + n_lay * SOLID_NW);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(layers, d_rec.p, (size_t)n_lay * sizeof(SolidRec), hipMemcpyDeviceToHost, st));
+    if (n_copy > 0) HIPCHK(hipMemcpyAsync(grains, d_rec.p + n_lay * SOLID_NW, (size_t)n_copy * sizeof(SolidRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h->cnt.bytes_d2h += (n_lay + std::max<int64_t>(n_copy, 0)) * (int64_t)sizeof(SolidRec);
+    return 0;
+}
+
+int cetkmc_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers, int64_t cap,
+                         struct cetkmc_solid_rec* grains)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !args || !layers) return fail("null argument");
+    if (ens_of(handle)) return fail("cetkmc_solid_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_solid_profile");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_solid_profile needs the whole lattice in one slab");
+    if (!h->solid_on) return fail("cetkmc_solid_profile needs a map (cetkmc_solid_begin)");
+    CHK(solid_scales("cetkmc_solid_profile", args));
+    if (grains && h->cc_n_clusters < 0) return fail("cetkmc_solid_profile needs a preceding cetkmc_cluster for its grain records");
+    const int64_t nc = grains ? h->cc_n_clusters : 0, n = std::min<int64_t>(cap, nc);
+    const bool with_grains = grains && n > 0;
+    HIPCHK(hipSetDevice(h->dev));
+    // the device table holds every grain (the pass adds by label); the first n records are the caller's
+    return solid_records(h, h->stream, h->L, with_grains ? nc : 0, with_grains ? n : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
+        launch(k_solid_profile<>, dim3(solid_blocks(h->L)), dim3(256), 0, h->stream, nullptr, nullptr, h->solid, nullptr, h->L,
+               with_grains ? (const int*)h->d_cc_labels : nullptr, (int)nc, args->qscale[0], args->qscale[1], args->qscale[2], args->qscale[3], d_lay, d_gr);
+    });
+}
+
+static int solid_ensemble(const char* fn, void* handle, bool need_map, Ens** out)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (need_map && !(e->d_solid_block && e->reps[0]->solid_on)) return fail(std::string(fn) + " needs the maps (cetkmc_ensemble_solid_begin)");
+    *out = e;
+    return 0;
+}
+
+int cetkmc_ensemble_solid_begin(void* handle)
+{
+    Ens* e = nullptr;
+    CHK(solid_ensemble("cetkmc_ensemble_solid_begin", handle, false, &e));
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    CHK(ens_push_views(e));
+    const EnsSel sel{e->d_table, 0, 0, 0, nullptr};
+    return solid_begin(e->reps, &e->d_solid_block, &e->d_solid_maps, st, [&] {
+        launch(k_solid_snapshot<EnsSel>, solid_update_grid(e->L, h0->pitchT, e->R, 256), dim3(256), 0, st, nullptr, nullptr, SlabView{}, SolidMap{},
+               (const SolidMap*)e->d_solid_maps, sel);
+    });
+}
+
+int cetkmc_ensemble_solid_end(void* handle)
+{
+    Ens* e = nullptr;
+    CHK(solid_ensemble("cetkmc_ensemble_solid_end", handle, false, &e));
+    if (!e->d_solid_block) return fail("cetkmc_ensemble_solid_end needs the maps (cetkmc_ensemble_solid_begin)");
+    HIPCHK(hipSetDevice(e->reps[0]->dev));
+    HIPCHK(hipStreamSynchronize(e->reps[0]->stream));
+    HIPCHK(hipFree(e->d_solid_block));
+    e->d_solid_block = nullptr; e->d_solid_maps = nullptr;
+    for (Handle* h : e->reps) { h->solid = SolidMap{}; h->solid_on = false; h->solid_recorded = 0; }
+    return 0;
+}
+
+int cetkmc_ensemble_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info)
+{
+    Ens* e = nullptr;
+    CHK(solid_ensemble("cetkmc_ensemble_solid_update", handle, true, &e));
+    CHK(solid_update_args("cetkmc_ensemble_solid_update", stamp, inv_dx, dt));
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    CHK(ens_push_views(e));
+    HIPCHK(hipMemsetAsync(h0->solid.cnt, 0, (size_t)e->R * 3 * 8, st));       // replica 0's counters head the block's [R][3]
+    const EnsSel sel{e->d_table, 0, 0, 0, nullptr};
+    launch(k_solid_update<EnsSel>, solid_update_grid(e->L, h0->pitchT, e->R, SOLID_PPB), dim3(256), 0, st, nullptr, nullptr, SlabView{}, SolidMap{},
+           (const SolidMap*)e->d_solid_maps, (long long)stamp, inv_dx, dt, sel);
+    HIPCHK(hipGetLastError());
+    return solid_collect(e->reps, h0->solid.cnt, st, info);
+}
+
+int cetkmc_ensemble_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers,
+                                  struct cetkmc_solid_rec* grains)
+{
+    Ens* e = nullptr;
+    CHK(solid_ensemble("cetkmc_ensemble_solid_profile", handle, true, &e));
+    if (!args || !layers) return fail("null argument");
+    CHK(solid_scales("cetkmc_ensemble_solid_profile", args));
+    if (grains && e->an_clusters.empty()) return fail("cetkmc_ensemble_solid_profile needs a preceding cetkmc_ensemble_analyze for its grain records");
+    const int R = e->R, L = e->L;
+    int64_t total = 0;
+    if (grains) for (int r = 0; r < R; ++r) total += e->an_clusters[(size_t)r];
+    const bool with_grains = grains && total > 0;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
+    return solid_records(h0, st, (int64_t)R * L, with_grains ? total : 0, with_grains ? total : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
+        launch(k_solid_profile<EnsSel>, dim3(solid_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SolidMap{}, (const SolidMap*)e->d_solid_maps, L,
+               with_grains ? (const int*)e->d_cc_labels : nullptr, 0, args->qscale[0], args->qscale[1], args->qscale[2], args->qscale[3], d_lay, d_gr, sel);
     });
 }
 

@@ -34,7 +34,8 @@ from metrics import (compute_CET, compute_metrics, compute_metrics_device, compu
                      detect_CET_transition, front_metrics as _front_metrics, front_velocity as _front_velocity,
                      layer_metrics as _layer_metrics, texture_metrics as _texture_metrics,
                      write_layers_csv as _write_layers_csv, write_texture_csv as _write_texture_csv,
-                     grain_metrics as _grain_metrics, write_grains_csv as _write_grains_csv)
+                     grain_metrics as _grain_metrics, write_grains_csv as _write_grains_csv,
+                     solid_metrics as _solid_metrics, write_solid_csv as _write_solid_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
@@ -220,6 +221,30 @@ def _add_grain_columns(row, table):
     return grains
 
 
+def _add_solid_columns(row, profile, scales, remelted, clusters):
+    """solid_metrics=True: the solidification columns (metrics.SOLID_COLUMNS) behind every other column of ``row``, in place;
+    returns the per-plane table of the row (rows of solid_layers.csv) and the per-grain one (solid_grains.csv) or None."""
+    m = _solid_metrics(profile, scales, remelted, row["Step"], clusters)
+    planes, grains = m.pop("planes"), m.pop("grains", None)
+    row.update(m)
+    return planes, grains
+
+
+def _check_solid(solid_metrics, solid_every, checkpointing):
+    if not solid_metrics:
+        return
+    if isinstance(solid_every, bool) or not isinstance(solid_every, (int, np.integer)) or solid_every < THERMAL_EVERY or solid_every % THERMAL_EVERY:
+        raise ValueError(f"solid_every must be a positive multiple of {THERMAL_EVERY} (the map is updated right before a temperature update)")
+    if checkpointing:
+        raise ValueError("solid_metrics cannot be combined with checkpoint_every / resume_from (a checkpoint does not carry the map)")
+
+
+def _updates_between(a, b):
+    """temperature updates issued at the global steps (or super-steps) a <= g < b: the multiples of THERMAL_EVERY there"""
+    up = lambda x: -(-x // THERMAL_EVERY)        # noqa: E731
+    return up(b) - up(a) if b > a else 0
+
+
 def _print_row(step, row):
     print(
         f"Step {step}: AR={row['AspectRatio']:.2f}, "
@@ -290,6 +315,8 @@ def run_kmc(
     layer_metrics: bool = False,
     texture_metrics: bool = False,
     grain_metrics: bool = False,
+    solid_metrics: bool = False,
+    solid_every: int = 20,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -350,8 +377,28 @@ def run_kmc(
     grain columns of metrics.grain_metrics -- moment-based elongation and inclination of the grains, the columnar volume
     fraction, the largest grain's share, the same-grain share of the stencil contacts and the aligned volume fraction --
     from the row's own clustering, reduced on the device by cetkmc_grain_table (160 bytes per grain cross PCIe per row); the
-    per-grain table of the last row is written to ``outputs/<prefix>/grains.csv``."""
+    per-grain table of the last row is written to ``outputs/<prefix>/grains.csv``.
+
+    ``solid_metrics=True`` (both modes, with and without ``laser``): the device keeps a solidification map (cetkmc_solid_*,
+    DESIGN.md section 21) -- per voxel the step count, temperature, temperature gradient and cooling rate at the moment it
+    solidified.  The map begins after the initial upload (the initial lattice is substrate); ``solid_every`` is a multiple
+    of 20; dt = max(1, temperature updates since the previous map update) * 1e-6 s.  Mode A: the stepping batches are split
+    at the multiples of ``solid_every`` and the map is updated there, right BEFORE the step whose temperature update is due:
+    the recorded T is the field the batch's events saw and stamp = that multiple, the global step count.  Mode B: the map is
+    updated AFTER the super-step batch in which the count of executed events reaches or passes a multiple of ``solid_every``;
+    stamp = the events executed by then, which can lie up to (events per super-step - 1) past the multiple, and the recorded
+    T is the field as that batch left it.  With ``thermal_cadence="events"`` that is the field its events saw; with the
+    super-step cadence the engine updates T by the super-step index, not by the event count, so the field may already carry
+    an update that followed the events.  A voxel that solidifies and empties again between
+    two updates is not seen, and a row shows the map as of the last update (at most ``solid_every`` steps back).  Every
+    metrics row gains, behind every other column, the columns of metrics.solid_metrics (per-lattice means at freezing,
+    V_solid = -Cool_solid / Gi_solid, G_over_V_solid), reduced on the device by cetkmc_solid_profile under
+    cetkmc.engine.default_solid_scales(); ``outputs/<prefix>/solid_layers.csv`` gets one row per plane and metrics row and,
+    with ``grain_metrics=True``, ``solid_grains.csv`` one row per grain of the last row (thermal history beside the grain's
+    size and bounding-box aspect).  Refused with ValueError: ``solid_every`` not a positive multiple of 20; together with
+    ``checkpoint_every`` / ``resume_from`` (a checkpoint does not carry the map)."""
     import cetkmc
+    _check_solid(solid_metrics, solid_every, bool(checkpoint_every or resume_from))
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
     if laser is not None:
@@ -401,7 +448,17 @@ def run_kmc(
     step = -1
     next_step = 0
     nuc_offset = 0
-    layer_planes = texture_planes = grain_rows = None
+    layer_planes = texture_planes = grain_rows = solid_grain_rows = None
+    solid_planes = []
+    solid = dict(remelted=0, stamp=0, thermal=0)      # running n_cleared; step count and temperature updates at the last map update
+    solid_scales = cetkmc.engine.default_solid_scales()
+    if solid_metrics:
+        engine.solid_begin()
+
+    def solid_update(stamp, thermal_now):
+        """the map update at ``stamp`` executed steps, ``thermal_now`` temperature updates issued so far"""
+        info = engine.solid_update(stamp, max(1, thermal_now - solid["thermal"]) * THERMAL_DT)
+        solid.update(remelted=solid["remelted"] + info["n_cleared"], stamp=stamp, thermal=thermal_now)
     if ckpt:
         total_time, metrics_data, cet_detected = ckpt["total_time"], ckpt["metrics_data"], ckpt["cet_detected"]
         next_step, nuc_offset = ckpt["next_step"], ckpt["nucleation_count"]
@@ -409,10 +466,11 @@ def run_kmc(
     def metrics_row(step, refresh_defects):
         """kmc_simulation.py:335-389 for the lattice as it stands after event index `step` -- WITHOUT moving the lattice: the
         defect mask is refreshed from the carbon sites only, grains are clustered and species counted on the GPU."""
-        nonlocal n_flagged, cet_detected, layer_planes, texture_planes, grain_rows
+        nonlocal n_flagged, cet_detected, layer_planes, texture_planes, grain_rows, solid_grain_rows
         if refresh_defects:
             n_flagged, _ = refresh_defects_device(engine)       # kmc_simulation.py:335-338
-        row = _metrics_row(engine.clusters(0.5, labels=True), engine.species_counts(), engine.nucleation_count(), L, step,
+        cl = engine.clusters(0.5, labels=True)
+        row = _metrics_row(cl, engine.species_counts(), engine.nucleation_count(), L, step,
                            total_time, n_flagged, nuc_offset, cet_detected, G, R, R_phys, G_over_R_phys)
         cet_detected = row["CET_Detected"]
         if front_metrics:
@@ -423,6 +481,10 @@ def run_kmc(
             texture_planes = _add_texture_columns(row, engine.texture_profile(recluster=False))
         if grain_metrics:
             grain_rows = _add_grain_columns(row, engine.grain_table(recluster=False))
+        if solid_metrics:
+            planes, solid_grain_rows = _add_solid_columns(
+                row, engine.solid_profile(solid_scales, grains=grain_metrics, recluster=False), solid_scales, solid["remelted"], cl)
+            solid_planes.append(planes)
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -439,6 +501,8 @@ def run_kmc(
         stop = min(stop, n_steps - 1)
         if checkpoint_every > 0:      # also stop right before every checkpoint boundary
             stop = min(stop, (next_step // checkpoint_every + 1) * checkpoint_every - 1)
+        if solid_metrics:             # ... and right before every map update
+            stop = min(stop, (next_step // solid_every + 1) * solid_every - 1)
         done, terminated, last_total, dts, margin = _advance_to(engine, next_step, stop, L, defect_fraction, incremental=incremental,
                                                                  thermal_mode=1 if thermal_updates else 0, laser=laser)
         for dt in dts:
@@ -451,9 +515,12 @@ def run_kmc(
         step = stop
         next_step = stop + 1
 
+        if solid_metrics and next_step % solid_every == 0:
+            solid_update(next_step, _updates_between(0, next_step) if thermal_updates else 0)
         is_metric_step = (step % metrics_every == 0) or (step == n_steps - 1)
-        if not is_metric_step:        # a pure checkpoint stop
-            checkpoint(next_step)
+        if not is_metric_step:        # a pure checkpoint (or map-update) stop
+            if checkpoint_every > 0:
+                checkpoint(next_step)
             continue
         metrics_row(step, step % metrics_every == 0)
         if checkpoint_every > 0 and next_step % checkpoint_every == 0:
@@ -474,12 +541,15 @@ def run_kmc(
                 raise ValueError(f"checkpoint was written by a run with {ex}, this call asks for {mb_cfg}")
             executed, g, thermal_done = next_step, int(ex["superstep"]), int(ex["thermal_done"])
         by_events = thermal_cadence == "events" and thermal_updates
+        engine_thermal = 0
         while executed < n_steps:
             # super-steps until (at the earliest) the next metrics / checkpoint boundary or the end: a super-step executes
             # <= d_max events (a row is due once executed - 1 reaches the next multiple of metrics_every)
             boundary = min(((executed - 1) // metrics_every + 1) * metrics_every + 1, n_steps)
             if checkpoint_every > 0:
                 boundary = min(boundary, (executed // checkpoint_every + 1) * checkpoint_every)
+            if solid_metrics:
+                boundary = min(boundary, (executed // solid_every + 1) * solid_every)
             nb = max(1, (boundary - executed) // d_max)
             if by_events:
                 # kmc_simulation.py:248-250: event index e is preceded by e // 20 + 1 temperature updates; the super-step's
@@ -495,11 +565,15 @@ def run_kmc(
             for s in range(r["done"]):
                 executed += int(r["n_exec"][s])
                 total_time += int(r["n_exec"][s]) * float(r["dt_event"][s])
+            if not by_events and thermal_updates:      # (the engine updates T at every 20th super-step)
+                engine_thermal += _updates_between(g, g + r["done"])
             g += r["done"]
             step = executed - 1
             if r["status"] == 1:
                 print(f"Terminating at step {executed}: no valid events (rate={float(r['totals'][r['done']]):.2e})")
                 break
+            if solid_metrics and executed // solid_every > before // solid_every:
+                solid_update(executed, thermal_done if by_events else engine_thermal)
             crossed = (executed - 1) // metrics_every > (before - 1) // metrics_every
             if crossed or executed >= n_steps:
                 metrics_row(step, crossed)
@@ -516,6 +590,10 @@ def run_kmc(
         _write_texture_csv(os.path.join(output_dir, "texture.csv"), texture_planes)
     if grain_rows is not None:
         _write_grains_csv(os.path.join(output_dir, "grains.csv"), grain_rows)
+    if solid_planes:
+        _write_solid_csv(os.path.join(output_dir, "solid_layers.csv"), solid_planes)
+    if solid_grain_rows is not None:
+        _write_solid_csv(os.path.join(output_dir, "solid_grains.csv"), [solid_grain_rows])
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -614,7 +692,8 @@ def _replica_prefix(cfg, L):
 
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
-                     front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False):
+                     front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False, solid_metrics=False,
+                     solid_every=20):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -633,8 +712,12 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     ``texture_metrics=True``: run_kmc's option of that name (columns and ``texture.csv`` of every replica), from ONE batched
     cetkmc_ensemble_texture_profile call per metrics row on the row's own analysis.
     ``grain_metrics=True``: run_kmc's option of that name (columns and ``grains.csv`` of every replica), from ONE batched
-    cetkmc_ensemble_grain_table call per metrics row on the row's own analysis."""
+    cetkmc_ensemble_grain_table call per metrics row on the row's own analysis.
+    ``solid_metrics=True`` / ``solid_every``: run_kmc's options of that name (columns, ``solid_layers.csv`` and, with
+    ``grain_metrics``, ``solid_grains.csv`` of every replica), from ONE batched cetkmc_ensemble_solid_update per multiple of
+    ``solid_every`` steps and ONE batched cetkmc_ensemble_solid_profile per metrics row."""
     import cetkmc
+    _check_solid(solid_metrics, solid_every, False)
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
     caller_py, caller_np = random.getstate(), np.random.get_state()
@@ -667,6 +750,13 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         layer_planes = [None] * R
         texture_planes = [None] * R
         grain_rows = [None] * R
+        solid_planes = [[] for _ in range(R)]
+        solid_grain_rows = [None] * R
+        remelted = np.zeros(R, np.int64)
+        solid_thermal = 0                    # temperature updates issued before the last map update
+        solid_scales = cetkmc.engine.default_solid_scales()
+        if solid_metrics:
+            ens.solid_begin()
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -692,6 +782,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             s0 = next_step
             while s0 <= stop and any(alive):
                 n = min(stop - s0 + 1, cap)
+                if solid_metrics:            # the batch ends right before the next map update
+                    n = min(n, (s0 // solid_every + 1) * solid_every - s0)
                 if rng == "reference":
                     u_pick = np.zeros((R, n))
                     u_def = np.zeros((R, n)) if np.any(df > 0.0) else None
@@ -730,6 +822,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                         print(f"[{cfgs[r]['output_prefix']}] terminating at step {s0 + done}: no valid events "
                               f"(rate={float(res['totals'][r, done]):.2e})")
                 s0 += n
+                if solid_metrics and s0 % solid_every == 0 and any(alive):
+                    now = _updates_between(0, s0) if thermal_updates else 0
+                    remelted += ens.solid_update(s0, max(1, now - solid_thermal) * THERMAL_DT)["n_cleared"]
+                    solid_thermal = now
             # the metrics row of every live replica: one batched analysis (clustering, species and nucleation counts,
             # carbon gather) and one batched defect scatter -- launches independent of R
             if not any(alive):
@@ -748,6 +844,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             lp = ens.layer_profile(recluster=False) if layer_metrics else None
             tp = ens.texture_profile(recluster=False) if texture_metrics else None
             gt = ens.grain_table(recluster=False) if grain_metrics else None
+            sp = ens.solid_profile(solid_scales, grains=grain_metrics, recluster=False) if solid_metrics else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -765,6 +862,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                         row, {k: (v[r] if k in ("gb_hist", "pole_hist", "bad") else v) for k, v in tp.items()})
                 if gt is not None:
                     grain_rows[r] = _add_grain_columns(row, gt[r])
+                if sp is not None:
+                    prof = dict(layers={k: v[r] for k, v in sp["layers"].items()}, grains=sp["grains"][r] if sp["grains"] is not None else None)
+                    planes, solid_grain_rows[r] = _add_solid_columns(row, prof, solid_scales, int(remelted[r]), an[r]["clusters"])
+                    solid_planes[r].append(planes)
                 metrics[r].append(row)
             next_step = stop + 1
 
@@ -779,6 +880,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 _write_texture_csv(os.path.join(f"outputs/{c['output_prefix']}", "texture.csv"), texture_planes[r])
             if grain_rows[r] is not None:
                 _write_grains_csv(os.path.join(f"outputs/{c['output_prefix']}", "grains.csv"), grain_rows[r])
+            if solid_planes[r]:
+                _write_solid_csv(os.path.join(f"outputs/{c['output_prefix']}", "solid_layers.csv"), solid_planes[r])
+            if solid_grain_rows[r] is not None:
+                _write_solid_csv(os.path.join(f"outputs/{c['output_prefix']}", "solid_grains.csv"), [solid_grain_rows[r]])
             fields = ens.replica(r).download()
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))

@@ -11,6 +11,7 @@ outside the accelerated path and are not part of this package.
     python main.py --layers                       # layer columns in every metrics.csv and a layers.csv per level (run_kmc layer_metrics)
     python main.py --texture                      # texture columns in every metrics.csv and a texture.csv per level (run_kmc texture_metrics)
     python main.py --grains                       # grain columns in every metrics.csv and a grains.csv per level (run_kmc grain_metrics)
+    python main.py --solid                        # solidification columns in every metrics.csv and a solid_layers.csv per level (run_kmc solid_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
 every level like ``--mode B --box L`` with the super-step thermal cadence.
@@ -47,7 +48,7 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
-         layers=False, texture=False, grains=False, **run_kw):
+         layers=False, texture=False, grains=False, solid=False, **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
@@ -60,6 +61,8 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
         fm["texture_metrics"] = True
     if grains:                                        # --grains: grain columns and grains.csv (run_kmc grain_metrics)
         fm["grain_metrics"] = True
+    if solid:                                         # --solid: solidification columns, solid_layers.csv (run_kmc solid_metrics)
+        fm["solid_metrics"] = True
     if ensemble:                  # every level in one replica ensemble; the per-level epilogue below reads its results
         for c in carbon_levels:
             prefix = f"impurity_c_{int(c * 100)}"
@@ -127,6 +130,9 @@ if __name__ == "__main__":
                     help="texture columns (boundary misorientation, low-angle / lateral shares, pole alignment) and texture.csv")
     ap.add_argument("--grains", action="store_true",
                     help="grain columns (moment-based elongation and inclination, columnar volume fraction, contacts) and grains.csv")
+    ap.add_argument("--solid", action="store_true",
+                    help="solidification map on the device: G, cooling rate and V at freezing in every metrics.csv, solid_layers.csv "
+                         "(with --grains: solid_grains.csv)")
     a = ap.parse_args()
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
-         grains=a.grains, **(dict(mode="B", box=a.box) if a.mode == "B" else {}))
+         grains=a.grains, solid=a.solid, **(dict(mode="B", box=a.box) if a.mode == "B" else {}))

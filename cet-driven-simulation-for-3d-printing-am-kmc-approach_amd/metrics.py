@@ -393,6 +393,78 @@ def write_grains_csv(path, grains):
             w.writerow([grains[n][i].item() for n in names])
 
 
+SOLID_COLUMNS = ("SolidVoxels", "Remelted", "G_solid", "Gi_solid", "Cool_solid", "T_solid", "V_solid", "G_over_V_solid")
+
+
+def solid_metrics(profile, scales, remelted=0, step=0, clusters=None):
+    """Columns of a metrics row (SOLID_COLUMNS) from one lattice's solidification profile (Engine.solid_profile, or entry r
+    of Ensemble.solid_profile: dict(layers=..., grains=... or None)) taken with the quantisation ``scales``, plus the
+    per-plane table under "planes" (rows of solid_layers.csv, tagged with ``step``) and, when the profile has grain records,
+    the per-grain table under "grains" (rows of solid_grains.csv; ``clusters``, the row's clustering as Engine.clusters
+    returns it, puts each grain's size n and bounding-box aspect beside its thermal history).
+
+    SolidVoxels: voxels holding a record (solidified since the map began and not remelted; bad ones included).  Remelted:
+    ``remelted``, the running count of cleared voxels.  G_solid, Gi_solid, Cool_solid, T_solid: means over the good records
+    of |grad T| [K/m], its component along the build direction [K/m], the cooling rate [K/s] and the temperature [K] AT THE
+    MOMENT EACH VOXEL SOLIDIFIED, from the quantised integer sums (sum / (n * scale)); 0.0 without a good record.
+    V_solid = -Cool_solid / Gi_solid [m/s], the velocity of the isotherm the voxels froze on (0.0 when Gi_solid is 0);
+    G_over_V_solid = G_solid / V_solid (inf for V_solid == 0)."""
+    sc = [float(x) for x in scales]
+
+    def means(rec):
+        n = np.asarray(rec["n_rec"], dtype=np.int64).reshape(-1)
+        q = np.asarray(rec["q"], dtype=np.int64).reshape(len(n), 4).astype(np.float64)
+        safe = np.maximum(n, 1).astype(np.float64)
+        return n, [np.where(n > 0, q[:, c] / (safe * sc[c]), 0.0) for c in range(4)]
+
+    def table(rec, n, m):
+        st_min = np.asarray(rec["stamp_min"], dtype=np.int64).reshape(-1)
+        st_sum = np.asarray(rec["stamp_sum"], dtype=np.int64).reshape(-1)
+        return {"n_rec": n, "n_bad": np.asarray(rec["n_bad"], dtype=np.int64).reshape(-1),
+                "n_cooling": np.asarray(rec["n_cooling"], dtype=np.int64).reshape(-1),
+                "G": m[0], "Gi": m[1], "Cool": m[2], "T": m[3],
+                "stamp_first": np.where(n > 0, st_min, -1), "stamp_last": np.asarray(rec["stamp_max"], dtype=np.int64).reshape(-1),
+                "stamp_mean": np.where(n > 0, st_sum / np.maximum(n, 1), -1.0)}
+
+    lay = profile["layers"]
+    n, m = means(lay)
+    tot = int(n.sum())
+    q_tot = np.asarray(lay["q"], dtype=np.int64).reshape(len(n), 4).sum(axis=0)
+    G, Gi, cool, Ts = [(float(q_tot[c]) / (tot * sc[c]) if tot else 0.0) for c in range(4)]
+    V = (-cool / Gi) if Gi != 0.0 else 0.0
+    out = {"SolidVoxels": tot + int(np.asarray(lay["n_bad"], dtype=np.int64).sum()), "Remelted": int(remelted),
+           "G_solid": G, "Gi_solid": Gi, "Cool_solid": cool, "T_solid": Ts, "V_solid": V,
+           "G_over_V_solid": (G / V) if V != 0.0 else float("inf")}
+    planes = {"Step": np.full(len(n), int(step), np.int64), "plane": np.arange(len(n), dtype=np.int64)}
+    planes.update(table(lay, n, m))
+    out["planes"] = planes
+    if profile.get("grains") is not None:
+        gr = profile["grains"]
+        ng, mg = means(gr)
+        grains = {"id": np.arange(1, len(ng) + 1, dtype=np.int64)}
+        if clusters is not None:
+            bb = np.asarray(clusters["bbox"], dtype=np.int64).reshape(-1, 6)
+            d = bb[:, 3:] - bb[:, :3] + 1
+            grains["n"] = np.asarray(clusters["size"], dtype=np.int64).reshape(-1)
+            grains["aspect"] = (d.max(axis=1).astype(np.float64) / np.maximum(d.min(axis=1), 1).astype(np.float64)) if len(d) else np.zeros(0)
+        grains.update(table(gr, ng, mg))
+        out["grains"] = grains
+    return out
+
+
+def write_solid_csv(path, tables):
+    """solid_layers.csv / solid_grains.csv: the tables of :func:`solid_metrics` ("planes": one per metrics row, written one
+    below the other; "grains": the last row's) as a CSV."""
+    import csv
+    names = list(tables[0])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(names)
+        for t in tables:
+            for i in range(len(t[names[0]])):
+                w.writerow([t[n][i].item() for n in names])
+
+
 def front_velocity(row, prev, voxel_size=VOXEL_SIZE):
     """V_front of a metrics row: (Front_i - the previous row's) * voxel_size / (Time - the previous row's) in m/s; 0.0 on
     the first row (``prev`` None), when the time difference is 0 or when either row has no front."""

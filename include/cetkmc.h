@@ -187,7 +187,8 @@ int cetkmc_abi_version(void);
  * hand build): the binding compares it with the sources beside it and rebuilds / refuses a stale library */
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
- * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
+ * "solid_info", "solid_args", "solid_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -380,7 +381,7 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
  * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
  * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
  * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*,
- * front_stats, layer_profile, grain_table) except the
+ * front_stats, layer_profile, grain_table, solid_read, solid_profile) except the
  * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
  * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
  * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
@@ -582,6 +583,68 @@ int cetkmc_grain_table(void* handle, int64_t cap, struct cetkmc_grain_rec* out);
  * an import on top of it, in a launch sequence that does not depend on R: out[sum of n_clusters], the replicas' records one
  * behind the other in replica order.  A single-lattice handle is refused. */
 int cetkmc_ensemble_grain_table(void* handle, struct cetkmc_grain_rec* out);
+
+/* Solidification map (not in the reference): the thermal conditions at a voxel WHEN IT SOLIDIFIED,
+ * kept on the device between stepping calls, and a profile call that reduces them per build plane and per grain.
+ * The map of a handle holds, per voxel of the (L, L, L) lattice (row-major, axis 0 = build direction), stamp (int64, -1 = no
+ * record) and five doubles T_s, gi, gj, gk, cool, plus a private snapshot of the state bytes and of T.
+ *   cetkmc_solid_begin   allocates the map, sets stamp = -1 and the doubles to +0.0 everywhere and snapshots the current state
+ *                        and T.  Voxels occupied now are substrate: they have no record.  A second begin resets the map.
+ *   cetkmc_solid_end     frees it.  Every other solid call without a map is refused.
+ *   cetkmc_solid_update  stamp >= 0, dt finite and > 0, inv_dx finite (anything else is refused on the host before a launch).
+ *     For every voxel v with snapshot state s0 and current state s1:
+ *       s0 == 0 && s1 != 0 (solidified since the last update): stamp(v) = stamp; T_s = T(v); gi, gj, gk = the gradient
+ *         components of cetkmc_front_stats exactly ((T[x+1] - T[x-1]) * (0.5 * inv_dx) inside, (T[1] - T[0]) * inv_dx at
+ *         x == 0, (T[L-1] - T[L-2]) * inv_dx at x == L-1, 0.0 when L == 1); cool = (T(v) - T_snap(v)) / dt -- no contraction,
+ *         IEEE division, non-finite results stored as they come; info.n_new += 1;
+ *       s0 != 0 && s1 == 0 (remelted, or hopped away): stamp = -1, the five doubles = +0.0; info.n_cleared += 1 (a substrate
+ *         voxel that empties counts here too);
+ *       anything else, a change of species included: the record is untouched.
+ *     Then snapshot = state and T_snap = T for every voxel.  info.n_recorded = voxels with stamp >= 0 after the call.  A voxel
+ *     that solidifies and empties again between two updates is not seen.  The call reads the lattice as it stands (the
+ *     current buffer of the T pair, behind pending stepping work on the handle's stream), writes no lattice field and touches
+ *     no cached rate, list, row sum or staged batch.  info may be NULL.
+ *   cetkmc_solid_read    copies the map: stamp[L^3], T_s[L^3], g[L^3][3], cool[L^3]; any pointer may be NULL; counted in
+ *                        bytes_d2h.
+ *   cetkmc_solid_profile one record per plane i (layers[L]) and per grain id of the handle's last clustering (grains, the
+ *     first min(cap, n) records as cetkmc_grain_table treats cap; grains == NULL: no clustering is needed).  The four
+ *     quantities x0 = G = sqrt(gi*gi + gj*gj + gk*gk) (left to right), x1 = gi, x2 = cool, x3 = T_s are quantised with
+ *     qscale[c] (finite and > 0, otherwise refused).  A voxel with stamp >= 0 is GOOD when all four x are finite and every
+ *     |x_c * qscale[c]| < 2^38 (with L^3 <= 2^24 the sums stay inside int64).  A good voxel adds n_rec +1, stamp_sum + stamp,
+ *     stamp_min / stamp_max, q[c] += llrint(x_c * qscale[c]) (round to nearest even), n_cooling +1 if cool < 0; any other
+ *     recorded voxel adds n_bad +1 and nothing else.  A record without a good voxel has stamp_min = INT64_MAX and
+ *     stamp_max = -1.  A recorded voxel with label 0 counts in its plane only.  Everything in the reduction is integer
+ *     arithmetic (integer atomics): the result is defined to the bit given the map.  For a lattice changed since its
+ *     clustering the result is unspecified (the call stays inside its arrays).
+ * Handles: a single-slab, single-process handle.  begin / update / end refuse a handle that belongs to an ensemble (the
+ * batched calls keep every replica's map); read and profile take a replica handle; profile refuses the handle
+ * cetkmc_create_ensemble returned, as cetkmc_layer_profile does.  Multi-slab and multi-rank handles are refused.  Every
+ * refusal happens before anything is allocated or launched; a device allocation that fails is reported through
+ * cetkmc_last_error and leaves the handle usable (without a map).  cetkmc_destroy frees the map.
+ * (Struct tags without typedefs, as cetkmc_grain_rec.) */
+struct cetkmc_solid_info { int64_t n_new, n_cleared, n_recorded; };
+struct cetkmc_solid_args { double qscale[4]; };
+struct cetkmc_solid_rec {
+    int64_t n_rec, n_bad, n_cooling;
+    int64_t stamp_sum, stamp_min, stamp_max;
+    int64_t q[4];             /* quantised sums of G, gi, cool, T_s over the n_rec good voxels */
+};
+int cetkmc_solid_begin(void* handle);
+int cetkmc_solid_end(void* handle);
+int cetkmc_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info);
+int cetkmc_solid_read(void* handle, int64_t* stamp, double* T_s, double* g, double* cool);
+int cetkmc_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers, int64_t cap,
+                         struct cetkmc_solid_rec* grains);
+/* Every replica of an ensemble, frozen ones included (nothing changes in them; their snapshots are refreshed), in a launch
+ * sequence that does not depend on R.  stamp, inv_dx and dt are shared; info[R]; layers[R][L]; grains: the replicas' records
+ * one behind the other in replica order, as cetkmc_ensemble_grain_table lays them out (NULL: no clustering is needed;
+ * otherwise the clustering of the last cetkmc_ensemble_analyze or an import on top of it is required).  A replica's bits
+ * equal those of the same lattice on a single handle.  A single-lattice handle is refused. */
+int cetkmc_ensemble_solid_begin(void* handle);
+int cetkmc_ensemble_solid_end(void* handle);
+int cetkmc_ensemble_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info);
+int cetkmc_ensemble_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers,
+                                  struct cetkmc_solid_rec* grains);
 
 #ifdef __cplusplus
 }
