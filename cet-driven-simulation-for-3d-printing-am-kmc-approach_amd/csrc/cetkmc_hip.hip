@@ -150,6 +150,8 @@ struct Handle {
     int* d_dirty = nullptr;      // [1 + DIRTY_MAX] rows made stale by the last applied event (incremental mode)
     PendRec* d_pend = nullptr;   // the event of a deferred step, applied by the next sweep launch (k_select_pend -> k_sweep_stream_apply)
     int apply_in_sweep = 1;      // option "apply_in_sweep": defer the application of eligible batched steps into the next sweep
+    int fused_tiles = 1;         // option "fused_tiles": 1 = the sweep launch that applies a pending event runs census-free tiles
+                                 // (sweep_table_tile) at 128 < L <= 256, 2 = the plain launch at that shape as well, 0 = ring tiles
     bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
     BatchCfg pend_cfg{};         // ... with this batch configuration
     double* d_ktab = nullptr;
@@ -725,6 +727,14 @@ int launch_dirty_rows(Handle* h, hipEvent_t ev_a, hipEvent_t ev_b)
     return 0;
 }
 
+// Census-free tiles in the streaming launches (option fused_tiles >= level): one slab in one process, half-wave rows, 128 < L
+// (where the lattice's class bytes and rate table sit in the Infinity Cache; L <= 256 follows from the half-wave rows)
+bool table_tiles(const Handle* h, int level)
+{
+    return h->fused_tiles >= level && h->slabs.size() == 1 && !multi_rank(h) && h->L > 128 && row_shape(h).hw;
+}
+size_t apply_shmem() { return ((sizeof(KParams) + 15) & ~(size_t)15) + sizeof(SlabView); }
+
 // One full-lattice rate sweep: (rate table, if T changed) -> (interface kernel, if the listed voxels' sums are stale)
 // -> sweep kernel -> block sums (+ all-gather across ranks).  ev_pre | table + interface | ev_a | sweep | ev_b |
 // reduce | ev_post are the phase boundaries of cetkmc_get_counters.
@@ -777,7 +787,12 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
             // only under the streaming sweep with the rate table, and only where rows are half-wave rows)
             ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
                         (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
-            launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X);
+            if (table_tiles(h, 1))      // LDS: the apply block's KParams + SlabView copy alone
+                launch(k_sweep_stream_apply<true, 1, false, true>, dim3(table_tile_count(h->L, v.nloc, true) + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X);
+            else
+                launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X);
+        } else if (h->sweep_variant == 1 && table_tiles(h, 2)) {
+            launch(k_sweep_stream<true, true, 1, false, true>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
         } else if (h->sweep_variant >= 1) {
             auto go = [&](auto k) { launch(k, dim3(sa.group_count * njt), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, ss); };
             if (h->sweep_variant == 1) with_stream_kernel<true>(rs, go); else with_stream_kernel<false>(rs, go);
@@ -1250,6 +1265,11 @@ int cetkmc_stale_row(int type, const int pos[2], const int target[2], int gi, in
 {
     return stale_row(stale_ev_host(type, pos, target), gi, j) ? 1 : 0;
 }
+int cetkmc_table_tile_of(int L, int gi, int j)
+{
+    if (L <= 128 || L > 256 || gi < 0 || gi >= L || j < 0 || j >= L) return -1;
+    return table_tile_of(L, true, gi, j);
+}
 int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, int rows[][2])
 {
     const StaleEv se = stale_ev_host(type, pos, target);
@@ -1381,6 +1401,11 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
     }
     if (!strcmp(key, "thermal_lookahead")) { h->thermal_ahead = value ? 1 : 0; return 0; }
     if (!strcmp(key, "apply_in_sweep")) { h->apply_in_sweep = value ? 1 : 0; return 0; }
+    if (!strcmp(key, "fused_tiles")) {
+        if (value < 0 || value > 2) return fail("fused_tiles must be 0 (ring tiles), 1 (census-free tiles in the launch that applies a pending event, default) or 2 (in the plain streaming launch at that shape as well)");
+        h->fused_tiles = (int)value;
+        return 0;
+    }
     if (!strcmp(key, "thermal_table")) { h->thermal_table = value ? 1 : 0; return 0; }
     if (!strcmp(key, "reserve_batch")) {
         // device buffers (uniform streams, per-step logs, one laser source plane per temperature update) and hipEvents of a

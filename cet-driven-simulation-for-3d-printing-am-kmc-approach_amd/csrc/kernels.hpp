@@ -717,13 +717,6 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
         for (int lp = lp0; lp < lp1; ++lp) plane(lp, va, vb);     // two passes: va -> vb -> va
     }
 }
-template <bool TAB, bool HW, int NPF, bool CH2>
-__global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
-{
-    if (ss && ss->status) return;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    sweep_stream_tile<TAB, HW, NPF, CH2>(A, blockIdx.x, smem);
-}
 
 // ----------------------------------------------------------------------------------------
 // k_sweep_table (variant 3): the rate sweep WITHOUT a neighbour census.  What the census of k_sweep_stream decides --
@@ -751,9 +744,11 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
     const int jr = min(jrow, A.L - 1);
     return *reinterpret_cast<const uint2*>(A.cls + ((int64_t)li * A.RJ + (jr + 2)) * A.pitchC + KOFFC + k0);
 }
-template <bool HW, bool CH2>
+// SK (the census-free tiles of a launch that applies a pending event, sites `sw`): a stale row is not stored, as in sweep_row().
+template <bool HW, bool CH2, bool SK = false>
 __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, int jrow, bool top, int lane, const double (&v0)[8],
-                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */)
+                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */,
+                                          const StaleWin& sw = StaleWin{})
 {
     static_assert(!(HW && CH2), "half-wave rows have one chunk");
     const int L = A.L;
@@ -842,7 +837,7 @@ __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, i
         n2 += packed & 0xFFFF;
         n1 = packed >> 16;
     }
-    if (sl == 0 && jrow < L) {
+    if (sl == 0 && jrow < L && !(SK && stale_row(sw, A.gi0 + lp, jrow))) {
         const int64_t o = (int64_t)lp * 3 * L + jrow;
         A.rowsum[o] = r0; A.rowsum[o + L] = r1; A.rowsum[o + 2 * (int64_t)L] = r2;
         A.rowcnt[o] = n0; A.rowcnt[o + L] = n1; A.rowcnt[o + 2 * (int64_t)L] = n2;
@@ -857,10 +852,91 @@ __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, i
 #define CETKMC_TABLE_IPW 8
 #endif
 constexpr int TABLE_IPW = CETKMC_TABLE_IPW;       // items per wave
+
+// The census-free tiles of the streaming launches at half-wave rows in one slab of 128 < L <= 256 (option fused_tiles; the
+// working set sits in the Infinity Cache there): k_sweep_table's decomposition as a tile body of k_sweep_stream_apply and
+// k_sweep_stream.  Tile b owns the TABLE_TILE_ITEMS consecutive items from b * TABLE_TILE_ITEMS on (item = plane * ipp + row
+// pair, so a tile's range runs on from the last pairs of a plane into the first of the next); wave w of its block takes the
+// items w, w + 4, ... of the range.  No shared memory, no barriers, no halo: 9 B per voxel requested for 9 B algorithmic.
+// MEASURED (DESIGN.md section 13, 256^3): the step takes 54.4 us with the ring tiles, 54.6 with 8 items per wave (1024 tiles, all
+// resident), 52.5 with 4, 50.8 with 2 -- many short blocks (4096 tiles + the apply block, about three rounds of the 1280
+// resident ones), each wave requesting both of its items before it reduces the first.  Natural against per-XCD block order,
+// 4 / 5 / 6 waves per SIMD and one item per wave (50.4) are within the run-to-run spread of that.
+#ifndef CETKMC_TILE_IPW
+#define CETKMC_TILE_IPW 2
+#endif
+constexpr int TABLE_TILE_IPW = CETKMC_TILE_IPW;                // items per wave
+constexpr int TABLE_TILE_ITEMS = 4 * TABLE_TILE_IPW;           // items per tile
+// items per plane, tiles per launch and the tile of a row: the one mapping for the kernels, the host's grid and cetkmc_table_tile_of
+__host__ __device__ constexpr int table_tile_ipp(int L, bool hw) { return hw ? (L + 1) >> 1 : L; }
+__host__ __device__ constexpr int table_tile_count(int L, int nloc, bool hw)
+{
+    return (table_tile_ipp(L, hw) * nloc + TABLE_TILE_ITEMS - 1) / TABLE_TILE_ITEMS;
+}
+__host__ __device__ constexpr int table_tile_of(int L, bool hw, int lp, int j)
+{
+    return (lp * table_tile_ipp(L, hw) + (hw ? j >> 1 : j)) / TABLE_TILE_ITEMS;
+}
+// One tile: IPW items per wave from item b * 4 * IPW on, values and class bytes of the next item requested before the current
+// one is reduced (two alternating buffers).  SK: table_row().
+template <bool HW, bool CH2, bool SK, int IPW>
+__device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int nblk, const StaleWin& sw = StaleWin{})
+{
+    static_assert(IPW % 2 == 0, "two alternating buffers");
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = A.L;
+    const int ipp = table_tile_ipp(L, HW);                       // items per plane (HW: pairs of rows)
+    const int n_items = ipp * A.nloc;
+    if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);      // contiguous item ranges per XCD
+    int item = b * 4 * IPW + w;
+    if (item >= n_items) return;
+    int lp = item / ipp, jp = item - lp * ipp;
+    const int sl = HW ? (lane & 31) : lane;
+    auto jrow_of = [&](int jpair) { return HW ? 2 * jpair + (lane >> 5) : jpair; };
+    double va[8], vb[8];
+    uint2 ca, cb;
+    load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
+    ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
+    // one item: `cur` holds its values on entry; the next item's are requested into `nxt` first (past the wave's last item
+    // the request repeats the current one: a cache hit)
+    auto step = [&](double (&cur)[8], uint2& ccur, double (&nxt)[8], uint2& cnxt, bool last) {
+        int lp2 = lp, jp2 = jp + 4;
+        while (jp2 >= ipp) { jp2 -= ipp; ++lp2; }
+        const bool more = !last && (item + 4 < n_items);
+        const int lpn = more ? lp2 : lp, jpn = more ? jp2 : jp;
+        load_vals<true, HW>(A, lpn + 2, jrow_of(jpn), lane, 0, nxt);
+        cnxt = load_cls8(A, lpn + 2, jrow_of(jpn), sl, 0);
+        table_row<HW, CH2, SK>(A, lp + 2, lp, jrow_of(jp), A.gi0 + lp == L - 1, lane, cur, ccur, nullptr, nullptr, sw);
+        item += 4; lp = lp2; jp = jp2;
+    };
+#pragma unroll 1
+    for (int t = 0; t < IPW; t += 2) {
+        step(va, ca, vb, cb, false);
+        if (item >= n_items) break;
+        step(vb, cb, va, ca, t + 2 >= IPW);
+        if (item >= n_items) break;
+    }
+}
+
+// TT: the launch's tiles are the census-free ones (sweep_table_tile; table variant only, no dynamic LDS)
+template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false>
+__global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
+{
+    static_assert(!TT || TAB, "census-free tiles read the rate table");
+    if (ss && ss->status) return;
+    if constexpr (TT) {
+        sweep_table_tile<HW, CH2, false, TABLE_TILE_IPW>(A, blockIdx.x, (int)gridDim.x);
+    } else {
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+        sweep_stream_tile<TAB, HW, NPF, CH2>(A, blockIdx.x, smem);
+    }
+}
+
 template <bool HW, bool CH2>
 __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_table(StreamArgs A, const StepState* __restrict__ ss)
 {
     if (ss && ss->status) return;
+#ifdef CETKMC_TABLE_DEPTH2
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int L = A.L;
     const int ipp = HW ? (L + 1) >> 1 : L;                       // items per plane (HW: pairs of rows)
@@ -872,7 +948,6 @@ __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_table(StreamArg
     int lp = item / ipp, jp = item - lp * ipp;
     const int sl = HW ? (lane & 31) : lane;
     auto jrow_of = [&](int jpair) { return HW ? 2 * jpair + (lane >> 5) : jpair; };
-#ifdef CETKMC_TABLE_DEPTH2
     // A/B: requests TWO items ahead (three rotating buffers)
     double va[8], vb[8], vc[8];
     uint2 ca, cb, cc;
@@ -907,29 +982,7 @@ __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_table(StreamArg
         if (done >= TABLE_IPW || item >= n_items) break;
     }
 #else
-    double va[8], vb[8];
-    uint2 ca, cb;
-    load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
-    ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
-    // one item: `cur` holds its values on entry; the next item's are requested into `nxt` first (past the wave's last item
-    // the request repeats the current one: a cache hit)
-    auto step = [&](double (&cur)[8], uint2& ccur, double (&nxt)[8], uint2& cnxt, bool last) {
-        int lp2 = lp, jp2 = jp + 4;
-        while (jp2 >= ipp) { jp2 -= ipp; ++lp2; }
-        const bool more = !last && (item + 4 < n_items);
-        const int lpn = more ? lp2 : lp, jpn = more ? jp2 : jp;
-        load_vals<true, HW>(A, lpn + 2, jrow_of(jpn), lane, 0, nxt);
-        cnxt = load_cls8(A, lpn + 2, jrow_of(jpn), sl, 0);
-        table_row<HW, CH2>(A, lp + 2, lp, jrow_of(jp), A.gi0 + lp == L - 1, lane, cur, ccur);
-        item += 4; lp = lp2; jp = jp2;
-    };
-#pragma unroll 1
-    for (int t = 0; t < TABLE_IPW; t += 2) {
-        step(va, ca, vb, cb, false);
-        if (item >= n_items) break;
-        step(vb, cb, va, ca, t + 2 >= TABLE_IPW);
-        if (item >= n_items) break;
-    }
+    sweep_table_tile<HW, CH2, false, TABLE_IPW>(A, blockIdx.x, (int)gridDim.x);
 #endif
 }
 
@@ -2022,10 +2075,11 @@ __global__ __launch_bounds__(256) void k_select_apply(KParams P, const SlabView*
 // A deferred step launches the selection alone (k_select_pend): the event and what k_select_apply carries in LDS go to a
 // device record.  The next sweep launch (k_sweep_stream_apply) carries one extra workgroup, blockIdx 0, that applies that
 // event exactly as k_select_apply would have and then re-evaluates and stores the rows the event makes stale (stale_row():
-// dirty_offset() around the record's sites).  The tiles are those of k_sweep_stream: every row that is not stale does not
-// depend on whether a tile read the lattice before or after the event.  A stale row is stored once, by the apply block: the
-// <= 8 tiles whose planes and rows meet the 5 x 5 window of a site run the same tile code with that row's store predicated
-// off (decided from the record's scalars; every other tile runs exactly k_sweep_stream's code).  k_plane_reduce is the plain
+// dirty_offset() around the record's sites).  Every row that is not stale does not depend on whether a tile read the lattice
+// before or after the event.  A stale row is stored once, by the apply block.  The tiles are the census-free ones
+// (sweep_table_tile, option fused_tiles: every tile tests each row against the record's scalars where it stores it) or those
+// of k_sweep_stream (the <= 8 ring tiles whose planes and rows meet the 5 x 5 window of a site run the same tile code with
+// that row's store predicated off, every other tile runs exactly k_sweep_stream's code).  k_plane_reduce is the plain
 // reduce.  Stream order between the launches is unchanged.
 struct PendRec {
     cetkmc_event ev;
@@ -2128,7 +2182,9 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
 #endif
 }
 
-template <bool HW, int NPF, bool CH2>
+// TT: census-free tiles (sweep_table_tile), every one with the stale-row test at its store; the dynamic LDS is then the apply
+// block's copy of KParams and SlabView alone.
+template <bool HW, int NPF, bool CH2, bool TT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_sweep_stream_apply(StreamArgs A,
                                                                                                     const StepState* __restrict__ ss,
                                                                                                     ApplyArgs X)
@@ -2139,16 +2195,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
         // the pending record was written by the previous launch and is only read in this one: uniform (scalar) loads
         const int b = (int)blockIdx.x - 1;
         const StaleEv se = stale_ev_of(X.pend->ev);
-        int ibr, jt;
-        stream_tile_of(A, b, ibr, jt);
-        const int g0 = A.gi0 + (A.group_first + ibr) * STREAM_NI, j0 = jt * SWEEP_TJ;
-        auto meets = [&](int ci, int cj) {          // the tile's planes x rows against the 5 x 5 window of a site
-            return ci + 2 >= g0 && ci - 2 < g0 + STREAM_NI && cj + 2 >= j0 && cj - 2 < j0 + SWEEP_TJ;
-        };
-        if (se.type >= 0 && (meets(se.pi, se.pj) || (se.type == EV_DIFF && meets(se.ti, se.tj))))
-            sweep_stream_tile<true, HW, NPF, CH2, true>(A, b, smem, stale_win(se));
-        else
-            sweep_stream_tile<true, HW, NPF, CH2>(A, b, smem);
+        if constexpr (TT) {
+            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW>(A, b, (int)gridDim.x - 1, stale_win(se));
+        } else {
+            int ibr, jt;
+            stream_tile_of(A, b, ibr, jt);
+            const int g0 = A.gi0 + (A.group_first + ibr) * STREAM_NI, j0 = jt * SWEEP_TJ;
+            auto meets = [&](int ci, int cj) {          // the tile's planes x rows against the 5 x 5 window of a site
+                return ci + 2 >= g0 && ci - 2 < g0 + STREAM_NI && cj + 2 >= j0 && cj - 2 < j0 + SWEEP_TJ;
+            };
+            if (se.type >= 0 && (meets(se.pi, se.pj) || (se.type == EV_DIFF && meets(se.ti, se.tj))))
+                sweep_stream_tile<true, HW, NPF, CH2, true>(A, b, smem, stale_win(se));
+            else
+                sweep_stream_tile<true, HW, NPF, CH2>(A, b, smem);
+        }
 #ifdef CETKMC_SEL_STAMPS
         if (threadIdx.x == 0) atomicMax(&g_pend_stamps[4], (unsigned long long)wall_clock64());
 #endif

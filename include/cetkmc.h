@@ -201,6 +201,10 @@ int cetkmc_dirty_offset(int di, int dj);
  * than 22; entries beyond 22 would not be written).  Host functions; need no device. */
 int cetkmc_stale_row(int type, const int pos[2], const int target[2], int gi, int j);
 int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, int rows[][2]);
+/* The tile of the census-free streaming launches (option fused_tiles) that owns row j of plane gi of a one-slab lattice with
+ * 128 < L <= 256: tiles own consecutive ranges of items, item = gi * ((L + 1) / 2) + j / 2, a pair of rows.  -1 outside that
+ * shape or the lattice.  Host function; needs no device. */
+int cetkmc_table_tile_of(int L, int gi, int j);
 int cetkmc_device_count(int* n);
 
 /* Lifetime.  n_slabs > 1 with all device_ids equal splits the lattice into axis-0 slabs
@@ -246,7 +250,10 @@ int cetkmc_sync(void* handle);
  * device buffers and hipEvents of a batch of n steps now (a bench keeps hipMalloc / hipEventCreate out of its timed region);
  * "apply_in_sweep" 1 (default) = cetkmc_run_steps applies the event of a step whose successor is no temperature-update step
  * (and is not the call's last) inside the next sweep launch (one process, one slab, sweep_variant 1, 128 < L <= 256, full
- * sweeps; same bits), 0 = every step's event applied by its own selection launch */
+ * sweeps; same bits), 0 = every step's event applied by its own selection launch;
+ * "fused_tiles" 1 (default) = the sweep launch that applies a pending event reduces its rows without the neighbour census, from
+ * each voxel's own class byte and the rate table (no LDS ring, no barriers; one process, one slab, 128 < L <= 256; same bits),
+ * 2 = the plain streaming launch at that shape as well, 0 = the ring tiles of sweep_variant 1 in both */
 int cetkmc_set_option(void* handle, const char* key, int64_t value);
 /* planes [*i0,*i1) owned by this handle (whole lattice unless created with create_rank) */
 int cetkmc_owned_planes(void* handle, int* i0, int* i1);
