@@ -243,6 +243,76 @@ struct Handle {
     int64_t solid_recorded = 0;  // voxels with stamp >= 0
 };
 
+// ---- cache state ------------------------------------------------------------------------------------
+// What a handle keeps between calls -- swept (SWEEP), table_fresh (TABLE), ifc_fresh (IFC), therm_applied_g (APPLIED),
+// staged.valid (STAGED) -- goes stale HERE and nowhere else: a call site names what happened (a Cause), the table says which
+// caches that costs, invalidate() clears them.  A cache becomes fresh where the launch that makes it so is issued
+// (ensure_table, launch_sweep, launch_dirty_rows, the temperature tiles that write the table, the look-ahead adoption,
+// cetkmc_stage_inputs).  cetkmc_invalidates() exports the table by name.
+enum class Cause : int {
+    upload, upload_T_or_state, set_params, option_sweep_variant, option_interface_every_step, option_reserve_batch, set_defects,
+    set_prev_state_null, set_prev_state_array, apply, thermal_update, thermal_update_wrote_table, lookahead_adopted, step,
+    step_no_upkeep, batch_stopped, ensemble_stepped, batch_begin, table_written, marker_taken, count
+};
+struct CauseRow { Cause cause; const char* name; unsigned stale; };
+constexpr unsigned SWEEP = CETKMC_CACHE_SWEEP, TABLE = CETKMC_CACHE_TABLE, IFC = CETKMC_CACHE_IFC, APPLIED = CETKMC_CACHE_APPLIED,
+                   STAGED = CETKMC_CACHE_STAGED;
+// two rules, each stated once: whoever writes the table overwrites the listed voxels' entries with it (the interface kernel has
+// to follow), and a new field -- an upload, a temperature update -- is no longer the one the stopped batch's update produced
+constexpr unsigned WROTE_TABLE = IFC, NEW_FIELD = APPLIED;
+constexpr CauseRow INVALIDATES[] = {
+    // cetkmc_upload / _upload_planes, any field (orientations only and defects only as well: every rate may read them) ...
+    {Cause::upload, "upload", SWEEP | IFC | NEW_FIELD},
+    // ... with T or state: a new state also changes the interface list, and a voxel that leaves it keeps its interface sum in
+    // the table until the table is rewritten
+    {Cause::upload_T_or_state, "upload_T_or_state", SWEEP | TABLE | IFC | NEW_FIELD},
+    {Cause::set_params, "set_params", SWEEP | TABLE | IFC},
+    {Cause::option_sweep_variant, "option_sweep_variant", SWEEP | TABLE | IFC},
+    {Cause::option_interface_every_step, "option_interface_every_step", IFC},
+    {Cause::option_reserve_batch, "option_reserve_batch", STAGED},        // growing a buffer moves it
+    // the defect mask replaced: cetkmc_set_defects, _set_defects_sparse, a replica with counts[r] >= 0 of the ensemble call
+    {Cause::set_defects, "set_defects", SWEEP | IFC},
+    {Cause::set_prev_state_null, "set_prev_state_null", IFC},             // the interface list is rebuilt in address order
+    {Cause::set_prev_state_array, "set_prev_state_array", 0},
+    {Cause::apply, "apply", SWEEP | IFC},                                 // the touched voxels' codes are current, their sums are not
+    {Cause::thermal_update, "thermal_update", SWEEP | TABLE | NEW_FIELD},
+    {Cause::thermal_update_wrote_table, "thermal_update_wrote_table", SWEEP | WROTE_TABLE | NEW_FIELD},
+    // the field a batch computed ahead (with its table) becomes the current one.  No NEW_FIELD: a look-ahead is
+    // launched behind a synchronous update of the same batch, which dropped the marker
+    {Cause::lookahead_adopted, "lookahead_adopted", SWEEP | WROTE_TABLE},
+    {Cause::step, "step", SWEEP},                                         // a batched step executed (Mode A, Mode B)
+    // ... whose apply kernel did not re-evaluate the listed voxels it touched (interface_every_step, sweep_variant 0)
+    {Cause::step_no_upkeep, "step_no_upkeep", SWEEP | IFC},
+    // A batch stopped early (status != 0): the steps still queued behind the stop ran as pass-throughs (temperature copied
+    // through, buffer pair flipped, rate table / interface kernels returning at once), so the host's flags describe work the
+    // device skipped.  Both are recomputed from the field as it stands.
+    {Cause::batch_stopped, "batch_stopped", SWEEP | TABLE | IFC},
+    // a replica stepped by cetkmc_run_ensemble: its flags describe nothing the ensemble kernels maintained
+    {Cause::ensemble_stepped, "ensemble_stepped", SWEEP | TABLE | IFC | NEW_FIELD},
+    // a stepping call begins (cetkmc_run_steps, _run_supersteps, _stage_inputs): a staged batch is consumed or dropped, the
+    // batch buffers are reused
+    {Cause::batch_begin, "batch_begin", STAGED},
+    {Cause::table_written, "table_written", WROTE_TABLE},                 // ensure_table
+    {Cause::marker_taken, "marker_taken", APPLIED},                       // cetkmc_run_steps hands the marker to its batch
+};
+constexpr int N_CAUSES = (int)Cause::count;
+constexpr bool causes_in_order()
+{
+    for (int c = 0; c < N_CAUSES; ++c) if ((int)INVALIDATES[c].cause != c) return false;
+    return true;
+}
+static_assert(sizeof INVALIDATES / sizeof *INVALIDATES == N_CAUSES && causes_in_order(), "INVALIDATES[]: one row per Cause, in its order");
+
+void invalidate(Handle* h, Cause c)
+{
+    const unsigned stale = INVALIDATES[(int)c].stale;
+    if (stale & SWEEP) h->swept = false;
+    if (stale & TABLE) h->table_fresh = false;
+    if (stale & IFC) h->ifc_fresh = false;
+    if (stale & APPLIED) h->therm_applied_g = -1;
+    if (stale & STAGED) h->staged.valid = false;
+}
+
 KParams make_kparams(const cetkmc_params& p)
 {
     KParams k{};
@@ -571,11 +641,7 @@ int upload_impl(Handle* h, int i_begin, int i_end, const I* state, const double*
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->swept = false;
-    // a new state changes the interface list: a voxel that leaves it keeps its interface sum in vval until the table is rewritten
-    if (T || state) h->table_fresh = false;
-    h->ifc_fresh = false;
-    h->therm_applied_g = -1;
+    invalidate(h, (T || state) ? Cause::upload_T_or_state : Cause::upload);
     return 0;
 }
 template <class I>
@@ -629,7 +695,7 @@ int ensure_table(Handle* h, hipStream_t st, const StepState* ss)
     if (h->table_fresh) return 0;
     CHK(launch_table(h, st, ss, h->cur));
     h->table_fresh = true;
-    h->ifc_fresh = false;
+    invalidate(h, Cause::table_written);
     return 0;
 }
 
@@ -981,10 +1047,9 @@ int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_l
         HIPCHK(hipGetLastError());
     }
     h->cur = nxt;
-    h->swept = false;
-    h->table_fresh = n_fused == h->slabs.size();      // every slab's update wrote its table as well
-    if (h->table_fresh) { h->ifc_fresh = false; ++h->cnt.table_updates; }       // the listed voxels' entries follow (k_interface)
-    h->therm_applied_g = -1;
+    const bool wrote_table = n_fused == h->slabs.size();      // every slab's update wrote its table as well
+    invalidate(h, wrote_table ? Cause::thermal_update_wrote_table : Cause::thermal_update);
+    if (wrote_table) { h->table_fresh = true; ++h->cnt.table_updates; }
     return 0;
 }
 
@@ -1043,9 +1108,8 @@ int thermal_step(Handle* h, int64_t g, double dt, int laser, const double* d_q, 
     HIPCHK(hipGetLastError());
     if (h->slabs.size() > 1) CHK(exchange_T_halo(h, nxt));      // the recomputed voxels may sit in a neighbour slab's halo
     h->cur = nxt;
-    h->swept = false;
+    invalidate(h, Cause::lookahead_adopted);
     h->table_fresh = true;       // computed ahead with the field
-    h->ifc_fresh = false;        // the listed voxels' entries are not: the interface kernel follows
     return 0;
 }
 
@@ -1282,6 +1346,13 @@ int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, in
     }
     return n;
 }
+// the table invalidate() clears by, by cause name
+int cetkmc_invalidates(const char* cause)
+{
+    for (const CauseRow& row : INVALIDATES)
+        if (cause && !strcmp(cause, row.name)) return (int)row.stale;
+    return -1;
+}
 
 int cetkmc_device_count(int* n)
 {
@@ -1373,7 +1444,7 @@ int cetkmc_set_params(void* handle, const cetkmc_params* p)
     if (!h || !p) return fail("null argument");
     HIPCHK(hipSetDevice(h->dev));
     h->p = *p; h->kp = make_kparams(*p);
-    h->swept = false; h->table_fresh = false; h->ifc_fresh = false;
+    invalidate(h, Cause::set_params);
     return upload_ktab(h);
 }
 
@@ -1385,10 +1456,10 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         if (value < 0 || value > 4) return fail("sweep_variant must be 0 (simple), 1 (streaming + rate table, default), 2 (streaming, recompute), 3 (census-free table sweep) or 4 (census-free, one block per plane, block sums in the same launch)");
         h->sweep_variant = (int)value;
         h->sweep_auto = 0;          // an explicit choice stands at every lattice size
-        h->swept = false; h->table_fresh = false; h->ifc_fresh = false;
+        invalidate(h, Cause::option_sweep_variant);
         return 0;
     }
-    if (!strcmp(key, "interface_every_step")) { h->ifc_every_step = value ? 1 : 0; h->ifc_fresh = false; return 0; }
+    if (!strcmp(key, "interface_every_step")) { h->ifc_every_step = value ? 1 : 0; invalidate(h, Cause::option_interface_every_step); return 0; }
     if (!strcmp(key, "thermal_planes_per_block")) {
         if (value < 1 || value > 64) return fail("thermal_planes_per_block must be 1..64");
         h->therm_ni = (int)value;
@@ -1412,7 +1483,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         // batch of `value` steps, allocated ahead of it: a bench keeps hipMalloc / hipEventCreate out of its timed region
         if (value < 0 || value > (1 << 22)) return fail("reserve_batch out of range");
         HIPCHK(hipSetDevice(h->dev));
-        h->staged.valid = false;           // growing a buffer moves it: a batch staged before this call is gone
+        invalidate(h, Cause::option_reserve_batch);      // growing a buffer moves it: a batch staged before this call is gone
         const size_t n = (size_t)value;
         CHK(reserve_steps(h, n));
         CHK(grow(&h->d_u_np, &h->cap_np, 2 * n + 2 + (size_t)h->L * h->L));
@@ -1495,7 +1566,7 @@ int cetkmc_set_defects(void* handle, const uint8_t* mask)
         ext_range(h, s, &a, &b);
         CHK(h2d_u8<uint8_t>(h, s, s.v.defects, mask, 0, a, b, false));
     }
-    h->swept = false; h->ifc_fresh = false;
+    invalidate(h, Cause::set_defects);
     return 0;
 }
 
@@ -1504,6 +1575,7 @@ int cetkmc_set_prev_state(void* handle, const int64_t* prev_state)
     Handle* h = (Handle*)handle;
     if (!h) return fail("null handle");
     HIPCHK(hipSetDevice(h->dev));
+    invalidate(h, prev_state ? Cause::set_prev_state_array : Cause::set_prev_state_null);
     for (auto& s : h->slabs) {
         if (prev_state) {
             int a, b;
@@ -1518,7 +1590,6 @@ int cetkmc_set_prev_state(void* handle, const int64_t* prev_state)
             // in its class byte and its sum in the table, and only the list's next evaluation brings both up to date
             hipLaunchKernelGGL(k_ifc_rebuild, dim3(2048), dim3(256), 0, h->stream, s.v);
             CHK(relist_slab(h, (int)(&s - h->slabs.data())));
-            h->ifc_fresh = false;
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1593,7 +1664,7 @@ int cetkmc_apply(void* handle, const cetkmc_event* ev, double theta_new, double 
                        (int)h->slabs.size(), e, make_defect, h->d_ss, (const double*)h->d_ktab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->swept = false; h->ifc_fresh = false;      // the touched voxels' codes are current, their sums are not
+    invalidate(h, Cause::apply);
     return 0;
 }
 
@@ -1709,7 +1780,7 @@ int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* a)
     Handle* h = (Handle*)handle;
     if (!h || !a) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
-    h->staged.valid = false;
+    invalidate(h, Cause::batch_begin);
     CHK(check_run_args(a, true));
     HIPCHK(hipSetDevice(h->dev));
     CHK(upload_run_inputs(h, a));
@@ -1766,7 +1837,7 @@ static int stage_run(Handle* h, const cetkmc_run_args* a)
     const bool staged = n > 0 && a->rng_mode != 2 && !a->u_pick && !a->u_defect && !a->u_np && !a->q_planes;
     CHK(check_run_args(a, !staged));
     const auto g = h->staged;
-    h->staged.valid = false;           // a staged batch is consumed (or dropped) by the next stepping call
+    invalidate(h, Cause::batch_begin);      // a staged batch is consumed (or dropped) by the next stepping call
     if (staged) {
         if (!g.valid) return fail("no input pointers and no staged batch (cetkmc_stage_inputs)");
         if (g.step0 != a->step0 || g.n_steps != n || g.np_cap != a->np_cap || g.n_q != a->n_q || g.thermal_mode != a->thermal_mode ||
@@ -1807,8 +1878,8 @@ static int enqueue_steps(Handle* h, const cetkmc_run_args* a, const BatchCfg& cf
             CHK(launch_dirty_rows(h, pe.pair(s, 0), pe.sweep(s, 1)));
             CHK(pe.record(s, 4));
             CHK(launch_select_apply(h, cfg, 1, h->d_dirty, s));
+            invalidate(h, Cause::step);
             CHK(pe.record(s, 5));
-            h->swept = false;
             continue;
         }
         ++res->full_sweeps;
@@ -1828,9 +1899,8 @@ static int enqueue_steps(Handle* h, const cetkmc_run_args* a, const BatchCfg& cf
         } else {
             CHK(launch_select_apply(h, cfg, (incr || eval_touched) ? 1 : 0, incr ? h->d_dirty : nullptr, s));
         }
-        if (!(incr || eval_touched)) h->ifc_fresh = false;
+        invalidate(h, (incr || eval_touched) ? Cause::step : Cause::step_no_upkeep);
         CHK(pe.record(s, 5));
-        h->swept = false;
     }
     return 0;
 }
@@ -1863,6 +1933,24 @@ static int download_run(Handle* h, int64_t n, StepState* ss, double* totals, cet
     return 0;
 }
 
+// The end of a stepping call, behind its synchronisation, with the step state it left (cetkmc_run_steps: its arguments and the
+// marker it took; cetkmc_run_supersteps: neither).  A look-ahead never outlives its batch; a batch that stopped early leaves
+// no cache (Cause::batch_stopped).  Mode A, stream exhausted (status 2) ON a temperature-update step: the continuation starts
+// at that step and must not apply its update a second time (Handle::therm_applied_g).
+static int end_batch(Handle* h, const StepState& ss, const cetkmc_run_args* a = nullptr, int64_t therm_skip_g = -1)
+{
+    if (h->spec.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); h->spec.valid = false; }
+    if (ss.status != 0) invalidate(h, Cause::batch_stopped);
+    if (a && ss.status == 2) {
+        const int64_t done = ss.cur, g = a->step0 + done;
+        if (done == 0 && a->step0 == therm_skip_g)
+            h->therm_applied_g = therm_skip_g;             // still the same pending step (nothing executed, nothing updated)
+        else if (a->thermal_mode && done < a->n_steps && g % 20 == 0)
+            h->therm_applied_g = g;                        // that step's update ran before the shortage was noticed
+    }
+    return 0;
+}
+
 int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* res, double* totals,
                      cetkmc_event* events, int64_t* n_events)
 {
@@ -1883,7 +1971,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     h->comm_ev_used = 0;
     // continuation of a batch that ran out of stream on a temperature-update step: that update is already in the field
     const int64_t therm_skip_g = h->therm_applied_g;
-    h->therm_applied_g = -1;
+    invalidate(h, Cause::marker_taken);
     int64_t q_idx = 0;
     res->full_sweeps = 0;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -1892,7 +1980,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     StepState ss;
     CHK(download_run(h, n, &ss, totals, events, n_events));
-    if (h->spec.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); h->spec.valid = false; }      // never outlives its batch
+    CHK(end_batch(h, ss, a, therm_skip_g));
     if (h->time_comm) {
         for (size_t q = 0; q + 1 < h->comm_ev_used; q += 2) {
             CHK(add_elapsed(h->comm_ev[q], h->comm_ev[q + 1], &h->cnt.ms_comm));
@@ -1911,17 +1999,6 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
     CHK(pe.collect(res));
     h->cnt.steps += done;
-    if (ss.status != 0) {
-        // the batch stopped early: the steps still queued behind the stop ran as pass-throughs (temperature copied through,
-        // buffer pair flipped, rate table / interface kernels returning at once), so the host's freshness flags describe
-        // work the device skipped.  Recompute both from the field as it stands.
-        h->table_fresh = false; h->ifc_fresh = false; h->swept = false;
-        if (ss.status == 2 && a->thermal_mode && done < n && (a->step0 + done) % 20 == 0 &&
-            !(done == 0 && a->step0 == therm_skip_g))
-            h->therm_applied_g = a->step0 + done;          // that step's update ran before the shortage was noticed
-        else if (ss.status == 2 && done == 0 && a->step0 == therm_skip_g)
-            h->therm_applied_g = therm_skip_g;             // still the same pending step (nothing executed, nothing updated)
-    }
     if (totals && ss.status == 1 && done < n) totals[done] = ss.total;
     return 0;
 }
@@ -1998,7 +2075,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     C.nranks = ranks ? h->nranks : 1;
     const int NE = D + 2 * nb2;                               // own events | lower neighbour's top layer | upper neighbour's bottom layer
     const size_t shmem = (size_t)C.PT * C.PH * C.PH * 19;     // heap: 2*NL doubles + 2*NL flags, NL leaf codes
-    h->staged.valid = false;            // the batch buffers are reused below
+    invalidate(h, Cause::batch_begin);      // the batch buffers are reused below
     CHK(reserve_steps(h, (size_t)n));
     if (a->thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
     // working buffers of the handle (grow-only; the previous call ended with a synchronisation, nothing still reads them)
@@ -2064,21 +2141,20 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
                            (int)h->slabs.size(), n_touch, (const cetkmc_event*)d_dom, (const StepState*)h->d_ss, (const double*)h->d_ktab);
         hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, d_cnt, h->d_log_total, h->d_log_nev,
                            C.null_events ? d_rmax : (double*)nullptr, std::min(C.nranks, 64));
-        h->swept = false;
+        invalidate(h, Cause::step);      // (k_domain_touch re-evaluated the listed voxels the events changed)
     }
     if (n > 0) CHK(relist(h));        // leave a complete, address-ordered interface list behind (Mode A reads it)
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipMemcpyAsync(&ss, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->spec.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); h->spec.valid = false; }
+    CHK(end_batch(h, ss));
     res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = q_idx;
     res->nucleation_count = ss.nuc_count;
     res->wall_ms = 0.0;
     CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
     res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = n; res->min_margin = 1.0;
     h->cnt.supersteps += ss.cur;
-    if (ss.status != 0) { h->table_fresh = false; h->ifc_fresh = false; h->swept = false; }     // as in cetkmc_run_steps
     CHK(refresh_ifc_grid(h));
     const int64_t done = ss.cur;
     if ((totals || dt_event) && done > 0) {
@@ -2298,7 +2374,7 @@ int cetkmc_set_defects_sparse(void* handle, const int64_t* lin_idx, int64_t n)
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->swept = false; h->ifc_fresh = false;
+    invalidate(h, Cause::set_defects);
     return 0;
 }
 
@@ -2651,8 +2727,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         Handle* h = e->reps[(size_t)r];
         const StepState& q = ss[(size_t)r];
         h->cur ^= flips & 1;
-        // the replica's freshness flags describe nothing the ensemble kernels maintained: recompute on demand
-        h->table_fresh = false; h->ifc_fresh = false; h->swept = false; h->therm_applied_g = -1;
+        invalidate(h, Cause::ensemble_stepped);      // recompute on demand
         grow_ifc_grid(h, list_len[(size_t)r]);
         h->cnt.steps += q.cur;
         if (q.status == 1) e->frozen[(size_t)r] = 1;
@@ -2880,7 +2955,7 @@ int cetkmc_ensemble_set_defects_sparse(void* handle, const int64_t* counts, cons
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     for (int r = 0; r < R; ++r)
-        if (counts[r] >= 0) { e->reps[(size_t)r]->swept = false; e->reps[(size_t)r]->ifc_fresh = false; }
+        if (counts[r] >= 0) invalidate(e->reps[(size_t)r], Cause::set_defects);
     return 0;
 }
 

@@ -100,7 +100,14 @@ typedef struct cetkmc_run_args {
     int32_t thermal_mode;     /* 0 none, 1 update_temperature_cet every 20 steps (:248-250),
                                  2 update_temperature (laser) every 20 steps             */
     double  thermal_dt;       /* dt of the thermal update (run_kmc uses 1e-6)           */
-    const double* q_planes;   /* thermal_mode 2: [n_q][L*L] source planes, consumed in order */
+    const double* q_planes;   /* thermal_mode 2: [n_q][L*L] source planes, consumed in order.
+                                 Continuing a batch that stopped with status 2 ON an update step (step0 + steps_done a
+                                 multiple of 20; that step's update is already in the field, cetkmc_run_result.status):
+                                 the continuation starts at the same step0 = that step and supplies that step's plane
+                                 again as q_planes[0].  It is not read a second time, but it is counted again in q_used.
+                                 The handle remembers the applied update only until the next upload (of any field, a
+                                 defects-only one included) or direct temperature update: after either, a call starting
+                                 at that step applies the update like any other (CETKMC_CACHE_APPLIED) */
     int64_t n_q;
     int32_t use_latent;       /* thermal_mode 2: latent-heat term on/off                */
     int32_t profile;          /* 1: time every rate-sweep launch with hipEvents; 3: every 8th launch, every 4th in batches of <= 64
@@ -113,7 +120,10 @@ typedef struct cetkmc_run_args {
 
 typedef struct cetkmc_run_result {
     int64_t steps_done;
-    int32_t status;           /* 0 ok, 1 terminated (no valid events, :260-262), 2 u_np exhausted */
+    int32_t status;           /* 0 ok, 1 terminated (no valid events, :260-262), 2 u_np exhausted: continue with a call
+                                 whose step0 is this call's step0 + steps_done and whose u_np starts at np_used.  When
+                                 that step is a temperature-update step its update has been applied already and the
+                                 continuation does not repeat it (cetkmc_run_args.q_planes says what it must supply) */
     int64_t np_used;          /* doubles of u_np consumed                               */
     int64_t q_used;           /* thermal_mode 2: source planes consumed by the executed steps (and by the step a batch
                                  stopped in: its update precedes the selection); planes queued behind an early stop
@@ -205,6 +215,18 @@ int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, in
  * 128 < L <= 256: tiles own consecutive ranges of items, item = gi * ((L + 1) / 2) + j / 2, a pair of rows.  -1 outside that
  * shape or the lattice.  Host function; needs no device. */
 int cetkmc_table_tile_of(int L, int gi, int j);
+/* What a handle keeps between calls, as bits of cetkmc_invalidates()'s result. */
+enum cetkmc_cache {
+    CETKMC_CACHE_SWEEP = 1,     /* row and block sums of the last rate sweep (cetkmc_select, cetkmc_row_sums read them) */
+    CETKMC_CACHE_TABLE = 2,     /* per-voxel rate table of the current temperature field and parameters */
+    CETKMC_CACHE_IFC = 4,       /* the listed (interface) voxels' sums and event counts */
+    CETKMC_CACHE_APPLIED = 8,   /* the temperature update a batch stopped with status 2 has already applied */
+    CETKMC_CACHE_STAGED = 16    /* a batch staged by cetkmc_stage_inputs */
+};
+/* The caches a named cause makes stale, as a mask of cetkmc_cache bits; -1 for an unknown name.  It reads the table every
+ * mutating entry point of the library invalidates by; the names are that table's (DESIGN.md section 20 lists them).  Host
+ * function; needs no device. */
+int cetkmc_invalidates(const char* cause);
 int cetkmc_device_count(int* n);
 
 /* Lifetime.  n_slabs > 1 with all device_ids equal splits the lattice into axis-0 slabs
