@@ -143,11 +143,16 @@ class SolidRec(C.Structure):
                 ("stamp_min", C.c_int64), ("stamp_max", C.c_int64), ("q", C.c_int64 * 4)]
 
 
+class OriginRec(C.Structure):
+    _fields_ = [("n_occ", C.c_int64), ("n_by", C.c_int64 * 4), ("n_unrec", C.c_int64), ("n_left", C.c_int64),
+                ("ord_sum", C.c_int64), ("ord_min", C.c_int64), ("ord_max", C.c_int64), ("birth", C.c_int64), ("pad", C.c_int64)]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
                   "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
-                  "solid_rec": SolidRec}
+                  "solid_rec": SolidRec, "origin_rec": OriginRec}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -224,6 +229,17 @@ PROTOTYPES = {
     "cetkmc_ensemble_solid_end": (C.c_int, [C.c_void_p]),
     "cetkmc_ensemble_solid_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     "cetkmc_ensemble_solid_profile": (C.c_int, [C.c_void_p, _P(SolidArgs), C.c_void_p, C.c_void_p]),
+    "cetkmc_origin_begin": (C.c_int, [C.c_void_p]),
+    "cetkmc_origin_end": (C.c_int, [C.c_void_p]),
+    "cetkmc_origin_absorb_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "cetkmc_origin_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cetkmc_origin_census": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cetkmc_origin_seq": (C.c_int64, [C.c_void_p]),
+    "cetkmc_origin_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cetkmc_ensemble_origin_begin": (C.c_int, [C.c_void_p]),
+    "cetkmc_ensemble_origin_end": (C.c_int, [C.c_void_p]),
+    "cetkmc_ensemble_origin_census": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cetkmc_ensemble_origin_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

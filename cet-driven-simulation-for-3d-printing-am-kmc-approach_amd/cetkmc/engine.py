@@ -24,6 +24,10 @@ SOLID_DTYPE = np.dtype([("n_rec", "<i8"), ("n_bad", "<i8"), ("n_cooling", "<i8")
 assert SOLID_DTYPE.itemsize == C.sizeof(_lib.SolidRec) == 80
 SOLID_INFO_DTYPE = np.dtype([("n_new", "<i8"), ("n_cleared", "<i8"), ("n_recorded", "<i8")])
 assert SOLID_INFO_DTYPE.itemsize == C.sizeof(_lib.SolidInfo) == 24
+ORIGIN_DTYPE = np.dtype([("n_occ", "<i8"), ("n_by", "<i8", 4), ("n_unrec", "<i8"), ("n_left", "<i8"), ("ord_sum", "<i8"),
+                         ("ord_min", "<i8"), ("ord_max", "<i8"), ("birth", "<i8"), ("pad", "<i8")])
+assert ORIGIN_DTYPE.itemsize == C.sizeof(_lib.OriginRec) == 96
+ORIGIN_CODES = ("none", "dep", "nuc", "att", "hop", "left")      # code of an origin word (word & 7)
 
 TYPE_BYTES = (b"dep", b"diff", b"nuc", b"att")   # kmc_event_rates.py:72,109,132,158
 
@@ -110,6 +114,16 @@ def _solid_args(scales):
 
 def _solid_fields(buf):
     return {f: buf[f].copy() for f in SOLID_DTYPE.names}
+
+
+def _origin_fields(buf):
+    return {f: buf[f].copy() for f in ORIGIN_DTYPE.names if f != "pad"}
+
+
+def origin_decode(words):
+    """(ordinal int64, -1 for none; code uint8) of origin words ((ordinal + 1) << 3 | code)."""
+    w = np.asarray(words, np.uint64)
+    return (w >> np.uint64(3)).astype(np.int64) - 1, (w & np.uint64(7)).astype(np.uint8)
 
 
 def device_count():
@@ -580,6 +594,63 @@ class Engine:
         self._ck(self.lib.cetkmc_solid_profile(self.h, C.byref(a), _ptr(lay), k, _ptr(gr)))
         return dict(layers=_solid_fields(lay), grains=_solid_fields(gr[:k]))
 
+    # -- origin map --------------------------------------------------------------
+    def origin_begin(self):
+        """cetkmc_origin_begin: start (or reset) the handle's origin map -- no voxel has a record, the census is zero, the
+        map's clock is 0.  From now on every stepping call and ``apply`` folds its executed events into the map."""
+        self._ck(self.lib.cetkmc_origin_begin(self.h))
+
+    def origin_end(self):
+        """cetkmc_origin_end: free the map."""
+        self._ck(self.lib.cetkmc_origin_end(self.h))
+
+    def origin_absorb(self, events, group=1):
+        """cetkmc_origin_absorb_events: host records (EVENT_DTYPE), ``group`` consecutive records per ordinal."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE).ravel()
+        self._ck(self.lib.cetkmc_origin_absorb_events(self.h, _ptr(ev) if len(ev) else None, len(ev), int(group)))
+
+    def origin_words(self):
+        """cetkmc_origin_read: the raw (L, L, L) uint64 words, ((ordinal + 1) << 3) | code, 0 = no record."""
+        w = np.zeros((self.L,) * 3, np.uint64)
+        self._ck(self.lib.cetkmc_origin_read(self.h, _ptr(w)))
+        return w
+
+    def origin_read(self):
+        """The map as dict(ordinal (L,L,L) int64, -1 = no record; code (L,L,L) uint8: 0 none, 1 dep, 2 nuc, 3 att, 4 hop,
+        5 left)."""
+        o, c = origin_decode(self.origin_words())
+        return dict(ordinal=o, code=c)
+
+    def origin_census(self):
+        """cetkmc_origin_census: (L, 5) int64 events absorbed per build plane -- dep, diff (left), nuc, att, diff (arrived)."""
+        c = np.zeros((max(self.L, 1), 5), np.int64)
+        self._ck(self.lib.cetkmc_origin_census(self.h, _ptr(c)))
+        return c
+
+    def origin_seq(self):
+        """cetkmc_origin_seq: the map's clock (ordinal of the next absorbed step); -1 without a map."""
+        return int(self.lib.cetkmc_origin_seq(self.h))
+
+    def origin_profile(self, grains=False, threshold=0.5, recluster=True):
+        """cetkmc_origin_profile: dict(layers=..., grains=...) of int64 field arrays (n_occ, n_by (.., 4: dep, nuc, att,
+        hop), n_unrec, n_left, ord_sum, ord_min, ord_max, birth) with leading dimension L (plane i of the build direction)
+        and, with ``grains``, n (grain id - 1 of the handle's last clustering; None otherwise).  With ``grains`` the call
+        clusters first with ``threshold`` unless ``recluster`` is False, which reuses the last clustering or import."""
+        lay = np.zeros(max(self.L, 1), ORIGIN_DTYPE)
+        if not grains:
+            self._ck(self.lib.cetkmc_origin_profile(self.h, _ptr(lay), 0, None))
+            return dict(layers=_origin_fields(lay), grains=None)
+        if recluster:
+            n = C.c_int64(0)
+            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+            self._cc_n = n.value
+        k = self._cc_n
+        if k is None:       # a clustering this object did not make: its size from the table call (fails without one)
+            k = len(self.grain_table(recluster=False)["n"])
+        gr = np.zeros(max(k, 1), ORIGIN_DTYPE)
+        self._ck(self.lib.cetkmc_origin_profile(self.h, _ptr(lay), k, _ptr(gr)))
+        return dict(layers=_origin_fields(lay), grains=_origin_fields(gr[:k]))
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -860,6 +931,52 @@ class Ensemble:
         gr = np.zeros(max(int(at[-1]), 1), SOLID_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_solid_profile(self.h, C.byref(a), _ptr(lay), _ptr(gr)))
         return dict(layers=_solid_fields(lay[:self.R]), grains=[_solid_fields(gr[at[r]:at[r + 1]]) for r in range(self.R)])
+
+    # -- origin maps of every replica -------------------------------------------
+    def origin_begin(self):
+        """cetkmc_ensemble_origin_begin: Engine.origin_begin for every replica."""
+        self._ck(self.lib.cetkmc_ensemble_origin_begin(self.h))
+
+    def origin_end(self):
+        self._ck(self.lib.cetkmc_ensemble_origin_end(self.h))
+
+    def origin_absorb(self, r, events, group=1):
+        """Host records into the map of replica r (Engine.origin_absorb on its handle)."""
+        self._reps[r].origin_absorb(events, group)
+
+    def origin_read(self, r=None):
+        """The map of replica r (Engine.origin_read on its handle); r None: every replica's, arrays (R, L, L, L)."""
+        if r is not None:
+            return self._reps[r].origin_read()
+        maps = [e.origin_read() for e in self._reps]
+        return dict(ordinal=np.stack([m["ordinal"] for m in maps]), code=np.stack([m["code"] for m in maps]))
+
+    def origin_seq(self):
+        """(R,) int64: every replica's map clock."""
+        return np.array([e.origin_seq() for e in self._reps], np.int64)
+
+    def origin_census(self):
+        """cetkmc_ensemble_origin_census: (R, L, 5) int64."""
+        c = np.zeros((max(self.R, 1), max(self.L, 1), 5), np.int64)
+        self._ck(self.lib.cetkmc_ensemble_origin_census(self.h, _ptr(c)))
+        return c[:self.R]
+
+    def origin_profile(self, grains=False, threshold=0.5, recluster=True):
+        """cetkmc_ensemble_origin_profile: Engine.origin_profile of every replica in launches that do not depend on R.
+        dict(layers=field arrays with leading dimensions (R, L), grains=one dict per replica or None).  With ``grains``
+        runs :meth:`analyze` first (without downloading labels) unless ``recluster`` is False."""
+        lay = np.zeros((max(self.R, 1), self.L), ORIGIN_DTYPE)
+        if not grains:
+            self._ck(self.lib.cetkmc_ensemble_origin_profile(self.h, _ptr(lay), None))
+            return dict(layers=_origin_fields(lay[:self.R]), grains=None)
+        if recluster:
+            self.analyze(threshold, labels=False)
+        if self._an_nc is None:
+            raise RuntimeError("cetkmc: Ensemble.origin_profile(grains=True) needs a preceding Ensemble.analyze")
+        at = np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
+        gr = np.zeros(max(int(at[-1]), 1), ORIGIN_DTYPE)
+        self._ck(self.lib.cetkmc_ensemble_origin_profile(self.h, _ptr(lay), _ptr(gr)))
+        return dict(layers=_origin_fields(lay[:self.R]), grains=[_origin_fields(gr[at[r]:at[r + 1]]) for r in range(self.R)])
 
     def set_defects_sparse(self, lists):
         """Engine.set_defects_sparse for every replica r with lists[r] not None, in launches that do not depend on R."""

@@ -31,6 +31,7 @@
 #include "texture.hpp"
 #include "grain.hpp"
 #include "solid.hpp"
+#include "origin.hpp"
 
 using namespace cetkmc;
 
@@ -241,6 +242,12 @@ struct Handle {
     void* d_solid_block = nullptr;
     bool solid_on = false;
     int64_t solid_recorded = 0;  // voxels with stamp >= 0
+    // origin map (cetkmc_origin_begin .. _end, origin.hpp): words and census of this lattice; d_origin_block owns them on a
+    // single handle, the ensemble's block on a replica
+    OriginMap origin{};
+    void* d_origin_block = nullptr;
+    bool origin_on = false;
+    int64_t origin_seq = 0;      // ordinal of the next absorbed step
 };
 
 // ---- cache state ------------------------------------------------------------------------------------
@@ -1187,6 +1194,7 @@ void destroy_impl(Handle* h)
         (void)hipFree(s.vvalbuf[0]); (void)hipFree(s.vvalbuf[1]); (void)hipFree(s.depbuf[0]); (void)hipFree(s.depbuf[1]); (void)hipFree(s.v.ifc_in); (void)hipFree(s.v.ifc_code); (void)hipFree(s.v.ifc_list); (void)hipFree(s.v.ifc_n);
     }
     if (h->d_solid_block) (void)hipFree(h->d_solid_block);
+    if (h->d_origin_block) (void)hipFree(h->d_origin_block);
     void* ccp[] = {h->d_cc_parent, h->d_cc_roots, h->d_cc_cid, h->d_cc_labels, h->d_cc_stats, h->d_cc_n};
     for (void* p : ccp) if (p) (void)hipFree(p);
     void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
@@ -1239,6 +1247,10 @@ struct Ens {
     int an_species = -1;
     void* d_solid_block = nullptr;       // cetkmc_ensemble_solid_begin: every replica's map, the counters [R][3], the map table [R]
     SolidMap* d_solid_maps = nullptr;    // (inside the block)
+    void* d_origin_block = nullptr;      // cetkmc_ensemble_origin_begin: every replica's words and census, the map table [R], the run table [R]
+    OriginMap* d_origin_maps = nullptr;  // (inside the block)
+    OriginRun* d_origin_runs = nullptr;
+    std::vector<OriginRun> origin_runs;  // host copy of the run table of the last stepping call
 };
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
 bool shared_params_equal(cetkmc_params a, cetkmc_params b)
@@ -1266,7 +1278,7 @@ void destroy_ens(Ens* e)
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
                     e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_front_part, e->d_front_out,
-                    e->d_layer_part, e->d_layer_out, e->d_layer_eq, e->d_solid_block};
+                    e->d_layer_part, e->d_layer_out, e->d_layer_eq, e->d_solid_block, e->d_origin_block};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1313,8 +1325,30 @@ int cetkmc_struct_size(const char* name)
     SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec); SZ("texture_args", struct cetkmc_texture_args);
     SZ("grain_rec", struct cetkmc_grain_rec);
     SZ("solid_info", struct cetkmc_solid_info); SZ("solid_args", struct cetkmc_solid_args); SZ("solid_rec", struct cetkmc_solid_rec);
+    SZ("origin_rec", struct cetkmc_origin_rec);
 #undef SZ
     return -1;
+}
+
+// ---- origin map: the part the stepping calls use (origin.hpp; its entry points close the file) -------
+constexpr int64_t ORIGIN_SEQ_LIMIT = (int64_t)1 << 36;
+// a call that may absorb up to n ordinals: refused, before it does anything, when the map's clock could reach 2^36
+static int origin_room(const Handle* h, int64_t n, const char* fn)
+{
+    if (h->origin_on && n > 0 && (n >= ORIGIN_SEQ_LIMIT || h->origin_seq + n >= ORIGIN_SEQ_LIMIT))
+        return fail(std::string(fn) + ": the origin map's clock (seq " + std::to_string(h->origin_seq) + ") would reach 2^36");
+    return 0;
+}
+// n records of the device log d_log, `group` of them per ordinal, into the handle's map: one launch on its stream, behind the
+// stepping call's closing event
+static int origin_absorb_log(Handle* h, const cetkmc_event* d_log, int64_t n, int64_t group)
+{
+    if (!h->origin_on || n <= 0) return 0;
+    launch(k_origin_absorb<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nullptr, nullptr, d_log, (long long)n, (long long)group,
+           (long long)h->origin_seq, h->L, h->origin, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    h->origin_seq += n / group;
+    return 0;
 }
 
 // the kernels' own stale-row rule (kernels.hpp), for host-side checks of its footprint
@@ -1657,6 +1691,7 @@ int cetkmc_apply(void* handle, const cetkmc_event* ev, double theta_new, double 
     for (int a = 0; a < 3; ++a) if (ev->pos[a] < 0 || ev->pos[a] >= h->L) return fail("event position out of range");
     if (ev->type == CETKMC_DIFF || ev->type == CETKMC_ATT)
         for (int a = 0; a < 3; ++a) if (ev->target[a] < 0 || ev->target[a] >= h->L) return fail("event target out of range");
+    CHK(origin_room(h, 1, "cetkmc_apply"));
     HIPCHK(hipSetDevice(h->dev));
     cetkmc_event e = *ev;
     if (e.type == CETKMC_DEP || e.type == CETKMC_NUC) { e.theta = theta_new; e.phi = phi_new; }
@@ -1665,6 +1700,11 @@ int cetkmc_apply(void* handle, const cetkmc_event* ev, double theta_new, double 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     invalidate(h, Cause::apply);
+    if (h->origin_on) {      // the event joins the origin map under one ordinal
+        launch(k_origin_absorb_one, dim3(1), dim3(64), 0, h->stream, nullptr, nullptr, e, (long long)h->origin_seq, h->L, h->origin);
+        HIPCHK(hipGetLastError());
+        ++h->origin_seq;
+    }
     return 0;
 }
 
@@ -1958,6 +1998,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     const int64_t n = a->n_steps;
+    CHK(origin_room(h, n, "cetkmc_run_steps"));
     CHK(stage_run(h, a));
     // reset the batch part of the step state (nucleation_count persists): a one-thread kernel, no host round trip
     hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
@@ -1981,6 +2022,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     StepState ss;
     CHK(download_run(h, n, &ss, totals, events, n_events));
     CHK(end_batch(h, ss, a, therm_skip_g));
+    CHK(origin_absorb_log(h, h->d_log_event, ss.cur, 1));      // the executed steps' events join the origin map
     if (h->time_comm) {
         for (size_t q = 0; q + 1 < h->comm_ev_used; q += 2) {
             CHK(add_elapsed(h->comm_ev[q], h->comm_ev[q + 1], &h->cnt.ms_comm));
@@ -2058,6 +2100,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     if (a->thermal_mode == 2 && (n_therm > a->n_q || (n_therm > 0 && !a->q_planes)))
         return fail("thermal_mode 2 needs one q plane per thermal update in the batch");
+    CHK(origin_room(h, n, "cetkmc_run_supersteps"));
     HIPCHK(hipSetDevice(h->dev));
     const size_t L2 = (size_t)h->L * h->L;
     SuperCfg C{};
@@ -2083,12 +2126,13 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     CHK(grow(&h->d_sup_dom, &h->cap_sup_dom, (size_t)NE));
     CHK(grow(&h->d_sup_picks, &h->cap_sup_picks, (size_t)D));
     CHK(grow(&h->d_sup_cnt, &h->cap_sup_cnt, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE));
-    if (events && n > 0) CHK(grow(&h->d_sup_log, &h->cap_sup_log, (size_t)n * D));
+    const bool keep_log = (events || h->origin_on) && n > 0;      // an origin map reads the log on the device
+    if (keep_log) CHK(grow(&h->d_sup_log, &h->cap_sup_log, (size_t)n * D));
     double* const d_rmax = h->d_sup_rmax;
     cetkmc_event* const d_dom = h->d_sup_dom;
     DomPick* const d_picks = h->d_sup_picks;
     unsigned long long* const d_cnt = h->d_sup_cnt;
-    cetkmc_event* const d_log = (events && n > 0) ? h->d_sup_log : nullptr;
+    cetkmc_event* const d_log = keep_log ? h->d_sup_log : nullptr;
     HIPCHK(hipMemsetAsync(d_rmax, 0, (size_t)std::max(C.nranks, 1) * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(d_dom, 0xFF, (size_t)NE * sizeof(cetkmc_event), h->stream));      // type -1: nothing received
     const size_t cnt_bytes = (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE * sizeof(unsigned long long);
@@ -2149,6 +2193,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     HIPCHK(hipMemcpyAsync(&ss, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     CHK(end_batch(h, ss));
+    CHK(origin_absorb_log(h, d_log, ss.cur * D, D));      // every record of super-step t under the ordinal seq + t
     res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = q_idx;
     res->nucleation_count = ss.nuc_count;
     res->wall_ms = 0.0;
@@ -2614,6 +2659,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     Handle* h0 = e->reps[0];
     for (Handle* h : e->reps)          // cetkmc_set_params on a replica must keep the shared fields shared
         if (!shared_params_equal(h0->p, h->p)) return fail(SHARED_PARAMS_MSG);
+    for (Handle* h : e->reps) CHK(origin_room(h, n, "cetkmc_run_ensemble"));
     HIPCHK(hipSetDevice(h0->dev));
     HIPCHK(hipStreamSynchronize(h0->stream));
     hipStream_t st = h0->stream;
@@ -2748,6 +2794,21 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         }
         if (dt && a->rng_mode == 2)
             for (int64_t s = 0; s < done; ++s) dt[(size_t)r * n + s] = superstep_dt_event(a->seed[r], a->step0 + s, tot[(size_t)r * n + s]);
+    }
+    if (e->d_origin_block && h0->origin_on && n > 0) {
+        // every replica's executed steps join its origin map: its log from the replica table, its clock and step count from a
+        // run table pushed once, one launch whatever R
+        e->origin_runs.resize((size_t)R);
+        for (int r = 0; r < R; ++r) {
+            Handle* h = e->reps[(size_t)r];
+            e->origin_runs[(size_t)r] = OriginRun{(long long)h->origin_seq, (long long)ss[(size_t)r].cur};
+            h->origin_seq += ss[(size_t)r].cur;
+        }
+        HIPCHK(hipMemcpyAsync(e->d_origin_runs, e->origin_runs.data(), (size_t)R * sizeof(OriginRun), hipMemcpyHostToDevice, st));
+        const EnsSel osel{e->d_table, 0, 0, 0, nullptr};
+        launch(k_origin_absorb<EnsSel>, dim3((unsigned)((n + 255) / 256), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, nullptr, 0LL, 1LL, 0LL, L,
+               OriginMap{}, (const OriginMap*)e->d_origin_maps, (const OriginRun*)e->d_origin_runs, osel);
+        HIPCHK(hipGetLastError());
     }
     return 0;
 }
@@ -3506,6 +3567,271 @@ int cetkmc_ensemble_solid_profile(void* handle, const struct cetkmc_solid_args* 
     return solid_records(h0, st, (int64_t)R * L, with_grains ? total : 0, with_grains ? total : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
         launch(k_solid_profile<EnsSel>, dim3(solid_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SolidMap{}, (const SolidMap*)e->d_solid_maps, L,
                with_grains ? (const int*)e->d_cc_labels : nullptr, 0, args->qscale[0], args->qscale[1], args->qscale[2], args->qscale[3], d_lay, d_gr, sel);
+    });
+}
+
+// ---- origin map (origin.hpp) --------------------------------------------------------------------
+// One device block for the maps of hs (one handle, or every replica of an ensemble): all words, all censuses, the map table
+// [n] and the run table [n] -- so that begin clears the block with one memset whatever n.
+struct OriginLayout { size_t n, o_census, o_tab, o_runs, bytes; };
+static OriginLayout origin_layout(int L, size_t R)
+{
+    OriginLayout y{};
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    y.n = (size_t)L * L * L;
+    y.o_census = up(R * y.n * 8);
+    y.o_tab = y.o_census + up(R * (size_t)L * 5 * 8);
+    y.o_runs = y.o_tab + up(R * sizeof(OriginMap));
+    y.bytes = y.o_runs + up(R * sizeof(OriginRun));
+    return y;
+}
+static unsigned origin_blocks(int L) { return (unsigned)(((int64_t)L * L * L + ORIGIN_VPB - 1) / ORIGIN_VPB); }
+
+// (re)start the maps of hs in *block (allocated here if null)
+static int origin_begin(std::vector<Handle*>& hs, void** block, OriginMap** d_maps, OriginRun** d_runs, hipStream_t st)
+{
+    Handle* h0 = hs[0];
+    const size_t R = hs.size();
+    const OriginLayout y = origin_layout(h0->L, R);
+    if (!*block) {
+        if (hipMalloc(block, y.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *block = nullptr;
+            return fail("origin map: no device memory for " + std::to_string(y.bytes) + " bytes");
+        }
+    }
+    // no handle has a map until everything below has completed: an error on the way leaves none (a second begin included)
+    for (Handle* h : hs) { h->origin_on = false; h->origin_seq = 0; }
+    char* b = (char*)*block;
+    std::vector<OriginMap> tab(R);
+    for (size_t r = 0; r < R; ++r) {
+        tab[r].words = (unsigned long long*)b + r * y.n;
+        tab[r].census = (long long*)(b + y.o_census) + r * (size_t)h0->L * 5;
+        hs[r]->origin = tab[r];
+    }
+    if (d_maps) *d_maps = (OriginMap*)(b + y.o_tab);
+    if (d_runs) *d_runs = (OriginRun*)(b + y.o_runs);
+    auto issue = [&]() -> int {
+        HIPCHK(hipMemsetAsync(b, 0, y.bytes, st));
+        HIPCHK(hipMemcpyAsync(b + y.o_tab, tab.data(), R * sizeof(OriginMap), hipMemcpyHostToDevice, st));
+        return 0;
+    };
+    const int rc = issue();
+    const hipError_t synced = hipStreamSynchronize(st);         // also after an error: the table is copied from this frame
+    if (rc) return rc;
+    HIPCHK(synced);
+    for (Handle* h : hs) h->origin_on = true;
+    return 0;
+}
+// the single-lattice handle of begin / end, or a refusal
+static int origin_single(const char* fn, Handle* h)
+{
+    const std::string f(fn);
+    if (!h) return fail("null handle");
+    if (h->in_ensemble) return fail(f + " takes a single-lattice handle: an ensemble's maps are kept by cetkmc_ensemble_origin_*");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
+    return 0;
+}
+// the lattice handle (single or replica) of read / census / profile / absorb_events, with a map
+static int origin_lattice(const char* fn, Handle* h)
+{
+    const std::string f(fn);
+    if (!h) return fail("null argument");
+    if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
+    if (!h->origin_on) return fail(f + " needs a map (cetkmc_origin_begin)");
+    return 0;
+}
+
+int cetkmc_origin_begin(void* handle)
+{
+    Handle* h = (Handle*)handle;
+    CHK(origin_single("cetkmc_origin_begin", h));
+    if (h->L > 256) return fail("cetkmc_origin_begin: L > 256 (the profile packs a voxel's linear index into 24 bits)");
+    HIPCHK(hipSetDevice(h->dev));
+    std::vector<Handle*> hs{h};
+    return origin_begin(hs, &h->d_origin_block, nullptr, nullptr, h->stream);
+}
+
+int cetkmc_origin_end(void* handle)
+{
+    Handle* h = (Handle*)handle;
+    CHK(origin_single("cetkmc_origin_end", h));
+    if (!h->d_origin_block) return fail("cetkmc_origin_end needs a map (cetkmc_origin_begin)");      // (a begin that failed half way keeps its block)
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipFree(h->d_origin_block));
+    h->d_origin_block = nullptr; h->origin = OriginMap{}; h->origin_on = false; h->origin_seq = 0;
+    return 0;
+}
+
+int64_t cetkmc_origin_seq(void* handle)
+{
+    Handle* h = (Handle*)handle;
+    return (h && h->origin_on) ? h->origin_seq : -1;
+}
+
+int cetkmc_origin_absorb_events(void* handle, const cetkmc_event* ev, int64_t n, int64_t group)
+{
+    Handle* h = (Handle*)handle;
+    CHK(origin_lattice("cetkmc_origin_absorb_events", h));
+    if (n < 0) return fail("cetkmc_origin_absorb_events: n < 0");
+    if (group < 1) return fail("cetkmc_origin_absorb_events: group must be >= 1");
+    if (n % group) return fail("cetkmc_origin_absorb_events: n must be a multiple of group");
+    if (n > 0 && !ev) return fail("null argument");
+    const int L = h->L;
+    for (int64_t q = 0; q < n; ++q) {
+        const cetkmc_event& r = ev[q];
+        if (r.type < 0 || r.type > 3) continue;
+        for (int c = 0; c < 3; ++c)
+            if (r.pos[c] < 0 || r.pos[c] >= L) return fail("cetkmc_origin_absorb_events: record " + std::to_string(q) + ": position outside the lattice");
+        if (r.type == CETKMC_DIFF && r.target[0] >= 0)
+            for (int c = 0; c < 3; ++c)
+                if (r.target[c] < 0 || r.target[c] >= L) return fail("cetkmc_origin_absorb_events: record " + std::to_string(q) + ": diffusion target outside the lattice");
+    }
+    CHK(origin_room(h, n / group, "cetkmc_origin_absorb_events"));
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->dev));
+    DevTmp<cetkmc_event> d_ev;
+    if (d_ev.alloc((size_t)n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("cetkmc_origin_absorb_events: no device memory for " + std::to_string(n) + " records");
+    }
+    HIPCHK(hipMemcpyAsync(d_ev.p, ev, (size_t)n * sizeof(cetkmc_event), hipMemcpyHostToDevice, h->stream));
+    h->cnt.bytes_h2d += n * (int64_t)sizeof(cetkmc_event);
+    CHK(origin_absorb_log(h, d_ev.p, n, group));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cetkmc_origin_read(void* handle, uint64_t* words)
+{
+    Handle* h = (Handle*)handle;
+    if (!words) return fail("null argument");
+    CHK(origin_lattice("cetkmc_origin_read", h));
+    HIPCHK(hipSetDevice(h->dev));
+    const size_t n = (size_t)h->L * h->L * h->L;
+    HIPCHK(hipMemcpyAsync(words, h->origin.words, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cnt.bytes_d2h += (int64_t)n * 8;
+    return 0;
+}
+
+int cetkmc_origin_census(void* handle, int64_t* out)
+{
+    Handle* h = (Handle*)handle;
+    if (!out) return fail("null argument");
+    CHK(origin_lattice("cetkmc_origin_census", h));
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipMemcpyAsync(out, h->origin.census, (size_t)h->L * 5 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->cnt.bytes_d2h += (int64_t)h->L * 5 * 8;
+    return 0;
+}
+
+// initialise n_lay + n_gr records on the stream, fill them (go = the launch) and copy n_lay layer and n_copy grain records out
+extern "C++" template <class Go>
+static int origin_records(Handle* h, hipStream_t st, int64_t n_lay, int64_t n_gr, int64_t n_copy, struct cetkmc_origin_rec* layers,
+                          struct cetkmc_origin_rec* grains, Go&& go)
+{
+    DevTmp<long long> d_rec;
+    const int64_t words = (n_lay + n_gr) * ORIGIN_NW;
+    if (d_rec.alloc((size_t)words) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("origin profile: no device memory for " + std::to_string(n_lay + n_gr) + " records of " + std::to_string(sizeof(OriginRec)) + " bytes");
+    }
+    launch(k_origin_rec_init, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, st, nullptr, nullptr, d_rec.p, words);
+    CHK(go(d_rec.p, d_rec.p + n_lay * ORIGIN_NW));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(layers, d_rec.p, (size_t)n_lay * sizeof(OriginRec), hipMemcpyDeviceToHost, st));
+    if (n_copy > 0) HIPCHK(hipMemcpyAsync(grains, d_rec.p + n_lay * ORIGIN_NW, (size_t)n_copy * sizeof(OriginRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h->cnt.bytes_d2h += (n_lay + std::max<int64_t>(n_copy, 0)) * (int64_t)sizeof(OriginRec);
+    return 0;
+}
+
+int cetkmc_origin_profile(void* handle, struct cetkmc_origin_rec* layers, int64_t cap, struct cetkmc_origin_rec* grains)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !layers) return fail("null argument");
+    if (ens_of(handle)) return fail("cetkmc_origin_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_origin_profile");
+    CHK(origin_lattice("cetkmc_origin_profile", h));
+    if (grains && h->cc_n_clusters < 0) return fail("cetkmc_origin_profile needs a preceding cetkmc_cluster for its grain records");
+    const int64_t nc = grains ? h->cc_n_clusters : 0, n = std::min<int64_t>(cap, nc);
+    const bool with_grains = grains && n > 0;
+    HIPCHK(hipSetDevice(h->dev));
+    // the device table holds every grain (the pass adds by label); the first n records are the caller's
+    return origin_records(h, h->stream, h->L, with_grains ? nc : 0, with_grains ? n : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
+        launch(k_origin_profile<>, dim3(origin_blocks(h->L)), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), h->origin, nullptr,
+               with_grains ? (const int*)h->d_cc_labels : nullptr, (int)nc, d_lay, d_gr);
+        return 0;
+    });
+}
+
+static int origin_ensemble(const char* fn, void* handle, bool need_map, Ens** out)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+    if (need_map && !(e->d_origin_block && e->reps[0]->origin_on)) return fail(std::string(fn) + " needs the maps (cetkmc_ensemble_origin_begin)");
+    *out = e;
+    return 0;
+}
+
+int cetkmc_ensemble_origin_begin(void* handle)
+{
+    Ens* e = nullptr;
+    CHK(origin_ensemble("cetkmc_ensemble_origin_begin", handle, false, &e));
+    Handle* h0 = e->reps[0];
+    HIPCHK(hipSetDevice(h0->dev));
+    return origin_begin(e->reps, &e->d_origin_block, &e->d_origin_maps, &e->d_origin_runs, h0->stream);
+}
+
+int cetkmc_ensemble_origin_end(void* handle)
+{
+    Ens* e = nullptr;
+    CHK(origin_ensemble("cetkmc_ensemble_origin_end", handle, false, &e));
+    if (!e->d_origin_block) return fail("cetkmc_ensemble_origin_end needs the maps (cetkmc_ensemble_origin_begin)");
+    HIPCHK(hipSetDevice(e->reps[0]->dev));
+    HIPCHK(hipStreamSynchronize(e->reps[0]->stream));
+    HIPCHK(hipFree(e->d_origin_block));
+    e->d_origin_block = nullptr; e->d_origin_maps = nullptr; e->d_origin_runs = nullptr;
+    for (Handle* h : e->reps) { h->origin = OriginMap{}; h->origin_on = false; h->origin_seq = 0; }
+    return 0;
+}
+
+int cetkmc_ensemble_origin_census(void* handle, int64_t* out)
+{
+    Ens* e = nullptr;
+    CHK(origin_ensemble("cetkmc_ensemble_origin_census", handle, true, &e));
+    if (!out) return fail("null argument");
+    Handle* h0 = e->reps[0];
+    HIPCHK(hipSetDevice(h0->dev));
+    const size_t bytes = (size_t)e->R * e->L * 5 * 8;       // replica 0's census heads the block's [R][L][5]
+    HIPCHK(hipMemcpyAsync(out, h0->origin.census, bytes, hipMemcpyDeviceToHost, h0->stream));
+    HIPCHK(hipStreamSynchronize(h0->stream));
+    h0->cnt.bytes_d2h += (int64_t)bytes;
+    return 0;
+}
+
+int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layers, struct cetkmc_origin_rec* grains)
+{
+    Ens* e = nullptr;
+    CHK(origin_ensemble("cetkmc_ensemble_origin_profile", handle, true, &e));
+    if (!layers) return fail("null argument");
+    if (grains && e->an_clusters.empty()) return fail("cetkmc_ensemble_origin_profile needs a preceding cetkmc_ensemble_analyze for its grain records");
+    const int R = e->R, L = e->L;
+    int64_t total = 0;
+    if (grains) for (int r = 0; r < R; ++r) total += e->an_clusters[(size_t)r];
+    const bool with_grains = grains && total > 0;
+    Handle* h0 = e->reps[0];
+    hipStream_t st = h0->stream;
+    HIPCHK(hipSetDevice(h0->dev));
+    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
+    return origin_records(h0, st, (int64_t)R * L, with_grains ? total : 0, with_grains ? total : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
+        CHK(ens_push_views(e));      // the pass reads every replica's state through its current view
+        launch(k_origin_profile<EnsSel>, dim3(origin_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, OriginMap{},
+               (const OriginMap*)e->d_origin_maps, with_grains ? (const int*)e->d_cc_labels : nullptr, 0, d_lay, d_gr, sel);
+        return 0;
     });
 }
 

@@ -16,13 +16,15 @@
 // k_solid_profile: a stream over the dense map and the label volume of the last clustering.  A block owns SOLID_VPB
 // consecutive voxels in row-major order.  Every recorded voxel contributes one vector of ten 64-bit integers in the word
 // order of cetkmc_solid_rec (sums, a minimum and a maximum) to the record of its plane and, with a label, to the record of
-// its grain.  Both reductions are by a run-time key and use the scheme of grain.hpp with 64-bit counters: a wave-leader loop
+// its grain.  Both reductions are by a run-time key and use the scheme of grain.hpp with 64-bit counters (keyed.hpp, shared
+// with origin.hpp): a wave-leader loop
 // over the distinct keys of a wave (butterfly over the lanes that hold the key), a direct-mapped slot table in LDS claimed
 // with a compare-and-swap, and once per block integer atomics (add / min / max) into the records, which the host initialises
 // on the stream before the launch.  Integer arithmetic only behind the quantisation: every order gives the same bits.
 #pragma once
 #include "voxel.hpp"
 #include "kernels.hpp"
+#include "keyed.hpp"
 
 namespace cetkmc {
 
@@ -40,8 +42,8 @@ constexpr int SOLID_UP = 4, SOLID_PPB = 256 * SOLID_UP;     // pairs per thread 
 constexpr int SOLID_NV = 8, SOLID_VPB = 256 * SOLID_NV;     // chunks / voxels of a profile block
 constexpr int SOLID_NW = 10;                                // int64 words of a record
 constexpr int SOLID_WMIN = 4, SOLID_WMAX = 5;               // the words that are a minimum / a maximum; all others are sums
-constexpr int SOLID_PSLOTS = 16, SOLID_GSLOTS = 128, SOLID_ROUNDS = 4;
-constexpr long long SOLID_NONE_MIN = 0x7fffffffffffffffLL, SOLID_NONE_MAX = -1;
+constexpr int SOLID_PSLOTS = 16, SOLID_GSLOTS = 128;
+constexpr long long SOLID_NONE_MIN = KEYED_NONE_MIN, SOLID_NONE_MAX = KEYED_NONE_MAX;
 using SolidRec = struct ::cetkmc_solid_rec;
 static_assert(sizeof(SolidRec) == SOLID_NW * 8, "cetkmc_solid_rec is 10 int64 words");
 static_assert(offsetof(SolidRec, stamp_min) == SOLID_WMIN * 8 && offsetof(SolidRec, stamp_max) == SOLID_WMAX * 8, "word order of cetkmc_solid_rec");
@@ -162,62 +164,12 @@ __global__ __launch_bounds__(256) void k_solid_rec_init(long long* rec, int64_t 
     }
 }
 
-// word w of a record (+ / min / max)= x; the neutral element is skipped
-__device__ __forceinline__ void solid_word(long long* p, int w, long long x)
-{
-    if (w == SOLID_WMIN) { if (x != SOLID_NONE_MIN) atomicMin(p, x); }
-    else if (w == SOLID_WMAX) { if (x != SOLID_NONE_MAX) atomicMax(p, x); }
-    else if (x != 0) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)x);
-}
-__device__ __forceinline__ long long solid_join(int w, long long a, long long b)
-{
-    return w == SOLID_WMIN ? (b < a ? b : a) : w == SOLID_WMAX ? (b > a ? b : a) : (long long)((unsigned long long)a + (unsigned long long)b);
-}
-__device__ __forceinline__ long long solid_neutral(int w) { return w == SOLID_WMIN ? SOLID_NONE_MIN : w == SOLID_WMAX ? SOLID_NONE_MAX : 0; }
-
-// Key key (>= 1) of the lanes with `part` set gets their vectors c: record key - 1 of `out`, through the block's slot table
-// (tag / tab, SLOTS entries) where the key owns or claims its slot.  Wave uniform: every lane of the wave calls it.
-template <int SLOTS>
-__device__ __forceinline__ void solid_reduce(bool part, int key, const long long (&c)[SOLID_NW], unsigned* tag, long long* tab, long long* out, int lane)
-{
-    auto put = [&](int kq, int w, long long x) {         // one word of key kq
-        const unsigned old = atomicCAS(&tag[kq & (SLOTS - 1)], 0u, (unsigned)kq);
-        long long* p = (old == 0u || old == (unsigned)kq) ? tab + (kq & (SLOTS - 1)) * SOLID_NW + w : out + (int64_t)(kq - 1) * SOLID_NW + w;
-        solid_word(p, w, x);
-    };
-    unsigned long long todo = __ballot(part);
-#pragma unroll 1
-    for (int round = 0; todo != 0; ++round) {            // wave uniform
-        if (round == SOLID_ROUNDS) {
-            if ((todo >> lane) & 1ull) {
-#pragma unroll
-                for (int w = 0; w < SOLID_NW; ++w) put(key, w, c[w]);
-            }
-            break;
-        }
-        const int lead = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-        const int kq = __builtin_amdgcn_readlane(key, lead);
-        const bool mine = part && key == kq;
-        const unsigned long long m = __ballot(mine);
-        todo &= ~m;
-        if (__popcll(m) == 1) {
-            if (mine) {
-#pragma unroll
-                for (int w = 0; w < SOLID_NW; ++w) put(key, w, c[w]);
-            }
-            continue;
-        }
-        long long sel = 0;                               // lane w < 10: word w joined over the lanes of kq
-#pragma unroll
-        for (int w = 0; w < SOLID_NW; ++w) {
-            long long x = mine ? c[w] : solid_neutral(w);
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) x = solid_join(w, x, __shfl_xor(x, d));
-            if (lane == w) sel = x;
-        }
-        if (lane < SOLID_NW) put(kq, lane, sel);
-    }
-}
+// the record's words for the shared keyed reduction (keyed.hpp): sums but for one minimum and one maximum
+struct SolidWords {
+    static constexpr int NW = SOLID_NW;
+    __device__ static constexpr bool is_min(int w) { return w == SOLID_WMIN; }
+    __device__ static constexpr bool is_max(int w) { return w == SOLID_WMAX; }
+};
 
 // layers[i] and grains[id - 1] get the records of the map M.  grid: x = blocks of SOLID_VPB voxels, y = replica (variadic
 // trailing EnsSel: map from the device table, labels at r * stride, layers at r * L, the replica's grain records at entry
@@ -241,8 +193,8 @@ __global__ __launch_bounds__(256) void k_solid_profile(SolidMap M, const SolidMa
     const int tid = threadIdx.x, lane = tid & 63;
     for (int q = tid; q < SOLID_PSLOTS; q += 256) ptag[q] = 0;
     for (int q = tid; q < SOLID_GSLOTS; q += 256) gtag[q] = 0;
-    for (int q = tid; q < SOLID_PSLOTS * SOLID_NW; q += 256) ptab[q] = solid_neutral(q % SOLID_NW);
-    for (int q = tid; q < SOLID_GSLOTS * SOLID_NW; q += 256) gtab[q] = solid_neutral(q % SOLID_NW);
+    for (int q = tid; q < SOLID_PSLOTS * SOLID_NW; q += 256) ptab[q] = keyed_neutral<SolidWords>(q % SOLID_NW);
+    for (int q = tid; q < SOLID_GSLOTS * SOLID_NW; q += 256) gtab[q] = keyed_neutral<SolidWords>(q % SOLID_NW);
     __syncthreads();
     const double lim = 274877906944.0;                    // 2^38
     const int64_t v0 = (int64_t)blockIdx.x * SOLID_VPB;
@@ -255,7 +207,7 @@ __global__ __launch_bounds__(256) void k_solid_profile(SolidMap M, const SolidMa
         if (__ballot(rec) == 0) continue;                 // wave uniform: nothing recorded among these 64 voxels
         long long c[SOLID_NW];
 #pragma unroll
-        for (int w = 0; w < SOLID_NW; ++w) c[w] = solid_neutral(w);
+        for (int w = 0; w < SOLID_NW; ++w) c[w] = keyed_neutral<SolidWords>(w);
         int g = 0;
         if (rec) {
             const double gi = M.g[3 * v], gj = M.g[3 * v + 1], gk = M.g[3 * v + 2], cool = M.cool[v], Ts = M.Ts[v];
@@ -271,17 +223,17 @@ __global__ __launch_bounds__(256) void k_solid_profile(SolidMap M, const SolidMa
             }
             if (labels) { g = labels[v]; if (g < 0 || g > n) g = 0; }
         }
-        solid_reduce<SOLID_PSLOTS>(rec, rec ? (int)(v / LL) + 1 : 0, c, ptag, ptab, layers, lane);
-        if (labels && __ballot(g > 0) != 0) solid_reduce<SOLID_GSLOTS>(g > 0, g, c, gtag, gtab, grains, lane);
+        keyed_reduce<SolidWords, SOLID_PSLOTS>(rec, rec ? (int)(v / LL) + 1 : 0, c, ptag, ptab, layers, lane);
+        if (labels && __ballot(g > 0) != 0) keyed_reduce<SolidWords, SOLID_GSLOTS>(g > 0, g, c, gtag, gtab, grains, lane);
     }
     __syncthreads();
     for (int q = tid; q < SOLID_PSLOTS * SOLID_NW; q += 256) {
         const unsigned key = ptag[q / SOLID_NW];
-        if (key != 0) solid_word(layers + (int64_t)(key - 1) * SOLID_NW + q % SOLID_NW, q % SOLID_NW, ptab[q]);
+        if (key != 0) keyed_word<SolidWords>(layers + (int64_t)(key - 1) * SOLID_NW + q % SOLID_NW, q % SOLID_NW, ptab[q]);
     }
     for (int q = tid; q < SOLID_GSLOTS * SOLID_NW; q += 256) {
         const unsigned key = gtag[q / SOLID_NW];
-        if (key != 0) solid_word(grains + (int64_t)(key - 1) * SOLID_NW + q % SOLID_NW, q % SOLID_NW, gtab[q]);
+        if (key != 0) keyed_word<SolidWords>(grains + (int64_t)(key - 1) * SOLID_NW + q % SOLID_NW, q % SOLID_NW, gtab[q]);
     }
 }
 

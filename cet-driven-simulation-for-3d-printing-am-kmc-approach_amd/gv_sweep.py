@@ -9,7 +9,7 @@ collects the CET classification of the last metrics row of every run into ``outp
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
                        [--mode B --box 8] [--seeds K] [--ensemble [--rng counter]]
                        [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]] [--front] [--layers] [--texture]
-                       [--grains] [--solid]
+                       [--grains] [--solid] [--origin]
 
 ``--seeds K`` runs every point with the seeds RANDOM_SEED .. RANDOM_SEED + K - 1 (one gv_map.csv row per point and seed, with
 a ``seed`` column when K > 1); ``--ensemble`` runs all of them as one replica ensemble (run_kmc_ensemble): with the default
@@ -44,6 +44,12 @@ the grain columns, every run directory a grains.csv, and gv_map.csv the columns 
 solidification columns, every run directory a solid_layers.csv (with ``--grains`` a solid_grains.csv), and gv_map.csv the
 columns ``G_solid_K_per_m``, ``V_solid_m_per_s`` and ``G_over_V_solid`` -- gradient and isotherm velocity at the voxels WHEN
 THEY FROZE -- from each run's last row (behind the grain columns).  Without the flag the files are what they were.
+
+``--origin`` keeps an origin map of every run on the device (run_kmc's ``origin_metrics``): every metrics.csv gains the origin
+columns, every run directory an origin_layers.csv (with ``--grains`` an origin_grains.csv), and gv_map.csv the columns
+``Nucleated_grain_volume_frac`` and ``Nucleated_voxel_frac`` -- the share of the grain volume, and of the filled voxels, that
+came from nucleation events -- from each run's last row (behind the solidification columns).  Without the flag the files are
+what they were.
 """
 import argparse
 import os
@@ -78,7 +84,7 @@ def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_p
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
              laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, texture=False,
-             grains=False, solid=False, **run_kw):
+             grains=False, solid=False, origin=False, **run_kw):
     """``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
     engine (same metrics.csv columns; n_steps stays the number of executed events).  ``seeds=K`` runs every point with the
     seeds RANDOM_SEED .. RANDOM_SEED + K - 1; ``ensemble=True`` runs all runs of the map as one replica ensemble.
@@ -90,7 +96,9 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
     gv_map.csv gains ``GB_low_angle_frac`` and ``Pole_aligned_frac`` of each run's last row behind those.  ``grains=True``:
     every run with ``grain_metrics=True``; gv_map.csv gains ``Columnar_vol_frac`` and ``Grain_elong_mean`` of each run's last
     row behind those.  ``solid=True``: every run with ``solid_metrics=True``; gv_map.csv gains ``G_solid_K_per_m``,
-    ``V_solid_m_per_s`` and ``G_over_V_solid`` (inf when V is 0) of each run's last row behind those."""
+    ``V_solid_m_per_s`` and ``G_over_V_solid`` (inf when V is 0) of each run's last row behind those.  ``origin=True``: every
+    run with ``origin_metrics=True``; gv_map.csv gains ``Nucleated_grain_volume_frac`` and ``Nucleated_voxel_frac`` of each
+    run's last row behind those."""
     check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers, scan_speeds)
     seeds = int(seeds)
     beams = [(p, v) for p in laser_powers for v in scan_speeds] if laser_powers else [None]
@@ -108,7 +116,7 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
            for T_sub, nu_dep, seed, prefix, beam in runs]
     opt = dict(**({"front_metrics": True} if front else {}), **({"layer_metrics": True} if layers else {}),
                **({"texture_metrics": True} if texture else {}), **({"grain_metrics": True} if grains else {}),
-               **({"solid_metrics": True} if solid else {}))
+               **({"solid_metrics": True} if solid else {}), **({"origin_metrics": True} if origin else {}))
     if ensemble:
         run_kmc_ensemble(cfg, L, n_steps, rng=rng, **opt)
     else:
@@ -140,6 +148,9 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
         if solid:
             Gs, Vs = float(last["G_solid"]), float(last["V_solid"])
             row.update({"G_solid_K_per_m": Gs, "V_solid_m_per_s": Vs, "G_over_V_solid": Gs / Vs if Vs != 0.0 else float("inf")})
+        if origin:
+            row.update({"Nucleated_grain_volume_frac": float(last["Nucleated_grain_volume_frac"]),
+                        "Nucleated_voxel_frac": float(last["Nucleated_voxel_frac"])})
         rows.append(row)
     os.makedirs(out_dir, exist_ok=True)
     df = pd.DataFrame(rows)
@@ -175,8 +186,10 @@ if __name__ == "__main__":
                     help="per-grain table on the device: grain columns in every metrics.csv, grains.csv, gv_map.csv")
     ap.add_argument("--solid", action="store_true",
                     help="solidification map on the device: G and V at freezing in every metrics.csv, solid_layers.csv, gv_map.csv")
+    ap.add_argument("--origin", action="store_true",
+                    help="origin map on the device: origin columns in every metrics.csv, origin_layers.csv, gv_map.csv")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
-                   layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, **kw).to_string(index=False))
+                   layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, origin=a.origin, **kw).to_string(index=False))

@@ -35,7 +35,8 @@ from metrics import (compute_CET, compute_metrics, compute_metrics_device, compu
                      layer_metrics as _layer_metrics, texture_metrics as _texture_metrics,
                      write_layers_csv as _write_layers_csv, write_texture_csv as _write_texture_csv,
                      grain_metrics as _grain_metrics, write_grains_csv as _write_grains_csv,
-                     solid_metrics as _solid_metrics, write_solid_csv as _write_solid_csv)
+                     solid_metrics as _solid_metrics, write_solid_csv as _write_solid_csv,
+                     origin_metrics as _origin_metrics, write_origin_csv as _write_origin_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
 from thermal_solver import laser_scan_planes
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
@@ -230,6 +231,20 @@ def _add_solid_columns(row, profile, scales, remelted, clusters):
     return planes, grains
 
 
+def _add_origin_columns(row, profile, census):
+    """origin_metrics=True: the origin columns (metrics.ORIGIN_COLUMNS) behind every other column of ``row``, in place;
+    returns the per-plane table of the row (rows of origin_layers.csv) and the per-grain one (origin_grains.csv) or None."""
+    m = _origin_metrics(profile, census, row["Step"])
+    planes, grains = m.pop("planes"), m.pop("grains", None)
+    row.update(m)
+    return planes, grains
+
+
+def _check_origin(origin_metrics, checkpointing):
+    if origin_metrics and checkpointing:
+        raise ValueError("origin_metrics cannot be combined with checkpoint_every / resume_from (a checkpoint does not carry the map)")
+
+
 def _check_solid(solid_metrics, solid_every, checkpointing):
     if not solid_metrics:
         return
@@ -317,6 +332,7 @@ def run_kmc(
     grain_metrics: bool = False,
     solid_metrics: bool = False,
     solid_every: int = 20,
+    origin_metrics: bool = False,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -396,9 +412,22 @@ def run_kmc(
     cetkmc.engine.default_solid_scales(); ``outputs/<prefix>/solid_layers.csv`` gets one row per plane and metrics row and,
     with ``grain_metrics=True``, ``solid_grains.csv`` one row per grain of the last row (thermal history beside the grain's
     size and bounding-box aspect).  Refused with ValueError: ``solid_every`` not a positive multiple of 20; together with
-    ``checkpoint_every`` / ``resume_from`` (a checkpoint does not carry the map)."""
+    ``checkpoint_every`` / ``resume_from`` (a checkpoint does not carry the map).
+
+    ``origin_metrics=True`` (both modes, with and without ``laser``): the device keeps an origin map (cetkmc_origin_*,
+    DESIGN.md section 22) -- per voxel how it was last filled (deposition, nucleation, attachment to an existing grain, a
+    diffusion hop) and at which executed step (Mode A) or super-step (Mode B), folded on the device from the event log every
+    stepping call writes there anyway; the stepping itself is unchanged.  The map begins after the initial upload (the
+    initial lattice is unrecorded substrate).  Every metrics row gains, behind every other column, the columns of
+    metrics.origin_metrics (voxels by origin, grains by the origin of their earliest voxel, the volume fraction of the
+    nucleation-born grains, the nucleation events and their mean height), reduced on the device by cetkmc_origin_profile;
+    ``outputs/<prefix>/origin_layers.csv`` gets one row per plane and metrics row and, with ``grain_metrics=True``,
+    ``origin_grains.csv`` one row per grain of the last row (the grain records themselves always come from the row's own
+    clustering).  Refused with ValueError together with ``checkpoint_every`` /
+    ``resume_from`` (a checkpoint does not carry the map)."""
     import cetkmc
     _check_solid(solid_metrics, solid_every, bool(checkpoint_every or resume_from))
+    _check_origin(origin_metrics, bool(checkpoint_every or resume_from))
     if mode not in ("A", "B"):
         raise ValueError("mode must be 'A' (exact, one event per sweep) or 'B' (super-steps)")
     if laser is not None:
@@ -454,6 +483,9 @@ def run_kmc(
     solid_scales = cetkmc.engine.default_solid_scales()
     if solid_metrics:
         engine.solid_begin()
+    origin_planes, origin_grain_rows = [], None
+    if origin_metrics:
+        engine.origin_begin()
 
     def solid_update(stamp, thermal_now):
         """the map update at ``stamp`` executed steps, ``thermal_now`` temperature updates issued so far"""
@@ -466,7 +498,7 @@ def run_kmc(
     def metrics_row(step, refresh_defects):
         """kmc_simulation.py:335-389 for the lattice as it stands after event index `step` -- WITHOUT moving the lattice: the
         defect mask is refreshed from the carbon sites only, grains are clustered and species counted on the GPU."""
-        nonlocal n_flagged, cet_detected, layer_planes, texture_planes, grain_rows, solid_grain_rows
+        nonlocal n_flagged, cet_detected, layer_planes, texture_planes, grain_rows, solid_grain_rows, origin_grain_rows
         if refresh_defects:
             n_flagged, _ = refresh_defects_device(engine)       # kmc_simulation.py:335-338
         cl = engine.clusters(0.5, labels=True)
@@ -485,6 +517,11 @@ def run_kmc(
             planes, solid_grain_rows = _add_solid_columns(
                 row, engine.solid_profile(solid_scales, grains=grain_metrics, recluster=False), solid_scales, solid["remelted"], cl)
             solid_planes.append(planes)
+        if origin_metrics:
+            # grain records from the row's own clustering (the grain columns need them); their table only with grain_metrics
+            planes, g_rows = _add_origin_columns(row, engine.origin_profile(grains=True, recluster=False), engine.origin_census())
+            origin_grain_rows = g_rows if grain_metrics else None
+            origin_planes.append(planes)
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -594,6 +631,10 @@ def run_kmc(
         _write_solid_csv(os.path.join(output_dir, "solid_layers.csv"), solid_planes)
     if solid_grain_rows is not None:
         _write_solid_csv(os.path.join(output_dir, "solid_grains.csv"), [solid_grain_rows])
+    if origin_planes:
+        _write_origin_csv(os.path.join(output_dir, "origin_layers.csv"), origin_planes)
+    if origin_grain_rows is not None:
+        _write_origin_csv(os.path.join(output_dir, "origin_grains.csv"), [origin_grain_rows])
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -693,7 +734,7 @@ def _replica_prefix(cfg, L):
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
                      front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False, solid_metrics=False,
-                     solid_every=20):
+                     solid_every=20, origin_metrics=False):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -715,7 +756,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     cetkmc_ensemble_grain_table call per metrics row on the row's own analysis.
     ``solid_metrics=True`` / ``solid_every``: run_kmc's options of that name (columns, ``solid_layers.csv`` and, with
     ``grain_metrics``, ``solid_grains.csv`` of every replica), from ONE batched cetkmc_ensemble_solid_update per multiple of
-    ``solid_every`` steps and ONE batched cetkmc_ensemble_solid_profile per metrics row."""
+    ``solid_every`` steps and ONE batched cetkmc_ensemble_solid_profile per metrics row.
+    ``origin_metrics=True``: run_kmc's option of that name (columns, ``origin_layers.csv`` and, with ``grain_metrics``,
+    ``origin_grains.csv`` of every replica): every cetkmc_run_ensemble call folds the replicas' executed events into their
+    origin maps in one launch, and every metrics row takes ONE batched cetkmc_ensemble_origin_profile and census."""
     import cetkmc
     _check_solid(solid_metrics, solid_every, False)
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
@@ -757,6 +801,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         solid_scales = cetkmc.engine.default_solid_scales()
         if solid_metrics:
             ens.solid_begin()
+        origin_planes = [[] for _ in range(R)]
+        origin_grain_rows = [None] * R
+        if origin_metrics:
+            ens.origin_begin()
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -845,6 +893,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             tp = ens.texture_profile(recluster=False) if texture_metrics else None
             gt = ens.grain_table(recluster=False) if grain_metrics else None
             sp = ens.solid_profile(solid_scales, grains=grain_metrics, recluster=False) if solid_metrics else None
+            op = ens.origin_profile(grains=True, recluster=False) if origin_metrics else None
+            oc = ens.origin_census() if origin_metrics else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -866,6 +916,11 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                     prof = dict(layers={k: v[r] for k, v in sp["layers"].items()}, grains=sp["grains"][r] if sp["grains"] is not None else None)
                     planes, solid_grain_rows[r] = _add_solid_columns(row, prof, solid_scales, int(remelted[r]), an[r]["clusters"])
                     solid_planes[r].append(planes)
+                if op is not None:
+                    prof = dict(layers={k: v[r] for k, v in op["layers"].items()}, grains=op["grains"][r] if op["grains"] is not None else None)
+                    planes, g_rows = _add_origin_columns(row, prof, oc[r])
+                    origin_grain_rows[r] = g_rows if grain_metrics else None
+                    origin_planes[r].append(planes)
                 metrics[r].append(row)
             next_step = stop + 1
 
@@ -884,6 +939,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 _write_solid_csv(os.path.join(f"outputs/{c['output_prefix']}", "solid_layers.csv"), solid_planes[r])
             if solid_grain_rows[r] is not None:
                 _write_solid_csv(os.path.join(f"outputs/{c['output_prefix']}", "solid_grains.csv"), [solid_grain_rows[r]])
+            if origin_planes[r]:
+                _write_origin_csv(os.path.join(f"outputs/{c['output_prefix']}", "origin_layers.csv"), origin_planes[r])
+            if origin_grain_rows[r] is not None:
+                _write_origin_csv(os.path.join(f"outputs/{c['output_prefix']}", "origin_grains.csv"), [origin_grain_rows[r]])
             fields = ens.replica(r).download()
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))

@@ -12,6 +12,7 @@ outside the accelerated path and are not part of this package.
     python main.py --texture                      # texture columns in every metrics.csv and a texture.csv per level (run_kmc texture_metrics)
     python main.py --grains                       # grain columns in every metrics.csv and a grains.csv per level (run_kmc grain_metrics)
     python main.py --solid                        # solidification columns in every metrics.csv and a solid_layers.csv per level (run_kmc solid_metrics)
+    python main.py --origin                       # origin columns in every metrics.csv and an origin_layers.csv per level (run_kmc origin_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
 every level like ``--mode B --box L`` with the super-step thermal cadence.
@@ -48,7 +49,7 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
-         layers=False, texture=False, grains=False, solid=False, **run_kw):
+         layers=False, texture=False, grains=False, solid=False, origin=False, **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
@@ -63,6 +64,8 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
         fm["grain_metrics"] = True
     if solid:                                         # --solid: solidification columns, solid_layers.csv (run_kmc solid_metrics)
         fm["solid_metrics"] = True
+    if origin:                                        # --origin: origin columns, origin_layers.csv (run_kmc origin_metrics)
+        fm["origin_metrics"] = True
     if ensemble:                  # every level in one replica ensemble; the per-level epilogue below reads its results
         for c in carbon_levels:
             prefix = f"impurity_c_{int(c * 100)}"
@@ -133,6 +136,9 @@ if __name__ == "__main__":
     ap.add_argument("--solid", action="store_true",
                     help="solidification map on the device: G, cooling rate and V at freezing in every metrics.csv, solid_layers.csv "
                          "(with --grains: solid_grains.csv)")
+    ap.add_argument("--origin", action="store_true",
+                    help="origin map on the device: voxels and grains by how they were filled (deposition, nucleation, attachment, "
+                         "hop) in every metrics.csv, origin_layers.csv (with --grains: origin_grains.csv)")
     a = ap.parse_args()
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
-         grains=a.grains, solid=a.solid, **(dict(mode="B", box=a.box) if a.mode == "B" else {}))
+         grains=a.grains, solid=a.solid, origin=a.origin, **(dict(mode="B", box=a.box) if a.mode == "B" else {}))

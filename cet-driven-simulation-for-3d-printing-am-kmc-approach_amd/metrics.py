@@ -465,6 +465,86 @@ def write_solid_csv(path, tables):
                 w.writerow([t[n][i].item() for n in names])
 
 
+ORIGIN_COLUMNS = ("Origin_dep", "Origin_nuc", "Origin_att", "Origin_hop", "Origin_unrecorded", "Nucleated_voxel_frac",
+                  "Grains_born_nuc", "Grains_born_dep", "Grains_born_att", "Grains_born_hop", "Grains_substrate",
+                  "Nucleated_grain_volume_frac", "Nuc_events", "Nuc_events_mean_i")
+ORIGIN_CODE_NAMES = ("dep", "nuc", "att", "hop")      # fill codes 1..4 of an origin word
+
+
+def origin_metrics(profile, census, step=0):
+    """Columns of a metrics row (ORIGIN_COLUMNS) from one lattice's origin profile (Engine.origin_profile, or entry r of
+    Ensemble.origin_profile: dict(layers=..., grains=... or None)) and its census (L, 5), plus the per-plane table under
+    "planes" (rows of origin_layers.csv, tagged with ``step``) and, when the profile has grain records, the per-grain table
+    under "grains" (rows of origin_grains.csv).
+
+    Origin_dep / _nuc / _att / _hop: occupied voxels whose last recorded event was a deposition, a nucleation, an attachment
+    to an existing grain, the arrival of a diffusing atom; Origin_unrecorded: occupied voxels without such a record
+    (substrate, uploads).  Nucleated_voxel_frac: nuc over the four fill counts (0.0 when there are none).  A grain is born
+    where its earliest recorded voxel was filled (the code inside ``birth``): Grains_born_nuc / _dep / _att / _hop count
+    the grains all of whose voxels are recorded (n_unrec == 0) by that code, Grains_substrate those with n_unrec > 0.
+    Nucleated_grain_volume_frac: the volume (n_occ) of the nucleation-born grains over all labelled volume -- the equiaxed
+    fraction read from provenance instead of a bounding box (0.0 without grains).  Nuc_events: nucleation events absorbed
+    since the map began, overwritten ones included; Nuc_events_mean_i: their mean build-plane index (0.0 when none)."""
+    lay = profile["layers"]
+    n_by = np.asarray(lay["n_by"], dtype=np.int64).reshape(-1, 4)
+    by = n_by.sum(axis=0)
+    filled = int(by.sum())
+    cen = np.asarray(census, dtype=np.int64).reshape(-1, 5)
+    nuc_ev = int(cen[:, 2].sum())
+    out = {"Origin_dep": int(by[0]), "Origin_nuc": int(by[1]), "Origin_att": int(by[2]), "Origin_hop": int(by[3]),
+           "Origin_unrecorded": int(np.asarray(lay["n_unrec"], dtype=np.int64).sum()),
+           "Nucleated_voxel_frac": (float(by[1]) / filled) if filled else 0.0}
+    born = {c: 0 for c in ORIGIN_CODE_NAMES}
+    substrate, vol_nuc, vol_all = 0, 0, 0
+    gr = profile.get("grains")
+    if gr is not None:
+        g_occ = np.asarray(gr["n_occ"], dtype=np.int64).reshape(-1)
+        g_unrec = np.asarray(gr["n_unrec"], dtype=np.int64).reshape(-1)
+        g_code = (np.asarray(gr["birth"], dtype=np.int64).reshape(-1) >> 24) & 7
+        whole = g_unrec == 0
+        for c, name in enumerate(ORIGIN_CODE_NAMES, start=1):
+            born[name] = int(np.count_nonzero(whole & (g_occ > 0) & (g_code == c)))
+        substrate = int(np.count_nonzero(g_unrec > 0))
+        vol_all = int(g_occ.sum())
+        vol_nuc = int(g_occ[whole & (g_occ > 0) & (g_code == 2)].sum())
+    out.update({"Grains_born_nuc": born["nuc"], "Grains_born_dep": born["dep"], "Grains_born_att": born["att"],
+                "Grains_born_hop": born["hop"], "Grains_substrate": substrate,
+                "Nucleated_grain_volume_frac": (float(vol_nuc) / vol_all) if vol_all else 0.0,
+                "Nuc_events": nuc_ev,
+                "Nuc_events_mean_i": (float((cen[:, 2] * np.arange(len(cen), dtype=np.int64)).sum()) / nuc_ev) if nuc_ev else 0.0})
+
+    def table(rec):
+        n_occ = np.asarray(rec["n_occ"], dtype=np.int64).reshape(-1)
+        nb = np.asarray(rec["n_by"], dtype=np.int64).reshape(-1, 4)
+        nf = nb.sum(axis=1)
+        birth = np.asarray(rec["birth"], dtype=np.int64).reshape(-1)
+        t = {"n_occ": n_occ, "n_dep": nb[:, 0].copy(), "n_nuc": nb[:, 1].copy(), "n_att": nb[:, 2].copy(), "n_hop": nb[:, 3].copy(),
+             "n_unrec": np.asarray(rec["n_unrec"], dtype=np.int64).reshape(-1),
+             "n_left": np.asarray(rec["n_left"], dtype=np.int64).reshape(-1),
+             "ord_first": np.where(nf > 0, np.asarray(rec["ord_min"], dtype=np.int64).reshape(-1), -1),
+             "ord_last": np.asarray(rec["ord_max"], dtype=np.int64).reshape(-1),
+             "ord_mean": np.where(nf > 0, np.asarray(rec["ord_sum"], dtype=np.int64).reshape(-1) / np.maximum(nf, 1), -1.0),
+             "birth_code": np.where(nf > 0, (birth >> 24) & 7, 0), "birth_voxel": np.where(nf > 0, birth & ((1 << 24) - 1), -1)}
+        return t
+
+    planes = {"Step": np.full(len(n_by), int(step), np.int64), "plane": np.arange(len(n_by), dtype=np.int64)}
+    planes.update(table(lay))
+    planes.update({"ev_dep": cen[:, 0].copy(), "ev_diff_out": cen[:, 1].copy(), "ev_nuc": cen[:, 2].copy(), "ev_att": cen[:, 3].copy(),
+                   "ev_diff_in": cen[:, 4].copy()})
+    out["planes"] = planes
+    if gr is not None:
+        grains = {"id": np.arange(1, len(np.asarray(gr["n_occ"]).reshape(-1)) + 1, dtype=np.int64)}
+        grains.update(table(gr))
+        out["grains"] = grains
+    return out
+
+
+def write_origin_csv(path, tables):
+    """origin_layers.csv / origin_grains.csv: the tables of :func:`origin_metrics` ("planes": one per metrics row, written
+    one below the other; "grains": the last row's) as a CSV."""
+    write_solid_csv(path, tables)
+
+
 def front_velocity(row, prev, voxel_size=VOXEL_SIZE):
     """V_front of a metrics row: (Front_i - the previous row's) * voxel_size / (Time - the previous row's) in m/s; 0.0 on
     the first row (``prev`` None), when the time difference is 0 or when either row has no front."""

@@ -198,7 +198,7 @@ int cetkmc_abi_version(void);
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
- * "solid_info", "solid_args", "solid_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "solid_info", "solid_args", "solid_rec", "origin_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -410,7 +410,8 @@ int cetkmc_comm_selftest(void* handle, int64_t bytes, double* times_us);
  * per-lattice calls; cetkmc_destroy on it releases the whole ensemble.
  * cetkmc_ensemble_replica: the handle of replica r, accepted by every per-lattice call (upload, download, set_defects,
  * set_prev_state, thermal_cet, thermal_laser, rate_sweep, species_counts, gather_species, set_defects_sparse, nucleation_count, cluster*,
- * front_stats, layer_profile, grain_table, solid_read, solid_profile) except the
+ * front_stats, layer_profile, grain_table, solid_read, solid_profile, origin_read, origin_census, origin_seq, origin_profile,
+ * origin_absorb_events) except the
  * stepping calls (run_steps, run_supersteps, stage_inputs refuse it); it belongs to the ensemble (cetkmc_destroy refuses
  * it).  A single-lattice handle is refused.  Uploading a new lattice (state) into a frozen replica unfreezes it.
  * R is bounded by the grid (R * ceil(L / 4) <= 65535) and by the free device memory at creation.
@@ -674,6 +675,84 @@ int cetkmc_ensemble_solid_end(void* handle);
 int cetkmc_ensemble_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info);
 int cetkmc_ensemble_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers,
                                   struct cetkmc_solid_rec* grains);
+
+/* Origin map (not in the reference): HOW and WHEN each voxel was last filled -- by deposition,
+ * nucleation, attachment to an existing grain or a diffusion hop -- kept on the device and fed from the event log every
+ * stepping call already writes there, and a profile call that reduces it per build plane and per grain.
+ * Map: per voxel of the (L, L, L) lattice (row-major, axis 0 = build direction) one uint64 word.  0 = no record; otherwise
+ *   ((ordinal + 1) << 3) | code with code 1 DEP, 2 NUC, 3 ATT, 4 HOP (a diffusion arrived here), 5 LEFT (a diffusion left
+ *   here).  Codes 1..4 are the fill codes.
+ * Ordinal: the map has its own clock seq, 0 at cetkmc_origin_begin, never going back.  A Mode A call (cetkmc_run_steps,
+ *   cetkmc_run_ensemble per replica, cetkmc_run_supersteps with box == L) that executed steps_done steps gives slot s of its
+ *   log the ordinal seq + s and advances seq by steps_done; a Mode B call gives every record of super-step t the ordinal
+ *   seq + t (the events of one super-step never touch the same voxel) and advances seq by its executed super-steps;
+ *   cetkmc_apply uses one ordinal.  The map does not depend on the caller's step0.  A call that could take seq to 2^36 or
+ *   beyond is refused before it does anything.
+ * Absorbing one record (cetkmc_event) with ordinal o, enc(o, code) = ((o + 1) << 3) | code:
+ *   type outside 0..3 (idle -1, null -2): skipped;
+ *   dep, nuc, att: word(pos) = max(word(pos), enc(o, DEP / NUC / ATT));
+ *   diff with target[0] >= 0: word(pos) = max(word(pos), enc(o, LEFT)), word(target) = max(word(target), enc(o, HOP));
+ *   a diff with target[0] < 0 is skipped.
+ *   "Later wins" is this maximum, so the result does not depend on the order in which records are processed.  A hop does
+ *   not carry the moved atom's provenance: it becomes HOP (the profile counts these).  Defect injection changes no code.
+ * Census: int64 census[L][5], running since begin: every absorbed record adds 1 at [pos[0]][type] (0 dep, 1 diff, 2 nuc,
+ *   3 att), a diffusion also at [target[0]][4].  It counts events whether or not a later one overwrote the voxel: column 2
+ *   is the nucleation-rate profile along the build axis.
+ * While a map exists cetkmc_run_steps absorbs slots [0, steps_done) of its log, cetkmc_run_supersteps its done x D records
+ * (single-process handles), cetkmc_run_ensemble every replica's executed steps and cetkmc_apply its event; the slot of a
+ * step that terminated (status 1) or ran out of its stream (status 2) is not absorbed.  The absorbing launch follows the
+ * call's closing event on the handle's stream: wall_ms and the counters do not include it, and no stepping kernel changes.
+ * Uploads, defect masks and temperature updates are no events: an upload is simply not recorded (its atoms are unrecorded).
+ * The origin calls invalidate no cache of the handle, and nothing invalidates the map.
+ *   cetkmc_origin_begin   allocates the map (words and census 0, seq 0); a second begin resets it.  L > 256 is refused.
+ *   cetkmc_origin_end     frees it.  Every other origin call without a map is refused (cetkmc_origin_seq returns -1).
+ *   cetkmc_origin_absorb_events  n host records, records [g * group, (g + 1) * group) with ordinal seq + g; seq advances by
+ *                         n / group.  group >= 1, n >= 0 and n % group == 0; an event (type 0..3) whose position, or a
+ *                         diffusion whose target with target[0] >= 0, lies outside the lattice refuses the call.
+ *   cetkmc_origin_read    words[L^3];  cetkmc_origin_census  out[L][5];  both counted in bytes_d2h.
+ *   cetkmc_origin_profile one record per plane i (layers[L]) and per grain id of the handle's last clustering
+ *     (cetkmc_cluster or cetkmc_cluster_import; grains: the first min(cap, n) records as cetkmc_grain_table treats cap;
+ *     grains == NULL: no clustering is needed).
+ *     Plane record: a voxel with state != 0 counts in n_occ and in n_by[code - 1] if its word has a fill code, otherwise
+ *       (word 0 or LEFT) in n_unrec; a voxel with state == 0 and code LEFT counts in n_left; any other empty voxel in nothing.
+ *     Grain record: every voxel with label == id counts in n_occ and is classified by its word alone, as above (labels are
+ *       not checked against the state); n_left is 0.
+ *     Over the voxels counted with a fill code: ord_sum, ord_min, ord_max over their ordinals; birth = the minimum of
+ *       (ordinal << 27) | (code << 24) | lin with lin = (i * L + j) * L + k -- the earliest fill, ties (Mode B) broken by code
+ *       and then by position.  A record without such a voxel has ord_min = birth = INT64_MAX and ord_max = -1.  pad is 0.
+ *     Integer add / min / max only: the result is defined to the bit, two calls return the same bytes and a replica's bytes
+ *     equal those of the same lattice on a single handle.  For a lattice changed since its clustering the result is
+ *     unspecified (the call stays inside its arrays).
+ * Handles: a single-slab, single-process handle.  begin / end refuse a handle that belongs to an ensemble (the batched calls
+ * keep every replica's map); read, census, seq, profile and absorb_events take a replica handle; profile refuses the handle
+ * cetkmc_create_ensemble returned, as cetkmc_layer_profile does.  Multi-slab and multi-rank handles are refused.  Every
+ * refusal happens before anything is allocated or launched; a device allocation that fails is reported through
+ * cetkmc_last_error and leaves the handle usable.  cetkmc_destroy frees the map.
+ * (A struct tag without a typedef, as cetkmc_grain_rec.) */
+enum { CETKMC_ORIGIN_DEP = 1, CETKMC_ORIGIN_NUC = 2, CETKMC_ORIGIN_ATT = 3, CETKMC_ORIGIN_HOP = 4, CETKMC_ORIGIN_LEFT = 5 };
+struct cetkmc_origin_rec {
+    int64_t n_occ;
+    int64_t n_by[4];          /* DEP, NUC, ATT, HOP */
+    int64_t n_unrec, n_left;
+    int64_t ord_sum, ord_min, ord_max;
+    int64_t birth;
+    int64_t pad;
+};
+int cetkmc_origin_begin(void* handle);
+int cetkmc_origin_end(void* handle);
+int cetkmc_origin_absorb_events(void* handle, const cetkmc_event* ev, int64_t n, int64_t group);
+int cetkmc_origin_read(void* handle, uint64_t* words);
+int cetkmc_origin_census(void* handle, int64_t* out);
+int64_t cetkmc_origin_seq(void* handle);
+int cetkmc_origin_profile(void* handle, struct cetkmc_origin_rec* layers, int64_t cap, struct cetkmc_origin_rec* grains);
+/* Every replica of an ensemble, frozen ones included, in a launch sequence that does not depend on R.  census out[R][L][5];
+ * layers[R][L]; grains: the replicas' records one behind the other in replica order, as cetkmc_ensemble_grain_table lays
+ * them out (NULL: no clustering is needed; otherwise the clustering of the last cetkmc_ensemble_analyze or an import on top
+ * of it is required).  A single-lattice handle is refused. */
+int cetkmc_ensemble_origin_begin(void* handle);
+int cetkmc_ensemble_origin_end(void* handle);
+int cetkmc_ensemble_origin_census(void* handle, int64_t* out);
+int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layers, struct cetkmc_origin_rec* grains);
 
 #ifdef __cplusplus
 }
