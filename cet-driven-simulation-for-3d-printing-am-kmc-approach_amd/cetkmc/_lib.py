@@ -60,6 +60,14 @@ class SuperArgs(C.Structure):
     ]
 
 
+class LocalArgs(C.Structure):
+    _fields_ = [
+        ("step0", C.c_int64), ("n_steps", C.c_int64), ("box", C.c_int32), ("defect_fraction", C.c_double),
+        ("seed", C.c_uint64), ("thermal_mode", C.c_int32), ("thermal_dt", C.c_double), ("max_events", C.c_int32),
+        ("horizon_events", C.c_double),
+    ]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("steps", "sweeps", "incremental_steps", "thermal_updates", "supersteps", "bytes_h2d",
                                          "bytes_d2h", "alg_bytes_sweep", "alg_bytes_thermal", "profiled_steps")] + \
@@ -152,7 +160,7 @@ STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "ru
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
                   "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
-                  "solid_rec": SolidRec, "origin_rec": OriginRec}
+                  "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -192,6 +200,8 @@ PROTOTYPES = {
     "cetkmc_run_steps": (C.c_int, [C.c_void_p, _P(RunArgs), _P(RunResult), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cetkmc_stage_inputs": (C.c_int, [C.c_void_p, _P(RunArgs)]),
     "cetkmc_run_supersteps": (C.c_int, [C.c_void_p, _P(SuperArgs), _P(RunResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_run_supersteps_local": (C.c_int, [C.c_void_p, _P(LocalArgs), _P(RunResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "cetkmc_get_counters": (C.c_int, [C.c_void_p, _P(Counters), C.c_int]),
     "cetkmc_cluster": (C.c_int, [C.c_void_p, C.c_double, _P(C.c_int64)]),
     "cetkmc_cluster_stats": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Counters, EnsAnalysis, EnsArgs, Event, Params, RunArgs, RunResult, SuperArgs, SweepInfo, build_library  # noqa: F401
+from ._lib import Counters, EnsAnalysis, EnsArgs, Event, LocalArgs, Params, RunArgs, RunResult, SuperArgs, SweepInfo, build_library  # noqa: F401
 
 EVENT_DTYPE = np.dtype([("type", "<i4"), ("pos", "<i4", 3), ("target", "<i4", 3), ("atom", "<i4"),
                         ("rate", "<f8"), ("dep_rank", "<i8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
@@ -407,6 +407,33 @@ class Engine:
         return dict(done=done, status=int(res.status), q_used=int(res.q_used), nucleation_count=int(res.nucleation_count),
                     wall_ms=res.wall_ms, totals=totals[:done + (1 if res.status == 1 else 0)], n_exec=n_exec[:done],
                     events=None if events is None else events[:done], domains=D, dt_event=dt_event[:done])
+
+    def run_supersteps_local(self, step0, n, defect_fraction, seed, max_events, horizon_events, thermal_mode=1, thermal_dt=1e-6,
+                             want_events=False):
+        """Mode B with a local event loop (cetkmc_run_supersteps_local; box 8): every box executes up to ``max_events``
+        events per super-step, until its waiting times pass the horizon ``horizon_events / R_max``.  Returns the keys of
+        run_supersteps plus ``horizon`` (tau of every super-step) and ``n_capped`` (boxes stopped by max_events); events are
+        shaped (n, D, max_events), unused slots of type -1."""
+        a = LocalArgs()
+        a.step0, a.n_steps, a.box, a.defect_fraction, a.seed = int(step0), int(n), 8, float(defect_fraction), int(seed)
+        a.thermal_mode, a.thermal_dt = int(thermal_mode), float(thermal_dt)
+        a.max_events, a.horizon_events = int(max_events), float(horizon_events)
+        D = max(1, self.L // 8) ** 3
+        K = min(max(int(max_events), 1), 64)
+        res = RunResult()
+        totals = np.zeros(n + 1, np.float64)
+        n_exec = np.zeros(max(n, 1), np.int64)
+        n_capped = np.zeros(max(n, 1), np.int64)
+        dt_event = np.zeros(max(n, 1), np.float64)
+        horizon = np.zeros(max(n, 1), np.float64)
+        events = np.zeros((max(n, 1), D, K), dtype=EVENT_DTYPE) if want_events else None
+        self._ck(self.lib.cetkmc_run_supersteps_local(self.h, C.byref(a), C.byref(res), _ptr(totals), _ptr(events), _ptr(n_exec),
+                                                      _ptr(dt_event), _ptr(horizon), _ptr(n_capped)))
+        done = int(res.steps_done)
+        return dict(done=done, status=int(res.status), q_used=int(res.q_used), nucleation_count=int(res.nucleation_count),
+                    wall_ms=res.wall_ms, totals=totals[:done + (1 if res.status == 1 else 0)], n_exec=n_exec[:done],
+                    events=None if events is None else events[:done], domains=D, dt_event=dt_event[:done],
+                    horizon=horizon[:done], n_capped=n_capped[:done])
 
     # -- grain clustering (utils.get_clusters on the device) --------------------------------------
     def clusters(self, threshold=0.5, labels=False):

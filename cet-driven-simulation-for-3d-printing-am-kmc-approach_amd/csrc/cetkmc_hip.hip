@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "cluster.hpp"
 #include "superstep.hpp"
+#include "local.hpp"
 #include "ensemble.hpp"
 #include "front.hpp"
 #include "layer.hpp"
@@ -232,6 +233,9 @@ struct Handle {
     unsigned long long* d_sup_cnt = nullptr; size_t cap_sup_cnt = 0;
     cetkmc_event* d_sup_log = nullptr; size_t cap_sup_log = 0;
     double* d_sup_rmax = nullptr; size_t cap_sup_rmax = 0;
+    // cetkmc_run_supersteps_local: per-super-step logs of the horizon and of the capped boxes
+    double* d_loc_horizon = nullptr; size_t cap_loc_horizon = 0;
+    int64_t* d_loc_capped = nullptr; size_t cap_loc_capped = 0;
     bool own_streams = true;     // false: a replica of an ensemble, on the streams of replica 0
     bool ens_member = false;     // replica r >= 1 of an ensemble (released with it)
     bool in_ensemble = false;    // any replica: stepped by cetkmc_run_ensemble only
@@ -1199,7 +1203,8 @@ void destroy_impl(Handle* h)
     for (void* p : ccp) if (p) (void)hipFree(p);
     void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
-                    h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax};
+                    h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
+                    h->d_loc_horizon, h->d_loc_capped};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -1325,7 +1330,7 @@ int cetkmc_struct_size(const char* name)
     SZ("front_stats", struct cetkmc_front_stats); SZ("layer_rec", struct cetkmc_layer_rec); SZ("texture_args", struct cetkmc_texture_args);
     SZ("grain_rec", struct cetkmc_grain_rec);
     SZ("solid_info", struct cetkmc_solid_info); SZ("solid_args", struct cetkmc_solid_args); SZ("solid_rec", struct cetkmc_solid_rec);
-    SZ("origin_rec", struct cetkmc_origin_rec);
+    SZ("origin_rec", struct cetkmc_origin_rec); SZ("local_args", cetkmc_local_args);
 #undef SZ
     return -1;
 }
@@ -2211,6 +2216,109 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     if (totals && ss.status == 1 && done < n) totals[done] = ss.total;
     if (n_executed && done > 0) HIPCHK(hipMemcpy(n_executed, h->d_log_nev, (size_t)done * 8, hipMemcpyDeviceToHost));
     if (events && done > 0) HIPCHK(hipMemcpy(events, d_log, (size_t)done * D * sizeof(cetkmc_event), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- Mode B with a local event loop (local.hpp) ------------------------------------------------------
+int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc_run_result* res, double* totals,
+                                cetkmc_event* events, int64_t* n_executed, double* dt_event, double* horizon, int64_t* n_capped)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !a || !res) return fail("null argument");
+    if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
+    const int64_t n = a->n_steps;
+    if (n < 0) return fail("n_steps < 0");
+    if (a->box != 8 || h->L % 8) return fail("cetkmc_run_supersteps_local: box must be 8 and divide L");
+    if (a->max_events < 1 || a->max_events > 64) return fail("cetkmc_run_supersteps_local: max_events must be 1..64");
+    if (!(a->horizon_events > 0.0)) return fail("cetkmc_run_supersteps_local: horizon_events must be > 0 (it may be +inf)");
+    if (a->thermal_mode == 2) return fail("cetkmc_run_supersteps_local: thermal_mode 2 (laser) is not supported in this mode");
+    if (a->thermal_mode != 0 && a->thermal_mode != 1) return fail("cetkmc_run_supersteps_local: thermal_mode must be 0 or 1");
+    if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h))
+        return fail("cetkmc_run_supersteps_local needs the whole lattice in one slab of one process");
+    if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps_local needs a streaming sweep_variant (1 or 2)");
+    CHK(origin_room(h, n, "cetkmc_run_supersteps_local"));
+    HIPCHK(hipSetDevice(h->dev));
+    SuperCfg C{};
+    C.step0 = a->step0; C.defect_fraction = a->defect_fraction; C.seed = a->seed;
+    C.box = 8; C.H = 4; C.PH = 4; C.PT = 16; C.nb = h->L / 8;
+    const int D = C.nb * C.nb * C.nb, K = a->max_events;
+    C.d0 = 0; C.D_loc = D; C.null_events = 0; C.nranks = 1;
+    LocalCfg LC{};
+    LC.max_events = K; LC.horizon_events = a->horizon_events;
+    const size_t NR = (size_t)D * K;                              // records per super-step
+    invalidate(h, Cause::batch_begin);      // the batch buffers are reused below
+    CHK(reserve_steps(h, (size_t)n));
+    CHK(grow(&h->d_sup_rmax, &h->cap_sup_rmax, (size_t)1));
+    CHK(grow(&h->d_sup_dom, &h->cap_sup_dom, NR));
+    CHK(grow(&h->d_sup_picks, &h->cap_sup_picks, (size_t)D));
+    CHK(grow(&h->d_sup_cnt, &h->cap_sup_cnt, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE));
+    CHK(grow(&h->d_loc_horizon, &h->cap_loc_horizon, (size_t)std::max<int64_t>(n, 1)));
+    CHK(grow(&h->d_loc_capped, &h->cap_loc_capped, (size_t)std::max<int64_t>(n, 1)));
+    const bool keep_log = (events || h->origin_on) && n > 0;      // an origin map reads the log on the device
+    if (keep_log) CHK(grow(&h->d_sup_log, &h->cap_sup_log, (size_t)n * NR));
+    double* const d_rmax = h->d_sup_rmax;
+    cetkmc_event* const d_dom = h->d_sup_dom;
+    DomPick* const d_picks = h->d_sup_picks;
+    unsigned long long* const d_cnt = h->d_sup_cnt;
+    cetkmc_event* const d_log = keep_log ? h->d_sup_log : nullptr;
+    HIPCHK(hipMemsetAsync(d_rmax, 0, sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE * sizeof(unsigned long long), h->stream));
+    StepState ss;
+    hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
+    BatchCfg cfg{};
+    cfg.step0 = a->step0; cfg.np_cap = 0; cfg.defect_fraction = a->defect_fraction; cfg.seed = a->seed;
+    cfg.rng_mode = 1; cfg.batch = 1;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    int64_t q_idx = 0;
+    const SlabView* views = nullptr;
+    for (int64_t s = 0; s < n; ++s) {
+        const int64_t g = a->step0 + s;
+        if (a->thermal_mode && g % 20 == 0) CHK(batch_thermal(h, g, a->step0 + n, a->thermal_mode, a->thermal_dt, 0, &q_idx));
+        if (s > 0 && (!h->table_fresh || !h->ifc_fresh)) CHK(relist(h));      // as cetkmc_run_supersteps
+        CHK(launch_sweep(h, true, nullptr, nullptr, true));
+        CHK(launch_select(h, cfg, 0.0, 1));                              // total, counts, termination test
+        views = (const SlabView*)h->d_views[h->cur];
+        hipLaunchKernelGGL(k_domain_pick8, dim3(D), dim3(64), 0, h->stream, h->kp, views, 1, h->L, C, (const StepState*)h->d_ss,
+                           (const double*)h->d_ktab, d_picks, (long long)s);
+        hipLaunchKernelGGL(k_domain_rmax, dim3((D + 1023) / 1024), dim3(1024), 0, h->stream, (const DomPick*)d_picks, D, (const StepState*)h->d_ss,
+                           d_rmax, 0);
+        hipLaunchKernelGGL(k_domain_local, dim3(D), dim3(64), 0, h->stream, h->kp, views, h->L, D, C, LC, (const StepState*)h->d_ss,
+                           (const double*)h->d_ktab, (const DomPick*)d_picks, (const double*)d_rmax, d_dom, d_cnt, d_log);
+        // upkeep of everything touched, after all lattice writes of the super-step (evaluates the lattice as it stands now:
+        // several records of one neighbourhood give the same result)
+        hipLaunchKernelGGL(k_domain_touch, dim3(2 * (unsigned)((NR + 15) / 16)), dim3(256), 0, h->stream, h->kp, views, 1, (int)NR,
+                           (const cetkmc_event*)d_dom, (const StepState*)h->d_ss, (const double*)h->d_ktab);
+        hipLaunchKernelGGL(k_local_commit, dim3(1), dim3(64), 0, h->stream, (const StepState*)h->d_ss, d_cnt, (const double*)d_rmax, LC,
+                           h->d_loc_horizon, h->d_loc_capped);
+        hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, d_cnt, h->d_log_total, h->d_log_nev, d_rmax, 1);
+        invalidate(h, Cause::step);
+    }
+    if (n > 0) CHK(relist(h));        // leave a complete, address-ordered interface list behind (Mode A reads it)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipMemcpyAsync(&ss, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHK(end_batch(h, ss));
+    CHK(origin_absorb_log(h, d_log, ss.cur * (int64_t)NR, (int64_t)NR));      // every record of super-step t under the ordinal seq + t
+    res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = 0;
+    res->nucleation_count = ss.nuc_count;
+    res->wall_ms = 0.0;
+    CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
+    res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = n; res->min_margin = 1.0;
+    h->cnt.supersteps += ss.cur;
+    CHK(refresh_ifc_grid(h));
+    const int64_t done = ss.cur;
+    if ((totals || dt_event) && done > 0) {
+        std::vector<double> tot((size_t)done);
+        HIPCHK(hipMemcpy(tot.data(), h->d_log_total, (size_t)done * 8, hipMemcpyDeviceToHost));
+        if (totals) memcpy(totals, tot.data(), (size_t)done * 8);
+        if (dt_event) for (int64_t s = 0; s < done; ++s) dt_event[s] = superstep_dt_event(a->seed, a->step0 + s, tot[(size_t)s]);
+    }
+    if (totals && ss.status == 1 && done < n) totals[done] = ss.total;
+    if (n_executed && done > 0) HIPCHK(hipMemcpy(n_executed, h->d_log_nev, (size_t)done * 8, hipMemcpyDeviceToHost));
+    if (horizon && done > 0) HIPCHK(hipMemcpy(horizon, h->d_loc_horizon, (size_t)done * 8, hipMemcpyDeviceToHost));
+    if (n_capped && done > 0) HIPCHK(hipMemcpy(n_capped, h->d_loc_capped, (size_t)done * 8, hipMemcpyDeviceToHost));
+    if (events && done > 0) HIPCHK(hipMemcpy(events, d_log, (size_t)done * NR * sizeof(cetkmc_event), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -94,6 +94,57 @@ struct DomPick {          // the chosen event of one box, before the uniforms ar
     double R;              // total rate of the box's window (canonical window tree); 0 for an idle box
 };
 
+// The canonical window tree over NL = PT * PH * PH leaves in LDS (hs[NL + q] leaf sums, hf[NL + q] "holds events" flags,
+// lc[q] leaf codes: event count | 128 if the voxel needs the slot scan), by ONE wave: heap, then the descent with
+// r = u * R.  cat < 0: an idle window (no events, R < 1e-25 or not finite).  Leaf q = ((3 ii + cat) * PH + jj) * PH + kk.
+struct WinPick { int ii, jj, kk, cat, simple; double base, r, leaf_rate, R; };
+__device__ __forceinline__ WinPick window_heap_pick(double* hs, uint8_t* hf, const uint8_t* lc, int PT, int PH, double u, int lane)
+{
+    const int NL = PT * PH * PH;
+    // heap: the lane's NL/64 consecutive leaves fold locally, the six levels above by shuffles (a + b and b + a are the same
+    // double, so both lanes of a pair hold the node's value).  One wave: LDS operations complete in program order.
+    const int per = NL >> 6;                                   // >= 4
+    for (int w = per >> 1, lvl = NL >> 1; w >= 1; w >>= 1, lvl >>= 1)
+        for (int q = 0; q < w; ++q) {
+            const int node = lvl + w * lane + q;
+            hs[node] = hs[2 * node] + hs[2 * node + 1];
+            hf[node] = hf[2 * node] | hf[2 * node + 1];
+        }
+    {
+        double v = hs[64 + lane];
+        int f = hf[64 + lane];
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+            v = v + __shfl_xor(v, 1 << l);
+            f |= __shfl_xor(f, 1 << l);
+            if ((lane & ((2 << l) - 1)) == 0) {
+                const int node = (64 >> (l + 1)) + (lane >> (l + 1));
+                hs[node] = v; hf[node] = (uint8_t)f;
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // descent (every lane walks the same path: LDS broadcasts)
+    WinPick wp;
+    wp.ii = 0; wp.jj = 0; wp.kk = 0; wp.cat = -1; wp.simple = 0; wp.base = 0.0; wp.r = 0.0; wp.leaf_rate = 0.0;
+    wp.R = hs[1];
+    if (hf[1] && !(wp.R < 1e-25) && finite_d(wp.R)) {
+        wp.r = u * wp.R;
+        int n = 1;
+        while (n < NL) {
+            const int l = 2 * n;
+            if (hf[l + 1] == 0 || (hf[l] != 0 && wp.base + hs[l] >= wp.r)) n = l;
+            else { wp.base += hs[l]; n = l + 1; }
+        }
+        const int q = n - NL;
+        const int b = q / (PH * PH);
+        wp.ii = b / 3; wp.cat = b % 3; wp.jj = (q / PH) % PH; wp.kk = q % PH;
+        wp.leaf_rate = hs[NL + q];
+        wp.simple = (lc[q] == 1 && wp.cat != CAT_DIFF) ? 1 : 0;       // one event, voxel not listed (or a deposition leaf)
+    }
+    return wp;
+}
+
 // One wave per box: leaves = category sums of the window's voxels, LDS heap of NL = PT*PH*PH leaves built by the wave
 // (lane-local levels + shuffles, no block barriers), descent, slot scan inside the chosen voxel (slot_scan_wave).
 // The uniforms and the lattice write follow in k_domain_apply, one THREAD per box (fused into this kernel's lane 0 they
@@ -157,47 +208,10 @@ __global__ __launch_bounds__(64) void k_domain_pick(KParams P, const SlabView* _
         }
     }
     __builtin_amdgcn_wave_barrier();
-    // heap: the lane's NL/64 consecutive leaves fold locally, the six levels above by shuffles (a + b and b + a are the same
-    // double, so both lanes of a pair hold the node's value).  One wave: LDS operations complete in program order.
-    const int per = NL >> 6;                                   // >= 4
-    for (int w = per >> 1, lvl = NL >> 1; w >= 1; w >>= 1, lvl >>= 1)
-        for (int q = 0; q < w; ++q) {
-            const int node = lvl + w * lane + q;
-            hs[node] = hs[2 * node] + hs[2 * node + 1];
-            hf[node] = hf[2 * node] | hf[2 * node + 1];
-        }
-    {
-        double v = hs[64 + lane];
-        int f = hf[64 + lane];
-#pragma unroll
-        for (int l = 0; l < 6; ++l) {
-            v = v + __shfl_xor(v, 1 << l);
-            f |= __shfl_xor(f, 1 << l);
-            if ((lane & ((2 << l) - 1)) == 0) {
-                const int node = (64 >> (l + 1)) + (lane >> (l + 1));
-                hs[node] = v; hf[node] = (uint8_t)f;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // descent (every lane walks the same path: LDS broadcasts)
-    int pi = 0, pj = 0, pkk = 0, cat = -1, simple = 0;
-    double base = 0.0, r = 0.0, leaf_rate = 0.0;
-    const double R = hs[1];
-    if (hf[1] && !(R < 1e-25) && finite_d(R)) {
-        r = counter_uniform(C.seed, (uint64_t)g, KEY_PICK | (uint64_t)d) * R;
-        int n = 1;
-        while (n < NL) {
-            const int l = 2 * n;
-            if (hf[l + 1] == 0 || (hf[l] != 0 && base + hs[l] >= r)) n = l;
-            else { base += hs[l]; n = l + 1; }
-        }
-        const int q = n - NL;
-        const int b = q / (C.PH * C.PH);
-        pi = i0 + b / 3; cat = b % 3; pj = j0 + (q / C.PH) % C.PH; pkk = k0 + q % C.PH;
-        leaf_rate = hs[NL + q];
-        simple = (lc[q] == 1 && cat != CAT_DIFF) ? 1 : 0;       // one event, voxel not listed (or a deposition leaf)
-    }
+    const WinPick wp = window_heap_pick(hs, hf, lc, C.PT, C.PH, counter_uniform(C.seed, (uint64_t)g, KEY_PICK | (uint64_t)d), lane);
+    const int cat = wp.cat, simple = wp.simple;
+    const int pi = cat >= 0 ? i0 + wp.ii : 0, pj = cat >= 0 ? j0 + wp.jj : 0, pkk = cat >= 0 ? k0 + wp.kk : 0;
+    const double base = wp.base, r = wp.r, leaf_rate = wp.leaf_rate, R = wp.R;
     DomPick pk;
     pk.i = pi; pk.j = pj; pk.k = pkk; pk.type = -1; pk.m = -1; pk.atom = 0; pk.rate = 0.0;
     pk.R = (cat >= 0) ? R : 0.0;
@@ -373,33 +387,17 @@ __global__ __launch_bounds__(1024) void k_domain_rmax(const DomPick* __restrict_
     }
 }
 
-// One thread per box: event record, uniforms, lattice write (kmc_simulation.py:276-327).  Reads stay within +-2 of the
-// chosen voxel and so do the writes of every other box's event (>= 5 away on some axis): no box reads what another writes.
-__global__ __launch_bounds__(64) void k_domain_apply(KParams P, const SlabView* __restrict__ slabs, int nslabs, int L, int D,
-                                                     SuperCfg C, StepState* ss, const DomPick* __restrict__ picks,
-                                                     cetkmc_event* __restrict__ dom_events,
-                                                     unsigned long long* counters /* per slot: [0] executed, [1] nucleations */,
-                                                     cetkmc_event* log_events /* [n][D] or null */,
-                                                     const double* __restrict__ rmax /* [C.nranks] window-total maxima (null events) */)
+// The record of a box's pick with the uniforms of its application (kmc_simulation.py:276-327).  md keys the orientation
+// draws and dep_hi the deposition species: md = d, dep_hi = 0 in k_domain_apply; event m of a box's local loop (local.hpp)
+// takes md = m << 24 | d, dep_hi = m << 44.  !accepted: a null event (type -2), nothing drawn.
+__device__ __forceinline__ cetkmc_event draw_event(const KParams& P, const SlabView* __restrict__ slabs, int nslabs, int L, uint64_t seed,
+                                                   int64_t g, uint64_t md, uint64_t dep_hi, const DomPick& pk, bool accepted)
 {
-    if (ss->status) return;
-    const int dl = blockIdx.x * 64 + threadIdx.x;       // local box
-    if (dl >= D) return;
-    const int d = C.d0 + dl;                            // global box index (keys the uniforms)
-    const int64_t cur = ss->cur;
-    const int64_t g = C.step0 + cur;
-    const DomPick pk = picks[dl];
     cetkmc_event ev;
     ev.type = pk.type;
     ev.pos[0] = ev.pos[1] = ev.pos[2] = 0;
     ev.target[0] = ev.target[1] = ev.target[2] = -1;
     ev.atom = 0; ev.rate = 0.0; ev.dep_rank = -1; ev.theta = 0.0; ev.phi = 0.0;
-    bool accepted = true;
-    if (pk.type >= 0 && C.null_events) {
-        double Rmax = rmax[0];
-        for (int q = 1; q < C.nranks; ++q) Rmax = rmax[q] > Rmax ? rmax[q] : Rmax;
-        accepted = counter_uniform(C.seed, (uint64_t)g, KEY_ACCEPT | (uint64_t)d) * Rmax < pk.R;
-    }
     if (pk.type >= 0) {
         const int i = pk.i, j = pk.j, k = pk.k;
         ev.pos[0] = i; ev.pos[1] = j; ev.pos[2] = k;
@@ -421,12 +419,38 @@ __global__ __launch_bounds__(64) void k_domain_apply(KParams P, const SlabView* 
             ev.theta = S.theta[src]; ev.phi = S.phi[src];
         }
         if (pk.type == EV_DEP)
-            ev.atom = dep_species(P, counter_uniform(C.seed, (uint64_t)g, (uint64_t)j * (uint64_t)L + (uint64_t)k));
+            ev.atom = dep_species(P, counter_uniform(seed, (uint64_t)g, dep_hi | ((uint64_t)j * (uint64_t)L + (uint64_t)k)));
         if (pk.type == EV_DEP || pk.type == EV_NUC) {
-            ev.theta = 0.0 + (3.141592653589793 - 0.0) * counter_uniform(C.seed, (uint64_t)g, KEY_THETA | (uint64_t)d);
-            ev.phi = 0.0 + (6.283185307179586 - 0.0) * counter_uniform(C.seed, (uint64_t)g, KEY_PHI | (uint64_t)d);
+            ev.theta = 0.0 + (3.141592653589793 - 0.0) * counter_uniform(seed, (uint64_t)g, KEY_THETA | md);
+            ev.phi = 0.0 + (6.283185307179586 - 0.0) * counter_uniform(seed, (uint64_t)g, KEY_PHI | md);
         }
     }
+    return ev;
+}
+
+// One thread per box: event record, uniforms, lattice write (kmc_simulation.py:276-327).  Reads stay within +-2 of the
+// chosen voxel and so do the writes of every other box's event (>= 5 away on some axis): no box reads what another writes.
+__global__ __launch_bounds__(64) void k_domain_apply(KParams P, const SlabView* __restrict__ slabs, int nslabs, int L, int D,
+                                                     SuperCfg C, StepState* ss, const DomPick* __restrict__ picks,
+                                                     cetkmc_event* __restrict__ dom_events,
+                                                     unsigned long long* counters /* per slot: [0] executed, [1] nucleations */,
+                                                     cetkmc_event* log_events /* [n][D] or null */,
+                                                     const double* __restrict__ rmax /* [C.nranks] window-total maxima (null events) */)
+{
+    if (ss->status) return;
+    const int dl = blockIdx.x * 64 + threadIdx.x;       // local box
+    if (dl >= D) return;
+    const int d = C.d0 + dl;                            // global box index (keys the uniforms)
+    const int64_t cur = ss->cur;
+    const int64_t g = C.step0 + cur;
+    const DomPick pk = picks[dl];
+    bool accepted = true;
+    if (pk.type >= 0 && C.null_events) {
+        double Rmax = rmax[0];
+        for (int q = 1; q < C.nranks; ++q) Rmax = rmax[q] > Rmax ? rmax[q] : Rmax;
+        accepted = counter_uniform(C.seed, (uint64_t)g, KEY_ACCEPT | (uint64_t)d) * Rmax < pk.R;
+    }
+    const cetkmc_event ev = draw_event(P, slabs, nslabs, L, C.seed, g, (uint64_t)d, 0ull, pk, accepted);
     dom_events[dl] = ev;
     if (log_events) log_events[cur * (int64_t)D + dl] = ev;
     if (ev.type < 0) return;

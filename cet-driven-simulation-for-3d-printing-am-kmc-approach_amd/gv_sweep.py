@@ -7,7 +7,7 @@ run_kmc (initial T ramp, lattice_init.py:31) for G, and the deposition attempt f
 collects the CET classification of the last metrics row of every run into ``outputs/gv_sweep/gv_map.csv``.
 
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
-                       [--mode B --box 8] [--seeds K] [--ensemble [--rng counter]]
+                       [--mode B --box 8 [--local-events K --local-horizon X]] [--seeds K] [--ensemble [--rng counter]]
                        [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]] [--front] [--layers] [--texture]
                        [--grains] [--solid] [--origin]
 
@@ -188,8 +188,13 @@ if __name__ == "__main__":
                     help="solidification map on the device: G and V at freezing in every metrics.csv, solid_layers.csv, gv_map.csv")
     ap.add_argument("--origin", action="store_true",
                     help="origin map on the device: origin columns in every metrics.csv, origin_layers.csv, gv_map.csv")
+    ap.add_argument("--local-events", type=int, default=0,
+                    help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
+    ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
+    if a.local_events:
+        kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
                    layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, origin=a.origin, **kw).to_string(index=False))

@@ -333,6 +333,8 @@ def run_kmc(
     solid_metrics: bool = False,
     solid_every: int = 20,
     origin_metrics: bool = False,
+    local_events: int = 0,
+    local_horizon: float = 1.0,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -362,6 +364,15 @@ def run_kmc(
     (kmc_simulation.py:248-250): before every super-step the field is brought to ``executed // 20 + 1`` updates;
     ``"supersteps"`` updates once per 20 super-steps inside the engine (throughput setting for large lattices: the
     temperature history per executed event then differs from the reference's).
+    ``local_events=K > 0`` (mode "B", ``box`` 8) selects the local event loop (cetkmc_run_supersteps_local, DESIGN.md
+    section 23): every box executes up to K events per super-step, until its waiting times pass the horizon
+    ``local_horizon / R_max``; the event mix stays rate-proportional and ``null_events`` is not consulted.  Both
+    ``thermal_cadence`` settings work, ``Time`` advances per executed event as above, and ``last_run_info`` gains
+    ``horizon_time`` (the sum of horizon / 8 over the super-steps: the sublattice picture's clock) and ``capped_boxes``
+    (boxes that stopped at K events).  With ``origin_metrics=True`` all events of a super-step share one ordinal of the
+    origin map, whose fold keeps the largest (ordinal, code) word per voxel: a voxel that is left and filled again within
+    ONE super-step (a hop away and another atom in) keeps the code "left" while occupied, and the origin columns count it
+    as unrecorded.
 
     ``laser`` (mode "A"): every temperature update is the laser update of thermal_solver.update_temperature -- a moving
     Gaussian source on plane L-1 and, with ``latent`` (default on), latent heat where a voxel solidified since the previous
@@ -440,6 +451,12 @@ def run_kmc(
             raise ValueError("laser needs thermal_updates=True (the source acts through the temperature update)")
     if thermal_cadence not in ("events", "supersteps"):
         raise ValueError("thermal_cadence must be 'events' or 'supersteps'")
+    local_events = int(local_events)
+    if local_events:
+        if mode != "B" or box != 8 or L % 8:
+            raise ValueError("local_events needs mode 'B' with box 8 dividing L")
+        if not 1 <= local_events <= 64 or not float(local_horizon) > 0.0:
+            raise ValueError("local_events must be 1..64 and local_horizon > 0")
     run_seed = RANDOM_SEED if seed is None else int(seed)
     metrics_every = int(metrics_every)
 
@@ -568,15 +585,21 @@ def run_kmc(
         # g % 8, keys the counter uniforms together with run_seed).
         nbx = L // box if (box and L % box == 0) else 1
         d_max = 1 if box == L else nbx ** 3                       # events per super-step at most
+        if local_events:
+            d_max *= local_events
         executed, g, thermal_done = 0, 0, 0
+        horizon_time, capped_boxes = 0.0, 0
         mb_cfg = dict(mode="B", box=int(box), seed=run_seed, null_events=bool(null_events), thermal_cadence=thermal_cadence,
                       thermal_updates=bool(thermal_updates))
+        if local_events:        # (only then: the checkpoints of every other run stay as they were)
+            mb_cfg.update(local_events=local_events, local_horizon=float(local_horizon))
         if ckpt:
             ex = ckpt["extra"]
-            if {k: ex.get(k) for k in mb_cfg} != mb_cfg:
+            if {k: ex.get(k) for k in mb_cfg} != mb_cfg or ("local_events" in ex) != bool(local_events):
                 engine.close()
                 raise ValueError(f"checkpoint was written by a run with {ex}, this call asks for {mb_cfg}")
             executed, g, thermal_done = next_step, int(ex["superstep"]), int(ex["thermal_done"])
+            horizon_time, capped_boxes = float(ex.get("horizon_time", 0.0)), int(ex.get("capped_boxes", 0))
         by_events = thermal_cadence == "events" and thermal_updates
         engine_thermal = 0
         while executed < n_steps:
@@ -596,8 +619,16 @@ def run_kmc(
                 for _ in range(due - thermal_done):
                     engine.thermal_cet(THERMAL_DT, scrub_nan=True)
                 thermal_done = due
-            r = engine.run_supersteps(g, nb, box, defect_fraction, run_seed, thermal_mode=0 if (by_events or not thermal_updates) else 1,
-                                      thermal_dt=THERMAL_DT, null_events=null_events)
+            engine_mode = 0 if (by_events or not thermal_updates) else 1
+            if local_events:
+                r = engine.run_supersteps_local(g, nb, defect_fraction, run_seed, local_events, float(local_horizon),
+                                                thermal_mode=engine_mode, thermal_dt=THERMAL_DT)
+                for s in range(r["done"]):
+                    horizon_time += float(r["horizon"][s]) / 8.0
+                    capped_boxes += int(r["n_capped"][s])
+            else:
+                r = engine.run_supersteps(g, nb, box, defect_fraction, run_seed, thermal_mode=engine_mode,
+                                          thermal_dt=THERMAL_DT, null_events=null_events)
             before = executed
             for s in range(r["done"]):
                 executed += int(r["n_exec"][s])
@@ -616,7 +647,10 @@ def run_kmc(
                 metrics_row(step, crossed)
             if checkpoint_every > 0 and executed // checkpoint_every > before // checkpoint_every:
                 # after the row of this super-step: a resumed run continues with the next super-step
-                checkpoint(executed, dict(mb_cfg, superstep=g, thermal_done=thermal_done))
+                extra = dict(mb_cfg, superstep=g, thermal_done=thermal_done)
+                if local_events:
+                    extra.update(horizon_time=horizon_time, capped_boxes=capped_boxes)
+                checkpoint(executed, extra)
         next_step = executed
 
     if metrics_data:
@@ -642,6 +676,8 @@ def run_kmc(
     engine.close()
     last_run_info.clear()
     last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1)
+    if local_events:
+        last_run_info.update(horizon_time=horizon_time, capped_boxes=capped_boxes)
     if mode == "A" and min_margin < MARGIN_WARN:
         print(f"Note: smallest selection margin {min_margin:.2e} < {MARGIN_WARN:.0e} of the total rate -- a pick this close to an "
               "event boundary may differ from the reference's sequential scan")

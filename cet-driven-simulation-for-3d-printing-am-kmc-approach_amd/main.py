@@ -139,6 +139,12 @@ if __name__ == "__main__":
     ap.add_argument("--origin", action="store_true",
                     help="origin map on the device: voxels and grains by how they were filled (deposition, nucleation, attachment, "
                          "hop) in every metrics.csv, origin_layers.csv (with --grains: origin_grains.csv)")
+    ap.add_argument("--local-events", type=int, default=0,
+                    help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
+    ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
     a = ap.parse_args()
+    kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
+    if a.local_events:
+        kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
-         grains=a.grains, solid=a.solid, origin=a.origin, **(dict(mode="B", box=a.box) if a.mode == "B" else {}))
+         grains=a.grains, solid=a.solid, origin=a.origin, **kw)

@@ -198,7 +198,7 @@ int cetkmc_abi_version(void);
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
- * "solid_info", "solid_args", "solid_rec", "origin_rec"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -349,6 +349,38 @@ int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* args);
  * halo planes and of the owned planes a diffusion target reached. */
 int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_result* res, double* totals,
                           cetkmc_event* events, int64_t* n_executed, double* dt_event);
+
+/* Mode B with a local event loop (NOT in the reference): every box executes SEVERAL events per
+ * super-step, up to a common time horizon (Shim & Amar's synchronous sublattice scheme), so the event mix stays
+ * rate-proportional without idling the boxes.  box 8 only (windows of 4 x 4 x 4 voxels), L % 8 == 0.  Per super-step g:
+ * temperature update, sweep, totals[g], dt_event[g] and every box's first pick exactly as cetkmc_run_supersteps; then
+ * R_max = the largest window total of the non-idle boxes, horizon[g] = horizon_events / R_max (0 when every box is idle),
+ * and box d runs: t = 0, m = 0; while it holds a pick: stop when m == max_events (the box counts in n_capped[g]); draw
+ * u = u(seed, g, 7<<40 | m<<24 | d), w = -ln(u) / R with R the window total the pick was made from (u == 0: w = +inf);
+ * stop when t + w > horizon[g] (with an infinite horizon that never holds, also for w = +inf: the event executes); else t += w, apply the pick (uniforms: theta 2<<40 | m<<24 | d, phi 3<<40 | m<<24 | d,
+ * defect 4<<40 | m<<24 | d, deposition species m<<44 | j * L + k), ++m, and while m < max_events pick again from the same
+ * window on the lattice as the box's own events left it (uniform 1<<40 | m<<24 | d; same leaves, window tree, descent and
+ * slot scan as the first pick).  The windows' read ranges do not reach what another box writes, so the result is that of
+ * the boxes running one after the other.  For m = 0 every key is cetkmc_run_supersteps'; with max_events = 1 and an
+ * infinite horizon the call is cetkmc_run_supersteps(null_events = 0).
+ * events[n][D][max_events] or NULL: the executed events of every box in order, unused slots as an idle box's record
+ * (type -1); n_executed[n], dt_event[n] as above; horizon[n]; n_capped[n] boxes that executed max_events events.
+ * Refused: box != 8 or L % 8 != 0, max_events outside 1..64, horizon_events <= 0 or NaN, thermal_mode 2, more than one
+ * slab or a rank handle, an ensemble replica, sweep_variant < 1.  An origin map absorbs D * max_events records per
+ * super-step ordinal; cetkmc_counters.supersteps counts these super-steps too. */
+typedef struct cetkmc_local_args {
+    int64_t step0, n_steps;
+    int32_t box;              /* 8 */
+    double  defect_fraction;
+    uint64_t seed;
+    int32_t thermal_mode;     /* 0 or 1 */
+    double  thermal_dt;
+    int32_t max_events;       /* 1..64 */
+    double  horizon_events;   /* > 0, may be +inf */
+} cetkmc_local_args;
+int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc_run_result* res, double* totals,
+                                cetkmc_event* events /* [n][D][max_events] or NULL */, int64_t* n_executed,
+                                double* dt_event, double* horizon, int64_t* n_capped);
 
 int cetkmc_get_counters(void* handle, cetkmc_counters* out, int reset);
 
@@ -699,7 +731,8 @@ int cetkmc_ensemble_solid_profile(void* handle, const struct cetkmc_solid_args* 
  *   3 att), a diffusion also at [target[0]][4].  It counts events whether or not a later one overwrote the voxel: column 2
  *   is the nucleation-rate profile along the build axis.
  * While a map exists cetkmc_run_steps absorbs slots [0, steps_done) of its log, cetkmc_run_supersteps its done x D records
- * (single-process handles), cetkmc_run_ensemble every replica's executed steps and cetkmc_apply its event; the slot of a
+ * (single-process handles), cetkmc_run_supersteps_local its done x D x max_events records (several records of one voxel
+ * under one ordinal resolve by the maximum like any others: by the code, not by their sequence), cetkmc_run_ensemble every replica's executed steps and cetkmc_apply its event; the slot of a
  * step that terminated (status 1) or ran out of its stream (status 2) is not absorbed.  The absorbing launch follows the
  * call's closing event on the handle's stream: wall_ms and the counters do not include it, and no stepping kernel changes.
  * Uploads, defect masks and temperature updates are no events: an upload is simply not recorded (its atoms are unrecorded).

@@ -1,30 +1,112 @@
 #!/usr/bin/env python3
-"""Mode B (super-steps over boxes) on the bench workload: executed events/s.  GPU box only."""
+"""Mode B (super-steps over boxes) on the bench workload: executed events/s.  GPU box only.
+
+    python tools/bench_mode_b.py [L] [box] [n]                 the laser-driven run of the bench lattice, REPS batches
+    python tools/bench_mode_b.py [L] 8 [n] --compare [--out F] null-event, no-null and local-loop rows side by side
+
+--compare: the bench's melt-pool lattice (synthetic.planes, seed 42) under the engine's own temperature update ("melt_pool")
+and with the field held still ("stationary"); for each, a fresh engine per row runs n warm-up and n timed super-steps.  Rows:
+null events, no null events, and the local event loop (cetkmc_run_supersteps_local) at (max_events, horizon_events) =
+(4, 1), (8, 4), (16, 8).  Per row: executed events/s, ms per super-step and, for the local loop, from 4 further super-steps:
+the mean events per non-idle box (a box holding a first pick, counted by a twin engine that makes the same first picks on a
+copy of the lattice), the mean per box that executed any, and the share of the non-idle boxes stopped by max_events.
+"""
+import argparse
+import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cet-driven-simulation-for-3d-printing-am-kmc-approach_amd"))
 import cetkmc  # noqa: E402
 from cetkmc import synthetic  # noqa: E402
 
-L = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-box = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-n = int(sys.argv[3]) if len(sys.argv) > 3 else 40
-st, th, ph, T, df = synthetic.planes(L, 0, L, seed=42)
-e = cetkmc.Engine(L, impurity_c=0.2)
-e.upload_planes(0, L, st, th, ph, T, df)
-e.set_prev_state(None)
-step = 0
-for rep in range(int(os.environ.get("REPS", "4"))):
-    q = synthetic.laser_planes(L, step, n)
-    r = e.run_supersteps(step, n, box, 3e-3, seed=42, thermal_mode=2, q_planes=q)
-    ex = int(r["n_exec"].sum())
-    print(f"steps {step}..{step + r['done']}: {r['wall_ms'] / max(r['done'], 1) * 1e3:.1f} us/super-step, "
-          f"{ex / max(r['done'], 1):.0f} events/super-step, {ex / (r['wall_ms'] * 1e-3):.3e} executed events/s, "
-          f"empty voxels left {e.species_counts()[0]}", flush=True)
-    step += r["done"]
-    if r["status"]:
-        break
+LOCAL_SETTINGS = ((4, 1.0), (8, 4.0), (16, 8.0))
+DEFECT_FRACTION = 3e-3
+
+
+def fresh_engine(L):
+    st, th, ph, T, df = synthetic.planes(L, 0, L, seed=42)
+    e = cetkmc.Engine(L, impurity_c=0.2)
+    e.upload_planes(0, L, st, th, ph, T, df)
+    e.set_prev_state(None)
+    return e
+
+
+def laser_run(L, box, n):
+    e = fresh_engine(L)
+    step = 0
+    for rep in range(int(os.environ.get("REPS", "4"))):
+        q = synthetic.laser_planes(L, step, n)
+        r = e.run_supersteps(step, n, box, DEFECT_FRACTION, seed=42, thermal_mode=2, q_planes=q)
+        ex = int(r["n_exec"].sum())
+        print(f"steps {step}..{step + r['done']}: {r['wall_ms'] / max(r['done'], 1) * 1e3:.1f} us/super-step, "
+              f"{ex / max(r['done'], 1):.0f} events/super-step, {ex / (r['wall_ms'] * 1e-3):.3e} executed events/s, "
+              f"empty voxels left {e.species_counts()[0]}", flush=True)
+        step += r["done"]
+        if r["status"]:
+            break
+    e.close()
+
+
+def compare(L, n):
+    rows = []
+    for field, thermal_mode in (("melt_pool", 1), ("stationary", 0)):
+        settings = [("null_events", None), ("no_null_events", None)] + [("local", s) for s in LOCAL_SETTINGS]
+        for name, s in settings:
+            e = fresh_engine(L)
+
+            def run(step, count, want_events=False):
+                if s is None:
+                    return e.run_supersteps(step, count, 8, DEFECT_FRACTION, seed=42, thermal_mode=thermal_mode,
+                                            null_events=name == "null_events", want_events=want_events)
+                return e.run_supersteps_local(step, count, DEFECT_FRACTION, 42, s[0], s[1], thermal_mode=thermal_mode,
+                                              want_events=want_events)
+            run(0, n)                                        # warm-up: buffers, first interface evaluation
+            r = run(n, n)
+            ex = int(r["n_exec"].sum())
+            row = dict(field=field, mode=name, super_steps=int(r["done"]), executed=ex,
+                       ms_per_super_step=r["wall_ms"] / max(r["done"], 1), events_per_s=ex / (r["wall_ms"] * 1e-3),
+                       status=int(r["status"]))
+            if s is not None:
+                row.update(max_events=s[0], horizon_events=s[1])
+                # 4 further super-steps, one at a time.  A non-idle box is one that holds a first pick; the loop's log does not
+                # show it when the first waiting time already passes the horizon, so a twin engine takes a copy of the lattice
+                # before each super-step and makes the same first picks (one event per box, no null events: type >= 0)
+                twin = cetkmc.Engine(L, impurity_c=0.2)
+                executed = non_idle = busy = capped = 0
+                for g in range(2 * n, 2 * n + 4):
+                    f = e.download_planes(0, L, state=True, theta=True, phi=True, T=True, defects=True)
+                    twin.upload_planes(0, L, f["state"], f["theta"], f["phi"], f["T"], f["defects"])
+                    p = twin.run_supersteps(g, 1, 8, DEFECT_FRACTION, seed=42, thermal_mode=thermal_mode, null_events=False,
+                                            want_events=True)
+                    t = run(g, 1, want_events=True)
+                    per_box = (t["events"]["type"] >= 0).sum(axis=2)
+                    executed += int(per_box.sum())
+                    busy += int((per_box > 0).sum())
+                    non_idle += int((p["events"]["type"] >= 0).sum())
+                    capped += int(t["n_capped"].sum())
+                twin.close()
+                row.update(non_idle_boxes=non_idle, executing_boxes=busy, events_per_non_idle_box=executed / max(non_idle, 1),
+                           events_per_executing_box=executed / max(busy, 1), capped_share=capped / max(non_idle, 1))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            e.close()
+    return rows
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("L", type=int, nargs="?", default=256)
+    ap.add_argument("box", type=int, nargs="?", default=8)
+    ap.add_argument("n", type=int, nargs="?", default=40)
+    ap.add_argument("--compare", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.compare:
+        rows = compare(a.L, a.n)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(dict(L=a.L, n=a.n, defect_fraction=DEFECT_FRACTION, rows=rows), f, indent=1)
+    else:
+        laser_run(a.L, a.box, a.n)

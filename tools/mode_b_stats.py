@@ -5,6 +5,7 @@ Mode B executed, same seed (same initial lattice: initialize_lattice is seeded b
 metrics row of both runs per seed.
 
     python tools/mode_b_stats.py [--L 64] [--events 60000] [--seeds 8] [--box 8] [--no-null] [--cadence events]
+                                    [--no-thermal] [--local-events K --local-horizon X]
 """
 import argparse
 import json
@@ -23,7 +24,8 @@ COLS = ("Step", "AspectRatio", "EquiaxedFraction", "GrainCount", "AvgGrainSize",
 
 
 def collect(L=64, n_events=60000, seeds=range(8), box=8, null_events=True, thermal_cadence="events", impurity_c=0.1,
-            defect_fraction=3e-3, n_seeds=20, metrics_every=None, quiet=True, thermal_updates=True):
+            defect_fraction=3e-3, n_seeds=20, metrics_every=None, quiet=True, thermal_updates=True, local_events=0,
+            local_horizon=1.0):
     import contextlib
     import io
 
@@ -42,6 +44,8 @@ def collect(L=64, n_events=60000, seeds=range(8), box=8, null_events=True, therm
                               output_prefix=f"stat_{mode}_{seed}", seed=seed, metrics_every=me, thermal_updates=thermal_updates)
                     if mode == "B":
                         kw.update(mode="B", box=box, null_events=null_events, thermal_cadence=thermal_cadence)
+                        if local_events:
+                            kw.update(local_events=local_events, local_horizon=local_horizon)
                     with contextlib.redirect_stdout(io.StringIO() if quiet else sys.stdout):
                         kmc_simulation.run_kmc(**kw)
                     last = pd.read_csv(f"outputs/stat_{mode}_{seed}/metrics.csv").iloc[-1]
@@ -78,7 +82,9 @@ if __name__ == "__main__":
     ap.add_argument("--cadence", default="events")
     ap.add_argument("--carbon", type=float, default=0.1)
     ap.add_argument("--no-thermal", action="store_true")
+    ap.add_argument("--local-events", type=int, default=0, help="local event loop: up to K events per box and super-step")
+    ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max")
     a = ap.parse_args()
     rows = collect(a.L, a.events, range(a.seeds), a.box, not a.no_null, a.cadence, impurity_c=a.carbon,
-                   thermal_updates=not a.no_thermal)
+                   thermal_updates=not a.no_thermal, local_events=a.local_events, local_horizon=a.local_horizon)
     print(json.dumps(dict(args=vars(a), summary=summarize(rows), rows=rows), indent=1, default=str))
