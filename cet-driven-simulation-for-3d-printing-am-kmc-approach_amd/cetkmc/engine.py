@@ -396,17 +396,24 @@ class Engine:
         # their events / executed counts; global box order = rank order)
         nbx = self.L // int(box) if box and self.L % int(box) == 0 else 1
         D = max(1, (self.i1 - self.i0) // int(box)) * nbx * nbx if box and self.L % int(box) == 0 else 1
+        return self._supersteps(self.lib.cetkmc_run_supersteps, a, n, D, (D,) if want_events else None)
+
+    def _supersteps(self, call, a, n, D, event_shape, more=()):
+        """A cetkmc_run_supersteps* ``call`` of n super-steps over D boxes: its output arrays (events of shape (n,) +
+        event_shape, or none; ``more``: (name, dtype) of the (n,) logs it takes behind dt_event) and its result dict."""
         res = RunResult()
         totals = np.zeros(n + 1, np.float64)
         n_exec = np.zeros(max(n, 1), np.int64)
         dt_event = np.zeros(max(n, 1), np.float64)
-        events = np.zeros((max(n, 1), D), dtype=EVENT_DTYPE) if want_events else None
-        self._ck(self.lib.cetkmc_run_supersteps(self.h, C.byref(a), C.byref(res), _ptr(totals), _ptr(events), _ptr(n_exec),
-                                                _ptr(dt_event)))
+        events = None if event_shape is None else np.zeros((max(n, 1),) + event_shape, dtype=EVENT_DTYPE)
+        logs = {name: np.zeros(max(n, 1), dtype) for name, dtype in more}
+        self._ck(call(self.h, C.byref(a), C.byref(res), _ptr(totals), _ptr(events), _ptr(n_exec), _ptr(dt_event),
+                      *[_ptr(v) for v in logs.values()]))
         done = int(res.steps_done)
         return dict(done=done, status=int(res.status), q_used=int(res.q_used), nucleation_count=int(res.nucleation_count),
                     wall_ms=res.wall_ms, totals=totals[:done + (1 if res.status == 1 else 0)], n_exec=n_exec[:done],
-                    events=None if events is None else events[:done], domains=D, dt_event=dt_event[:done])
+                    events=None if events is None else events[:done], domains=D, dt_event=dt_event[:done],
+                    **{name: v[:done] for name, v in logs.items()})
 
     def run_supersteps_local(self, step0, n, defect_fraction, seed, max_events, horizon_events, thermal_mode=1, thermal_dt=1e-6,
                              want_events=False):
@@ -420,34 +427,14 @@ class Engine:
         a.max_events, a.horizon_events = int(max_events), float(horizon_events)
         D = max(1, self.L // 8) ** 3
         K = min(max(int(max_events), 1), 64)
-        res = RunResult()
-        totals = np.zeros(n + 1, np.float64)
-        n_exec = np.zeros(max(n, 1), np.int64)
-        n_capped = np.zeros(max(n, 1), np.int64)
-        dt_event = np.zeros(max(n, 1), np.float64)
-        horizon = np.zeros(max(n, 1), np.float64)
-        events = np.zeros((max(n, 1), D, K), dtype=EVENT_DTYPE) if want_events else None
-        self._ck(self.lib.cetkmc_run_supersteps_local(self.h, C.byref(a), C.byref(res), _ptr(totals), _ptr(events), _ptr(n_exec),
-                                                      _ptr(dt_event), _ptr(horizon), _ptr(n_capped)))
-        done = int(res.steps_done)
-        return dict(done=done, status=int(res.status), q_used=int(res.q_used), nucleation_count=int(res.nucleation_count),
-                    wall_ms=res.wall_ms, totals=totals[:done + (1 if res.status == 1 else 0)], n_exec=n_exec[:done],
-                    events=None if events is None else events[:done], domains=D, dt_event=dt_event[:done],
-                    horizon=horizon[:done], n_capped=n_capped[:done])
+        return self._supersteps(self.lib.cetkmc_run_supersteps_local, a, n, D, (D, K) if want_events else None,
+                                more=(("horizon", np.float64), ("n_capped", np.int64)))
 
     # -- grain clustering (utils.get_clusters on the device) --------------------------------------
     def clusters(self, threshold=0.5, labels=False):
         """dict(first (n,3) int32, size (n,) int64, bbox (n,6) int32[, labels (L,L,L) int32]); clusters are
         numbered in the reference's order (first voxel, row-major)."""
-        n = C.c_int64(0)
-        self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-        k = self._cc_n = n.value
-        first = np.zeros((max(k, 1), 3), np.int32)
-        size = np.zeros(max(k, 1), np.int64)
-        bbox = np.zeros((max(k, 1), 6), np.int32)
-        if k:
-            self._ck(self.lib.cetkmc_cluster_stats(self.h, k, _ptr(first), _ptr(size), _ptr(bbox)))
-        out = dict(first=first[:k], size=size[:k], bbox=bbox[:k])
+        out = self._cluster_table(self._recluster(threshold, True))
         if labels:
             lab = np.zeros((self.L,) * 3, np.int32)
             self._ck(self.lib.cetkmc_cluster_labels(self.h, _ptr(lab)))
@@ -463,7 +450,21 @@ class Engine:
         assert lab.shape == (self.L,) * 3, lab.shape
         n = C.c_int64(0)
         self._ck(self.lib.cetkmc_cluster_import(self.h, _ptr(lab), C.byref(n)))
-        k = self._cc_n = n.value
+        self._cc_n = n.value
+        return self._cluster_table(n.value)
+
+    _cc_n = None        # grains of the handle's last clustering, when it was made through this object
+
+    def _recluster(self, threshold, recluster):
+        """cetkmc_cluster with ``threshold`` unless ``recluster`` is False; returns ``_cc_n``."""
+        if recluster:
+            n = C.c_int64(0)
+            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
+            self._cc_n = n.value
+        return self._cc_n
+
+    def _cluster_table(self, k):
+        """dict(first, size, bbox) of the k grains of the handle's clustering (cetkmc_cluster_stats)."""
         first = np.zeros((max(k, 1), 3), np.int32)
         size = np.zeros(max(k, 1), np.int64)
         bbox = np.zeros((max(k, 1), 6), np.int32)
@@ -509,10 +510,7 @@ class Engine:
         handle's last clustering (Engine.clusters; the lattice must not have changed since).  ``ar_threshold`` defaults to
         constants.CET_AR_THRESHOLD.  metrics.layer_metrics turns it into the row's columns.  The ensemble's own handle
         (replica 0) is refused: Ensemble.layer_profile covers every replica."""
-        if recluster:
-            n = C.c_int64(0)
-            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-            self._cc_n = n.value
+        self._recluster(threshold, recluster)
         buf = np.zeros(max(self.L, 1), dtype=LAYER_DTYPE)
         self._ck(self.lib.cetkmc_layer_profile(self.h, float(_default_ar_threshold() if ar_threshold is None else ar_threshold),
                                                _ptr(buf)))
@@ -532,17 +530,12 @@ class Engine:
         convention for the default axis.  Clusters first with ``threshold`` unless ``recluster`` is False, which reuses the
         handle's last clustering or import (the lattice must not have changed since).  metrics.texture_metrics turns the
         profile into columns.  The ensemble's own handle is refused: Ensemble.texture_profile covers every replica."""
-        if recluster:
-            n = C.c_int64(0)
-            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-            self._cc_n = n.value
+        self._recluster(threshold, recluster)
         a, _keep, gb_deg, pole_deg = _texture_args(n_bins, gb_edges_deg, pole_edges_deg, axis)
         nb, L = max(int(n_bins), 1), max(self.L, 1)
         gb, pole, bad = np.zeros((L, 3, nb), np.int64), np.zeros((L, nb), np.int64), np.zeros((L, 4), np.int64)
         self._ck(self.lib.cetkmc_texture_profile(self.h, C.byref(a), _ptr(gb), _ptr(pole), _ptr(bad)))
         return dict(gb_hist=gb, pole_hist=pole, bad=bad, gb_edges_deg=gb_deg, pole_edges_deg=pole_deg)
-
-    _cc_n = None        # grains of the handle's last clustering, when it was made through this object
 
     def grain_table(self, threshold=0.5, recluster=True):
         """cetkmc_grain_table (per-grain table) of the resident lattice: a dict of arrays with leading
@@ -552,11 +545,7 @@ class Engine:
         ``recluster`` is False, which reuses the handle's last clustering or import (the lattice must not have changed
         since).  metrics.grain_metrics turns it into columns.  The ensemble's own handle is refused: Ensemble.grain_table
         covers every replica."""
-        if recluster:
-            n = C.c_int64(0)
-            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-            self._cc_n = n.value
-        k = self._cc_n
+        k = self._recluster(threshold, recluster)
         if k is None:
             # a clustering this object did not make (or none: then the call fails in the library's words): every grain
             # has n >= 1, so the first record left at zero ends the table
@@ -610,11 +599,7 @@ class Engine:
         if not grains:
             self._ck(self.lib.cetkmc_solid_profile(self.h, C.byref(a), _ptr(lay), 0, None))
             return dict(layers=_solid_fields(lay), grains=None)
-        if recluster:
-            n = C.c_int64(0)
-            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-            self._cc_n = n.value
-        k = self._cc_n
+        k = self._recluster(threshold, recluster)
         if k is None:       # a clustering this object did not make: its size from the stats call (fails without one)
             k = len(self.grain_table(recluster=False)["n"])
         gr = np.zeros(max(k, 1), SOLID_DTYPE)
@@ -667,11 +652,7 @@ class Engine:
         if not grains:
             self._ck(self.lib.cetkmc_origin_profile(self.h, _ptr(lay), 0, None))
             return dict(layers=_origin_fields(lay), grains=None)
-        if recluster:
-            n = C.c_int64(0)
-            self._ck(self.lib.cetkmc_cluster(self.h, float(threshold), C.byref(n)))
-            self._cc_n = n.value
-        k = self._cc_n
+        k = self._recluster(threshold, recluster)
         if k is None:       # a clustering this object did not make: its size from the table call (fails without one)
             k = len(self.grain_table(recluster=False)["n"])
         gr = np.zeros(max(k, 1), ORIGIN_DTYPE)
@@ -829,18 +810,12 @@ class Ensemble:
         a.nucleation_count, a.n_gathered = nuc.ctypes.data_as(C.POINTER(C.c_int64)), ng.ctypes.data_as(C.POINTER(C.c_int64))
         self._ck(self.lib.cetkmc_ensemble_analyze(self.h, C.byref(a)))
         self._an_nc = nc.copy()
-        tot, gt = int(nc.sum()), int(ng.sum())
-        first = np.zeros((max(tot, 1), 3), np.int32)
-        size = np.zeros(max(tot, 1), np.int64)
-        bbox = np.zeros((max(tot, 1), 6), np.int32)
+        gt = int(ng.sum())
         lab = np.zeros((R,) + (self.L,) * 3, np.int32) if labels else None
         gi, gT = np.zeros(max(gt, 1), np.int64), np.zeros(max(gt, 1), np.float64)
-        self._ck(self.lib.cetkmc_ensemble_analysis_data(self.h, _ptr(first), _ptr(size), _ptr(bbox), _ptr(lab),
-                                                        _ptr(gi) if species >= 0 else None, _ptr(gT) if species >= 0 else None))
-        out, c0, g0 = [], 0, 0
-        for r in range(R):
-            k = int(nc[r])
-            cl = dict(first=first[c0:c0 + k], size=size[c0:c0 + k], bbox=bbox[c0:c0 + k])
+        tables = self._cluster_tables(nc, lab, gi if species >= 0 else None, gT if species >= 0 else None)
+        out, g0 = [], 0
+        for r, cl in enumerate(tables):
             if labels:
                 cl["labels"] = lab[r]
             d = dict(clusters=cl, counts=cnt[r], nucleation_count=int(nuc[r]))
@@ -850,9 +825,34 @@ class Ensemble:
                 order = np.argsort(idx, kind="stable")
                 d["gather"] = (idx[order], Tv[order])
                 g0 += m
-            c0 += k
             out.append(d)
         return out
+
+    _an_nc = None       # grains per replica of the last analysis or import
+
+    def _cluster_tables(self, nc, labels=None, lin_idx=None, T_vals=None):
+        """One dict(first, size, bbox) per replica of the analysis in force, ``nc`` grains per replica
+        (cetkmc_ensemble_analysis_data, which also fills the arrays given for its labels and gather)."""
+        at = np.concatenate(([0], np.cumsum(nc[:self.R]))).astype(np.int64)
+        tot = int(at[-1])
+        first = np.zeros((max(tot, 1), 3), np.int32)
+        size = np.zeros(max(tot, 1), np.int64)
+        bbox = np.zeros((max(tot, 1), 6), np.int32)
+        self._ck(self.lib.cetkmc_ensemble_analysis_data(self.h, _ptr(first), _ptr(size), _ptr(bbox), _ptr(labels), _ptr(lin_idx),
+                                                        _ptr(T_vals)))
+        return [dict(first=first[at[r]:at[r + 1]], size=size[at[r]:at[r + 1]], bbox=bbox[at[r]:at[r + 1]]) for r in range(self.R)]
+
+    def _reanalyze(self, threshold, recluster, what=None):
+        """:meth:`analyze` (without downloading labels) unless ``recluster`` is False; returns the offsets of every
+        replica's grains in the concatenated tables ((R + 1,) int64).  Without an analysis made through this object:
+        raises in the name of Ensemble.``what``, or (``what`` None) returns None and leaves the refusal to the library."""
+        if recluster:
+            self.analyze(threshold, labels=False)
+        if self._an_nc is None:
+            if what is None:
+                return None
+            raise RuntimeError(f"cetkmc: Ensemble.{what} needs a preceding Ensemble.analyze")
+        return np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
 
     def import_clusters(self, labels):
         """cetkmc_ensemble_cluster_import: Engine.import_clusters for every replica at once, ``labels`` (R, L, L, L), in
@@ -864,13 +864,7 @@ class Ensemble:
         nc = np.zeros(max(R, 1), np.int64)
         self._ck(self.lib.cetkmc_ensemble_cluster_import(self.h, _ptr(lab), _ptr(nc)))
         self._an_nc = nc[:R].copy()
-        tot = int(nc[:R].sum())
-        first = np.zeros((max(tot, 1), 3), np.int32)
-        size = np.zeros(max(tot, 1), np.int64)
-        bbox = np.zeros((max(tot, 1), 6), np.int32)
-        self._ck(self.lib.cetkmc_ensemble_analysis_data(self.h, _ptr(first), _ptr(size), _ptr(bbox), None, None, None))
-        at = np.concatenate(([0], np.cumsum(nc[:R])))
-        return [dict(first=first[at[r]:at[r + 1]], size=size[at[r]:at[r + 1]], bbox=bbox[at[r]:at[r + 1]]) for r in range(R)]
+        return self._cluster_tables(nc)
 
     def front_stats(self, inv_dx=None):
         """cetkmc_ensemble_front_stats: Engine.front_stats of every replica (frozen ones included) in launches that do not
@@ -883,8 +877,7 @@ class Ensemble:
         """cetkmc_ensemble_layer_profile: Engine.layer_profile of every replica (frozen ones included) in launches that do
         not depend on R.  A dict of int64 arrays with leading dimensions (R, L).  Runs :meth:`analyze` first (without
         downloading labels) unless ``recluster`` is False, which reuses the last analysis."""
-        if recluster:
-            self.analyze(threshold, labels=False)
+        self._reanalyze(threshold, recluster)
         buf = np.zeros((max(self.R, 1), self.L), dtype=LAYER_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_layer_profile(
             self.h, float(_default_ar_threshold() if ar_threshold is None else ar_threshold), _ptr(buf)))
@@ -896,27 +889,21 @@ class Ensemble:
         whatever R.  The int64 arrays gain the leading dimension R: gb_hist (R, L, 3, n_bins), pole_hist (R, L, n_bins), bad
         (R, L, 4).  Runs :meth:`analyze` first (without downloading labels) unless ``recluster`` is False, which reuses the
         last analysis or import."""
-        if recluster:
-            self.analyze(threshold, labels=False)
+        self._reanalyze(threshold, recluster)
         a, _keep, gb_deg, pole_deg = _texture_args(n_bins, gb_edges_deg, pole_edges_deg, axis)
         nb, L, R = max(int(n_bins), 1), self.L, max(self.R, 1)
         gb, pole, bad = np.zeros((R, L, 3, nb), np.int64), np.zeros((R, L, nb), np.int64), np.zeros((R, L, 4), np.int64)
         self._ck(self.lib.cetkmc_ensemble_texture_profile(self.h, C.byref(a), _ptr(gb), _ptr(pole), _ptr(bad)))
         return dict(gb_hist=gb[:self.R], pole_hist=pole[:self.R], bad=bad[:self.R], gb_edges_deg=gb_deg, pole_edges_deg=pole_deg)
 
-    _an_nc = None       # grains per replica of the last analysis or import
-
     def grain_table(self, threshold=0.5, recluster=True):
         """cetkmc_ensemble_grain_table: Engine.grain_table of every replica (frozen ones included) in launches that do not
         depend on R.  Returns one dict per replica, as :meth:`analyze` lays out its per-cluster data; entry r has the bits
         of replica(r).grain_table().  Runs :meth:`analyze` first (without downloading labels) unless ``recluster`` is
         False, which reuses the last analysis or import."""
-        if recluster:
-            self.analyze(threshold, labels=False)
-        if self._an_nc is None:            # no analysis yet: fails in the library's words
+        if not recluster and self._an_nc is None:            # no analysis yet: fails in the library's words
             self._ck(self.lib.cetkmc_ensemble_grain_table(self.h, None))
-            raise RuntimeError("cetkmc: Ensemble.grain_table needs a preceding Ensemble.analyze")
-        at = np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
+        at = self._reanalyze(threshold, recluster, "grain_table")
         buf = np.zeros(max(int(at[-1]), 1), dtype=GRAIN_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_grain_table(self.h, _ptr(buf)))
         return [{f: buf[f][at[r]:at[r + 1]].copy() for f in GRAIN_DTYPE.names} for r in range(self.R)]
@@ -950,11 +937,7 @@ class Ensemble:
         if not grains:
             self._ck(self.lib.cetkmc_ensemble_solid_profile(self.h, C.byref(a), _ptr(lay), None))
             return dict(layers=_solid_fields(lay[:self.R]), grains=None)
-        if recluster:
-            self.analyze(threshold, labels=False)
-        if self._an_nc is None:
-            raise RuntimeError("cetkmc: Ensemble.solid_profile(grains=True) needs a preceding Ensemble.analyze")
-        at = np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
+        at = self._reanalyze(threshold, recluster, "solid_profile(grains=True)")
         gr = np.zeros(max(int(at[-1]), 1), SOLID_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_solid_profile(self.h, C.byref(a), _ptr(lay), _ptr(gr)))
         return dict(layers=_solid_fields(lay[:self.R]), grains=[_solid_fields(gr[at[r]:at[r + 1]]) for r in range(self.R)])
@@ -996,11 +979,7 @@ class Ensemble:
         if not grains:
             self._ck(self.lib.cetkmc_ensemble_origin_profile(self.h, _ptr(lay), None))
             return dict(layers=_origin_fields(lay[:self.R]), grains=None)
-        if recluster:
-            self.analyze(threshold, labels=False)
-        if self._an_nc is None:
-            raise RuntimeError("cetkmc: Ensemble.origin_profile(grains=True) needs a preceding Ensemble.analyze")
-        at = np.concatenate(([0], np.cumsum(self._an_nc))).astype(np.int64)
+        at = self._reanalyze(threshold, recluster, "origin_profile(grains=True)")
         gr = np.zeros(max(int(at[-1]), 1), ORIGIN_DTYPE)
         self._ck(self.lib.cetkmc_ensemble_origin_profile(self.h, _ptr(lay), _ptr(gr)))
         return dict(layers=_origin_fields(lay[:self.R]), grains=[_origin_fields(gr[at[r]:at[r + 1]]) for r in range(self.R)])

@@ -236,6 +236,13 @@ struct Handle {
     // cetkmc_run_supersteps_local: per-super-step logs of the horizon and of the capped boxes
     double* d_loc_horizon = nullptr; size_t cap_loc_horizon = 0;
     int64_t* d_loc_capped = nullptr; size_t cap_loc_capped = 0;
+    // front statistics and layer profile: block partials and results of the pass issued on this handle, [R] lattices each
+    // (grow-only, as above), and the class byte of every grain (offs[r] + r + id)
+    FrontPart* d_front_part = nullptr; size_t cap_front_part = 0;
+    FrontStats* d_front_out = nullptr; size_t cap_front_out = 0;
+    LayerRec* d_layer_part = nullptr; size_t cap_layer_part = 0;
+    LayerRec* d_layer_out = nullptr; size_t cap_layer_out = 0;
+    uint8_t* d_layer_eq = nullptr; size_t cap_layer_eq = 0;
     bool own_streams = true;     // false: a replica of an ensemble, on the streams of replica 0
     bool ens_member = false;     // replica r >= 1 of an ensemble (released with it)
     bool in_ensemble = false;    // any replica: stepped by cetkmc_run_ensemble only
@@ -1204,7 +1211,7 @@ void destroy_impl(Handle* h)
     void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
-                    h->d_loc_horizon, h->d_loc_capped};
+                    h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -1243,11 +1250,6 @@ struct Ens {
     size_t cap_sc_idx = 0;
     double* d_g_T = nullptr;
     unsigned long long *d_counts = nullptr, *d_g_n = nullptr;
-    FrontPart* d_front_part = nullptr;   // cetkmc_ensemble_front_stats: [R][blocks of a lattice] partials, [R] results
-    FrontStats* d_front_out = nullptr;
-    LayerRec *d_layer_part = nullptr, *d_layer_out = nullptr;   // cetkmc_ensemble_layer_profile: [R][L][tiles] partials, [R][L] records
-    uint8_t* d_layer_eq = nullptr;       // class byte of every replica's grains (offs[r] + r + id)
-    size_t cap_layer_eq = 0;
     std::vector<int64_t> an_clusters, an_gathered;     // per replica, of the last analysis (-1: none yet)
     int an_species = -1;
     void* d_solid_block = nullptr;       // cetkmc_ensemble_solid_begin: every replica's map, the counters [R][3], the map table [R]
@@ -1282,8 +1284,8 @@ void destroy_ens(Ens* e)
     }
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
-                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_front_part, e->d_front_out,
-                    e->d_layer_part, e->d_layer_out, e->d_layer_eq, e->d_solid_block, e->d_origin_block};
+                    e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_solid_block,
+                    e->d_origin_block};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -2069,6 +2071,100 @@ static double superstep_dt_event(uint64_t seed, int64_t g, double total)
     return (1e-12 > dt) ? 1e-12 : dt;                       // max(dt, 1e-12)
 }
 
+// What the two Mode B drivers share (cetkmc_run_supersteps with box < L, cetkmc_run_supersteps_local): the batch of n
+// super-steps over this handle's D boxes, NR log records per super-step.  super_begin readies the buffers and the step
+// state, super_step_head issues a super-step up to the selection's totals, super_end closes the batch and hands the logs
+// out; between head and end a driver issues its own pick / apply / exchange / touch / commit launches.  A new Mode B
+// variant is a third driver of this shape.
+struct SuperBatch {
+    int64_t n = 0;
+    int D = 0;
+    size_t NR = 0;
+    int thermal_mode = 0, use_latent = 0;
+    double thermal_dt = 0.0;
+    SuperCfg C{};
+    BatchCfg cfg{};
+    double* d_rmax = nullptr;
+    cetkmc_event *d_dom = nullptr, *d_log = nullptr;
+    DomPick* d_picks = nullptr;
+    unsigned long long* d_cnt = nullptr;
+};
+
+// n_dom records of d_dom (dom_fill: set to type -1, nothing received); the log is kept for the caller's `events` and for an
+// origin map; n_therm source planes from q_planes (thermal_mode 2)
+static int super_begin(Handle* h, SuperBatch& B, size_t n_dom, bool dom_fill, bool want_events, const double* q_planes, int64_t n_therm)
+{
+    const size_t L2 = (size_t)h->L * h->L, n_rmax = (size_t)std::max(B.C.nranks, 1);
+    invalidate(h, Cause::batch_begin);      // the batch buffers are reused below
+    CHK(reserve_steps(h, (size_t)B.n));
+    if (B.thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
+    // working buffers of the handle (grow-only; the previous call ended with a synchronisation, nothing still reads them)
+    CHK(grow(&h->d_sup_rmax, &h->cap_sup_rmax, n_rmax));
+    CHK(grow(&h->d_sup_dom, &h->cap_sup_dom, n_dom));
+    CHK(grow(&h->d_sup_picks, &h->cap_sup_picks, (size_t)B.D));
+    CHK(grow(&h->d_sup_cnt, &h->cap_sup_cnt, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE));
+    const bool keep_log = (want_events || h->origin_on) && B.n > 0;      // an origin map reads the log on the device
+    if (keep_log) CHK(grow(&h->d_sup_log, &h->cap_sup_log, (size_t)B.n * B.NR));
+    B.d_rmax = h->d_sup_rmax; B.d_dom = h->d_sup_dom; B.d_picks = h->d_sup_picks; B.d_cnt = h->d_sup_cnt;
+    B.d_log = keep_log ? h->d_sup_log : nullptr;
+    HIPCHK(hipMemsetAsync(B.d_rmax, 0, n_rmax * sizeof(double), h->stream));
+    if (dom_fill) HIPCHK(hipMemsetAsync(B.d_dom, 0xFF, n_dom * sizeof(cetkmc_event), h->stream));
+    HIPCHK(hipMemsetAsync(B.d_cnt, 0, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE * sizeof(unsigned long long), h->stream));
+    if (B.thermal_mode == 2 && n_therm > 0)
+        HIPCHK(hipMemcpyAsync(h->d_q, q_planes, (size_t)n_therm * L2 * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);     // the batch part of the step state, on the stream
+    B.cfg.step0 = B.C.step0; B.cfg.np_cap = 0; B.cfg.defect_fraction = B.C.defect_fraction; B.cfg.seed = B.C.seed;
+    B.cfg.rng_mode = 1; B.cfg.batch = 1;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    return 0;
+}
+
+// super-step s up to its selection: temperature update, interface list, sweep, total / counts / termination test
+static int super_step_head(Handle* h, const SuperBatch& B, int64_t s, int64_t* q_idx)
+{
+    const int64_t g = B.C.step0 + s;
+    if (B.thermal_mode && g % 20 == 0) CHK(batch_thermal(h, g, B.C.step0 + B.n, B.thermal_mode, B.thermal_dt, B.use_latent, q_idx));
+    // interface sums: the list kernel after a temperature update / when something else made them stale (list
+    // rebuilt in address order first: k_domain_touch flags new interface voxels without appending them); otherwise
+    // they are current -- k_domain_touch re-evaluated what the events changed
+    if (s > 0 && (!h->table_fresh || !h->ifc_fresh)) CHK(relist(h));
+    CHK(launch_sweep(h, true, nullptr, nullptr, true));
+    CHK(launch_select(h, B.cfg, 0.0, 1));
+    return 0;
+}
+
+// the batch closed: result, origin map, per-super-step logs; *done = super-steps executed (for a driver's own logs)
+static int super_end(Handle* h, const SuperBatch& B, int64_t q_used, cetkmc_run_result* res, double* totals, cetkmc_event* events,
+                     int64_t* n_executed, double* dt_event, int64_t* done_out)
+{
+    StepState ss;
+    if (B.n > 0) CHK(relist(h));        // leave a complete, address-ordered interface list behind (Mode A reads it)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipMemcpyAsync(&ss, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHK(end_batch(h, ss));
+    CHK(origin_absorb_log(h, B.d_log, ss.cur * (int64_t)B.NR, (int64_t)B.NR));      // every record of super-step t under the ordinal seq + t
+    res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = q_used;
+    res->nucleation_count = ss.nuc_count;
+    res->wall_ms = 0.0;
+    CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
+    res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = B.n; res->min_margin = 1.0;
+    h->cnt.supersteps += ss.cur;
+    CHK(refresh_ifc_grid(h));
+    const int64_t done = *done_out = ss.cur;
+    if ((totals || dt_event) && done > 0) {
+        std::vector<double> tot((size_t)done);
+        HIPCHK(hipMemcpy(tot.data(), h->d_log_total, (size_t)done * 8, hipMemcpyDeviceToHost));
+        if (totals) memcpy(totals, tot.data(), (size_t)done * 8);
+        if (dt_event) for (int64_t s = 0; s < done; ++s) dt_event[s] = superstep_dt_event(B.C.seed, B.C.step0 + s, tot[(size_t)s]);
+    }
+    if (totals && ss.status == 1 && done < B.n) totals[done] = ss.total;
+    if (n_executed && done > 0) HIPCHK(hipMemcpy(n_executed, h->d_log_nev, (size_t)done * 8, hipMemcpyDeviceToHost));
+    if (events && done > 0) HIPCHK(hipMemcpy(events, B.d_log, (size_t)done * B.NR * sizeof(cetkmc_event), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_result* res, double* totals,
                           cetkmc_event* events, int64_t* n_executed, double* dt_event)
 {
@@ -2107,8 +2203,9 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
         return fail("thermal_mode 2 needs one q plane per thermal update in the batch");
     CHK(origin_room(h, n, "cetkmc_run_supersteps"));
     HIPCHK(hipSetDevice(h->dev));
-    const size_t L2 = (size_t)h->L * h->L;
-    SuperCfg C{};
+    SuperBatch B;
+    B.n = n; B.thermal_mode = a->thermal_mode; B.thermal_dt = a->thermal_dt; B.use_latent = a->use_latent;
+    SuperCfg& C = B.C;
     C.step0 = a->step0; C.defect_fraction = a->defect_fraction; C.seed = a->seed;
     C.box = a->box; C.H = a->box / 2; C.nb = h->L / a->box;
     C.PH = 1; while (C.PH < C.H) C.PH <<= 1;
@@ -2121,48 +2218,16 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     C.D_loc = D;
     C.null_events = a->null_events ? 1 : 0;
     C.nranks = ranks ? h->nranks : 1;
+    B.D = D; B.NR = (size_t)D;
     const int NE = D + 2 * nb2;                               // own events | lower neighbour's top layer | upper neighbour's bottom layer
     const size_t shmem = (size_t)C.PT * C.PH * C.PH * 19;     // heap: 2*NL doubles + 2*NL flags, NL leaf codes
-    invalidate(h, Cause::batch_begin);      // the batch buffers are reused below
-    CHK(reserve_steps(h, (size_t)n));
-    if (a->thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
-    // working buffers of the handle (grow-only; the previous call ended with a synchronisation, nothing still reads them)
-    CHK(grow(&h->d_sup_rmax, &h->cap_sup_rmax, (size_t)std::max(C.nranks, 1)));
-    CHK(grow(&h->d_sup_dom, &h->cap_sup_dom, (size_t)NE));
-    CHK(grow(&h->d_sup_picks, &h->cap_sup_picks, (size_t)D));
-    CHK(grow(&h->d_sup_cnt, &h->cap_sup_cnt, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE));
-    const bool keep_log = (events || h->origin_on) && n > 0;      // an origin map reads the log on the device
-    if (keep_log) CHK(grow(&h->d_sup_log, &h->cap_sup_log, (size_t)n * D));
-    double* const d_rmax = h->d_sup_rmax;
-    cetkmc_event* const d_dom = h->d_sup_dom;
-    DomPick* const d_picks = h->d_sup_picks;
-    unsigned long long* const d_cnt = h->d_sup_cnt;
-    cetkmc_event* const d_log = keep_log ? h->d_sup_log : nullptr;
-    HIPCHK(hipMemsetAsync(d_rmax, 0, (size_t)std::max(C.nranks, 1) * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(d_dom, 0xFF, (size_t)NE * sizeof(cetkmc_event), h->stream));      // type -1: nothing received
-    const size_t cnt_bytes = (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE * sizeof(unsigned long long);
-    HIPCHK(hipMemsetAsync(d_cnt, 0, cnt_bytes, h->stream));
-    if (a->thermal_mode == 2 && n_therm > 0)
-        HIPCHK(hipMemcpyAsync(h->d_q, a->q_planes, (size_t)n_therm * L2 * 8, hipMemcpyHostToDevice, h->stream));
-    StepState ss;
-    hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);     // the batch part of the step state, on the stream
-    BatchCfg cfg{};
-    cfg.step0 = a->step0; cfg.np_cap = 0; cfg.defect_fraction = a->defect_fraction; cfg.seed = a->seed;
-    cfg.rng_mode = 1; cfg.batch = 1;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    CHK(super_begin(h, B, (size_t)NE, true, events != nullptr, a->q_planes, n_therm));
+    double* const d_rmax = B.d_rmax;
+    cetkmc_event* const d_dom = B.d_dom;
+    DomPick* const d_picks = B.d_picks;
     int64_t q_idx = 0;
     for (int64_t s = 0; s < n; ++s) {
-        const int64_t g = a->step0 + s;
-        const bool therm = a->thermal_mode && g % 20 == 0;
-        if (therm) {
-            CHK(batch_thermal(h, g, a->step0 + n, a->thermal_mode, a->thermal_dt, a->use_latent, &q_idx));
-        }
-        // interface sums: the list kernel after a temperature update / when something else made them stale (list
-        // rebuilt in address order first: k_domain_touch flags new interface voxels without appending them); otherwise
-        // they are current -- k_domain_touch re-evaluated what the events changed
-        if (s > 0 && (!h->table_fresh || !h->ifc_fresh)) CHK(relist(h));
-        CHK(launch_sweep(h, true, nullptr, nullptr, true));
-        CHK(launch_select(h, cfg, 0.0, 1));                              // total, counts, termination test
+        CHK(super_step_head(h, B, s, &q_idx));
         if (C.H == 4)       // box 8: window tree in registers
             hipLaunchKernelGGL(k_domain_pick8, dim3(D), dim3(64), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
                                (int)h->slabs.size(), h->L, C, (const StepState*)h->d_ss, (const double*)h->d_ktab, d_picks, (long long)s);
@@ -2176,7 +2241,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
             if (ranks) CHK(comm_allgather(h, d_rmax, sizeof(double)));
         }
         hipLaunchKernelGGL(k_domain_apply, dim3((D + 63) / 64), dim3(64), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
-                           (int)h->slabs.size(), h->L, D, C, h->d_ss, (const DomPick*)d_picks, d_dom, d_cnt, d_log, (const double*)d_rmax);
+                           (int)h->slabs.size(), h->L, D, C, h->d_ss, (const DomPick*)d_picks, d_dom, B.d_cnt, B.d_log, (const double*)d_rmax);
         int n_touch = D;
         if (ranks) {
             // the events of my bottom / top box layer go to the ranks below / above, theirs come here: every rank applies
@@ -2188,35 +2253,12 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
         }
         hipLaunchKernelGGL(k_domain_touch, dim3(2 * ((n_touch + 15) / 16)), dim3(256), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
                            (int)h->slabs.size(), n_touch, (const cetkmc_event*)d_dom, (const StepState*)h->d_ss, (const double*)h->d_ktab);
-        hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, d_cnt, h->d_log_total, h->d_log_nev,
+        hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, B.d_cnt, h->d_log_total, h->d_log_nev,
                            C.null_events ? d_rmax : (double*)nullptr, std::min(C.nranks, 64));
         invalidate(h, Cause::step);      // (k_domain_touch re-evaluated the listed voxels the events changed)
     }
-    if (n > 0) CHK(relist(h));        // leave a complete, address-ordered interface list behind (Mode A reads it)
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipMemcpyAsync(&ss, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    CHK(end_batch(h, ss));
-    CHK(origin_absorb_log(h, d_log, ss.cur * D, D));      // every record of super-step t under the ordinal seq + t
-    res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = q_idx;
-    res->nucleation_count = ss.nuc_count;
-    res->wall_ms = 0.0;
-    CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
-    res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = n; res->min_margin = 1.0;
-    h->cnt.supersteps += ss.cur;
-    CHK(refresh_ifc_grid(h));
-    const int64_t done = ss.cur;
-    if ((totals || dt_event) && done > 0) {
-        std::vector<double> tot((size_t)done);
-        HIPCHK(hipMemcpy(tot.data(), h->d_log_total, (size_t)done * 8, hipMemcpyDeviceToHost));
-        if (totals) memcpy(totals, tot.data(), (size_t)done * 8);
-        if (dt_event) for (int64_t s = 0; s < done; ++s) dt_event[s] = superstep_dt_event(a->seed, a->step0 + s, tot[(size_t)s]);
-    }
-    if (totals && ss.status == 1 && done < n) totals[done] = ss.total;
-    if (n_executed && done > 0) HIPCHK(hipMemcpy(n_executed, h->d_log_nev, (size_t)done * 8, hipMemcpyDeviceToHost));
-    if (events && done > 0) HIPCHK(hipMemcpy(events, d_log, (size_t)done * D * sizeof(cetkmc_event), hipMemcpyDeviceToHost));
-    return 0;
+    int64_t done = 0;
+    return super_end(h, B, q_idx, res, totals, events, n_executed, dt_event, &done);
 }
 
 // ---- Mode B with a local event loop (local.hpp) ------------------------------------------------------
@@ -2238,7 +2280,9 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps_local needs a streaming sweep_variant (1 or 2)");
     CHK(origin_room(h, n, "cetkmc_run_supersteps_local"));
     HIPCHK(hipSetDevice(h->dev));
-    SuperCfg C{};
+    SuperBatch B;
+    B.n = n; B.thermal_mode = a->thermal_mode; B.thermal_dt = a->thermal_dt;
+    SuperCfg& C = B.C;
     C.step0 = a->step0; C.defect_fraction = a->defect_fraction; C.seed = a->seed;
     C.box = 8; C.H = 4; C.PH = 4; C.PT = 16; C.nb = h->L / 8;
     const int D = C.nb * C.nb * C.nb, K = a->max_events;
@@ -2246,79 +2290,34 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     LocalCfg LC{};
     LC.max_events = K; LC.horizon_events = a->horizon_events;
     const size_t NR = (size_t)D * K;                              // records per super-step
-    invalidate(h, Cause::batch_begin);      // the batch buffers are reused below
-    CHK(reserve_steps(h, (size_t)n));
-    CHK(grow(&h->d_sup_rmax, &h->cap_sup_rmax, (size_t)1));
-    CHK(grow(&h->d_sup_dom, &h->cap_sup_dom, NR));
-    CHK(grow(&h->d_sup_picks, &h->cap_sup_picks, (size_t)D));
-    CHK(grow(&h->d_sup_cnt, &h->cap_sup_cnt, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE));
+    B.D = D; B.NR = NR;
     CHK(grow(&h->d_loc_horizon, &h->cap_loc_horizon, (size_t)std::max<int64_t>(n, 1)));
     CHK(grow(&h->d_loc_capped, &h->cap_loc_capped, (size_t)std::max<int64_t>(n, 1)));
-    const bool keep_log = (events || h->origin_on) && n > 0;      // an origin map reads the log on the device
-    if (keep_log) CHK(grow(&h->d_sup_log, &h->cap_sup_log, (size_t)n * NR));
-    double* const d_rmax = h->d_sup_rmax;
-    cetkmc_event* const d_dom = h->d_sup_dom;
-    DomPick* const d_picks = h->d_sup_picks;
-    unsigned long long* const d_cnt = h->d_sup_cnt;
-    cetkmc_event* const d_log = keep_log ? h->d_sup_log : nullptr;
-    HIPCHK(hipMemsetAsync(d_rmax, 0, sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)SUPER_CNT_SLOTS * SUPER_CNT_STRIDE * sizeof(unsigned long long), h->stream));
-    StepState ss;
-    hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
-    BatchCfg cfg{};
-    cfg.step0 = a->step0; cfg.np_cap = 0; cfg.defect_fraction = a->defect_fraction; cfg.seed = a->seed;
-    cfg.rng_mode = 1; cfg.batch = 1;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    CHK(super_begin(h, B, NR, false, events != nullptr, nullptr, 0));
+    double* const d_rmax = B.d_rmax;
     int64_t q_idx = 0;
-    const SlabView* views = nullptr;
     for (int64_t s = 0; s < n; ++s) {
-        const int64_t g = a->step0 + s;
-        if (a->thermal_mode && g % 20 == 0) CHK(batch_thermal(h, g, a->step0 + n, a->thermal_mode, a->thermal_dt, 0, &q_idx));
-        if (s > 0 && (!h->table_fresh || !h->ifc_fresh)) CHK(relist(h));      // as cetkmc_run_supersteps
-        CHK(launch_sweep(h, true, nullptr, nullptr, true));
-        CHK(launch_select(h, cfg, 0.0, 1));                              // total, counts, termination test
-        views = (const SlabView*)h->d_views[h->cur];
+        CHK(super_step_head(h, B, s, &q_idx));
+        const SlabView* views = (const SlabView*)h->d_views[h->cur];
         hipLaunchKernelGGL(k_domain_pick8, dim3(D), dim3(64), 0, h->stream, h->kp, views, 1, h->L, C, (const StepState*)h->d_ss,
-                           (const double*)h->d_ktab, d_picks, (long long)s);
-        hipLaunchKernelGGL(k_domain_rmax, dim3((D + 1023) / 1024), dim3(1024), 0, h->stream, (const DomPick*)d_picks, D, (const StepState*)h->d_ss,
+                           (const double*)h->d_ktab, B.d_picks, (long long)s);
+        hipLaunchKernelGGL(k_domain_rmax, dim3((D + 1023) / 1024), dim3(1024), 0, h->stream, (const DomPick*)B.d_picks, D, (const StepState*)h->d_ss,
                            d_rmax, 0);
         hipLaunchKernelGGL(k_domain_local, dim3(D), dim3(64), 0, h->stream, h->kp, views, h->L, D, C, LC, (const StepState*)h->d_ss,
-                           (const double*)h->d_ktab, (const DomPick*)d_picks, (const double*)d_rmax, d_dom, d_cnt, d_log);
+                           (const double*)h->d_ktab, (const DomPick*)B.d_picks, (const double*)d_rmax, B.d_dom, B.d_cnt, B.d_log);
         // upkeep of everything touched, after all lattice writes of the super-step (evaluates the lattice as it stands now:
         // several records of one neighbourhood give the same result)
         hipLaunchKernelGGL(k_domain_touch, dim3(2 * (unsigned)((NR + 15) / 16)), dim3(256), 0, h->stream, h->kp, views, 1, (int)NR,
-                           (const cetkmc_event*)d_dom, (const StepState*)h->d_ss, (const double*)h->d_ktab);
-        hipLaunchKernelGGL(k_local_commit, dim3(1), dim3(64), 0, h->stream, (const StepState*)h->d_ss, d_cnt, (const double*)d_rmax, LC,
+                           (const cetkmc_event*)B.d_dom, (const StepState*)h->d_ss, (const double*)h->d_ktab);
+        hipLaunchKernelGGL(k_local_commit, dim3(1), dim3(64), 0, h->stream, (const StepState*)h->d_ss, B.d_cnt, (const double*)d_rmax, LC,
                            h->d_loc_horizon, h->d_loc_capped);
-        hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, d_cnt, h->d_log_total, h->d_log_nev, d_rmax, 1);
+        hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, B.d_cnt, h->d_log_total, h->d_log_nev, d_rmax, 1);
         invalidate(h, Cause::step);
     }
-    if (n > 0) CHK(relist(h));        // leave a complete, address-ordered interface list behind (Mode A reads it)
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipMemcpyAsync(&ss, h->d_ss, sizeof ss, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    CHK(end_batch(h, ss));
-    CHK(origin_absorb_log(h, d_log, ss.cur * (int64_t)NR, (int64_t)NR));      // every record of super-step t under the ordinal seq + t
-    res->steps_done = ss.cur; res->status = ss.status; res->np_used = 0; res->q_used = 0;
-    res->nucleation_count = ss.nuc_count;
-    res->wall_ms = 0.0;
-    CHK(add_elapsed(h->ev0, h->ev1, &res->wall_ms));
-    res->sweep_ms_total = 0.0; res->sweep_launches = 0; res->full_sweeps = n; res->min_margin = 1.0;
-    h->cnt.supersteps += ss.cur;
-    CHK(refresh_ifc_grid(h));
-    const int64_t done = ss.cur;
-    if ((totals || dt_event) && done > 0) {
-        std::vector<double> tot((size_t)done);
-        HIPCHK(hipMemcpy(tot.data(), h->d_log_total, (size_t)done * 8, hipMemcpyDeviceToHost));
-        if (totals) memcpy(totals, tot.data(), (size_t)done * 8);
-        if (dt_event) for (int64_t s = 0; s < done; ++s) dt_event[s] = superstep_dt_event(a->seed, a->step0 + s, tot[(size_t)s]);
-    }
-    if (totals && ss.status == 1 && done < n) totals[done] = ss.total;
-    if (n_executed && done > 0) HIPCHK(hipMemcpy(n_executed, h->d_log_nev, (size_t)done * 8, hipMemcpyDeviceToHost));
+    int64_t done = 0;
+    CHK(super_end(h, B, q_idx, res, totals, events, n_executed, dt_event, &done));
     if (horizon && done > 0) HIPCHK(hipMemcpy(horizon, h->d_loc_horizon, (size_t)done * 8, hipMemcpyDeviceToHost));
     if (n_capped && done > 0) HIPCHK(hipMemcpy(n_capped, h->d_loc_capped, (size_t)done * 8, hipMemcpyDeviceToHost));
-    if (events && done > 0) HIPCHK(hipMemcpy(events, d_log, (size_t)done * NR * sizeof(cetkmc_event), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2929,6 +2928,7 @@ static int ens_push_views(Ens* e)
         e->table[(size_t)r].view[0] = view_of(h, 0, h->cur);
         e->table[(size_t)r].view[1] = view_of(h, 0, h->cur ^ 1);
         e->table[(size_t)r].ss = h->d_ss;      // k_ens_collect reads it: an analysis may precede the ensemble's first run
+        e->table[(size_t)r].kp = h->kp;        // (k_front_stats: T_melt of the replica's own parameters)
     }
     HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)e->R * sizeof(EnsRep), hipMemcpyHostToDevice, e->reps[0]->stream));
     return 0;
@@ -3128,6 +3128,102 @@ int cetkmc_ensemble_set_defects_sparse(void* handle, const int64_t* counts, cons
     return 0;
 }
 
+// ---- diagnostics: what a pass runs over ---------------------------------------------------------
+// Every diagnostic below is ONE body, entered twice: cetkmc_x for one lattice, cetkmc_ensemble_x for every replica of an
+// ensemble.  lattices() turns (the entry point's name, its handle, which of the two it is, what the pass needs) into a
+// Lattices or the refusal; the body issues its launches through Lattices::run, which appends the ensemble's selector to the
+// kernel's arguments or nothing at all.  A new diagnostic is one more such body and two entry points.
+extern "C++" {
+enum EnsUse { ENS_VIEWS, ENS_LABELS, ENS_GRAINS };      // what the kernel takes per replica: its view; + its labels; + its grains
+struct Lattices {
+    Handle* h0 = nullptr;            // the handle the pass is issued on: its stream, counters and scratch buffers
+    Ens* e = nullptr;                // null: one lattice
+    std::vector<Handle*> hs;         // the R lattices
+    hipStream_t stream = nullptr;
+    int L = 0, R = 1;
+    SlabView view{};                 // the lattice's view (an ensemble's kernels take theirs from the replica table)
+    // the clustering in force (cetkmc_cluster / _cluster_import, cetkmc_ensemble_analyze / _cluster_import); grains < 0: none
+    const int *labels = nullptr, *roots = nullptr, *stats = nullptr;
+    int64_t grains = -1, max_grains = 0;      // of all lattices together, of the lattice that has most
+    int n = 0;                                // the kernels' grain count (an ensemble's take theirs from the offsets)
+    // f(ens...) with no argument or with the ensemble's selector: launch(k_x<decltype(ens)...>, ..., ens...)
+    template <class F> void run(EnsUse use, F&& f) const
+    {
+        if (e) f(EnsSel{e->d_table, 0, 0, use == ENS_VIEWS ? 0 : (int64_t)L * L * L, use == ENS_GRAINS ? e->d_cc_offs : nullptr});
+        else f();
+    }
+    // blocks of 256 threads over the grains of a lattice (grid-stride kernels), times the lattices
+    dim3 grain_grid(int64_t blocks) const { return dim3((unsigned)std::min<int64_t>(blocks, 4096), (unsigned)R); }
+};
+}
+// needs: ONE_LATTICE refuses an ensemble's own handle (a replica is a lattice), OWNER anything but a handle that keeps its own
+// maps; CLUSTERS a clustering; SOLID / ORIGIN name the map family, MAP asks for its maps to be on; VIEWS: the ensemble's
+// kernels read the replicas' views
+enum : unsigned { ONE_LATTICE = 1, OWNER = 2, CLUSTERS = 4, SOLID = 8, ORIGIN = 16, MAP = 32, VIEWS = 64 };
+static std::string no_clusters(const char* fn, bool ens) { return std::string(fn) + (ens ? " needs a preceding cetkmc_ensemble_analyze" : " needs a preceding cetkmc_cluster"); }
+static std::string no_map(const char* fn, bool ens, unsigned needs)
+{
+    const std::string fam = needs & SOLID ? "solid" : "origin";
+    return std::string(fn) + (ens ? " needs the maps (cetkmc_ensemble_" : " needs a map (cetkmc_") + fam + "_begin)";
+}
+static int lattices(const char* fn, void* handle, bool ens, unsigned needs, Lattices* out)
+{
+    const std::string f(fn);
+    Lattices& A = *out;
+    if (!handle) return fail(!ens && (needs & OWNER) ? "null handle" : "null argument");
+    if (ens) {
+        Ens* e = A.e = ens_of(handle);
+        if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
+        A.h0 = e->reps[0]; A.hs = e->reps; A.R = e->R;
+        if ((needs & MAP) && !((needs & SOLID ? e->d_solid_block && A.h0->solid_on : e->d_origin_block && A.h0->origin_on)))
+            return fail(no_map(fn, true, needs));
+        if (!e->an_clusters.empty()) {
+            A.labels = e->d_cc_labels; A.roots = e->d_cc_roots; A.stats = e->d_cc_stats; A.grains = 0;
+            for (int64_t c : e->an_clusters) { A.grains += c; A.max_grains = std::max(A.max_grains, c); }
+        }
+    } else {
+        Handle* h = A.h0 = (Handle*)handle;
+        if ((needs & ONE_LATTICE) && ens_of(handle)) return fail(f + " takes one lattice: an ensemble handle goes to cetkmc_ensemble_" + (fn + 7));
+        if ((needs & OWNER) && h->in_ensemble)
+            return fail(f + " takes a single-lattice handle: an ensemble's maps are kept by cetkmc_ensemble_" + (needs & SOLID ? "solid_*" : "origin_*"));
+        if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
+        if ((needs & MAP) && !(needs & SOLID ? h->solid_on : h->origin_on)) return fail(no_map(fn, false, needs));
+        A.hs = {h}; A.view = view_of(h, 0);
+        if (h->cc_n_clusters >= 0) {
+            A.labels = h->d_cc_labels; A.roots = h->d_cc_roots; A.stats = h->d_cc_stats;
+            A.grains = A.max_grains = h->cc_n_clusters; A.n = (int)h->cc_n_clusters;
+        }
+    }
+    if ((needs & CLUSTERS) && A.grains < 0) return fail(no_clusters(fn, ens));
+    A.stream = A.h0->stream; A.L = A.h0->L;
+    HIPCHK(hipSetDevice(A.h0->dev));
+    if (A.e && (needs & VIEWS)) CHK(ens_push_views(A.e));
+    return 0;
+}
+
+// n_lay + n_gr records of NW words W for a pass: initialised on the stream (init: the k_*_rec_init kernel; null: zeroes),
+// filled (go = the launches, or its error) and copied out, n_lay records to `layers` and the first n_copy of the others to `grains`
+extern "C++" template <class W, class Go>
+static int fill_records(Handle* h, hipStream_t st, const char* what, int NW, void (*init)(W*, int64_t), int64_t n_lay, int64_t n_gr, int64_t n_copy,
+                        void* layers, void* grains, Go&& go)
+{
+    DevTmp<W> d_rec;
+    const int64_t words = (n_lay + n_gr) * NW, rec_bytes = NW * (int64_t)sizeof(W);
+    if (d_rec.alloc((size_t)words) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(std::string(what) + ": no device memory for " + std::to_string(n_lay + n_gr) + " records of " + std::to_string(rec_bytes) + " bytes");
+    }
+    if (init) launch(init, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, st, nullptr, nullptr, d_rec.p, words);
+    else HIPCHK(hipMemsetAsync(d_rec.p, 0, (size_t)(words * (int64_t)sizeof(W)), st));
+    CHK(go(d_rec.p, d_rec.p + n_lay * NW));
+    HIPCHK(hipGetLastError());
+    if (n_lay > 0) HIPCHK(hipMemcpyAsync(layers, d_rec.p, (size_t)(n_lay * rec_bytes), hipMemcpyDeviceToHost, st));
+    if (n_copy > 0) HIPCHK(hipMemcpyAsync(grains, d_rec.p + n_lay * NW, (size_t)(n_copy * rec_bytes), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h->cnt.bytes_d2h += (n_lay + std::max<int64_t>(n_copy, 0)) * rec_bytes;
+    return 0;
+}
+
 // ---- solidification-front diagnostics (front.hpp) ----------------------------------------------
 static dim3 front_grid(int L, int R)
 {
@@ -3135,52 +3231,30 @@ static dim3 front_grid(int L, int R)
                 (unsigned)R);
 }
 
-int cetkmc_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out)
-{
-    Handle* h = (Handle*)handle;
-    if (!h || !out) return fail("null argument");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_front_stats needs the whole lattice in one slab");
-    HIPCHK(hipSetDevice(h->dev));
-    const dim3 g = front_grid(h->L, 1);
-    const int nb = (int)(g.x * g.y);
-    DevTmp<FrontPart> part;
-    DevTmp<FrontStats> d_out;
-    HIPCHK(part.alloc((size_t)nb));
-    HIPCHK(d_out.alloc(1));
-    hipLaunchKernelGGL(k_front_stats, g, dim3(256), 0, h->stream, view_of(h, 0), h->kp.T_melt, inv_dx, part.p);
-    hipLaunchKernelGGL(k_front_fold, dim3(1), dim3(256), 0, h->stream, (const FrontPart*)part.p, nb, h->L, d_out.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(FrontStats), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->cnt.bytes_d2h += (int64_t)sizeof(FrontStats);
-    return 0;
-}
-
-int cetkmc_ensemble_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out)
+static int front_stats(const char* fn, void* handle, bool ens, double inv_dx, struct cetkmc_front_stats* out)
 {
     if (!handle || !out) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
-    const int R = e->R, L = e->L;
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    const dim3 g = front_grid(L, R);
+    Lattices A;
+    CHK(lattices(fn, handle, ens, VIEWS, &A));
+    Handle* h = A.h0;
+    const dim3 g = front_grid(A.L, A.R);
     const int nb = (int)(g.x * g.y);
-    if (!e->d_front_part) {
-        HIPCHK(hipMalloc((void**)&e->d_front_part, (size_t)R * nb * sizeof(FrontPart)));
-        HIPCHK(hipMalloc((void**)&e->d_front_out, (size_t)R * sizeof(FrontStats)));
-    }
-    for (int r = 0; r < R; ++r) e->table[(size_t)r].kp = e->reps[(size_t)r]->kp;      // T_melt of the replica's own parameters
-    CHK(ens_push_views(e));
-    EnsSel sel{e->d_table, 0, 0, 0, nullptr};
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_front_stats<EnsSel>), g, dim3(256), 0, st, SlabView{}, 0.0, inv_dx, e->d_front_part, sel);
-    hipLaunchKernelGGL(k_front_fold, dim3((unsigned)R), dim3(256), 0, st, (const FrontPart*)e->d_front_part, nb, L, e->d_front_out);
+    CHK(grow(&h->d_front_part, &h->cap_front_part, (size_t)A.R * nb));      // [R][blocks of a lattice] partials, [R] results
+    CHK(grow(&h->d_front_out, &h->cap_front_out, (size_t)A.R));
+    A.run(ENS_VIEWS, [&](auto... sel) {      // (a replica's kernel takes T_melt from its own parameters)
+        launch(k_front_stats<decltype(sel)...>, g, dim3(256), 0, A.stream, nullptr, nullptr, A.view, h->kp.T_melt, inv_dx, h->d_front_part, sel...);
+    });
+    launch(k_front_fold, dim3((unsigned)A.R), dim3(256), 0, A.stream, nullptr, nullptr, h->d_front_part, nb, A.L, h->d_front_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, e->d_front_out, (size_t)R * sizeof(FrontStats), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h0->cnt.bytes_d2h += (int64_t)R * (int64_t)sizeof(FrontStats);
+    HIPCHK(hipMemcpyAsync(out, h->d_front_out, (size_t)A.R * sizeof(FrontStats), hipMemcpyDeviceToHost, A.stream));
+    HIPCHK(hipStreamSynchronize(A.stream));
+    h->cnt.bytes_d2h += (int64_t)A.R * (int64_t)sizeof(FrontStats);
     return 0;
+}
+int cetkmc_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out) { return front_stats("cetkmc_front_stats", handle, false, inv_dx, out); }
+int cetkmc_ensemble_front_stats(void* handle, double inv_dx, struct cetkmc_front_stats* out)
+{
+    return front_stats("cetkmc_ensemble_front_stats", handle, true, inv_dx, out);
 }
 
 // ---- layer-resolved grain structure (layer.hpp) ------------------------------------------------
@@ -3190,62 +3264,37 @@ static dim3 layer_grid(int L, int R)
                 (unsigned)R);
 }
 
-int cetkmc_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out)
-{
-    Handle* h = (Handle*)handle;
-    if (!h || !out) return fail("null argument");
-    if (ens_of(handle)) return fail("cetkmc_layer_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_layer_profile");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_layer_profile needs the whole lattice in one slab");
-    if (h->cc_n_clusters < 0) return fail("cetkmc_layer_profile needs a preceding cetkmc_cluster");
-    HIPCHK(hipSetDevice(h->dev));
-    const int L = h->L, nc = (int)h->cc_n_clusters;
-    const dim3 g = layer_grid(L, 1);
-    DevTmp<uint8_t> eq;
-    DevTmp<LayerRec> part, d_out;
-    HIPCHK(eq.alloc((size_t)nc + 1));
-    HIPCHK(part.alloc((size_t)L * g.x));
-    HIPCHK(d_out.alloc((size_t)L));
-    hipLaunchKernelGGL(k_layer_class, dim3((unsigned)(nc / 256 + 1)), dim3(256), 0, h->stream, (const int*)h->d_cc_stats, nc, ar_threshold, eq.p);
-    hipLaunchKernelGGL(k_layer_profile, g, dim3(256), 0, h->stream, view_of(h, 0), (const int*)h->d_cc_labels, (const int*)h->d_cc_roots,
-                       (const uint8_t*)eq.p, part.p);
-    hipLaunchKernelGGL(k_layer_fold, dim3((unsigned)L, 1), dim3(64), 0, h->stream, (const LayerRec*)part.p, (int)g.x, d_out.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)L * sizeof(LayerRec), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->cnt.bytes_d2h += (int64_t)L * (int64_t)sizeof(LayerRec);
-    return 0;
-}
-
-int cetkmc_ensemble_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out)
+static int layer_profile(const char* fn, void* handle, bool ens, double ar_threshold, struct cetkmc_layer_rec* out)
 {
     if (!handle || !out) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
-    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_layer_profile needs a preceding cetkmc_ensemble_analyze");
-    const int R = e->R, L = e->L;
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
+    Lattices A;
+    CHK(lattices(fn, handle, ens, ONE_LATTICE | CLUSTERS | VIEWS, &A));
+    Handle* h = A.h0;
+    const int L = A.L, R = A.R;
     const dim3 g = layer_grid(L, R);
-    int64_t total = 0, maxc = 0;
-    for (int r = 0; r < R; ++r) { total += e->an_clusters[(size_t)r]; maxc = std::max(maxc, e->an_clusters[(size_t)r]); }
-    if (!e->d_layer_part) {
-        HIPCHK(hipMalloc((void**)&e->d_layer_part, (size_t)R * L * g.x * sizeof(LayerRec)));
-        HIPCHK(hipMalloc((void**)&e->d_layer_out, (size_t)R * L * sizeof(LayerRec)));
-    }
-    CHK(grow(&e->d_layer_eq, &e->cap_layer_eq, (size_t)(total + R)));
-    CHK(ens_push_views(e));
-    EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer_class<EnsSel>), dim3((unsigned)std::min<int64_t>(maxc / 256 + 1, 4096), (unsigned)R), dim3(256), 0, st,
-                       (const int*)e->d_cc_stats, 0, ar_threshold, e->d_layer_eq, sel);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer_profile<EnsSel>), g, dim3(256), 0, st, SlabView{}, (const int*)e->d_cc_labels,
-                       (const int*)e->d_cc_roots, (const uint8_t*)e->d_layer_eq, e->d_layer_part, sel);
-    hipLaunchKernelGGL(k_layer_fold, dim3((unsigned)L, (unsigned)R), dim3(64), 0, st, (const LayerRec*)e->d_layer_part, (int)g.x, e->d_layer_out);
+    CHK(grow(&h->d_layer_eq, &h->cap_layer_eq, (size_t)(A.grains + R)));          // a lattice has one more byte than grains
+    CHK(grow(&h->d_layer_part, &h->cap_layer_part, (size_t)R * L * g.x));         // [R][L][tiles] partials, [R][L] records
+    CHK(grow(&h->d_layer_out, &h->cap_layer_out, (size_t)R * L));
+    A.run(ENS_GRAINS, [&](auto... sel) {
+        launch(k_layer_class<decltype(sel)...>, A.grain_grid(A.max_grains / 256 + 1), dim3(256), 0, A.stream, nullptr, nullptr, A.stats, A.n, ar_threshold,
+               h->d_layer_eq, sel...);
+        launch(k_layer_profile<decltype(sel)...>, g, dim3(256), 0, A.stream, nullptr, nullptr, A.view, A.labels, A.roots, h->d_layer_eq, h->d_layer_part,
+               sel...);
+    });
+    launch(k_layer_fold, dim3((unsigned)L, (unsigned)R), dim3(64), 0, A.stream, nullptr, nullptr, h->d_layer_part, (int)g.x, h->d_layer_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, e->d_layer_out, (size_t)R * L * sizeof(LayerRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h0->cnt.bytes_d2h += (int64_t)R * L * (int64_t)sizeof(LayerRec);
+    HIPCHK(hipMemcpyAsync(out, h->d_layer_out, (size_t)R * L * sizeof(LayerRec), hipMemcpyDeviceToHost, A.stream));
+    HIPCHK(hipStreamSynchronize(A.stream));
+    h->cnt.bytes_d2h += (int64_t)R * L * (int64_t)sizeof(LayerRec);
     return 0;
+}
+int cetkmc_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out)
+{
+    return layer_profile("cetkmc_layer_profile", handle, false, ar_threshold, out);
+}
+int cetkmc_ensemble_layer_profile(void* handle, double ar_threshold, struct cetkmc_layer_rec* out)
+{
+    return layer_profile("cetkmc_ensemble_layer_profile", handle, true, ar_threshold, out);
 }
 
 // ---- grain-boundary misorientation and pole histograms (texture.hpp) ---------------------------
@@ -3301,102 +3350,61 @@ static int texture_rows(Handle* h, hipStream_t st, int64_t rows, int nb, int64_t
     return 0;
 }
 
-int cetkmc_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist, int64_t* bad)
+static int texture_profile(const char* fn, void* handle, bool ens, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist,
+                           int64_t* bad)
 {
-    Handle* h = (Handle*)handle;
-    if (!h || !args) return fail("null argument");
-    if (ens_of(handle)) return fail("cetkmc_texture_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_texture_profile");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_texture_profile needs the whole lattice in one slab");
-    if (h->cc_n_clusters < 0) return fail("cetkmc_texture_profile needs a preceding cetkmc_cluster");
-    TexArgs A;
-    CHK(texture_args("cetkmc_texture_profile", args, &A));
-    HIPCHK(hipSetDevice(h->dev));
-    return texture_rows(h, h->stream, h->L, A.n_bins, gb_hist, pole_hist, bad, [&](unsigned long long* d_rows) {
-        launch(k_texture_profile<>, texture_grid(h->L, 1), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), (const int*)h->d_cc_labels, A, d_rows);
+    if (!handle || !args) return fail("null argument");
+    Lattices A;
+    CHK(lattices(fn, handle, ens, ONE_LATTICE | CLUSTERS | VIEWS, &A));
+    TexArgs T;
+    CHK(texture_args(fn, args, &T));
+    return texture_rows(A.h0, A.stream, (int64_t)A.R * A.L, T.n_bins, gb_hist, pole_hist, bad, [&](unsigned long long* d_rows) {
+        A.run(ENS_LABELS, [&](auto... sel) {
+            launch(k_texture_profile<decltype(sel)...>, texture_grid(A.L, A.R), dim3(256), 0, A.stream, nullptr, nullptr, A.view, A.labels, T, d_rows, sel...);
+        });
     });
 }
-
+int cetkmc_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist, int64_t* bad)
+{
+    return texture_profile("cetkmc_texture_profile", handle, false, args, gb_hist, pole_hist, bad);
+}
 int cetkmc_ensemble_texture_profile(void* handle, const struct cetkmc_texture_args* args, int64_t* gb_hist, int64_t* pole_hist,
                                     int64_t* bad)
 {
-    if (!handle || !args) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
-    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_texture_profile needs a preceding cetkmc_ensemble_analyze");
-    TexArgs A;
-    CHK(texture_args("cetkmc_ensemble_texture_profile", args, &A));
-    const int R = e->R, L = e->L;
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    CHK(ens_push_views(e));
-    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, nullptr};
-    return texture_rows(h0, st, (int64_t)R * L, A.n_bins, gb_hist, pole_hist, bad, [&](unsigned long long* d_rows) {
-        launch(k_texture_profile<EnsSel>, texture_grid(L, R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, (const int*)e->d_cc_labels, A, d_rows, sel);
-    });
+    return texture_profile("cetkmc_ensemble_texture_profile", handle, true, args, gb_hist, pole_hist, bad);
 }
+
 
 // ---- per-grain table (grain.hpp) ----------------------------------------------------------------
-// zero `total` records on the stream, fill them (go = the two launches) and copy the first `n` to the caller
-extern "C++" template <class Go>
-static int grain_records(Handle* h, hipStream_t st, int64_t total, int64_t n, struct cetkmc_grain_rec* out, Go&& go)
-{
-    DevTmp<unsigned long long> d_rec;
-    if (d_rec.alloc((size_t)total * GRAIN_NW) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("per-grain table: no device memory for " + std::to_string(total) + " records of " + std::to_string(sizeof(GrainRec)) + " bytes");
-    }
-    HIPCHK(hipMemsetAsync(d_rec.p, 0, (size_t)total * sizeof(GrainRec), st));
-    go(d_rec.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_rec.p, (size_t)n * sizeof(GrainRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h->cnt.bytes_d2h += n * (int64_t)sizeof(GrainRec);
-    return 0;
-}
 static unsigned grain_blocks(int L) { return (unsigned)(((int64_t)L * L * L + GRAIN_VPB - 1) / GRAIN_VPB); }
 
-int cetkmc_grain_table(void* handle, int64_t cap, struct cetkmc_grain_rec* out)
+// cap: how many records the caller takes (the ensemble call: all of them)
+static int grain_table(const char* fn, void* handle, bool ens, int64_t cap, struct cetkmc_grain_rec* out)
 {
-    Handle* h = (Handle*)handle;
-    if (!h) return fail("null handle");
-    if (ens_of(handle)) return fail("cetkmc_grain_table takes one lattice: an ensemble handle goes to cetkmc_ensemble_grain_table");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_grain_table needs the whole lattice in one slab");
-    if (h->cc_n_clusters < 0) return fail("cetkmc_grain_table needs a preceding cetkmc_cluster");
-    const int64_t nc = h->cc_n_clusters, n = std::min<int64_t>(cap, nc);
+    if (!handle) return fail(ens ? "null argument" : "null handle");
+    Lattices A;
+    CHK(lattices(fn, handle, ens, ONE_LATTICE | CLUSTERS | VIEWS, &A));
+    const int64_t nc = A.grains, n = std::min<int64_t>(cap, nc);
     if (n <= 0) return 0;
     if (!out) return fail("null argument");
-    HIPCHK(hipSetDevice(h->dev));
     // the device table holds every grain (the pass adds by label); the first n records are the caller's
-    return grain_records(h, h->stream, nc, n, out, [&](unsigned long long* d_rec) {
-        launch(k_grain_table<>, dim3(grain_blocks(h->L)), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), (const int*)h->d_cc_labels, (int)nc, d_rec);
-        launch(k_grain_first<>, dim3((unsigned)std::min<int64_t>((nc + 255) / 256, 4096)), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0),
-               (const int*)h->d_cc_roots, (int)nc, d_rec);
+    return fill_records<unsigned long long>(A.h0, A.stream, "per-grain table", GRAIN_NW, nullptr, 0, nc, n, nullptr, out,
+                                            [&](unsigned long long*, unsigned long long* d_rec) {
+        A.run(ENS_GRAINS, [&](auto... sel) {
+            launch(k_grain_table<decltype(sel)...>, dim3(grain_blocks(A.L), (unsigned)A.R), dim3(256), 0, A.stream, nullptr, nullptr, A.view, A.labels, A.n, d_rec,
+                   sel...);
+            launch(k_grain_first<decltype(sel)...>, A.grain_grid((A.max_grains + 255) / 256), dim3(256), 0, A.stream, nullptr, nullptr, A.view, A.roots, A.n,
+                   d_rec, sel...);
+        });
+        return 0;
     });
 }
-
+int cetkmc_grain_table(void* handle, int64_t cap, struct cetkmc_grain_rec* out) { return grain_table("cetkmc_grain_table", handle, false, cap, out); }
 int cetkmc_ensemble_grain_table(void* handle, struct cetkmc_grain_rec* out)
 {
-    if (!handle) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
-    if (e->an_clusters.empty()) return fail("cetkmc_ensemble_grain_table needs a preceding cetkmc_ensemble_analyze");
-    const int R = e->R, L = e->L;
-    int64_t total = 0, maxc = 0;
-    for (int r = 0; r < R; ++r) { total += e->an_clusters[(size_t)r]; maxc = std::max(maxc, e->an_clusters[(size_t)r]); }
-    if (total <= 0) return 0;
-    if (!out) return fail("null argument");
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    CHK(ens_push_views(e));
-    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
-    return grain_records(h0, st, total, total, out, [&](unsigned long long* d_rec) {
-        launch(k_grain_table<EnsSel>, dim3(grain_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, (const int*)e->d_cc_labels, 0, d_rec, sel);
-        launch(k_grain_first<EnsSel>, dim3((unsigned)std::min<int64_t>((maxc + 255) / 256, 4096), (unsigned)R), dim3(256), 0, st, nullptr, nullptr,
-               SlabView{}, (const int*)e->d_cc_roots, 0, d_rec, sel);
-    });
+    return grain_table("cetkmc_ensemble_grain_table", handle, true, INT64_MAX, out);
 }
+
 
 // ---- solidification map (solid.hpp) -------------------------------------------------------------
 // One device block for the maps of hs (one handle, or every replica of an ensemble): all stamps, then all doubles, the two
@@ -3422,51 +3430,6 @@ static dim3 solid_update_grid(int L, int pitchT, int R, int pairs_per_block)
 }
 static unsigned solid_blocks(int L) { return (unsigned)(((int64_t)L * L * L + SOLID_VPB - 1) / SOLID_VPB); }
 
-// (re)start the maps of hs in *block (allocated here if null); go = the snapshot launch
-extern "C++" template <class Go>
-static int solid_begin(std::vector<Handle*>& hs, void** block, SolidMap** d_maps, hipStream_t st, Go&& go)
-{
-    Handle* h0 = hs[0];
-    const size_t R = hs.size();
-    const SolidLayout y = solid_layout(h0->L, h0->pitchT, R);
-    if (!*block) {
-        if (hipMalloc(block, y.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *block = nullptr;
-            return fail("solidification map: no device memory for " + std::to_string(y.bytes) + " bytes");
-        }
-    }
-    // no handle has a map until everything below has completed: an error on the way leaves none (a second begin included)
-    for (Handle* h : hs) { h->solid_on = false; h->solid_recorded = 0; }
-    char* b = (char*)*block;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    std::vector<SolidMap> tab(R);
-    for (size_t r = 0; r < R; ++r) {
-        SolidMap& m = tab[r];
-        m.stamp = (long long*)b + r * y.n;
-        double* d = (double*)(b + y.o_dbl) + r * 5 * y.n;
-        m.Ts = d; m.g = d + y.n; m.cool = d + 4 * y.n;
-        m.snap = (uint8_t*)(b + y.o_snap + r * up(y.nsnap));
-        m.Tsnap = (double*)(b + y.o_tsnap + r * up(y.nsnap * 8));
-        m.cnt = (unsigned long long*)(b + y.o_cnt) + 3 * r;
-        hs[r]->solid = m;
-    }
-    if (d_maps) *d_maps = (SolidMap*)(b + y.o_tab);
-    auto issue = [&]() -> int {
-        HIPCHK(hipMemsetAsync(b, 0xff, R * y.n * 8, st));                           // stamp = -1
-        HIPCHK(hipMemsetAsync(b + y.o_dbl, 0, y.bytes - y.o_dbl, st));               // +0.0, snapshots, counters, table
-        HIPCHK(hipMemcpyAsync(b + y.o_tab, tab.data(), R * sizeof(SolidMap), hipMemcpyHostToDevice, st));
-        go();
-        HIPCHK(hipGetLastError());
-        return 0;
-    };
-    const int rc = issue();
-    const hipError_t synced = hipStreamSynchronize(st);         // also after an error: the table is copied from this frame
-    if (rc) return rc;
-    HIPCHK(synced);
-    for (Handle* h : hs) h->solid_on = true;
-    return 0;
-}
 static int solid_update_args(const char* fn, int64_t stamp, double inv_dx, double dt)
 {
     const std::string f(fn);
@@ -3481,16 +3444,7 @@ static int solid_scales(const char* fn, const struct cetkmc_solid_args* a)
         if (!std::isfinite(a->qscale[c]) || !(a->qscale[c] > 0.0)) return fail(std::string(fn) + ": qscale[" + std::to_string(c) + "] must be finite and > 0");
     return 0;
 }
-// the single-lattice handle of begin / update / end, or a refusal
-static int solid_single(const char* fn, Handle* h, bool need_map)
-{
-    const std::string f(fn);
-    if (!h) return fail("null handle");
-    if (h->in_ensemble) return fail(f + " takes a single-lattice handle: an ensemble's maps are kept by cetkmc_ensemble_solid_*");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
-    if (need_map && !h->solid_on) return fail(f + " needs a map (cetkmc_solid_begin)");
-    return 0;
-}
+
 // the counters of n lattices behind an update -> info, and each handle's running record count
 static int solid_collect(std::vector<Handle*>& hs, const unsigned long long* d_cnt, hipStream_t st, struct cetkmc_solid_info* info)
 {
@@ -3505,42 +3459,102 @@ static int solid_collect(std::vector<Handle*>& hs, const unsigned long long* d_c
     return 0;
 }
 
-int cetkmc_solid_begin(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    CHK(solid_single("cetkmc_solid_begin", h, false));
-    HIPCHK(hipSetDevice(h->dev));
-    std::vector<Handle*> hs{h};
-    return solid_begin(hs, &h->d_solid_block, nullptr, h->stream, [&] {
-        launch(k_solid_snapshot<>, solid_update_grid(h->L, h->pitchT, 1, 256), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), h->solid, nullptr);
-    });
-}
+// the device table of the maps a launch indexes by replica (null: one lattice, its map goes by value)
+static const SolidMap* solid_maps(const Lattices& A) { return A.e ? A.e->d_solid_maps : nullptr; }
 
-int cetkmc_solid_end(void* handle)
+// (re)start the maps of the pass's lattices in their block (allocated here if there is none)
+static int solid_begin(const char* fn, void* handle, bool ens)
 {
-    Handle* h = (Handle*)handle;
-    CHK(solid_single("cetkmc_solid_end", h, false));
-    if (!h->d_solid_block) return fail("cetkmc_solid_end needs a map (cetkmc_solid_begin)");      // (a begin that failed half way keeps its block)
-    HIPCHK(hipSetDevice(h->dev));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipFree(h->d_solid_block));
-    h->d_solid_block = nullptr; h->solid = SolidMap{}; h->solid_on = false; h->solid_recorded = 0;
+    Lattices A;
+    CHK(lattices(fn, handle, ens, OWNER | SOLID | VIEWS, &A));
+    Handle* h0 = A.h0;
+    hipStream_t st = A.stream;
+    void** block = A.e ? &A.e->d_solid_block : &h0->d_solid_block;
+    const size_t R = (size_t)A.R;
+    const SolidLayout y = solid_layout(A.L, h0->pitchT, R);
+    if (!*block) {
+        if (hipMalloc(block, y.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *block = nullptr;
+            return fail("solidification map: no device memory for " + std::to_string(y.bytes) + " bytes");
+        }
+    }
+    // no handle has a map until everything below has completed: an error on the way leaves none (a second begin included)
+    for (Handle* h : A.hs) { h->solid_on = false; h->solid_recorded = 0; }
+    char* b = (char*)*block;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    std::vector<SolidMap> tab(R);
+    for (size_t r = 0; r < R; ++r) {
+        SolidMap& m = tab[r];
+        m.stamp = (long long*)b + r * y.n;
+        double* d = (double*)(b + y.o_dbl) + r * 5 * y.n;
+        m.Ts = d; m.g = d + y.n; m.cool = d + 4 * y.n;
+        m.snap = (uint8_t*)(b + y.o_snap + r * up(y.nsnap));
+        m.Tsnap = (double*)(b + y.o_tsnap + r * up(y.nsnap * 8));
+        m.cnt = (unsigned long long*)(b + y.o_cnt) + 3 * r;
+        A.hs[r]->solid = m;
+    }
+    if (A.e) A.e->d_solid_maps = (SolidMap*)(b + y.o_tab);
+    auto issue = [&]() -> int {
+        HIPCHK(hipMemsetAsync(b, 0xff, R * y.n * 8, st));                           // stamp = -1
+        HIPCHK(hipMemsetAsync(b + y.o_dbl, 0, y.bytes - y.o_dbl, st));               // +0.0, snapshots, counters, table
+        HIPCHK(hipMemcpyAsync(b + y.o_tab, tab.data(), R * sizeof(SolidMap), hipMemcpyHostToDevice, st));
+        A.run(ENS_VIEWS, [&](auto... sel) {
+            launch(k_solid_snapshot<decltype(sel)...>, solid_update_grid(A.L, h0->pitchT, A.R, 256), dim3(256), 0, st, nullptr, nullptr, A.view, h0->solid,
+                   solid_maps(A), sel...);
+        });
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    const int rc = issue();
+    const hipError_t synced = hipStreamSynchronize(st);         // also after an error: the table is copied from this frame
+    if (rc) return rc;
+    HIPCHK(synced);
+    for (Handle* h : A.hs) h->solid_on = true;
     return 0;
 }
+int cetkmc_solid_begin(void* handle) { return solid_begin("cetkmc_solid_begin", handle, false); }
+int cetkmc_ensemble_solid_begin(void* handle) { return solid_begin("cetkmc_ensemble_solid_begin", handle, true); }
 
+static int solid_end(const char* fn, void* handle, bool ens)
+{
+    Lattices A;
+    CHK(lattices(fn, handle, ens, OWNER | SOLID, &A));
+    void*& block = A.e ? A.e->d_solid_block : A.h0->d_solid_block;
+    if (!block) return fail(no_map(fn, ens, SOLID));      // (a begin that failed half way keeps its block)
+    HIPCHK(hipStreamSynchronize(A.stream));
+    HIPCHK(hipFree(block));
+    block = nullptr;
+    if (A.e) A.e->d_solid_maps = nullptr;
+    for (Handle* h : A.hs) { h->solid = SolidMap{}; h->solid_on = false; h->solid_recorded = 0; }
+    return 0;
+}
+int cetkmc_solid_end(void* handle) { return solid_end("cetkmc_solid_end", handle, false); }
+int cetkmc_ensemble_solid_end(void* handle) { return solid_end("cetkmc_ensemble_solid_end", handle, true); }
+
+static int solid_update(const char* fn, void* handle, bool ens, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info)
+{
+    Lattices A;
+    CHK(lattices(fn, handle, ens, OWNER | SOLID | MAP | VIEWS, &A));
+    CHK(solid_update_args(fn, stamp, inv_dx, dt));
+    Handle* h0 = A.h0;
+    HIPCHK(hipMemsetAsync(h0->solid.cnt, 0, (size_t)A.R * 3 * 8, A.stream));       // replica 0's counters head the block's [R][3]
+    A.run(ENS_VIEWS, [&](auto... sel) {
+        launch(k_solid_update<decltype(sel)...>, solid_update_grid(A.L, h0->pitchT, A.R, SOLID_PPB), dim3(256), 0, A.stream, nullptr, nullptr, A.view,
+               h0->solid, solid_maps(A), (long long)stamp, inv_dx, dt, sel...);
+    });
+    HIPCHK(hipGetLastError());
+    return solid_collect(A.hs, h0->solid.cnt, A.stream, info);
+}
 int cetkmc_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info)
 {
-    Handle* h = (Handle*)handle;
-    CHK(solid_single("cetkmc_solid_update", h, true));
-    CHK(solid_update_args("cetkmc_solid_update", stamp, inv_dx, dt));
-    HIPCHK(hipSetDevice(h->dev));
-    HIPCHK(hipMemsetAsync(h->solid.cnt, 0, 3 * 8, h->stream));
-    launch(k_solid_update<>, solid_update_grid(h->L, h->pitchT, 1, SOLID_PPB), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), h->solid, nullptr,
-           (long long)stamp, inv_dx, dt);
-    HIPCHK(hipGetLastError());
-    std::vector<Handle*> hs{h};
-    return solid_collect(hs, h->solid.cnt, h->stream, info);
+    return solid_update("cetkmc_solid_update", handle, false, stamp, inv_dx, dt, info);
 }
+int cetkmc_ensemble_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info)
+{
+    return solid_update("cetkmc_ensemble_solid_update", handle, true, stamp, inv_dx, dt, info);
+}
+
 
 int cetkmc_solid_read(void* handle, int64_t* stamp, double* T_s, double* g, double* cool)
 {
@@ -3560,123 +3574,41 @@ int cetkmc_solid_read(void* handle, int64_t* stamp, double* T_s, double* g, doub
     return 0;
 }
 
-// initialise n_lay + n_gr records on the stream, fill them (go = the launch) and copy n_lay layer and n_copy grain records out
-extern "C++" template <class Go>
-static int solid_records(Handle* h, hipStream_t st, int64_t n_lay, int64_t n_gr, int64_t n_copy, struct cetkmc_solid_rec* layers,
-                         struct cetkmc_solid_rec* grains, Go&& go)
+// cap: how many grain records the caller takes (the ensemble call: all of them)
+static int solid_profile(const char* fn, void* handle, bool ens, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers, int64_t cap,
+                         struct cetkmc_solid_rec* grains)
 {
-    DevTmp<long long> d_rec;
-    const int64_t words = (n_lay + n_gr) * SOLID_NW;
-    if (d_rec.alloc((size_t)words) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("solidification profile: no device memory for " + std::to_string(n_lay + n_gr) + " records of " + std::to_string(sizeof(SolidRec)) + " bytes");
-    }
-    launch(k_solid_rec_init, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, st, nullptr, nullptr, d_rec.p, words);
-    go(d_rec.p, d_rec.p + n_lay * SOLID_NW);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(layers, d_rec.p, (size_t)n_lay * sizeof(SolidRec), hipMemcpyDeviceToHost, st));
-    if (n_copy > 0) HIPCHK(hipMemcpyAsync(grains, d_rec.p + n_lay * SOLID_NW, (size_t)n_copy * sizeof(SolidRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h->cnt.bytes_d2h += (n_lay + std::max<int64_t>(n_copy, 0)) * (int64_t)sizeof(SolidRec);
-    return 0;
+    const bool outputs = args && layers;      // the single call asks for them first, the ensemble call for its maps
+    if (!ens && !outputs) return fail("null argument");
+    Lattices A;
+    CHK(lattices(fn, handle, ens, ONE_LATTICE | SOLID | MAP, &A));
+    if (!outputs) return fail("null argument");
+    CHK(solid_scales(fn, args));
+    if (grains && A.grains < 0) return fail(no_clusters(fn, ens) + " for its grain records");
+    const int64_t nc = grains ? A.grains : 0, n = std::min<int64_t>(cap, nc);
+    const bool with_grains = grains && n > 0;
+    // the device table holds every grain (the pass adds by label); the first n records are the caller's
+    return fill_records<long long>(A.h0, A.stream, "solidification profile", SOLID_NW, k_solid_rec_init, (int64_t)A.R * A.L, with_grains ? nc : 0,
+                                   with_grains ? n : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
+        A.run(ENS_GRAINS, [&](auto... sel) {
+            launch(k_solid_profile<decltype(sel)...>, dim3(solid_blocks(A.L), (unsigned)A.R), dim3(256), 0, A.stream, nullptr, nullptr, A.h0->solid,
+                   solid_maps(A), A.L, with_grains ? A.labels : nullptr, grains ? A.n : 0, args->qscale[0], args->qscale[1], args->qscale[2], args->qscale[3],
+                   d_lay, d_gr, sel...);
+        });
+        return 0;
+    });
 }
-
 int cetkmc_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers, int64_t cap,
                          struct cetkmc_solid_rec* grains)
 {
-    Handle* h = (Handle*)handle;
-    if (!h || !args || !layers) return fail("null argument");
-    if (ens_of(handle)) return fail("cetkmc_solid_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_solid_profile");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail("cetkmc_solid_profile needs the whole lattice in one slab");
-    if (!h->solid_on) return fail("cetkmc_solid_profile needs a map (cetkmc_solid_begin)");
-    CHK(solid_scales("cetkmc_solid_profile", args));
-    if (grains && h->cc_n_clusters < 0) return fail("cetkmc_solid_profile needs a preceding cetkmc_cluster for its grain records");
-    const int64_t nc = grains ? h->cc_n_clusters : 0, n = std::min<int64_t>(cap, nc);
-    const bool with_grains = grains && n > 0;
-    HIPCHK(hipSetDevice(h->dev));
-    // the device table holds every grain (the pass adds by label); the first n records are the caller's
-    return solid_records(h, h->stream, h->L, with_grains ? nc : 0, with_grains ? n : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
-        launch(k_solid_profile<>, dim3(solid_blocks(h->L)), dim3(256), 0, h->stream, nullptr, nullptr, h->solid, nullptr, h->L,
-               with_grains ? (const int*)h->d_cc_labels : nullptr, (int)nc, args->qscale[0], args->qscale[1], args->qscale[2], args->qscale[3], d_lay, d_gr);
-    });
+    return solid_profile("cetkmc_solid_profile", handle, false, args, layers, cap, grains);
 }
-
-static int solid_ensemble(const char* fn, void* handle, bool need_map, Ens** out)
-{
-    if (!handle) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
-    if (need_map && !(e->d_solid_block && e->reps[0]->solid_on)) return fail(std::string(fn) + " needs the maps (cetkmc_ensemble_solid_begin)");
-    *out = e;
-    return 0;
-}
-
-int cetkmc_ensemble_solid_begin(void* handle)
-{
-    Ens* e = nullptr;
-    CHK(solid_ensemble("cetkmc_ensemble_solid_begin", handle, false, &e));
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    CHK(ens_push_views(e));
-    const EnsSel sel{e->d_table, 0, 0, 0, nullptr};
-    return solid_begin(e->reps, &e->d_solid_block, &e->d_solid_maps, st, [&] {
-        launch(k_solid_snapshot<EnsSel>, solid_update_grid(e->L, h0->pitchT, e->R, 256), dim3(256), 0, st, nullptr, nullptr, SlabView{}, SolidMap{},
-               (const SolidMap*)e->d_solid_maps, sel);
-    });
-}
-
-int cetkmc_ensemble_solid_end(void* handle)
-{
-    Ens* e = nullptr;
-    CHK(solid_ensemble("cetkmc_ensemble_solid_end", handle, false, &e));
-    if (!e->d_solid_block) return fail("cetkmc_ensemble_solid_end needs the maps (cetkmc_ensemble_solid_begin)");
-    HIPCHK(hipSetDevice(e->reps[0]->dev));
-    HIPCHK(hipStreamSynchronize(e->reps[0]->stream));
-    HIPCHK(hipFree(e->d_solid_block));
-    e->d_solid_block = nullptr; e->d_solid_maps = nullptr;
-    for (Handle* h : e->reps) { h->solid = SolidMap{}; h->solid_on = false; h->solid_recorded = 0; }
-    return 0;
-}
-
-int cetkmc_ensemble_solid_update(void* handle, int64_t stamp, double inv_dx, double dt, struct cetkmc_solid_info* info)
-{
-    Ens* e = nullptr;
-    CHK(solid_ensemble("cetkmc_ensemble_solid_update", handle, true, &e));
-    CHK(solid_update_args("cetkmc_ensemble_solid_update", stamp, inv_dx, dt));
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    CHK(ens_push_views(e));
-    HIPCHK(hipMemsetAsync(h0->solid.cnt, 0, (size_t)e->R * 3 * 8, st));       // replica 0's counters head the block's [R][3]
-    const EnsSel sel{e->d_table, 0, 0, 0, nullptr};
-    launch(k_solid_update<EnsSel>, solid_update_grid(e->L, h0->pitchT, e->R, SOLID_PPB), dim3(256), 0, st, nullptr, nullptr, SlabView{}, SolidMap{},
-           (const SolidMap*)e->d_solid_maps, (long long)stamp, inv_dx, dt, sel);
-    HIPCHK(hipGetLastError());
-    return solid_collect(e->reps, h0->solid.cnt, st, info);
-}
-
 int cetkmc_ensemble_solid_profile(void* handle, const struct cetkmc_solid_args* args, struct cetkmc_solid_rec* layers,
                                   struct cetkmc_solid_rec* grains)
 {
-    Ens* e = nullptr;
-    CHK(solid_ensemble("cetkmc_ensemble_solid_profile", handle, true, &e));
-    if (!args || !layers) return fail("null argument");
-    CHK(solid_scales("cetkmc_ensemble_solid_profile", args));
-    if (grains && e->an_clusters.empty()) return fail("cetkmc_ensemble_solid_profile needs a preceding cetkmc_ensemble_analyze for its grain records");
-    const int R = e->R, L = e->L;
-    int64_t total = 0;
-    if (grains) for (int r = 0; r < R; ++r) total += e->an_clusters[(size_t)r];
-    const bool with_grains = grains && total > 0;
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
-    return solid_records(h0, st, (int64_t)R * L, with_grains ? total : 0, with_grains ? total : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
-        launch(k_solid_profile<EnsSel>, dim3(solid_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SolidMap{}, (const SolidMap*)e->d_solid_maps, L,
-               with_grains ? (const int*)e->d_cc_labels : nullptr, 0, args->qscale[0], args->qscale[1], args->qscale[2], args->qscale[3], d_lay, d_gr, sel);
-    });
+    return solid_profile("cetkmc_ensemble_solid_profile", handle, true, args, layers, INT64_MAX, grains);
 }
+
 
 // ---- origin map (origin.hpp) --------------------------------------------------------------------
 // One device block for the maps of hs (one handle, or every replica of an ensemble): all words, all censuses, the map table
@@ -3695,12 +3627,15 @@ static OriginLayout origin_layout(int L, size_t R)
 }
 static unsigned origin_blocks(int L) { return (unsigned)(((int64_t)L * L * L + ORIGIN_VPB - 1) / ORIGIN_VPB); }
 
-// (re)start the maps of hs in *block (allocated here if null)
-static int origin_begin(std::vector<Handle*>& hs, void** block, OriginMap** d_maps, OriginRun** d_runs, hipStream_t st)
+// (re)start the maps of the pass's lattices in their block (allocated here if there is none); max_L: the single call's limit
+static int origin_begin(const char* fn, void* handle, bool ens, int max_L)
 {
-    Handle* h0 = hs[0];
-    const size_t R = hs.size();
-    const OriginLayout y = origin_layout(h0->L, R);
+    Lattices A;
+    CHK(lattices(fn, handle, ens, OWNER | ORIGIN, &A));
+    if (A.L > max_L) return fail(std::string(fn) + ": L > " + std::to_string(max_L) + " (the profile packs a voxel's linear index into 24 bits)");
+    void** block = A.e ? &A.e->d_origin_block : &A.h0->d_origin_block;
+    const size_t R = (size_t)A.R;
+    const OriginLayout y = origin_layout(A.L, R);
     if (!*block) {
         if (hipMalloc(block, y.bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -3709,68 +3644,45 @@ static int origin_begin(std::vector<Handle*>& hs, void** block, OriginMap** d_ma
         }
     }
     // no handle has a map until everything below has completed: an error on the way leaves none (a second begin included)
-    for (Handle* h : hs) { h->origin_on = false; h->origin_seq = 0; }
+    for (Handle* h : A.hs) { h->origin_on = false; h->origin_seq = 0; }
     char* b = (char*)*block;
     std::vector<OriginMap> tab(R);
     for (size_t r = 0; r < R; ++r) {
         tab[r].words = (unsigned long long*)b + r * y.n;
-        tab[r].census = (long long*)(b + y.o_census) + r * (size_t)h0->L * 5;
-        hs[r]->origin = tab[r];
+        tab[r].census = (long long*)(b + y.o_census) + r * (size_t)A.L * 5;
+        A.hs[r]->origin = tab[r];
     }
-    if (d_maps) *d_maps = (OriginMap*)(b + y.o_tab);
-    if (d_runs) *d_runs = (OriginRun*)(b + y.o_runs);
+    if (A.e) { A.e->d_origin_maps = (OriginMap*)(b + y.o_tab); A.e->d_origin_runs = (OriginRun*)(b + y.o_runs); }
     auto issue = [&]() -> int {
-        HIPCHK(hipMemsetAsync(b, 0, y.bytes, st));
-        HIPCHK(hipMemcpyAsync(b + y.o_tab, tab.data(), R * sizeof(OriginMap), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(b, 0, y.bytes, A.stream));
+        HIPCHK(hipMemcpyAsync(b + y.o_tab, tab.data(), R * sizeof(OriginMap), hipMemcpyHostToDevice, A.stream));
         return 0;
     };
     const int rc = issue();
-    const hipError_t synced = hipStreamSynchronize(st);         // also after an error: the table is copied from this frame
+    const hipError_t synced = hipStreamSynchronize(A.stream);         // also after an error: the table is copied from this frame
     if (rc) return rc;
     HIPCHK(synced);
-    for (Handle* h : hs) h->origin_on = true;
+    for (Handle* h : A.hs) h->origin_on = true;
     return 0;
 }
-// the single-lattice handle of begin / end, or a refusal
-static int origin_single(const char* fn, Handle* h)
-{
-    const std::string f(fn);
-    if (!h) return fail("null handle");
-    if (h->in_ensemble) return fail(f + " takes a single-lattice handle: an ensemble's maps are kept by cetkmc_ensemble_origin_*");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
-    return 0;
-}
-// the lattice handle (single or replica) of read / census / profile / absorb_events, with a map
-static int origin_lattice(const char* fn, Handle* h)
-{
-    const std::string f(fn);
-    if (!h) return fail("null argument");
-    if (h->slabs.size() != 1 || h->nranks != 1) return fail(f + " needs the whole lattice in one slab");
-    if (!h->origin_on) return fail(f + " needs a map (cetkmc_origin_begin)");
-    return 0;
-}
+int cetkmc_origin_begin(void* handle) { return origin_begin("cetkmc_origin_begin", handle, false, 256); }
+int cetkmc_ensemble_origin_begin(void* handle) { return origin_begin("cetkmc_ensemble_origin_begin", handle, true, INT_MAX); }
 
-int cetkmc_origin_begin(void* handle)
+static int origin_end(const char* fn, void* handle, bool ens)
 {
-    Handle* h = (Handle*)handle;
-    CHK(origin_single("cetkmc_origin_begin", h));
-    if (h->L > 256) return fail("cetkmc_origin_begin: L > 256 (the profile packs a voxel's linear index into 24 bits)");
-    HIPCHK(hipSetDevice(h->dev));
-    std::vector<Handle*> hs{h};
-    return origin_begin(hs, &h->d_origin_block, nullptr, nullptr, h->stream);
-}
-
-int cetkmc_origin_end(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    CHK(origin_single("cetkmc_origin_end", h));
-    if (!h->d_origin_block) return fail("cetkmc_origin_end needs a map (cetkmc_origin_begin)");      // (a begin that failed half way keeps its block)
-    HIPCHK(hipSetDevice(h->dev));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipFree(h->d_origin_block));
-    h->d_origin_block = nullptr; h->origin = OriginMap{}; h->origin_on = false; h->origin_seq = 0;
+    Lattices A;
+    CHK(lattices(fn, handle, ens, OWNER | ORIGIN, &A));
+    void*& block = A.e ? A.e->d_origin_block : A.h0->d_origin_block;
+    if (!block) return fail(no_map(fn, ens, ORIGIN));      // (a begin that failed half way keeps its block)
+    HIPCHK(hipStreamSynchronize(A.stream));
+    HIPCHK(hipFree(block));
+    block = nullptr;
+    if (A.e) { A.e->d_origin_maps = nullptr; A.e->d_origin_runs = nullptr; }
+    for (Handle* h : A.hs) { h->origin = OriginMap{}; h->origin_on = false; h->origin_seq = 0; }
     return 0;
 }
+int cetkmc_origin_end(void* handle) { return origin_end("cetkmc_origin_end", handle, false); }
+int cetkmc_ensemble_origin_end(void* handle) { return origin_end("cetkmc_ensemble_origin_end", handle, true); }
 
 int64_t cetkmc_origin_seq(void* handle)
 {
@@ -3781,7 +3693,8 @@ int64_t cetkmc_origin_seq(void* handle)
 int cetkmc_origin_absorb_events(void* handle, const cetkmc_event* ev, int64_t n, int64_t group)
 {
     Handle* h = (Handle*)handle;
-    CHK(origin_lattice("cetkmc_origin_absorb_events", h));
+    Lattices A;
+    CHK(lattices("cetkmc_origin_absorb_events", handle, false, ORIGIN | MAP, &A));
     if (n < 0) return fail("cetkmc_origin_absorb_events: n < 0");
     if (group < 1) return fail("cetkmc_origin_absorb_events: group must be >= 1");
     if (n % group) return fail("cetkmc_origin_absorb_events: n must be a multiple of group");
@@ -3798,7 +3711,6 @@ int cetkmc_origin_absorb_events(void* handle, const cetkmc_event* ev, int64_t n,
     }
     CHK(origin_room(h, n / group, "cetkmc_origin_absorb_events"));
     if (n == 0) return 0;
-    HIPCHK(hipSetDevice(h->dev));
     DevTmp<cetkmc_event> d_ev;
     if (d_ev.alloc((size_t)n) != hipSuccess) {
         (void)hipGetLastError();
@@ -3815,8 +3727,8 @@ int cetkmc_origin_read(void* handle, uint64_t* words)
 {
     Handle* h = (Handle*)handle;
     if (!words) return fail("null argument");
-    CHK(origin_lattice("cetkmc_origin_read", h));
-    HIPCHK(hipSetDevice(h->dev));
+    Lattices A;
+    CHK(lattices("cetkmc_origin_read", handle, false, ORIGIN | MAP, &A));
     const size_t n = (size_t)h->L * h->L * h->L;
     HIPCHK(hipMemcpyAsync(words, h->origin.words, n * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -3824,123 +3736,50 @@ int cetkmc_origin_read(void* handle, uint64_t* words)
     return 0;
 }
 
-int cetkmc_origin_census(void* handle, int64_t* out)
+static int origin_census(const char* fn, void* handle, bool ens, int64_t* out)
 {
-    Handle* h = (Handle*)handle;
+    if (!ens && !out) return fail("null argument");      // the single call asks for its output first, the ensemble call for its maps
+    Lattices A;
+    CHK(lattices(fn, handle, ens, ORIGIN | MAP, &A));
     if (!out) return fail("null argument");
-    CHK(origin_lattice("cetkmc_origin_census", h));
-    HIPCHK(hipSetDevice(h->dev));
-    HIPCHK(hipMemcpyAsync(out, h->origin.census, (size_t)h->L * 5 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->cnt.bytes_d2h += (int64_t)h->L * 5 * 8;
+    const size_t bytes = (size_t)A.R * A.L * 5 * 8;       // replica 0's census heads the block's [R][L][5]
+    HIPCHK(hipMemcpyAsync(out, A.h0->origin.census, bytes, hipMemcpyDeviceToHost, A.stream));
+    HIPCHK(hipStreamSynchronize(A.stream));
+    A.h0->cnt.bytes_d2h += (int64_t)bytes;
     return 0;
 }
+int cetkmc_origin_census(void* handle, int64_t* out) { return origin_census("cetkmc_origin_census", handle, false, out); }
+int cetkmc_ensemble_origin_census(void* handle, int64_t* out) { return origin_census("cetkmc_ensemble_origin_census", handle, true, out); }
 
-// initialise n_lay + n_gr records on the stream, fill them (go = the launch) and copy n_lay layer and n_copy grain records out
-extern "C++" template <class Go>
-static int origin_records(Handle* h, hipStream_t st, int64_t n_lay, int64_t n_gr, int64_t n_copy, struct cetkmc_origin_rec* layers,
-                          struct cetkmc_origin_rec* grains, Go&& go)
+// cap: how many grain records the caller takes (the ensemble call: all of them)
+static int origin_profile(const char* fn, void* handle, bool ens, struct cetkmc_origin_rec* layers, int64_t cap, struct cetkmc_origin_rec* grains)
 {
-    DevTmp<long long> d_rec;
-    const int64_t words = (n_lay + n_gr) * ORIGIN_NW;
-    if (d_rec.alloc((size_t)words) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("origin profile: no device memory for " + std::to_string(n_lay + n_gr) + " records of " + std::to_string(sizeof(OriginRec)) + " bytes");
-    }
-    launch(k_origin_rec_init, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, st, nullptr, nullptr, d_rec.p, words);
-    CHK(go(d_rec.p, d_rec.p + n_lay * ORIGIN_NW));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(layers, d_rec.p, (size_t)n_lay * sizeof(OriginRec), hipMemcpyDeviceToHost, st));
-    if (n_copy > 0) HIPCHK(hipMemcpyAsync(grains, d_rec.p + n_lay * ORIGIN_NW, (size_t)n_copy * sizeof(OriginRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h->cnt.bytes_d2h += (n_lay + std::max<int64_t>(n_copy, 0)) * (int64_t)sizeof(OriginRec);
-    return 0;
+    if (!ens && !layers) return fail("null argument");   // as in origin_census
+    Lattices A;
+    CHK(lattices(fn, handle, ens, ONE_LATTICE | ORIGIN | MAP, &A));
+    if (!layers) return fail("null argument");
+    if (grains && A.grains < 0) return fail(no_clusters(fn, ens) + " for its grain records");
+    const int64_t nc = grains ? A.grains : 0, n = std::min<int64_t>(cap, nc);
+    const bool with_grains = grains && n > 0;
+    // the device table holds every grain (the pass adds by label); the first n records are the caller's
+    return fill_records<long long>(A.h0, A.stream, "origin profile", ORIGIN_NW, k_origin_rec_init, (int64_t)A.R * A.L, with_grains ? nc : 0,
+                                   with_grains ? n : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
+        if (A.e) CHK(ens_push_views(A.e));      // the pass reads every replica's state through its current view
+        A.run(ENS_GRAINS, [&](auto... sel) {
+            launch(k_origin_profile<decltype(sel)...>, dim3(origin_blocks(A.L), (unsigned)A.R), dim3(256), 0, A.stream, nullptr, nullptr, A.view,
+                   A.h0->origin, A.e ? A.e->d_origin_maps : nullptr, with_grains ? A.labels : nullptr, grains ? A.n : 0, d_lay, d_gr, sel...);
+        });
+        return 0;
+    });
 }
-
 int cetkmc_origin_profile(void* handle, struct cetkmc_origin_rec* layers, int64_t cap, struct cetkmc_origin_rec* grains)
 {
-    Handle* h = (Handle*)handle;
-    if (!h || !layers) return fail("null argument");
-    if (ens_of(handle)) return fail("cetkmc_origin_profile takes one lattice: an ensemble handle goes to cetkmc_ensemble_origin_profile");
-    CHK(origin_lattice("cetkmc_origin_profile", h));
-    if (grains && h->cc_n_clusters < 0) return fail("cetkmc_origin_profile needs a preceding cetkmc_cluster for its grain records");
-    const int64_t nc = grains ? h->cc_n_clusters : 0, n = std::min<int64_t>(cap, nc);
-    const bool with_grains = grains && n > 0;
-    HIPCHK(hipSetDevice(h->dev));
-    // the device table holds every grain (the pass adds by label); the first n records are the caller's
-    return origin_records(h, h->stream, h->L, with_grains ? nc : 0, with_grains ? n : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
-        launch(k_origin_profile<>, dim3(origin_blocks(h->L)), dim3(256), 0, h->stream, nullptr, nullptr, view_of(h, 0), h->origin, nullptr,
-               with_grains ? (const int*)h->d_cc_labels : nullptr, (int)nc, d_lay, d_gr);
-        return 0;
-    });
+    return origin_profile("cetkmc_origin_profile", handle, false, layers, cap, grains);
 }
-
-static int origin_ensemble(const char* fn, void* handle, bool need_map, Ens** out)
-{
-    if (!handle) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("not an ensemble handle (cetkmc_create_ensemble)");
-    if (need_map && !(e->d_origin_block && e->reps[0]->origin_on)) return fail(std::string(fn) + " needs the maps (cetkmc_ensemble_origin_begin)");
-    *out = e;
-    return 0;
-}
-
-int cetkmc_ensemble_origin_begin(void* handle)
-{
-    Ens* e = nullptr;
-    CHK(origin_ensemble("cetkmc_ensemble_origin_begin", handle, false, &e));
-    Handle* h0 = e->reps[0];
-    HIPCHK(hipSetDevice(h0->dev));
-    return origin_begin(e->reps, &e->d_origin_block, &e->d_origin_maps, &e->d_origin_runs, h0->stream);
-}
-
-int cetkmc_ensemble_origin_end(void* handle)
-{
-    Ens* e = nullptr;
-    CHK(origin_ensemble("cetkmc_ensemble_origin_end", handle, false, &e));
-    if (!e->d_origin_block) return fail("cetkmc_ensemble_origin_end needs the maps (cetkmc_ensemble_origin_begin)");
-    HIPCHK(hipSetDevice(e->reps[0]->dev));
-    HIPCHK(hipStreamSynchronize(e->reps[0]->stream));
-    HIPCHK(hipFree(e->d_origin_block));
-    e->d_origin_block = nullptr; e->d_origin_maps = nullptr; e->d_origin_runs = nullptr;
-    for (Handle* h : e->reps) { h->origin = OriginMap{}; h->origin_on = false; h->origin_seq = 0; }
-    return 0;
-}
-
-int cetkmc_ensemble_origin_census(void* handle, int64_t* out)
-{
-    Ens* e = nullptr;
-    CHK(origin_ensemble("cetkmc_ensemble_origin_census", handle, true, &e));
-    if (!out) return fail("null argument");
-    Handle* h0 = e->reps[0];
-    HIPCHK(hipSetDevice(h0->dev));
-    const size_t bytes = (size_t)e->R * e->L * 5 * 8;       // replica 0's census heads the block's [R][L][5]
-    HIPCHK(hipMemcpyAsync(out, h0->origin.census, bytes, hipMemcpyDeviceToHost, h0->stream));
-    HIPCHK(hipStreamSynchronize(h0->stream));
-    h0->cnt.bytes_d2h += (int64_t)bytes;
-    return 0;
-}
-
 int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layers, struct cetkmc_origin_rec* grains)
 {
-    Ens* e = nullptr;
-    CHK(origin_ensemble("cetkmc_ensemble_origin_profile", handle, true, &e));
-    if (!layers) return fail("null argument");
-    if (grains && e->an_clusters.empty()) return fail("cetkmc_ensemble_origin_profile needs a preceding cetkmc_ensemble_analyze for its grain records");
-    const int R = e->R, L = e->L;
-    int64_t total = 0;
-    if (grains) for (int r = 0; r < R; ++r) total += e->an_clusters[(size_t)r];
-    const bool with_grains = grains && total > 0;
-    Handle* h0 = e->reps[0];
-    hipStream_t st = h0->stream;
-    HIPCHK(hipSetDevice(h0->dev));
-    const EnsSel sel{e->d_table, 0, 0, (int64_t)L * L * L, e->d_cc_offs};
-    return origin_records(h0, st, (int64_t)R * L, with_grains ? total : 0, with_grains ? total : 0, layers, grains, [&](long long* d_lay, long long* d_gr) {
-        CHK(ens_push_views(e));      // the pass reads every replica's state through its current view
-        launch(k_origin_profile<EnsSel>, dim3(origin_blocks(L), (unsigned)R), dim3(256), 0, st, nullptr, nullptr, SlabView{}, OriginMap{},
-               (const OriginMap*)e->d_origin_maps, with_grains ? (const int*)e->d_cc_labels : nullptr, 0, d_lay, d_gr, sel);
-        return 0;
-    });
+    return origin_profile("cetkmc_ensemble_origin_profile", handle, true, layers, INT64_MAX, grains);
 }
+
 
 }  // extern "C"
