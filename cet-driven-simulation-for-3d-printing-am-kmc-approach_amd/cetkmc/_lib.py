@@ -156,11 +156,16 @@ class OriginRec(C.Structure):
                 ("ord_sum", C.c_int64), ("ord_min", C.c_int64), ("ord_max", C.c_int64), ("birth", C.c_int64), ("pad", C.c_int64)]
 
 
+class RemeltInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("passes", "n_melted", "n_melted_last", "n_appended")]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
                   "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
-                  "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs}
+                  "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs,
+                  "remelt_info": RemeltInfo}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -250,6 +255,12 @@ PROTOTYPES = {
     "cetkmc_ensemble_origin_end": (C.c_int, [C.c_void_p]),
     "cetkmc_ensemble_origin_census": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cetkmc_ensemble_origin_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cetkmc_set_remelt": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "cetkmc_remelt": (C.c_int, [C.c_void_p, C.c_double, _P(RemeltInfo)]),
+    "cetkmc_time_remelt": (C.c_int, [C.c_void_p, C.c_double, C.c_int, _P(C.c_double)]),
+    "cetkmc_get_remelt_info": (C.c_int, [C.c_void_p, _P(RemeltInfo)]),
+    "cetkmc_ensemble_set_remelt": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "cetkmc_ensemble_remelt_info": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 

@@ -659,6 +659,31 @@ class Engine:
         self._ck(self.lib.cetkmc_origin_profile(self.h, _ptr(lay), k, _ptr(gr)))
         return dict(layers=_origin_fields(lay), grains=_origin_fields(gr[:k]))
 
+    # -- remelting ---------------------------------------------------------------
+    def set_remelt(self, on, threshold=None):
+        """cetkmc_set_remelt: with ``on`` every temperature-update step of ``run_steps`` turns the occupied voxels with
+        T >= ``threshold`` (default: the handle's T_melt) into empty ones, behind the update and before the step's rates."""
+        self._ck(self.lib.cetkmc_set_remelt(self.h, int(bool(on)), float(self.params.T_melt if threshold is None else threshold)))
+
+    def remelt(self, threshold=None):
+        """cetkmc_remelt: one pass now.  Returns the counters as ``remelt_info`` does."""
+        info = _lib.RemeltInfo()
+        self._ck(self.lib.cetkmc_remelt(self.h, float(self.params.T_melt if threshold is None else threshold), C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in _lib.RemeltInfo._fields_}
+
+    def time_remelt(self, n, threshold=None):
+        """cetkmc_time_remelt: device ms of n passes (one hipEvent pair), measurement only."""
+        ms = C.c_double(0.0)
+        self._ck(self.lib.cetkmc_time_remelt(self.h, float(self.params.T_melt if threshold is None else threshold), int(n), C.byref(ms)))
+        return ms.value
+
+    def remelt_info(self):
+        """cetkmc_get_remelt_info: dict(passes, n_melted, n_melted_last, n_appended), running totals of the handle as read
+        at the end of the last stepping call or direct pass."""
+        info = _lib.RemeltInfo()
+        self._ck(self.lib.cetkmc_get_remelt_info(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in _lib.RemeltInfo._fields_}
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -797,6 +822,18 @@ class Ensemble:
                     nucleation_count=np.array([x.nucleation_count for x in res], np.int64),
                     min_margin=np.array([x.min_margin for x in res], np.float64), totals=totals, dt=dt[:, :n],
                     wall_ms=float(res[0].wall_ms) if R else 0.0)
+
+    def set_remelt(self, on, threshold=None):
+        """cetkmc_ensemble_set_remelt: remelting in ``run`` for every replica, one threshold (default: T_melt, which the
+        replicas share)."""
+        thr = float(self.params[0].T_melt if threshold is None else threshold)
+        self._ck(self.lib.cetkmc_ensemble_set_remelt(self.h, int(bool(on)), thr))
+
+    def remelt_info(self):
+        """cetkmc_ensemble_remelt_info: one dict(passes, n_melted, n_melted_last, n_appended) per replica."""
+        buf = (_lib.RemeltInfo * max(self.R, 1))()
+        self._ck(self.lib.cetkmc_ensemble_remelt_info(self.h, buf))
+        return [{n: int(getattr(buf[r], n)) for n, _ in _lib.RemeltInfo._fields_} for r in range(self.R)]
 
     def analyze(self, threshold=0.5, species=-1, labels=True):
         """Clustering, species counts, nucleation counts and (species >= 0) the sorted (index, T) gather of every replica,

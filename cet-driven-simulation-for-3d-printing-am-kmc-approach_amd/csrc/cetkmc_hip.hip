@@ -33,6 +33,7 @@
 #include "grain.hpp"
 #include "solid.hpp"
 #include "origin.hpp"
+#include "melt.hpp"
 
 using namespace cetkmc;
 
@@ -259,6 +260,13 @@ struct Handle {
     void* d_origin_block = nullptr;
     bool origin_on = false;
     int64_t origin_seq = 0;      // ordinal of the next absorbed step
+    // remelting (cetkmc_set_remelt / cetkmc_remelt, melt.hpp): row flags and counters of this lattice, allocated when remelting
+    // is first used
+    MeltState melt{};
+    void* d_melt_block = nullptr;
+    int remelt_on = 0;           // the stepping loop melts behind every temperature update
+    double remelt_threshold = 0.0;
+    cetkmc_remelt_info melt_info{};      // the counters as last read (end of a stepping call, end of a direct pass)
 };
 
 // ---- cache state ------------------------------------------------------------------------------------
@@ -1131,6 +1139,51 @@ int thermal_step(Handle* h, int64_t g, double dt, int laser, const double* d_q, 
     return 0;
 }
 
+// ---- remelting (melt.hpp) ------------------------------------------------------------------------
+// what every remelt entry point refuses of a handle, before anything is allocated or launched
+int melt_refusals(const Handle* h, const char* fn, double threshold)
+{
+    const std::string f(fn);
+    if (std::isnan(threshold)) return fail(f + ": the threshold is NaN");
+    if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h))
+        return fail(f + " needs the whole lattice in one slab of one process (a melt in a halo plane would need the neighbour's field)");
+    return 0;
+}
+// row flags and counters of this lattice, zero, on first use
+int melt_ensure(Handle* h)
+{
+    if (h->d_melt_block) return 0;
+    const size_t nflag = ((size_t)(h->slabs[0].v.nloc + 4) * h->L + 255) / 256 * 256, bytes = nflag + MELT_NC * 8;
+    if (hipMalloc(&h->d_melt_block, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_melt_block = nullptr;
+        return fail("remelting: no device memory for " + std::to_string(bytes) + " bytes");
+    }
+    HIPCHK(hipMemsetAsync(h->d_melt_block, 0, bytes, h->stream));
+    h->melt.flags = (uint8_t*)h->d_melt_block;
+    h->melt.cnt = (unsigned long long*)((char*)h->d_melt_block + nflag);
+    return 0;
+}
+dim3 melt_scan_grid(const SlabView& v, int R = 1) { return dim3((unsigned)(((int64_t)v.nloc * v.L * (v.pitchT / 4) + MELT_QPB - 1) / MELT_QPB), (unsigned)R); }
+dim3 melt_touch_grid(const SlabView& v, int R = 1) { return dim3((unsigned)(((int64_t)v.nloc * v.L * ((v.L + 63) / 64) + 3) / 4), (unsigned)R); }
+dim3 melt_close_grid(const SlabView& v, int R = 1) { return dim3((unsigned)std::min<int64_t>(((int64_t)(v.nloc + 4) * v.L + 255) / 256, 64), (unsigned)R); }
+// one pass over the lattice of a single-slab handle, on its stream; batch: a pass-through behind an early stop
+int launch_melt(Handle* h, double threshold, bool batch)
+{
+    const SlabView v = view_of(h, 0);
+    const StepState* ss = batch ? h->d_ss : nullptr;
+    launch(k_melt_scan<>, melt_scan_grid(v), dim3(256), 0, h->stream, nullptr, nullptr, v, h->slabs[0].prev, h->melt, nullptr, threshold, ss);
+    launch(k_melt_touch<>, melt_touch_grid(v), dim3(256), 0, h->stream, nullptr, nullptr, v, h->melt, nullptr, ss);
+    launch(k_melt_close<>, melt_close_grid(v), dim3(256), 0, h->stream, nullptr, nullptr, v, h->melt, nullptr, ss);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+void melt_info_from(Handle* h, const unsigned long long* c)
+{
+    h->melt_info.passes = (int64_t)c[MELT_PASSES]; h->melt_info.n_melted = (int64_t)c[MELT_TOTAL];
+    h->melt_info.n_melted_last = (int64_t)c[MELT_LAST]; h->melt_info.n_appended = (int64_t)c[MELT_APPENDED];
+}
+
 // the update of global step g in a batch that ends before global step `end`; thermal_mode 2: from source plane *q_idx of h->d_q
 int batch_thermal(Handle* h, int64_t g, int64_t end, int thermal_mode, double dt, int use_latent, int64_t* q_idx)
 {
@@ -1206,6 +1259,7 @@ void destroy_impl(Handle* h)
     }
     if (h->d_solid_block) (void)hipFree(h->d_solid_block);
     if (h->d_origin_block) (void)hipFree(h->d_origin_block);
+    if (h->d_melt_block) (void)hipFree(h->d_melt_block);
     void* ccp[] = {h->d_cc_parent, h->d_cc_roots, h->d_cc_cid, h->d_cc_labels, h->d_cc_stats, h->d_cc_n};
     for (void* p : ccp) if (p) (void)hipFree(p);
     void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
@@ -1258,6 +1312,10 @@ struct Ens {
     OriginMap* d_origin_maps = nullptr;  // (inside the block)
     OriginRun* d_origin_runs = nullptr;
     std::vector<OriginRun> origin_runs;  // host copy of the run table of the last stepping call
+    MeltState* d_melt_tab = nullptr;     // cetkmc_ensemble_set_remelt: every replica's row flags and counters [R] (each replica owns its own)
+    unsigned long long* d_melt_out = nullptr;      // [R][4] counters gathered at the end of a call
+    int remelt_on = 0;
+    double remelt_threshold = 0.0;
 };
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
 bool shared_params_equal(cetkmc_params a, cetkmc_params b)
@@ -1285,7 +1343,7 @@ void destroy_ens(Ens* e)
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
                     e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_solid_block,
-                    e->d_origin_block};
+                    e->d_origin_block, e->d_melt_tab, e->d_melt_out};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1333,6 +1391,7 @@ int cetkmc_struct_size(const char* name)
     SZ("grain_rec", struct cetkmc_grain_rec);
     SZ("solid_info", struct cetkmc_solid_info); SZ("solid_args", struct cetkmc_solid_args); SZ("solid_rec", struct cetkmc_solid_rec);
     SZ("origin_rec", struct cetkmc_origin_rec); SZ("local_args", cetkmc_local_args);
+    SZ("remelt_info", struct cetkmc_remelt_info);
 #undef SZ
     return -1;
 }
@@ -1511,7 +1570,11 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         h->therm_ni16 = (int)value;
         return 0;
     }
-    if (!strcmp(key, "thermal_lookahead")) { h->thermal_ahead = value ? 1 : 0; return 0; }
+    if (!strcmp(key, "thermal_lookahead")) {
+        if (value && h->remelt_on) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while remelting is on (the field computed ahead knows no melt)");
+        h->thermal_ahead = value ? 1 : 0;
+        return 0;
+    }
     if (!strcmp(key, "apply_in_sweep")) { h->apply_in_sweep = value ? 1 : 0; return 0; }
     if (!strcmp(key, "fused_tiles")) {
         if (value < 0 || value > 2) return fail("fused_tiles must be 0 (ring tiles), 1 (census-free tiles in the launch that applies a pending event, default) or 2 (in the plain streaming launch at that shape as well)");
@@ -1530,7 +1593,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         CHK(grow(&h->d_u_np, &h->cap_np, 2 * n + 2 + (size_t)h->L * h->L));
         CHK(grow(&h->d_q, &h->cap_q, (n / 20 + 2) * (size_t)h->L * h->L));
         CHK(grow_pinned(&h->pin_in, &h->pin_in_cap, 2 * n * 8 + (2 * n + 2) * 8 + std::min<size_t>(PIN_SMALL_MAX, (n / 20 + 2) * (size_t)h->L * h->L * 8)));
-        CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, 64 + n * (16 + sizeof(cetkmc_event)) + h->slabs.size() * sizeof(int)));
+        CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, 64 + n * (16 + sizeof(cetkmc_event)) + h->slabs.size() * sizeof(int) + (h->remelt_on ? 8 + 4 * 8 : 0)));
         // events: the per-phase mode (7 per step) is used on short batches only; the sampled modes need 2 per (8th) step
         return reserve_events(h, std::max<int64_t>(7 * std::min<int64_t>(value, 256), value <= 64 ? 2 * value : 2 * (value / 8 + 1)));
     }
@@ -1934,6 +1997,10 @@ static int enqueue_steps(Handle* h, const cetkmc_run_args* a, const BatchCfg& cf
         CHK(pe.record(s, 0));
         if (therm) {
             CHK(batch_thermal(h, g, a->step0 + n, a->thermal_mode, a->thermal_dt, a->use_latent, q_idx));
+            // remelting: behind the update and its prev_state := state, in front of this step's table / interface / sweep (no
+            // event is pending here: a step before an update step is never deferred); the touched voxels are relisted and the
+            // interface kernel, which follows every update, evaluates them
+            if (h->remelt_on) { CHK(launch_melt(h, h->remelt_threshold, true)); invalidate(h, Cause::apply); }
             if (pe.mode == 2) pe.was_thermal[s] = 1;
         }
         const int rc_sw = launch_sweep(h, true, pe.sweep(s, 0), pe.sweep(s, 1), false, pe.phase(s, 1), pe.phase(s, 4));
@@ -1958,8 +2025,11 @@ static int download_run(Handle* h, int64_t n, StepState* ss, double* totals, cet
 {
     const size_t nsl = h->slabs.size();
     const size_t o_tot = 64, o_ev = o_tot + (size_t)n * 8, o_nev = o_ev + (size_t)n * sizeof(cetkmc_event), o_len = o_nev + (size_t)n * 8;
+    const size_t o_melt = (o_len + nsl * sizeof(int) + 7) & ~(size_t)7;        // the remelt counters, if the handle has any
     static_assert(sizeof(StepState) <= 64, "StepState grew: move the log offsets");
-    CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, o_len + nsl * sizeof(int)));
+    CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, o_melt + (h->remelt_on ? 4 * 8 : 0)));
+    const bool melt_read = h->remelt_on && h->d_melt_block;      // only a loop that may have run a pass reads the counters
+    if (melt_read) HIPCHK(hipMemcpyAsync(h->pin_out + o_melt, h->melt.cnt, 4 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(h->pin_out, h->d_ss, sizeof *ss, hipMemcpyDeviceToHost, h->stream));
     if (totals && n > 0) HIPCHK(hipMemcpyAsync(h->pin_out + o_tot, h->d_log_total, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
     if (events && n > 0) HIPCHK(hipMemcpyAsync(h->pin_out + o_ev, h->d_log_event, (size_t)n * sizeof(cetkmc_event), hipMemcpyDeviceToHost, h->stream));
@@ -1968,6 +2038,7 @@ static int download_run(Handle* h, int64_t n, StepState* ss, double* totals, cet
         HIPCHK(hipMemcpyAsync(h->pin_out + o_len + sl * sizeof(int), h->slabs[sl].v.ifc_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     memcpy(ss, h->pin_out, sizeof *ss);
+    if (melt_read) melt_info_from(h, (const unsigned long long*)(h->pin_out + o_melt));
     if (totals && n > 0) memcpy(totals, h->pin_out + o_tot, (size_t)n * 8);
     if (events && n > 0) memcpy(events, h->pin_out + o_ev, (size_t)n * sizeof(cetkmc_event));
     if (n_events && n > 0) memcpy(n_events, h->pin_out + o_nev, (size_t)n * 8);
@@ -2171,6 +2242,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     Handle* h = (Handle*)handle;
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
+    if (h->remelt_on) return fail("cetkmc_run_supersteps is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps needs a streaming sweep_variant (1 or 2)");
@@ -2268,6 +2340,7 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     Handle* h = (Handle*)handle;
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
+    if (h->remelt_on) return fail("cetkmc_run_supersteps_local is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (a->box != 8 || h->L % 8) return fail("cetkmc_run_supersteps_local: box must be 8 and divide L");
@@ -2853,6 +2926,13 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
             sel.rel ^= 1;
             sel.q_off += laser ? (int64_t)L2 : 0;
             ++flips;
+            if (e->remelt_on) {        // behind the update and its prev_state := state, in front of the table and the interface kernel
+                const SlabView& mv = e->table[0].view[0];
+                launch(k_melt_scan<EnsSel>, melt_scan_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, nullptr, MeltState{}, e->d_melt_tab,
+                       e->remelt_threshold, nullptr, sel);
+                launch(k_melt_touch<EnsSel>, melt_touch_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, MeltState{}, e->d_melt_tab, nullptr, sel);
+                launch(k_melt_close<EnsSel>, melt_close_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, MeltState{}, e->d_melt_tab, nullptr, sel);
+            }
             table_and_interface();
         }
         launch(k_sweep_plane<true, false, EnsSel>, g_sweep, dim3(1024), plane_shmem(L), st, nullptr, nullptr, sa0, nullptr, nullptr, sel);
@@ -2863,6 +2943,13 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     HIPCHK(hipEventRecord(e->ev1, st));
     hipLaunchKernelGGL(k_ens_collect, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, (const EnsRep*)e->d_table, R, e->d_ss_out, e->d_n_out);
     HIPCHK(hipGetLastError());
+    const bool melt_read = e->remelt_on && e->d_melt_tab;       // only a call that may have run a pass gathers the counters
+    std::vector<unsigned long long> melt_cnt(melt_read ? (size_t)R * 4 : 0);       // the remelt counters travel with the results
+    if (melt_read) {
+        launch(k_melt_collect, dim3((unsigned)((4 * R + 255) / 256)), dim3(256), 0, st, nullptr, nullptr, e->d_melt_tab, R, e->d_melt_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(melt_cnt.data(), e->d_melt_out, melt_cnt.size() * 8, hipMemcpyDeviceToHost, st));
+    }
     std::vector<StepState> ss((size_t)R);
     std::vector<int> list_len((size_t)R);
     std::vector<uint8_t> t_active((size_t)R);           // stepped by this call (not frozen when it began)
@@ -2879,6 +2966,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     for (int r = 0; r < R; ++r) {
         Handle* h = e->reps[(size_t)r];
         const StepState& q = ss[(size_t)r];
+        if (melt_read) melt_info_from(h, melt_cnt.data() + 4 * (size_t)r);
         h->cur ^= flips & 1;
         invalidate(h, Cause::ensemble_stepped);      // recompute on demand
         grow_ifc_grid(h, list_len[(size_t)r]);
@@ -3632,6 +3720,8 @@ static int origin_begin(const char* fn, void* handle, bool ens, int max_L)
 {
     Lattices A;
     CHK(lattices(fn, handle, ens, OWNER | ORIGIN, &A));
+    for (Handle* h : A.hs)
+        if (h->remelt_on) return fail(std::string(fn) + " is refused while remelting is on: the event log the origin map folds holds no melts");
     if (A.L > max_L) return fail(std::string(fn) + ": L > " + std::to_string(max_L) + " (the profile packs a voxel's linear index into 24 bits)");
     void** block = A.e ? &A.e->d_origin_block : &A.h0->d_origin_block;
     const size_t R = (size_t)A.R;
@@ -3779,6 +3869,108 @@ int cetkmc_origin_profile(void* handle, struct cetkmc_origin_rec* layers, int64_
 int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layers, struct cetkmc_origin_rec* grains)
 {
     return origin_profile("cetkmc_ensemble_origin_profile", handle, true, layers, INT64_MAX, grains);
+}
+
+// ---- remelting (melt.hpp) -----------------------------------------------------------------------
+int cetkmc_set_remelt(void* handle, int on, double threshold)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return fail("null handle");
+    CHK(melt_refusals(h, "cetkmc_set_remelt", threshold));
+    if (h->in_ensemble) return fail("cetkmc_set_remelt: the replicas of an ensemble are switched by cetkmc_ensemble_set_remelt");
+    if (on && h->origin_on) return fail("cetkmc_set_remelt is refused while an origin map is attached: the event log it folds holds no melts");
+    if (on && h->thermal_ahead) return fail("cetkmc_set_remelt is refused with option thermal_lookahead on (the field computed ahead knows no melt)");
+    HIPCHK(hipSetDevice(h->dev));
+    if (on) CHK(melt_ensure(h));
+    h->remelt_on = on ? 1 : 0;
+    h->remelt_threshold = threshold;
+    return 0;
+}
+
+int cetkmc_remelt(void* handle, double threshold, struct cetkmc_remelt_info* info)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return fail("null handle");
+    CHK(melt_refusals(h, "cetkmc_remelt", threshold));
+    if (h->origin_on) return fail("cetkmc_remelt is refused while an origin map is attached: the event log it folds holds no melts");
+    HIPCHK(hipSetDevice(h->dev));
+    CHK(melt_ensure(h));
+    CHK(launch_melt(h, threshold, false));
+    unsigned long long c[4];
+    int n_list = 0;
+    HIPCHK(hipMemcpyAsync(c, h->melt.cnt, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&n_list, h->slabs[0].v.ifc_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    melt_info_from(h, c);
+    grow_ifc_grid(h, n_list);               // the list may have grown, as after an upload
+    invalidate(h, Cause::apply);            // touched voxels relisted, not evaluated
+    if (info) *info = h->melt_info;
+    return 0;
+}
+
+int cetkmc_time_remelt(void* handle, double threshold, int n, double* ms_total)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !ms_total) return fail("null argument");
+    CHK(melt_refusals(h, "cetkmc_time_remelt", threshold));
+    if (h->origin_on) return fail("cetkmc_time_remelt is refused while an origin map is attached: the event log it folds holds no melts");
+    HIPCHK(hipSetDevice(h->dev));
+    CHK(melt_ensure(h));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    for (int s = 0; s < n; ++s) CHK(launch_melt(h, threshold, false));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    cetkmc_remelt_info info;
+    CHK(cetkmc_remelt(handle, threshold, &info));      // one more pass, untimed: reads the counters, grows the grid, names the cause
+    *ms_total = 0.0;
+    return add_elapsed(h->ev0, h->ev1, ms_total);
+}
+
+int cetkmc_get_remelt_info(void* handle, struct cetkmc_remelt_info* info)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !info) return fail("null argument");
+    *info = h->melt_info;
+    return 0;
+}
+
+int cetkmc_ensemble_set_remelt(void* handle, int on, double threshold)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("cetkmc_ensemble_set_remelt: not an ensemble handle (cetkmc_create_ensemble)");
+    Handle* h0 = e->reps[0];
+    CHK(melt_refusals(h0, "cetkmc_ensemble_set_remelt", threshold));
+    if (on && h0->origin_on) return fail("cetkmc_ensemble_set_remelt is refused while the origin maps are attached: the event log they fold holds no melts");
+    HIPCHK(hipSetDevice(h0->dev));
+    if (on) {
+        const size_t R = (size_t)e->R;
+        for (Handle* h : e->reps) CHK(melt_ensure(h));
+        if (!e->d_melt_tab) {
+            if (hipMalloc((void**)&e->d_melt_tab, R * sizeof(MeltState)) != hipSuccess || hipMalloc((void**)&e->d_melt_out, R * 4 * 8) != hipSuccess) {
+                (void)hipGetLastError();
+                if (e->d_melt_tab) (void)hipFree(e->d_melt_tab);
+                e->d_melt_tab = nullptr; e->d_melt_out = nullptr;
+                return fail("cetkmc_ensemble_set_remelt: no device memory for the replica table");
+            }
+            std::vector<MeltState> tab(R);
+            for (size_t r = 0; r < R; ++r) tab[r] = e->reps[r]->melt;
+            HIPCHK(hipMemcpyAsync(e->d_melt_tab, tab.data(), R * sizeof(MeltState), hipMemcpyHostToDevice, h0->stream));
+            HIPCHK(hipStreamSynchronize(h0->stream));       // the table is copied from this frame
+        }
+    }
+    e->remelt_on = on ? 1 : 0;
+    e->remelt_threshold = threshold;
+    for (Handle* h : e->reps) { h->remelt_on = e->remelt_on; h->remelt_threshold = threshold; }
+    return 0;
+}
+
+int cetkmc_ensemble_remelt_info(void* handle, struct cetkmc_remelt_info* info)
+{
+    if (!handle || !info) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("cetkmc_ensemble_remelt_info: not an ensemble handle (cetkmc_create_ensemble)");
+    for (int r = 0; r < e->R; ++r) info[r] = e->reps[(size_t)r]->melt_info;
+    return 0;
 }
 
 

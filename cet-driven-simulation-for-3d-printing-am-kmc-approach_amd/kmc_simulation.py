@@ -240,6 +240,34 @@ def _add_origin_columns(row, profile, census):
     return planes, grains
 
 
+def _remelt_threshold(remelt, where="remelt"):
+    """run_kmc's ``remelt`` option as a threshold temperature: None for off (False / None), T_MELT for True, else the number"""
+    if remelt is None or remelt is False:
+        return None
+    if remelt is True:
+        return float(T_MELT)
+    if isinstance(remelt, (int, float, np.integer, np.floating)) and not np.isnan(float(remelt)):
+        return float(remelt)
+    raise ValueError(f"{where} must be False, True (melt at T_MELT) or a threshold temperature")
+
+
+def _check_remelt(thr, mode_a, origin_metrics, thermal_updates):
+    if thr is None:
+        return
+    if not mode_a:
+        raise ValueError("remelt needs mode 'A' (the super-step engine has no melt)")
+    if origin_metrics:
+        raise ValueError("remelt cannot be combined with origin_metrics (the event log the origin map folds holds no melts)")
+    if not thermal_updates:
+        raise ValueError("remelt needs thermal_updates=True (the melt follows the temperature update)")
+
+
+def _add_remelt_columns(row, info, offset=(0, 0)):
+    """remelt: the running totals of cetkmc_remelt_info behind every other column of ``row``, in place"""
+    row["RemeltPasses"] = int(offset[0] + info["passes"])
+    row["RemeltedVoxels"] = int(offset[1] + info["n_melted"])
+
+
 def _check_origin(origin_metrics, checkpointing):
     if origin_metrics and checkpointing:
         raise ValueError("origin_metrics cannot be combined with checkpoint_every / resume_from (a checkpoint does not carry the map)")
@@ -333,6 +361,7 @@ def run_kmc(
     solid_metrics: bool = False,
     solid_every: int = 20,
     origin_metrics: bool = False,
+    remelt=False,
     local_events: int = 0,
     local_horizon: float = 1.0,
 ):
@@ -435,8 +464,17 @@ def run_kmc(
     ``outputs/<prefix>/origin_layers.csv`` gets one row per plane and metrics row and, with ``grain_metrics=True``,
     ``origin_grains.csv`` one row per grain of the last row (the grain records themselves always come from the row's own
     clustering).  Refused with ValueError together with ``checkpoint_every`` /
-    ``resume_from`` (a checkpoint does not carry the map)."""
+    ``resume_from`` (a checkpoint does not carry the map).
+
+    ``remelt=True`` (or a threshold temperature; mode "A" only, with or without ``laser``): remelting on the device
+    (cetkmc_set_remelt) -- behind every temperature update the occupied voxels with T >= T_MELT (or
+    the given threshold) become empty, before that step's rates are evaluated.  Every metrics row gains, behind every other
+    column, ``RemeltPasses`` and ``RemeltedVoxels`` (running totals); ``last_run_info["remelted"]`` carries the total.
+    Checkpoints carry the setting and the totals (only then), and a resumed run must ask for the same threshold.  Refused
+    with ValueError: ``mode="B"``, ``origin_metrics``, ``thermal_updates=False``."""
     import cetkmc
+    remelt_thr = _remelt_threshold(remelt)
+    _check_remelt(remelt_thr, mode == "A", origin_metrics, thermal_updates)
     _check_solid(solid_metrics, solid_every, bool(checkpoint_every or resume_from))
     _check_origin(origin_metrics, bool(checkpoint_every or resume_from))
     if mode not in ("A", "B"):
@@ -482,6 +520,14 @@ def run_kmc(
     params.nu_dep = nu_dep_eff
     engine = cetkmc.Engine(L, impurity_c=impurity_c, params=params)
     engine.upload(state, theta, phi, T, defects_mask)
+    remelt_off = (0, 0)            # passes and melted voxels of the run before the checkpoint it resumes from
+    if remelt_thr is not None or (ckpt and "remelt" in ckpt["extra"]):
+        ex = ckpt["extra"] if ckpt else {}
+        if ckpt and ex.get("remelt") != remelt_thr:
+            engine.close()
+            raise ValueError(f"checkpoint was written by a run with remelt={ex.get('remelt', False)}, this call asks for {remelt_thr or False}")
+        remelt_off = (int(ex.get("remelt_passes", 0)), int(ex.get("remelted", 0)))
+        engine.set_remelt(True, remelt_thr)
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -539,10 +585,15 @@ def run_kmc(
             planes, g_rows = _add_origin_columns(row, engine.origin_profile(grains=True, recluster=False), engine.origin_census())
             origin_grain_rows = g_rows if grain_metrics else None
             origin_planes.append(planes)
+        if remelt_thr is not None:
+            _add_remelt_columns(row, engine.remelt_info(), remelt_off)
         metrics_data.append(row)
         _print_row(step, row)
 
     def checkpoint(at, extra=None):
+        if remelt_thr is not None:       # (only then: the checkpoints of every other run stay as they were)
+            info = engine.remelt_info()
+            extra = dict(extra or {}, remelt=remelt_thr, remelt_passes=remelt_off[0] + info["passes"], remelted=remelt_off[1] + info["n_melted"])
         save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
                         engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
                         at, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected, extra=extra)
@@ -673,9 +724,12 @@ def run_kmc(
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
     atom_type = state.copy()
+    remelted = remelt_off[1] + engine.remelt_info()["n_melted"] if remelt_thr is not None else None
     engine.close()
     last_run_info.clear()
     last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1)
+    if remelt_thr is not None:
+        last_run_info.update(remelted=remelted)
     if local_events:
         last_run_info.update(horizon_time=horizon_time, capped_boxes=capped_boxes)
     if mode == "A" and min_margin < MARGIN_WARN:
@@ -687,15 +741,15 @@ def run_kmc(
 
 # ---- replica ensembles: many independent runs in the same launches -----------------------------
 _C_SITE = 3                 # carbon state (defects.py: only carbon sites can become defects)
-ENSEMBLE_KEYS = ("temp", "defect_fraction", "n_seeds", "impurity_c", "output_prefix", "nu_dep", "seed", "laser")
+ENSEMBLE_KEYS = ("temp", "defect_fraction", "n_seeds", "impurity_c", "output_prefix", "nu_dep", "seed", "laser", "remelt")
 _RUN_DEFAULTS = dict(temp=T_SUB, defect_fraction=0.0, n_seeds=5, impurity_c=0.0, output_prefix="cet_run", nu_dep=None, seed=None,
-                     laser=None)
+                     laser=None, remelt=False)
 # per-replica generators and counters of the last run_kmc_ensemble call (the return tuples have no room for them):
 # random_state / np_state (where run_kmc would have left the global generators), executed_events, min_margin
 last_ensemble_info = []
 
 
-def _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates=True):
+def _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates=True, origin_metrics=False):
     """Argument validation of run_kmc_ensemble (before any device call); returns the completed per-replica configs."""
     if rng not in ("reference", "counter"):
         raise ValueError("rng must be 'reference' (run_kmc's exact loop) or 'counter' (run_kmc mode 'B', box = L)")
@@ -719,7 +773,11 @@ def _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates=T
             raise ValueError(f"configs[{i}]: defect_fraction must be >= 0")
         if d["laser"] is not None:
             d["laser"] = _check_laser(d["laser"], f"configs[{i}]['laser']")
+        d["remelt"] = _remelt_threshold(d["remelt"], f"configs[{i}]['remelt']")
         out.append(d)
+    if len({d["remelt"] for d in out}) != 1:
+        raise ValueError("the 'remelt' setting must be the same in every config (it is shared by the ensemble)")
+    _check_remelt(out[0]["remelt"], rng == "reference", origin_metrics, thermal_updates)
     lasers = [d["laser"] is not None for d in out]
     if any(lasers):
         # the thermal mode belongs to the call, and a laser of zero power does not give the bits of the diffusion-only update
@@ -774,7 +832,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
-    output_prefix, nu_dep, seed, laser).  ``laser`` (run_kmc's laser dict): either every config has one or none has, with
+    output_prefix, nu_dep, seed, laser, remelt).  ``remelt`` (run_kmc's option of that name: rows gain ``RemeltPasses`` and
+    ``RemeltedVoxels``; ``last_ensemble_info[r]["remelted"]``) is shared like the lasers' ``latent``: the same in every config,
+    ``rng="reference"`` only.  ``laser`` (run_kmc's laser dict): either every config has one or none has, with
     the same ``latent`` setting; configs with equal dicts share one set of source planes on the device.  Returns one run_kmc return tuple per replica and writes each replica's
     ``outputs/<prefix>/metrics.csv`` and ``metrics_<tag>.csv``.
 
@@ -798,7 +858,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     origin maps in one launch, and every metrics row takes ONE batched cetkmc_ensemble_origin_profile and census."""
     import cetkmc
     _check_solid(solid_metrics, solid_every, False)
-    cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates)
+    cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates, origin_metrics)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
     caller_py, caller_np = random.getstate(), np.random.get_state()
     ens = None
@@ -841,6 +901,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         origin_grain_rows = [None] * R
         if origin_metrics:
             ens.origin_begin()
+        remelt_thr = cfgs[0]["remelt"]
+        if remelt_thr is not None:
+            ens.set_remelt(True, remelt_thr)
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -931,6 +994,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             sp = ens.solid_profile(solid_scales, grains=grain_metrics, recluster=False) if solid_metrics else None
             op = ens.origin_profile(grains=True, recluster=False) if origin_metrics else None
             oc = ens.origin_census() if origin_metrics else None
+            ri = ens.remelt_info() if remelt_thr is not None else None
             for r in range(R):
                 if not alive[r]:
                     continue
@@ -957,11 +1021,14 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                     planes, g_rows = _add_origin_columns(row, prof, oc[r])
                     origin_grain_rows[r] = g_rows if grain_metrics else None
                     origin_planes[r].append(planes)
+                if ri is not None:
+                    _add_remelt_columns(row, ri[r])
                 metrics[r].append(row)
             next_step = stop + 1
 
         out = []
         last_ensemble_info.clear()
+        ri = ens.remelt_info() if remelt_thr is not None else None
         for r, c in enumerate(cfgs):
             if metrics[r]:
                 _write_metrics(c["output_prefix"], metrics[r])
@@ -983,7 +1050,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             state = fields["state"]
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))
             last_ensemble_info.append(dict(random_state=gens[r].py, np_state=gens[r].np, executed_events=last_step[r] + 1,
-                                           min_margin=min_margin[r] if rng == "reference" else None))
+                                           min_margin=min_margin[r] if rng == "reference" else None,
+                                           **({"remelted": ri[r]["n_melted"]} if ri is not None else {})))
             print(f"[{c['output_prefix']}] completed {last_step[r] + 1} steps in {total_time[r]:.2e} s")
         return out
     finally:

@@ -12,6 +12,7 @@ outside the accelerated path and are not part of this package.
     python main.py --texture                      # texture columns in every metrics.csv and a texture.csv per level (run_kmc texture_metrics)
     python main.py --grains                       # grain columns in every metrics.csv and a grains.csv per level (run_kmc grain_metrics)
     python main.py --solid                        # solidification columns in every metrics.csv and a solid_layers.csv per level (run_kmc solid_metrics)
+    python main.py --remelt [T]                   # remelting on the device: solid at or above T_MELT (or T) turns liquid (run_kmc remelt)
     python main.py --origin                       # origin columns in every metrics.csv and an origin_layers.csv per level (run_kmc origin_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
@@ -49,8 +50,9 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
-         layers=False, texture=False, grains=False, solid=False, origin=False, **run_kw):
+         layers=False, texture=False, grains=False, solid=False, origin=False, remelt=False, **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
+    rm = {"remelt": remelt} if remelt is not False and remelt is not None else {}      # --remelt: run_kmc's option / config key
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
     summary = {"carbon_levels": [], "grain_sizes": [], "defect_densities": [], "aspect_ratios": []}
@@ -74,7 +76,7 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
             save_lattice(*init[:4], init[4], prefix=f"outputs/{prefix}/init")
         t0 = time.time()
         ens_out = run_kmc_ensemble([dict(temp=T_SUB, defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, impurity_c=c,
-                                         output_prefix=f"impurity_c_{int(c * 100)}") for c in carbon_levels], L, n_steps, rng=rng,
+                                         output_prefix=f"impurity_c_{int(c * 100)}", **rm) for c in carbon_levels], L, n_steps, rng=rng,
                                    **fm)
         ens_t = time.time() - t0
     for q, c in enumerate(carbon_levels):
@@ -89,7 +91,7 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
             save_lattice(*init[:4], init[4], prefix=f"{out_dir}/init")
             t0 = time.time()
             state, atom_type, total_time, theta, phi = run_kmc(L=L, n_steps=n_steps, temp=T_SUB, defect_fraction=DEFECT_PROB,
-                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw, **fm)
+                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw, **fm, **rm)
         else:
             state, atom_type, total_time, theta, phi = ens_out[q]
             t0 -= ens_t / len(carbon_levels)
@@ -139,6 +141,9 @@ if __name__ == "__main__":
     ap.add_argument("--origin", action="store_true",
                     help="origin map on the device: voxels and grains by how they were filled (deposition, nucleation, attachment, "
                          "hop) in every metrics.csv, origin_layers.csv (with --grains: origin_grains.csv)")
+    ap.add_argument("--remelt", type=float, nargs="?", const=True, default=False, metavar="T",
+                    help="remelting on the device: behind every temperature update occupied voxels at or above T (default T_MELT) "
+                         "become empty; RemeltPasses / RemeltedVoxels in every metrics.csv (mode A)")
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
@@ -147,4 +152,4 @@ if __name__ == "__main__":
     if a.local_events:
         kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
-         grains=a.grains, solid=a.solid, origin=a.origin, **kw)
+         grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt, **kw)

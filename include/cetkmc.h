@@ -198,7 +198,7 @@ int cetkmc_abi_version(void);
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
- * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -786,6 +786,52 @@ int cetkmc_ensemble_origin_begin(void* handle);
 int cetkmc_ensemble_origin_end(void* handle);
 int cetkmc_ensemble_origin_census(void* handle, int64_t* out);
 int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layers, struct cetkmc_origin_rec* grains);
+
+/* Remelting (not in the reference, which has no melting): solid at or above a threshold temperature
+ * turns liquid.  Opt-in; while it is off every launch and byte of a stepping call is what it was without it.
+ * One pass over the lattice, with m = (state != 0) & (T >= threshold) -- a NaN temperature never melts, +inf does, equality
+ * melts, a state-4 voxel (a defect written into the state) melts like an atom:
+ *   on m: state = 0, prev_state = 0, theta = phi = 0.0 (the voxel is written as the reference's own "site empties" write,
+ *   kmc_simulation.py:286-290).  prev_state is cleared so that a voxel that melts and refills before the next laser update
+ *   releases latent heat (thermal_solver.py:98).  Nothing else changes: the defect MASK, T, empty voxels and their
+ *   orientations, the nucleation count and cetkmc_counters stay.  No heat is absorbed (the reference's latent term is
+ *   release-only).  A pass is idempotent on an unchanged field.
+ * The voxels of the rows around a melted voxel are relisted (interface list, neighbourhood words), not evaluated.
+ *   cetkmc_remelt      one pass now, behind the pending work of the handle's stream; a single handle or a replica handle.
+ *                      It costs what cetkmc_apply costs (cause "apply" of cetkmc_invalidates: the row sums and the interface
+ *                      sums go stale, the rate table stays valid).  info may be NULL.  On a replica that has terminated the pass
+ *                      may create events, but the replica stays frozen for cetkmc_run_ensemble until a lattice is uploaded
+ *                      into it, as after any other change of a terminated replica.
+ *   cetkmc_time_remelt n passes bracketed by one hipEvent pair on the handle's stream (ms_total; as cetkmc_time_sweeps times
+ *                      sweeps), then one untimed cetkmc_remelt: measurement only (tools/remelt_timing.py).
+ *   cetkmc_set_remelt  on != 0: every temperature-update step (g % 20 == 0, thermal_mode 1 or 2) of cetkmc_run_steps runs a
+ *                      pass behind the update (and behind its prev_state := state) and before that step's rate evaluation.
+ *                      Nothing happens with thermal_mode 0.  Behind an early stop (status 1 or 2) the queued passes are
+ *                      pass-throughs, as the temperature kernels are; the continuation of a batch that stopped with status 2
+ *                      ON an update step skips the pass together with the update it skips, so it is counted once.  The call
+ *                      invalidates no cache and involves no cetkmc_set_option key.
+ *   cetkmc_get_remelt_info   the handle's counters as last read from the device: at the end of a stepping call made while
+ *                      remelting is on (with its results, no extra synchronisation inside a batch; a call made while it is
+ *                      off copies nothing, also on a handle that used remelting before) and at the end of cetkmc_remelt.
+ *   cetkmc_ensemble_set_remelt / cetkmc_ensemble_remelt_info   the same for cetkmc_run_ensemble, one threshold (T_melt is
+ *                      shared by the replicas), info[R]; the launch sequence does not depend on R; a replica that has
+ *                      terminated or is frozen is left alone.  A replica's bits equal those of a single handle.
+ * cetkmc_remelt_info: running totals on the handle since its creation (direct passes and passes of the stepping loop alike)
+ *   -- passes, n_melted, n_appended (voxels a pass added to the interface list) -- and n_melted_last, the last pass's count.
+ * Refused, before anything is launched: a NaN threshold; a handle with more than one slab or a rank handle (the halo copies
+ * would need the neighbour's field); cetkmc_set_remelt on an ensemble's handles (cetkmc_ensemble_set_remelt switches them)
+ * and with option thermal_lookahead on; cetkmc_remelt and switching on while an origin map is attached (the event log it
+ * folds holds no melts).  While remelting is on: cetkmc_run_supersteps, cetkmc_run_supersteps_local, option
+ * thermal_lookahead = 1, cetkmc_origin_begin and cetkmc_ensemble_origin_begin are refused.  The solidification map needs
+ * nothing: it sees occupied -> empty at its next update.
+ * (A struct tag without a typedef, as cetkmc_grain_rec.) */
+struct cetkmc_remelt_info { int64_t passes, n_melted, n_melted_last, n_appended; };
+int cetkmc_set_remelt(void* handle, int on, double threshold);
+int cetkmc_remelt(void* handle, double threshold, struct cetkmc_remelt_info* info);
+int cetkmc_time_remelt(void* handle, double threshold, int n, double* ms_total);
+int cetkmc_get_remelt_info(void* handle, struct cetkmc_remelt_info* info);
+int cetkmc_ensemble_set_remelt(void* handle, int on, double threshold);
+int cetkmc_ensemble_remelt_info(void* handle, struct cetkmc_remelt_info* info);
 
 #ifdef __cplusplus
 }
