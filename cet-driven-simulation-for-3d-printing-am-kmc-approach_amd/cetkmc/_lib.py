@@ -178,6 +178,7 @@ PROTOTYPES = {
     "cetkmc_stale_row": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_int, C.c_int]),
     "cetkmc_stale_rows": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_int, C.c_void_p]),
     "cetkmc_table_tile_of": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "cetkmc_lane_needs_values": (C.c_int, [C.c_uint64]),
     "cetkmc_invalidates": (C.c_int, [C.c_char_p]),
     "cetkmc_device_count": (C.c_int, [_P(C.c_int)]),
     "cetkmc_create": (C.c_int, [_P(Params), C.c_int, C.c_int, _P(C.c_int), _P(C.c_void_p)]),

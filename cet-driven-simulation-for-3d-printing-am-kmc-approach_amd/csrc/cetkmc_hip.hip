@@ -155,6 +155,8 @@ struct Handle {
     int apply_in_sweep = 1;      // option "apply_in_sweep": defer the application of eligible batched steps into the next sweep
     int fused_tiles = 1;         // option "fused_tiles": 1 = the sweep launch that applies a pending event runs census-free tiles
                                  // (sweep_table_tile) at 128 < L <= 256, 2 = the plain launch at that shape as well, 0 = ring tiles
+    int table_lane_skip = 1;     // option "table_lane_skip": 1 = those tiles request the class bytes first and the table entries only in
+                                 // the lanes that can use them (lane_needs_values()), 0 = every lane's entries; same bits
     bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
     BatchCfg pend_cfg{};         // ... with this batch configuration
     double* d_ktab = nullptr;
@@ -825,7 +827,7 @@ bool table_tiles(const Handle* h, int level)
 {
     return h->fused_tiles >= level && h->slabs.size() == 1 && !multi_rank(h) && h->L > 128 && row_shape(h).hw;
 }
-size_t apply_shmem() { return ((sizeof(KParams) + 15) & ~(size_t)15) + sizeof(SlabView); }
+size_t apply_shmem() { return APPLY_SHMEM; }
 
 // One full-lattice rate sweep: (rate table, if T changed) -> (interface kernel, if the listed voxels' sums are stale)
 // -> sweep kernel -> block sums (+ all-gather across ranks).  ev_pre | table + interface | ev_a | sweep | ev_b |
@@ -879,12 +881,16 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
             // only under the streaming sweep with the rate table, and only where rows are half-wave rows)
             ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
                         (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
-            if (table_tiles(h, 1))      // LDS: the apply block's KParams + SlabView copy alone
-                launch(k_sweep_stream_apply<true, 1, false, true>, dim3(table_tile_count(h->L, v.nloc, true) + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X);
+            if (table_tiles(h, 1))      // LDS: the apply block's KParams + SlabView + PendRec copy alone
+                with_flag(h->table_lane_skip != 0, [&](auto ls) {
+                    launch(k_sweep_stream_apply<true, 1, false, true, ls.value>, dim3(table_tile_count(h->L, v.nloc, true) + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X);
+                });
             else
                 launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X);
         } else if (h->sweep_variant == 1 && table_tiles(h, 2)) {
-            launch(k_sweep_stream<true, true, 1, false, true>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
+            with_flag(h->table_lane_skip != 0, [&](auto ls) {
+                launch(k_sweep_stream<true, true, 1, false, true, ls.value>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
+            });
         } else if (h->sweep_variant >= 1) {
             auto go = [&](auto k) { launch(k, dim3(sa.group_count * njt), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, ss); };
             if (h->sweep_variant == 1) with_stream_kernel<true>(rs, go); else with_stream_kernel<false>(rs, go);
@@ -1429,6 +1435,10 @@ int cetkmc_stale_row(int type, const int pos[2], const int target[2], int gi, in
 {
     return stale_row(stale_ev_host(type, pos, target), gi, j) ? 1 : 0;
 }
+int cetkmc_lane_needs_values(uint64_t class8)
+{
+    return lane_needs_values(make_uint2((unsigned)class8, (unsigned)(class8 >> 32))) ? 1 : 0;
+}
 int cetkmc_table_tile_of(int L, int gi, int j)
 {
     if (L <= 128 || L > 256 || gi < 0 || gi >= L || j < 0 || j >= L) return -1;
@@ -1581,6 +1591,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         h->fused_tiles = (int)value;
         return 0;
     }
+    if (!strcmp(key, "table_lane_skip")) { h->table_lane_skip = value ? 1 : 0; return 0; }
     if (!strcmp(key, "thermal_table")) { h->thermal_table = value ? 1 : 0; return 0; }
     if (!strcmp(key, "reserve_batch")) {
         // device buffers (uniform streams, per-step logs, one laser source plane per temperature update) and hipEvents of a

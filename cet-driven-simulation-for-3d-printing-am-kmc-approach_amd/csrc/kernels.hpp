@@ -744,6 +744,25 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
     const int jr = min(jrow, A.L - 1);
     return *reinterpret_cast<const uint2*>(A.cls + ((int64_t)li * A.RJ + (jr + 2)) * A.pitchC + KOFFC + k0);
 }
+// Whether table_row() can use any of the 8 table entries of the lane whose class bytes are `own`.  Its two uses of v[] are
+// ev[h] = mask_f64(v[h], E, ...), non-zero only where byte h has bit 0 (empty), and dv[h] = mask_f64(v[h], hasA, ...), only
+// where byte h is an atom (bit 1) with a non-zero count in bits 7:2.  A lane whose bytes are all 0x00 or 0x02 (defect, outside,
+// atom without an exposed neighbour) therefore contributes exact zeros whatever it holds in v[]: the tiles of option
+// table_lane_skip do not load its entries.  (A superset of the two masks: a count on a byte with neither bit also asks.)
+__host__ __device__ __forceinline__ bool lane_needs_values(uint2 own) { return ((own.x | own.y) & 0xFDFDFDFDu) != 0u; }
+// An empty statement that the compiler moves nothing across and that holds the two class words and the 2 x 8 (zeroed) value
+// registers of a pair of items: both class words have arrived here, and the zeros are written before the guarded loads below
+// it.  Without it the compiler waits for the second class word only behind the first item's table loads (a wait for those as
+// well: two round trips in a row) and zeroes the second item's idle lanes behind its loads (a wait for them before the first
+// item is reduced).
+__device__ __forceinline__ void pin_item_pair(uint2& ca, uint2& cb, double (&va)[8], double (&vb)[8])
+{
+#ifndef CETKMC_LANE_SKIP_TIMING
+    asm volatile("" : "+v"(ca.x), "+v"(ca.y), "+v"(cb.x), "+v"(cb.y));
+#endif
+    asm volatile("" : "+v"(va[0]), "+v"(va[1]), "+v"(va[2]), "+v"(va[3]), "+v"(va[4]), "+v"(va[5]), "+v"(va[6]), "+v"(va[7]),
+                      "+v"(vb[0]), "+v"(vb[1]), "+v"(vb[2]), "+v"(vb[3]), "+v"(vb[4]), "+v"(vb[5]), "+v"(vb[6]), "+v"(vb[7]));
+}
 // SK (the census-free tiles of a launch that applies a pending event, sites `sw`): a stale row is not stored, as in sweep_row().
 template <bool HW, bool CH2, bool SK = false>
 __device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, int jrow, bool top, int lane, const double (&v0)[8],
@@ -879,7 +898,13 @@ __host__ __device__ constexpr int table_tile_of(int L, bool hw, int lp, int j)
 }
 // One tile: IPW items per wave from item b * 4 * IPW on, values and class bytes of the next item requested before the current
 // one is reduced (two alternating buffers).  SK: table_row().
-template <bool HW, bool CH2, bool SK, int IPW>
+// LS (option table_lane_skip): class bytes first, table entries only for the lanes that can use them.  The wave requests the
+// class bytes of a pair of its items, then -- each item's class word at hand -- that item's table entries in the lanes where
+// lane_needs_values() holds, then reduces the two with the same table_row().  The predicate reads the very class word
+// table_row() masks with, so the row sums are those of the unconditional loads to the bit: mask_f64() zeroed a skipped lane's
+// entries before.  The price is one dependent round trip per pair of items; beside four other waves per SIMD it was not
+// measurable, the bytes were (131 MB per launch at 256^3 instead of 157 MB).
+template <bool HW, bool CH2, bool SK, int IPW, bool LS = false>
 __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int nblk, const StaleWin& sw = StaleWin{})
 {
     static_assert(IPW % 2 == 0, "two alternating buffers");
@@ -895,6 +920,41 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
     auto jrow_of = [&](int jpair) { return HW ? 2 * jpair + (lane >> 5) : jpair; };
     double va[8], vb[8];
     uint2 ca, cb;
+    if constexpr (LS) {
+#pragma unroll 1
+        for (int t = 0; t < IPW; t += 2) {
+            int lp2 = lp, jp2 = jp + 4;
+            while (jp2 >= ipp) { jp2 -= ipp; ++lp2; }
+            // past the wave's last item the second request repeats the first (a cache hit) and is not reduced
+            const bool two = item + 4 < n_items;
+            const int lpb = two ? lp2 : lp, jpb = two ? jp2 : jp;
+            ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
+            cb = load_cls8(A, lpb + 2, jrow_of(jpb), sl, 0);
+            // lanes that do not load hold +0.0 (whatever they held is masked by table_row(), but it must be a value); one wait
+            // for the two class words, then the two guarded requests back to back: the loads sit under the lanes' exec mask,
+            // so a masked lane requests no bytes
+#pragma unroll
+            for (int q = 0; q < 8; ++q) va[q] = vb[q] = 0.0;
+            pin_item_pair(ca, cb, va, vb);
+#ifdef CETKMC_LANE_SKIP_TIMING
+            // TIMING ONLY (results wrong unless k < 56 of every row is idle): lanes 0..6 skipped by lane index, no wait for the
+            // class words -- the byte saving at the benchmark's lattice without the dependent request
+            const bool na = sl >= 7, nb = sl >= 7;
+#else
+            const bool na = lane_needs_values(ca), nb = lane_needs_values(cb);
+#endif
+            if (na) load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
+            if (nb) load_vals<true, HW>(A, lpb + 2, jrow_of(jpb), lane, 0, vb);
+            table_row<HW, CH2, SK>(A, lp + 2, lp, jrow_of(jp), A.gi0 + lp == L - 1, lane, va, ca, nullptr, nullptr, sw);
+            if (!two) break;
+            table_row<HW, CH2, SK>(A, lpb + 2, lpb, jrow_of(jpb), A.gi0 + lpb == L - 1, lane, vb, cb, nullptr, nullptr, sw);
+            item += 8;
+            if (item >= n_items) break;
+            lp = lp2; jp = jp2 + 4;
+            while (jp >= ipp) { jp -= ipp; ++lp; }
+        }
+        return;
+    }
     load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
     ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
     // one item: `cur` holds its values on entry; the next item's are requested into `nxt` first (past the wave's last item
@@ -918,14 +978,16 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
     }
 }
 
-// TT: the launch's tiles are the census-free ones (sweep_table_tile; table variant only, no dynamic LDS)
-template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false>
+// TT: the launch's tiles are the census-free ones (sweep_table_tile; table variant only, no dynamic LDS); LS: its option
+// table_lane_skip
+template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false, bool LS = false>
 __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
 {
     static_assert(!TT || TAB, "census-free tiles read the rate table");
+    static_assert(!LS || TT, "lanes are skipped by the census-free tiles");
     if (ss && ss->status) return;
     if constexpr (TT) {
-        sweep_table_tile<HW, CH2, false, TABLE_TILE_IPW>(A, blockIdx.x, (int)gridDim.x);
+        sweep_table_tile<HW, CH2, false, TABLE_TILE_IPW, LS>(A, blockIdx.x, (int)gridDim.x);
     } else {
         extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
         sweep_stream_tile<TAB, HW, NPF, CH2>(A, blockIdx.x, smem);
@@ -2129,6 +2191,10 @@ __global__ __launch_bounds__(256) void k_select_pend(KParams P, const SlabView* 
 // It is latency-bound beside the tiles, so an empty voxel's neighbour gathers go one at a time: the kernel keeps the tiles'
 // register budget (5 waves per SIMD).
 constexpr int PEND_EB = 1;
+// the apply block's dynamic LDS: its copies of KParams, the SlabView and the pending record (the host's apply_shmem())
+constexpr size_t APPLY_SHMEM_VIEW = (sizeof(KParams) + 15) & ~(size_t)15;
+constexpr size_t APPLY_SHMEM_PEND = (APPLY_SHMEM_VIEW + sizeof(SlabView) + 15) & ~(size_t)15;
+constexpr size_t APPLY_SHMEM = APPLY_SHMEM_PEND + sizeof(PendRec);
 __device__ __forceinline__ StaleEv stale_ev_of(const cetkmc_event& ev)
 {
     StaleEv se;
@@ -2140,17 +2206,22 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
 {
     PEND_STAMP(0);
     // the rate constants and the slab view are read from LDS (the tiles' ring, unused by this block): vector registers
-    // instead of the scalar ones the apply would otherwise pin
-    static_assert(sizeof(KParams) % 8 == 0 && sizeof(SlabView) % 8 == 0, "8-byte copies");
+    // instead of the scalar ones the apply would otherwise pin.  The pending record (written by the previous launch) comes
+    // with them in the same round trip: thread 0 then reads the event and the carry from LDS, not in a dependent chain of
+    // global loads behind the barrier, beside the saturated tiles.
+    static_assert(sizeof(KParams) % 8 == 0 && sizeof(SlabView) % 8 == 0 && sizeof(PendRec) % 8 == 0, "8-byte copies");
     KParams* Pl = reinterpret_cast<KParams*>(smem);
-    SlabView* Sl = reinterpret_cast<SlabView*>(smem + ((sizeof(KParams) + 15) & ~(size_t)15));
+    SlabView* Sl = reinterpret_cast<SlabView*>(smem + APPLY_SHMEM_VIEW);
+    PendRec* Rl = reinterpret_cast<PendRec*>(smem + APPLY_SHMEM_PEND);
     for (int q = threadIdx.x; q < (int)(sizeof(KParams) / 8); q += blockDim.x)
         reinterpret_cast<uint64_t*>(Pl)[q] = reinterpret_cast<const uint64_t*>(&X.P)[q];
     for (int q = threadIdx.x; q < (int)(sizeof(SlabView) / 8); q += blockDim.x)
         reinterpret_cast<uint64_t*>(Sl)[q] = reinterpret_cast<const uint64_t*>(X.slabs)[q];
+    for (int q = threadIdx.x; q < (int)(sizeof(PendRec) / 8); q += blockDim.x)
+        reinterpret_cast<uint64_t*>(Rl)[q] = reinterpret_cast<const uint64_t*>(X.pend)[q];
     __syncthreads();
-    apply_batch_body<PEND_EB>(*Pl, Sl, 1, A.L, &X.pend->ev, 1, X.ss, X.cfg, X.u_defect, X.u_np, X.log_total, X.log_event, X.log_nev,
-                              X.ktab_g, 1, nullptr, &X.pend->carry);
+    apply_batch_body<PEND_EB>(*Pl, Sl, 1, A.L, &Rl->ev, 1, X.ss, X.cfg, X.u_defect, X.u_np, X.log_total, X.log_event, X.log_nev,
+                              X.ktab_g, 1, nullptr, &Rl->carry);
 #ifdef CETKMC_SEL_STAMPS
     if (threadIdx.x == 0) g_pend_stamps[1] = g_sel_stamps[10];
 #endif
@@ -2160,7 +2231,7 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     PEND_STAMP(2);
-    const StaleEv se = stale_ev_of(X.pend->ev);
+    const StaleEv se = stale_ev_of(Rl->ev);
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), L = A.L;
     // lane c = candidate c: every wave finds the same set of rows; wave w takes the rows of rank w, w + 4, ...
     int cgi = 0, cj = 0;
@@ -2183,12 +2254,13 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
 }
 
 // TT: census-free tiles (sweep_table_tile), every one with the stale-row test at its store; the dynamic LDS is then the apply
-// block's copy of KParams and SlabView alone.
-template <bool HW, int NPF, bool CH2, bool TT = false>
+// block's copy of KParams, SlabView and the pending record alone.  LS: the tiles' option table_lane_skip.
+template <bool HW, int NPF, bool CH2, bool TT = false, bool LS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_sweep_stream_apply(StreamArgs A,
                                                                                                     const StepState* __restrict__ ss,
                                                                                                     ApplyArgs X)
 {
+    static_assert(!LS || TT, "lanes are skipped by the census-free tiles");
     if (ss->status) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (blockIdx.x != 0) {
@@ -2196,7 +2268,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
         const int b = (int)blockIdx.x - 1;
         const StaleEv se = stale_ev_of(X.pend->ev);
         if constexpr (TT) {
-            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW>(A, b, (int)gridDim.x - 1, stale_win(se));
+            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW, LS>(A, b, (int)gridDim.x - 1, stale_win(se));
         } else {
             int ibr, jt;
             stream_tile_of(A, b, ibr, jt);

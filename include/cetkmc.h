@@ -215,6 +215,10 @@ int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, in
  * 128 < L <= 256: tiles own consecutive ranges of items, item = gi * ((L + 1) / 2) + j / 2, a pair of rows.  -1 outside that
  * shape or the lattice.  Host function; needs no device. */
 int cetkmc_table_tile_of(int L, int gi, int j);
+/* 1 when the census-free tiles (option table_lane_skip) load the 8 rate-table entries of the lane whose 8 class bytes are
+ * class8 (byte h = voxel k0 + h, little endian): some byte is empty (bit 0) or holds a non-zero count (bits 7:2).  0: all
+ * bytes are 0x00 or 0x02, the row reduction masks every entry of the lane.  Host function; needs no device. */
+int cetkmc_lane_needs_values(uint64_t class8);
 /* What a handle keeps between calls, as bits of cetkmc_invalidates()'s result. */
 enum cetkmc_cache {
     CETKMC_CACHE_SWEEP = 1,     /* row and block sums of the last rate sweep (cetkmc_select, cetkmc_row_sums read them) */
@@ -275,7 +279,9 @@ int cetkmc_sync(void* handle);
  * sweeps; same bits), 0 = every step's event applied by its own selection launch;
  * "fused_tiles" 1 (default) = the sweep launch that applies a pending event reduces its rows without the neighbour census, from
  * each voxel's own class byte and the rate table (no LDS ring, no barriers; one process, one slab, 128 < L <= 256; same bits),
- * 2 = the plain streaming launch at that shape as well, 0 = the ring tiles of sweep_variant 1 in both */
+ * 2 = the plain streaming launch at that shape as well, 0 = the ring tiles of sweep_variant 1 in both;
+ * "table_lane_skip" 1 (default) = those census-free tiles request a lane's class bytes first and its rate-table entries only if
+ * cetkmc_lane_needs_values() holds for them (same bits, fewer bytes), 0 = every lane's entries */
 int cetkmc_set_option(void* handle, const char* key, int64_t value);
 /* planes [*i0,*i1) owned by this handle (whole lattice unless created with create_rank) */
 int cetkmc_owned_planes(void* handle, int* i0, int* i1);
