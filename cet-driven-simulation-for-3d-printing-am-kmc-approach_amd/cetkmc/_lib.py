@@ -73,7 +73,8 @@ class Counters(C.Structure):
                                          "bytes_d2h", "alg_bytes_sweep", "alg_bytes_thermal", "profiled_steps")] + \
                [(n, C.c_double) for n in ("ms_thermal", "ms_interface", "ms_sweep", "ms_dirty_rows", "ms_reduce", "ms_select_apply")] + \
                [(n, C.c_int64) for n in ("alg_bytes_table", "table_updates", "interface_launches")] + \
-               [("ms_comm", C.c_double), ("comm_calls", C.c_int64), ("deferred_steps", C.c_int64)]
+               [("ms_comm", C.c_double), ("comm_calls", C.c_int64), ("deferred_steps", C.c_int64),
+                ("early_tiles", C.c_int64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -178,6 +179,7 @@ PROTOTYPES = {
     "cetkmc_stale_row": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_int, C.c_int]),
     "cetkmc_stale_rows": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_int, C.c_void_p]),
     "cetkmc_table_tile_of": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "cetkmc_early_tile_row": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "cetkmc_lane_needs_values": (C.c_int, [C.c_uint64]),
     "cetkmc_invalidates": (C.c_int, [C.c_char_p]),
     "cetkmc_device_count": (C.c_int, [_P(C.c_int)]),

@@ -133,6 +133,9 @@ struct Slab {
     double* Tbuf[2] = {nullptr, nullptr};
     double* vvalbuf[2] = {nullptr, nullptr};     // rate table of Tbuf[b] (the pair is flipped together)
     double* depbuf[2] = {nullptr, nullptr};      // plane L-1 deposition rates of Tbuf[b]
+    double* rowsumbuf[2] = {nullptr, nullptr};   // the two row-sum pairs (one allocation each: the sums, then the counts);
+    int32_t* rowcntbuf[2] = {nullptr, nullptr};  // v.rowsum / v.rowcnt are the pair Handle::row_par names
+    size_t nR = 0;                               // bytes of a pair
     size_t nS = 0, nT = 0, nC = 0;   // bytes of a u8 array, doubles of an f64 array, bytes of the class array
 };
 
@@ -143,8 +146,10 @@ struct Handle {
     int dev = 0;
     hipStream_t stream = nullptr, stream2 = nullptr;
     std::vector<Slab> slabs;
-    SlabView* d_views[2] = {nullptr, nullptr};   // per T-buffer parity
+    SlabView* d_views[4] = {nullptr, nullptr, nullptr, nullptr};   // [T-buffer parity + 2 * row-sum parity]
     int cur = 0;                                 // current T buffer
+    int row_par = 0;                             // current row-sum pair: the one every slab's v.rowsum / v.rowcnt point to, so
+                                                 // whatever takes a view (view_of, dviews) reads and writes the current pair
     int G = 1, my_first = 0;                     // global slab count, index of first local slab
     int own_i0 = 0, own_i1 = 0;
     BlockEnt* d_blocks = nullptr;
@@ -157,7 +162,14 @@ struct Handle {
                                  // (sweep_table_tile) at 128 < L <= 256, 2 = the plain launch at that shape as well, 0 = ring tiles
     int table_lane_skip = 1;     // option "table_lane_skip": 1 = those tiles request the class bytes first and the table entries only in
                                  // the lanes that can use them (lane_needs_values()), 0 = every lane's entries; same bits
+    int early_tiles = -1;        // option "early_tiles": tiles of the next step's sweep that a deferred step's selection launch runs
+                                 // (k_select_pend_tiles, into the other row-sum pair); 0 = k_select_pend and one pair; -1 (default) =
+                                 // a quarter of the tile range, 1024 of 4096 at 256^3, where it was measured
+    int early_blocks = 256;      // option "early_blocks": tile blocks of that launch (each takes several tiles in turn: one block per
+                                 // CU, four tiles each at 256^3); 0 = one per tile
+    int poison_alt_rows = 0;     // option "poison_alt_rows" (tests): the pair about to be written is filled with 0xFF first
     bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
+    int pend_early = 0;          // ... and leaves out its first pend_early tiles, which the selection launch ran
     BatchCfg pend_cfg{};         // ... with this batch configuration
     double* d_ktab = nullptr;
     KParams* d_kp = nullptr;
@@ -378,9 +390,14 @@ int upload_ktab(Handle* h)
 
 int push_views(Handle* h)
 {
-    for (int par = 0; par < 2; ++par) {
+    for (int par = 0; par < 4; ++par) {
         std::vector<SlabView> v;
-        for (auto& s : h->slabs) { SlabView x = s.v; x.T = s.Tbuf[par]; x.vval = s.vvalbuf[par]; x.dep_val = s.depbuf[par]; v.push_back(x); }
+        for (auto& s : h->slabs) {
+            SlabView x = s.v;
+            x.T = s.Tbuf[par & 1]; x.vval = s.vvalbuf[par & 1]; x.dep_val = s.depbuf[par & 1];
+            x.rowsum = s.rowsumbuf[par >> 1]; x.rowcnt = s.rowcntbuf[par >> 1];
+            v.push_back(x);
+        }
         HIPCHK(hipMemcpyAsync(h->d_views[par], v.data(), v.size() * sizeof(SlabView), hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -475,13 +492,17 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
         HIPCHK(hipMalloc((void**)&s.v.ifc_n, sizeof(int)));
         HIPCHK(hipMemsetAsync(s.v.ifc_in, 0, s.nT, h->stream));
         HIPCHK(hipMemsetAsync(s.v.ifc_n, 0, sizeof(int), h->stream));
-        HIPCHK(hipMalloc((void**)&s.v.rowsum, (size_t)r.second * 3 * L * sizeof(double)));
-        HIPCHK(hipMalloc((void**)&s.v.rowcnt, (size_t)r.second * 3 * L * sizeof(int32_t)));
-        HIPCHK(hipMemsetAsync(s.v.rowsum, 0, (size_t)r.second * 3 * L * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(s.v.rowcnt, 0, (size_t)r.second * 3 * L * sizeof(int32_t), h->stream));
+        const size_t n_rows = (size_t)r.second * 3 * L;
+        s.nR = n_rows * (sizeof(double) + sizeof(int32_t));
+        for (int b = 0; b < 2; ++b) {
+            HIPCHK(hipMalloc((void**)&s.rowsumbuf[b], s.nR));
+            HIPCHK(hipMemsetAsync(s.rowsumbuf[b], 0, s.nR, h->stream));
+            s.rowcntbuf[b] = reinterpret_cast<int32_t*>(s.rowsumbuf[b] + n_rows);
+        }
+        s.v.rowsum = s.rowsumbuf[0]; s.v.rowcnt = s.rowcntbuf[0];
         h->slabs.push_back(s);
     }
-    for (int par = 0; par < 2; ++par) HIPCHK(hipMalloc((void**)&h->d_views[par], h->slabs.size() * sizeof(SlabView)));
+    for (int par = 0; par < 4; ++par) HIPCHK(hipMalloc((void**)&h->d_views[par], h->slabs.size() * sizeof(SlabView)));
     HIPCHK(hipMalloc((void**)&h->d_blocks, (size_t)PMAX * sizeof(BlockEnt)));
     HIPCHK(hipMemsetAsync(h->d_blocks, 0, (size_t)PMAX * sizeof(BlockEnt), h->stream));
     HIPCHK(hipMalloc((void**)&h->d_events_all, (size_t)G * sizeof(cetkmc_event)));
@@ -503,6 +524,16 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
     HIPCHK(hipStreamSynchronize(h->stream));
     *out = h;
     return 0;
+}
+
+// the device views of the current T buffer and the current row-sum pair
+SlabView* dviews(const Handle* h) { return h->d_views[h->cur + 2 * h->row_par]; }
+// The other row-sum pair becomes the current one (a deferred step whose selection launch has run early tiles into it).  Host
+// state only: every launch issued from here on takes its views after the flip.
+void flip_rows(Handle* h)
+{
+    h->row_par ^= 1;
+    for (auto& s : h->slabs) { s.v.rowsum = s.rowsumbuf[h->row_par]; s.v.rowcnt = s.rowcntbuf[h->row_par]; }
 }
 
 SlabView view_of(Handle* h, int s, int par = -1)
@@ -879,14 +910,16 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
         } else if (h->sweep_variant >= 1 && h->pend_live) {
             // the previous step's event is applied by one extra workgroup (blockIdx 0) of this launch (run_steps defers
             // only under the streaming sweep with the rate table, and only where rows are half-wave rows)
-            ApplyArgs X{h->kp, (const SlabView*)h->d_views[h->cur], h->d_pend, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
+            ApplyArgs X{h->kp, (const SlabView*)dviews(h), h->d_pend, h->d_ss, h->pend_cfg, (const double*)h->d_u_defect,
                         (const double*)h->d_u_np, (const double*)h->d_ktab, h->d_log_total, h->d_log_event, h->d_log_nev};
-            if (table_tiles(h, 1))      // LDS: the apply block's KParams + SlabView + PendRec copy alone
+            if (table_tiles(h, 1))      // LDS: the apply block's KParams + SlabView + PendRec copy alone; the tiles the selection
+                                        // launch has not run (launch_select_pend)
                 with_flag(h->table_lane_skip != 0, [&](auto ls) {
-                    launch(k_sweep_stream_apply<true, 1, false, true, ls.value>, dim3(table_tile_count(h->L, v.nloc, true) + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X);
+                    const int late = table_tile_count(h->L, v.nloc, true) - h->pend_early;
+                    launch(k_sweep_stream_apply<true, 1, false, true, ls.value>, dim3(late + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X, h->pend_early);
                 });
             else
-                launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X);
+                launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X, 0);
         } else if (h->sweep_variant == 1 && table_tiles(h, 2)) {
             with_flag(h->table_lane_skip != 0, [&](auto ls) {
                 launch(k_sweep_stream<true, true, 1, false, true, ls.value>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
@@ -913,7 +946,7 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
 
 int launch_select(Handle* h, const BatchCfg& cfg, double r_direct, int info_only)
 {
-    hipLaunchKernelGGL(k_select, dim3(1), dim3(256), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+    hipLaunchKernelGGL(k_select, dim3(1), dim3(256), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                        (int)h->slabs.size(), h->L, h->PB, (const BlockEnt*)h->d_blocks, h->d_ss, cfg,
                        (const double*)h->d_u_pick, r_direct, (const double*)h->d_ktab,
                        h->d_events_all + h->my_first, info_only, h->sweep_variant >= 1 ? 1 : 0);
@@ -928,7 +961,7 @@ int launch_select_apply(Handle* h, const BatchCfg& cfg, int eval_touched, int* d
 {
     if (!multi_rank(h)) {
         with_flag(h->sweep_variant >= 1, [&](auto ifc) {
-            launch(k_select_apply<ifc.value>, dim3(1), dim3(256), 0, h->stream, nullptr, nullptr, h->kp, h->d_views[h->cur], (int)h->slabs.size(),
+            launch(k_select_apply<ifc.value>, dim3(1), dim3(256), 0, h->stream, nullptr, nullptr, h->kp, dviews(h), (int)h->slabs.size(),
                    h->L, h->PB, h->d_blocks, h->d_ss, cfg, h->d_u_pick, h->d_ktab, h->d_events_all + h->my_first, ifc.value ? 1 : 0,
                    h->d_u_defect, h->d_u_np, h->d_log_total, h->d_log_event, h->d_log_nev, eval_touched, dirty, (long long)cur_hint);
         });
@@ -936,7 +969,7 @@ int launch_select_apply(Handle* h, const BatchCfg& cfg, int eval_touched, int* d
         return 0;
     }
     CHK(launch_select(h, cfg, 0.0, 0));
-    hipLaunchKernelGGL(k_apply_batch, dim3(1), dim3(64), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+    hipLaunchKernelGGL(k_apply_batch, dim3(1), dim3(64), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                        (int)h->slabs.size(), h->L, (const cetkmc_event*)h->d_events_all, h->G, h->d_ss, cfg,
                        (const double*)h->d_u_defect, (const double*)h->d_u_np, h->d_log_total, h->d_log_event,
                        h->d_log_nev, (const double*)h->d_ktab, eval_touched, dirty);
@@ -944,10 +977,33 @@ int launch_select_apply(Handle* h, const BatchCfg& cfg, int eval_touched, int* d
     return 0;
 }
 
-// selection of a deferred step (single process): the event and its carry go to d_pend, the next sweep launch applies them
+// selection of a deferred step (single process): the event and its carry go to d_pend, the next sweep launch applies them.
+// Option early_tiles, where that launch runs the census-free tiles: the first E tiles of its range run here, beside the
+// selection block, and store into the other row-sum pair, which then becomes the current one -- the next sweep launch stores
+// the remaining rows into it, and its reduce and selection read it.
 int launch_select_pend(Handle* h, const BatchCfg& cfg, int64_t cur_hint)
 {
-    hipLaunchKernelGGL(k_select_pend, dim3(1), dim3(256), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+    h->pend_early = 0;
+    if (h->early_tiles != 0 && table_tiles(h, 1)) {
+        Slab& sl = h->slabs[0];
+        const int count = table_tile_count(h->L, sl.v.nloc, true);
+        const int E = h->early_tiles < 0 ? count / 4 : std::min(h->early_tiles, count);
+        if (h->poison_alt_rows) HIPCHK(hipMemsetAsync(sl.rowsumbuf[h->row_par ^ 1], 0xFF, sl.nR, h->stream));
+        const SlabView* sel_views = dviews(h);      // the selection reads the current pair
+        flip_rows(h);
+        const StreamArgs sa = stream_args(h, view_of(h, 0));      // the tiles write the other one
+        with_flag(h->table_lane_skip != 0, [&](auto ls) {
+            const int G = h->early_blocks > 0 ? std::min(h->early_blocks, E) : E;
+            launch(k_select_pend_tiles<ls.value>, dim3(G + 1), dim3(256), 0, h->stream, nullptr, nullptr, h->kp, sel_views, (int)h->slabs.size(), h->L,
+                   h->PB, (const BlockEnt*)h->d_blocks, h->d_ss, cfg, (const double*)h->d_u_pick, (const double*)h->d_ktab, h->d_pend,
+                   (const double*)h->d_u_defect, (const double*)h->d_u_np, (long long)cur_hint, sa, E);
+        });
+        HIPCHK(hipGetLastError());
+        h->pend_early = E;
+        h->cnt.early_tiles += E;
+        return 0;
+    }
+    hipLaunchKernelGGL(k_select_pend, dim3(1), dim3(256), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                        (int)h->slabs.size(), h->L, h->PB, (const BlockEnt*)h->d_blocks, h->d_ss, cfg,
                        (const double*)h->d_u_pick, (const double*)h->d_ktab, h->d_pend, (const double*)h->d_u_defect,
                        (const double*)h->d_u_np, (long long)cur_hint);
@@ -1260,7 +1316,7 @@ void destroy_impl(Handle* h)
     for (auto& s : h->slabs) {
         (void)hipFree(s.v.state); (void)hipFree(s.v.defects); (void)hipFree(s.prev); (void)hipFree(s.v.row_chg); (void)hipFree(s.v.cls);
         (void)hipFree(s.Tbuf[0]); (void)hipFree(s.Tbuf[1]); (void)hipFree(s.v.theta); (void)hipFree(s.v.phi); (void)hipFree(s.v.ovec);
-        (void)hipFree(s.v.rowsum); (void)hipFree(s.v.rowcnt);
+        (void)hipFree(s.rowsumbuf[0]); (void)hipFree(s.rowsumbuf[1]);
         (void)hipFree(s.vvalbuf[0]); (void)hipFree(s.vvalbuf[1]); (void)hipFree(s.depbuf[0]); (void)hipFree(s.depbuf[1]); (void)hipFree(s.v.ifc_in); (void)hipFree(s.v.ifc_code); (void)hipFree(s.v.ifc_list); (void)hipFree(s.v.ifc_n);
     }
     if (h->d_solid_block) (void)hipFree(h->d_solid_block);
@@ -1268,7 +1324,7 @@ void destroy_impl(Handle* h)
     if (h->d_melt_block) (void)hipFree(h->d_melt_block);
     void* ccp[] = {h->d_cc_parent, h->d_cc_roots, h->d_cc_cid, h->d_cc_labels, h->d_cc_stats, h->d_cc_n};
     for (void* p : ccp) if (p) (void)hipFree(p);
-    void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
+    void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_views[2], h->d_views[3], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
                     h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq};
@@ -1444,6 +1500,11 @@ int cetkmc_table_tile_of(int L, int gi, int j)
     if (L <= 128 || L > 256 || gi < 0 || gi >= L || j < 0 || j >= L) return -1;
     return table_tile_of(L, true, gi, j);
 }
+int cetkmc_early_tile_row(int L, int early_tiles, int gi, int j)
+{
+    const int t = cetkmc_table_tile_of(L, gi, j);
+    return t < 0 ? -1 : (t < early_tiles ? 1 : 0);
+}
 int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, int rows[][2])
 {
     const StaleEv se = stale_ev_host(type, pos, target);
@@ -1592,6 +1653,17 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         return 0;
     }
     if (!strcmp(key, "table_lane_skip")) { h->table_lane_skip = value ? 1 : 0; return 0; }
+    if (!strcmp(key, "early_tiles")) {
+        if (value < -1 || value > INT32_MAX) return fail("early_tiles must be a tile count >= 0, or -1 (a quarter of the tiles)");
+        h->early_tiles = (int)value;
+        return 0;
+    }
+    if (!strcmp(key, "early_blocks")) {
+        if (value < 0 || value > INT32_MAX) return fail("early_blocks must be a block count >= 0");
+        h->early_blocks = (int)value;
+        return 0;
+    }
+    if (!strcmp(key, "poison_alt_rows")) { h->poison_alt_rows = value ? 1 : 0; return 0; }
     if (!strcmp(key, "thermal_table")) { h->thermal_table = value ? 1 : 0; return 0; }
     if (!strcmp(key, "reserve_batch")) {
         // device buffers (uniform streams, per-step logs, one laser source plane per temperature update) and hipEvents of a
@@ -1776,7 +1848,7 @@ int cetkmc_apply(void* handle, const cetkmc_event* ev, double theta_new, double 
     HIPCHK(hipSetDevice(h->dev));
     cetkmc_event e = *ev;
     if (e.type == CETKMC_DEP || e.type == CETKMC_NUC) { e.theta = theta_new; e.phi = phi_new; }
-    hipLaunchKernelGGL(k_apply_direct, dim3(1), dim3(64), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+    hipLaunchKernelGGL(k_apply_direct, dim3(1), dim3(64), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                        (int)h->slabs.size(), e, make_defect, h->d_ss, (const double*)h->d_ktab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2312,10 +2384,10 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     for (int64_t s = 0; s < n; ++s) {
         CHK(super_step_head(h, B, s, &q_idx));
         if (C.H == 4)       // box 8: window tree in registers
-            hipLaunchKernelGGL(k_domain_pick8, dim3(D), dim3(64), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+            hipLaunchKernelGGL(k_domain_pick8, dim3(D), dim3(64), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                                (int)h->slabs.size(), h->L, C, (const StepState*)h->d_ss, (const double*)h->d_ktab, d_picks, (long long)s);
         else
-            hipLaunchKernelGGL(k_domain_pick, dim3(D), dim3(64), shmem, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+            hipLaunchKernelGGL(k_domain_pick, dim3(D), dim3(64), shmem, h->stream, h->kp, (const SlabView*)dviews(h),
                                (int)h->slabs.size(), h->L, C, (const StepState*)h->d_ss, (const double*)h->d_ktab, d_picks);
         if (C.null_events) {
             // R_max of the super-step: this rank's largest window total, then (across ranks) the largest of all ranks
@@ -2323,18 +2395,18 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
                                d_rmax, ranks ? h->rank : 0);
             if (ranks) CHK(comm_allgather(h, d_rmax, sizeof(double)));
         }
-        hipLaunchKernelGGL(k_domain_apply, dim3((D + 63) / 64), dim3(64), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+        hipLaunchKernelGGL(k_domain_apply, dim3((D + 63) / 64), dim3(64), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                            (int)h->slabs.size(), h->L, D, C, h->d_ss, (const DomPick*)d_picks, d_dom, B.d_cnt, B.d_log, (const double*)d_rmax);
         int n_touch = D;
         if (ranks) {
             // the events of my bottom / top box layer go to the ranks below / above, theirs come here: every rank applies
             // them to its own copy (owned planes: diffusion targets across the boundary; halo planes: the neighbour's state)
             CHK(comm_exchange(h, d_dom, d_dom + D, d_dom + (D - nb2), d_dom + D + nb2, (size_t)nb2 * sizeof(cetkmc_event)));
-            hipLaunchKernelGGL(k_domain_apply_remote, dim3((2 * nb2 + 63) / 64), dim3(64), 0, h->stream, (const SlabView*)h->d_views[h->cur],
+            hipLaunchKernelGGL(k_domain_apply_remote, dim3((2 * nb2 + 63) / 64), dim3(64), 0, h->stream, (const SlabView*)dviews(h),
                                (int)h->slabs.size(), C, (const StepState*)h->d_ss, (const cetkmc_event*)(d_dom + D));
             n_touch = NE;
         }
-        hipLaunchKernelGGL(k_domain_touch, dim3(2 * ((n_touch + 15) / 16)), dim3(256), 0, h->stream, h->kp, (const SlabView*)h->d_views[h->cur],
+        hipLaunchKernelGGL(k_domain_touch, dim3(2 * ((n_touch + 15) / 16)), dim3(256), 0, h->stream, h->kp, (const SlabView*)dviews(h),
                            (int)h->slabs.size(), n_touch, (const cetkmc_event*)d_dom, (const StepState*)h->d_ss, (const double*)h->d_ktab);
         hipLaunchKernelGGL(k_super_commit, dim3(1), dim3(64), 0, h->stream, h->d_ss, B.d_cnt, h->d_log_total, h->d_log_nev,
                            C.null_events ? d_rmax : (double*)nullptr, std::min(C.nranks, 64));
@@ -2382,7 +2454,7 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     int64_t q_idx = 0;
     for (int64_t s = 0; s < n; ++s) {
         CHK(super_step_head(h, B, s, &q_idx));
-        const SlabView* views = (const SlabView*)h->d_views[h->cur];
+        const SlabView* views = (const SlabView*)dviews(h);
         hipLaunchKernelGGL(k_domain_pick8, dim3(D), dim3(64), 0, h->stream, h->kp, views, 1, h->L, C, (const StepState*)h->d_ss,
                            (const double*)h->d_ktab, B.d_picks, (long long)s);
         hipLaunchKernelGGL(k_domain_rmax, dim3((D + 1023) / 1024), dim3(1024), 0, h->stream, (const DomPick*)B.d_picks, D, (const StepState*)h->d_ss,

@@ -904,8 +904,10 @@ __host__ __device__ constexpr int table_tile_of(int L, bool hw, int lp, int j)
 // table_row() masks with, so the row sums are those of the unconditional loads to the bit: mask_f64() zeroed a skipped lane's
 // entries before.  The price is one dependent round trip per pair of items; beside four other waves per SIMD it was not
 // measurable, the bytes were (131 MB per launch at 256^3 instead of 157 MB).
+// `first`: block b of the launch's nblk tile blocks runs tile first + b of the mapping above (a launch that runs a part of the
+// tile range: the early tiles of k_select_pend_tiles, the remaining ones of k_sweep_stream_apply).
 template <bool HW, bool CH2, bool SK, int IPW, bool LS = false>
-__device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int nblk, const StaleWin& sw = StaleWin{})
+__device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int nblk, const StaleWin& sw = StaleWin{}, int first = 0)
 {
     static_assert(IPW % 2 == 0, "two alternating buffers");
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -913,7 +915,7 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
     const int ipp = table_tile_ipp(L, HW);                       // items per plane (HW: pairs of rows)
     const int n_items = ipp * A.nloc;
     if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);      // contiguous item ranges per XCD
-    int item = b * 4 * IPW + w;
+    int item = (first + b) * 4 * IPW + w;
     if (item >= n_items) return;
     int lp = item / ipp, jp = item - lp * ipp;
     const int sl = HW ? (lane & 31) : lane;
@@ -1351,7 +1353,9 @@ __device__ __forceinline__ TreeSel tree_select(const double (&lf)[8], unsigned f
 // k_select: single block.  (1) total + termination checks, (2) block descent, (3) row descent
 // in the owning slab, (4) voxel descent (leaves looked up in the rate table), (5) slot scan.
 // cur_hint >= 0: the batch step index as the host knows it (== ss->cur while status == 0): saves a dependent load.
-template <bool IFC>
+// PM: leaves of its LDS trees (rows of a block, voxels of a row: Pk <= PM); k_select_pend_tiles, whose static LDS every one of
+// its tile blocks is charged with, runs at half-wave rows only and takes 256.
+template <bool IFC, int PM = PMAX>
 __device__ __forceinline__ void select_body(const KParams& P, const SlabView* __restrict__ slabs, int nslabs, int L,
                                             int PB, const BlockEnt* __restrict__ blocks, StepState* ss,
                                             const BatchCfg& cfg, const double* __restrict__ u_pick, double r_direct,
@@ -1359,8 +1363,8 @@ __device__ __forceinline__ void select_body(const KParams& P, const SlabView* __
                                             long long cur_hint = -1, SelCarry* carry = nullptr,
                                             const double* __restrict__ u_defect = nullptr, const double* __restrict__ u_np = nullptr)
 {
-    __shared__ double leafval[PMAX];           // the voxel tree's leaves (the chosen one is read back)
-    __shared__ int rowcnt_l[PMAX], voxcnt_l[PMAX];     // event counts of the chosen block's rows / the chosen row's voxels (deposition rank)
+    __shared__ double leafval[PM];             // the voxel tree's leaves (the chosen one is read back)
+    __shared__ int rowcnt_l[PM], voxcnt_l[PM];         // event counts of the chosen block's rows / the chosen row's voxels (deposition rank)
     __shared__ double ktab[225];
     __shared__ long long red[4];
     __shared__ TreeScratch X;
@@ -2182,6 +2186,32 @@ __global__ __launch_bounds__(256) void k_select_pend(KParams P, const SlabView* 
                       u_defect, u_np);
 }
 
+// k_select_pend with early tiles (option early_tiles; one slab, half-wave rows, census-free tiles): blockIdx 0 is k_select_pend's
+// block; the blocks behind it run the first n_early tiles of the NEXT step's sweep, which the next launch
+// (k_sweep_stream_apply with first_tile = n_early) then leaves out.  A row that is not stale under the event this launch is
+// choosing has the same sums before and after it, so these tiles read the lattice as it stands and store every row of
+// theirs; the next launch's apply block, which runs after this launch has ended, overwrites the stale ones.  They read no
+// step status and no pending record: behind a stop they store what the rows held anyway.  A.rowsum / A.rowcnt are the row-sum
+// pair the selection block of this launch does NOT read (Handle::row_par): no launch reads a row-sum buffer that another of
+// its blocks writes.
+template <bool LS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_select_pend_tiles(
+    KParams P, const SlabView* __restrict__ slabs, int nslabs, int L, int PB, const BlockEnt* __restrict__ blocks, StepState* ss,
+    BatchCfg cfg, const double* __restrict__ u_pick, const double* __restrict__ ktab_g, PendRec* pend,
+    const double* __restrict__ u_defect, const double* __restrict__ u_np, long long cur_hint, StreamArgs A, int n_early)
+{
+    if (blockIdx.x == 0) {
+        select_body<true, 256>(P, slabs, nslabs, L, PB, blocks, ss, cfg, u_pick, 0.0, ktab_g, &pend->ev, 0, 1, cur_hint, &pend->carry,
+                               u_defect, u_np);
+        return;
+    }
+    // option early_blocks: fewer tile blocks than tiles, block x takes the tiles x - 1, x - 1 + (blocks), ... one after the other
+    // (the early traffic spread over the selection's life instead of one burst beside its first loads)
+#pragma unroll 1
+    for (int t = (int)blockIdx.x - 1; t < n_early; t += (int)gridDim.x - 1)
+        sweep_table_tile<true, false, false, TABLE_TILE_IPW, LS>(A, t, n_early);
+}
+
 // The apply block: apply_batch_body of the fused launch (carry from the record instead of LDS), then the stale rows with
 // the census-free row reduction of the incremental mode's k_rows_eval, stored into rowsum / rowcnt.  Which rows follows from
 // the record alone, as for the tiles that left them out (a record that names an event is always applied: select_body sets
@@ -2254,11 +2284,13 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
 }
 
 // TT: census-free tiles (sweep_table_tile), every one with the stale-row test at its store; the dynamic LDS is then the apply
-// block's copy of KParams, SlabView and the pending record alone.  LS: the tiles' option table_lane_skip.
+// block's copy of KParams, SlabView and the pending record alone.  LS: the tiles' option table_lane_skip.  first_tile (TT): the
+// launch's tile blocks run the tiles from first_tile on -- the ones before it ran in the previous launch (k_select_pend_tiles);
+// with first_tile >= the tile count the grid is the apply block alone.
 template <bool HW, int NPF, bool CH2, bool TT = false, bool LS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_sweep_stream_apply(StreamArgs A,
                                                                                                     const StepState* __restrict__ ss,
-                                                                                                    ApplyArgs X)
+                                                                                                    ApplyArgs X, int first_tile)
 {
     static_assert(!LS || TT, "lanes are skipped by the census-free tiles");
     if (ss->status) return;
@@ -2268,7 +2300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
         const int b = (int)blockIdx.x - 1;
         const StaleEv se = stale_ev_of(X.pend->ev);
         if constexpr (TT) {
-            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW, LS>(A, b, (int)gridDim.x - 1, stale_win(se));
+            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW, LS>(A, b, (int)gridDim.x - 1, stale_win(se), first_tile);
         } else {
             int ibr, jt;
             stream_tile_of(A, b, ibr, jt);

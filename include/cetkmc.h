@@ -189,6 +189,8 @@ typedef struct cetkmc_counters {
     int64_t deferred_steps;     /* cetkmc_run_steps: steps launched as a selection alone, their event applied inside the next
                                    rate-sweep launch (option apply_in_sweep); counts launches issued, so a batch that stops
                                    early still counts every deferred step the host queued                           */
+    int64_t early_tiles;        /* tiles of the next step's sweep that those steps' selection launches ran (option
+                                   early_tiles); launches issued, as above                                             */
 } cetkmc_counters;
 
 const char* cetkmc_last_error(void);
@@ -215,6 +217,10 @@ int cetkmc_stale_rows(int type, const int pos[2], const int target[2], int L, in
  * 128 < L <= 256: tiles own consecutive ranges of items, item = gi * ((L + 1) / 2) + j / 2, a pair of rows.  -1 outside that
  * shape or the lattice.  Host function; needs no device. */
 int cetkmc_table_tile_of(int L, int gi, int j);
+/* Which launch stores row j of plane gi under option early_tiles = early_tiles, unless the pending event makes the row stale:
+ * 1 = a tile of the deferred step's selection launch (cetkmc_table_tile_of() < early_tiles), 0 = a tile of the sweep launch
+ * behind it, -1 where cetkmc_table_tile_of() is.  Host function; needs no device. */
+int cetkmc_early_tile_row(int L, int early_tiles, int gi, int j);
 /* 1 when the census-free tiles (option table_lane_skip) load the 8 rate-table entries of the lane whose 8 class bytes are
  * class8 (byte h = voxel k0 + h, little endian): some byte is empty (bit 0) or holds a non-zero count (bits 7:2).  0: all
  * bytes are 0x00 or 0x02, the row reduction masks every entry of the lane.  Host function; needs no device. */
@@ -281,7 +287,14 @@ int cetkmc_sync(void* handle);
  * each voxel's own class byte and the rate table (no LDS ring, no barriers; one process, one slab, 128 < L <= 256; same bits),
  * 2 = the plain streaming launch at that shape as well, 0 = the ring tiles of sweep_variant 1 in both;
  * "table_lane_skip" 1 (default) = those census-free tiles request a lane's class bytes first and its rate-table entries only if
- * cetkmc_lane_needs_values() holds for them (same bits, fewer bytes), 0 = every lane's entries */
+ * cetkmc_lane_needs_values() holds for them (same bits, fewer bytes), 0 = every lane's entries;
+ * "early_tiles" E = the selection launch of a deferred step also runs the first E census-free tiles of the next step's sweep
+ * (values past the tile count mean all of them), which the next sweep launch then leaves out; they store into the handle's
+ * second pair of row-sum buffers, which becomes the current pair (same bits; DESIGN.md sections 13 and 20), 0 = the selection
+ * block alone and one pair, -1 (default) = a quarter of the tiles (1024 of 4096 at 256^3, where it was measured);
+ * "early_blocks" G (default 256, one per CU) = those E tiles run in G blocks, each taking every G-th tile in turn (0 or G >= E:
+ * one block per tile); "poison_alt_rows" 1 (tests) = the pair such a step is about to write is filled with 0xFF bytes
+ * first, so that a row no launch stores would show as NaN in the next total, 0 (default) = no fill */
 int cetkmc_set_option(void* handle, const char* key, int64_t value);
 /* planes [*i0,*i1) owned by this handle (whole lattice unless created with create_rank) */
 int cetkmc_owned_planes(void* handle, int* i0, int* i1);
