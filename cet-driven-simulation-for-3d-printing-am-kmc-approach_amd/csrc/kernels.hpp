@@ -80,36 +80,58 @@ __device__ __forceinline__ double dpp_f64(double v, int ctrl_sel)
     else { a = __builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xF, 0xF, true); b = __builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xF, 0xF, true); }
     return __hiloint2double((int)b, (int)a);
 }
-__device__ __forceinline__ double wave_tree_sum(double v)
+// levels 16 and 32: the swap of a value with itself leaves the two sibling subtrees' sums in its two results, in the same
+// order in both partner lanes; every butterfly and kept-level tree below adds them through these two
+__device__ __forceinline__ double swap_add16(double v)
+{
+    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+    const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
+}
+__device__ __forceinline__ double swap_add32(double v)
+{
+    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+    const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
+}
+// The same tree with EVERY level kept: lv[0] is the lane's own value, lv[l] the sum of the aligned block of 2^l lanes the lane
+// belongs to (the selection trees descend through them with v_readlane)
+__device__ __forceinline__ void wave_tree_levels(double (&lv)[7])
+{
+    lv[1] = lv[0] + dpp_f64(lv[0], 0);
+    lv[2] = lv[1] + dpp_f64(lv[1], 1);
+    lv[3] = lv[2] + dpp_f64(lv[2], 2);
+    lv[4] = lv[3] + dpp_f64(lv[3], 3);
+    lv[5] = swap_add16(lv[4]);
+    lv[6] = swap_add32(lv[5]);
+}
+// HALF: butterfly over the 32 lanes of each half-wave only
+template <bool HALF>
+__device__ __forceinline__ double wave_tree_sum_h(double v)
 {
     v = v + dpp_f64(v, 0);
     v = v + dpp_f64(v, 1);
     v = v + dpp_f64(v, 2);
     v = v + dpp_f64(v, 3);
-    {
-        const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-        const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
-    {
-        const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-        const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
+    v = swap_add16(v);
+    if (!HALF) v = swap_add32(v);
     return v;
 }
-__device__ __forceinline__ int wave_sum_i(int v)
+template <bool HALF>
+__device__ __forceinline__ int wave_sum_i_h(int v)
 {
     v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0xB1, 0xF, 0xF, true);
     v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0x4E, 0xF, 0xF, true);
     v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0x141, 0xF, 0xF, true);
     v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0x140, 0xF, 0xF, true);
     { const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false); v = (int)(r[0] + r[1]); }
-    { const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false); v = (int)(r[0] + r[1]); }
+    if (!HALF) { const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false); v = (int)(r[0] + r[1]); }
     return v;
 }
+__device__ __forceinline__ double wave_tree_sum(double v) { return wave_tree_sum_h<false>(v); }
+__device__ __forceinline__ int wave_sum_i(int v) { return wave_sum_i_h<false>(v); }
 // Binary-counter merge of aligned power-of-two chunks: returns the merged value so far;
 // after the last chunk (m = nchunks-1) the return value is the full balanced-tree sum.
 template <int LV>
@@ -236,6 +258,9 @@ constexpr int STREAM_MAXPF = 3;   // 16-B chunks of a class slab per thread (L <
 
 // Block sum of (owned plane lp, category c) by one wave: balanced tree over j of the row sums.  COH: some row sums
 // were written by other blocks of the SAME launch (k_rows_eval's in-launch reduction) -> agent-scope loads.
+// (k_sweep_plane folds its LDS copy with the same loop written out in its own body: as a call of this function with the LDS
+// rows as source the compiler turned the tail of every plane's block into branches, and variant 4 measured 34.2 against
+// 33.8 us at 256^3, outside the parent's spread -- profiles/row_reduction_ab.json.)
 template <bool COH>
 __device__ __forceinline__ void plane_reduce_wave(const double* rowsum, const int32_t* rowcnt, BlockEnt* blocks,
                                                   int L, int Pk, int gi0, int lp, int c, int lane)
@@ -356,40 +381,6 @@ __device__ __forceinline__ double nuc_bulk(double T_melt, double delta_T_c, doub
     return r;
 }
 
-// half == true: butterfly over the 32 lanes of each half-wave only
-template <bool HALF>
-__device__ __forceinline__ double wave_tree_sum_h(double v)
-{
-    v = v + dpp_f64(v, 0);
-    v = v + dpp_f64(v, 1);
-    v = v + dpp_f64(v, 2);
-    v = v + dpp_f64(v, 3);
-    {
-        const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-        const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
-    if (!HALF) {
-        const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-        const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
-    return v;
-}
-template <bool HALF>
-__device__ __forceinline__ int wave_sum_i_h(int v)
-{
-    v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0xB1, 0xF, 0xF, true);
-    v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0x4E, 0xF, 0xF, true);
-    v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0x141, 0xF, 0xF, true);
-    v += (int)__builtin_amdgcn_update_dpp((unsigned)v, (unsigned)v, 0x140, 0xF, 0xF, true);
-    { const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false); v = (int)(r[0] + r[1]); }
-    if (!HALF) { const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false); v = (int)(r[0] + r[1]); }
-    return v;
-}
-
 __device__ __forceinline__ unsigned alignbyte(unsigned hi, unsigned lo, unsigned n) { return __builtin_amdgcn_alignbyte(hi, lo, n); }
 // v & (bit b of w ? ~0 : 0): one v_bfe_i32 + two v_and_b32
 __device__ __forceinline__ double mask_f64(double v, unsigned w, int b)
@@ -413,31 +404,36 @@ __device__ __forceinline__ void load_vals(const StreamArgs& A, int li, int jrow,
     // whatever they load
     const int k0 = min((m << 9) + 8 * (HW ? (lane & 31) : lane), A.pitchT - 8);
     const int jr = min(jrow, A.L - 1);
-#ifdef CETKMC_COALESCED_TIMING
-    // TIMING ONLY (results wrong): every load instruction reads whole lines -- lane l takes 16 B at 16 l + (HW ? 512 : 1024) q
-    (void)k0;
-    const double2* src = reinterpret_cast<const double2*>((TAB ? A.vval : A.T) + ((int64_t)li * A.L + jr) * A.pitchT + (m << 9));
-    const int nl = HW ? 32 : 64, sl_ = HW ? (lane & 31) : lane;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const double2 t = src[min(q * nl + sl_, A.pitchT / 2 - 1)]; v[2 * q] = t.x; v[2 * q + 1] = t.y; }
-#else
     const double2* src = reinterpret_cast<const double2*>((TAB ? A.vval : A.T) + ((int64_t)li * A.L + jr) * A.pitchT + k0);
 #pragma unroll
     for (int q = 0; q < 4; ++q) { const double2 t = src[q]; v[2 * q] = t.x; v[2 * q + 1] = t.y; }
-#endif
+}
+// the lane's own 8 class bytes of the same chunk (same clamping)
+__device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow, int sl, int m)
+{
+    const int k0 = min((m << 9) + 8 * sl, A.pitchT - 8);
+    const int jr = min(jrow, A.L - 1);
+    return *reinterpret_cast<const uint2*>(A.cls + ((int64_t)li * A.RJ + (jr + 2)) * A.pitchC + KOFFC + k0);
 }
 
-// One lattice row per wave (HW: per half-wave; `jrow` is then the lane's own row) of plane li: census + rates +
-// canonical row reduction, results to rowsum/rowcnt.  `rowp(d, dj)` returns the class-row pointer (at k = 0) of plane
-// li+d, row jrow+dj -- an LDS ring slot in the streaming kernel, the global class array in the dirty-row kernel;
-// everything else is shared, so both produce bit-identical row sums.  v0 = load_vals() of chunk 0.
+// THE row reduction: one lattice row per wave (HW: per half-wave; `jrow` is then the lane's own row) of plane li -- voxel
+// classes, rates, canonical row tree -- results to rowsum/rowcnt.  Every sweep path reduces its rows here, so they agree to
+// the bit.  v0 = load_vals() of chunk 0.  The paths differ only in `cls`, how a voxel is classified:
+//   census (cls = rowp, a callable: rowp(d, dj) is the class-row pointer (at k = 0) of plane li+d, row jrow+dj -- an LDS ring
+//     slot in the streaming kernel, the global class array in the dirty-row kernel): OR of the 14 neighbours' class bytes;
+//   census-free (cls = the lane's own class word of chunk 0, a uint2; TAB only): the count field of the voxel's own class byte
+//     (the comment above k_sweep_table says why that is the same classification).
 // CH2: rows of 513..1024 voxels (two 512-voxel chunks per row; only without HW).
 // SK (the tiles of k_sweep_stream_apply that can hold a stale row of the pending event, sites `sw`): such a row is not stored.
-template <bool TAB, bool HW, bool CH2, bool SK = false, class ROWP>
-__device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li, int lp, int jrow, bool top, int lane,
-                                          const double (&v0)[8], const StaleWin& sw = StaleWin{})
+// lds_sum / lds_cnt ([3][L] of the block's plane, k_sweep_plane): a copy of what is stored.
+template <bool TAB, bool HW, bool CH2, bool SK = false, class CLS>
+__device__ __forceinline__ void row_reduce(const StreamArgs& A, CLS cls, int li, int lp, int jrow, bool top, int lane,
+                                           const double (&v0)[8], const StaleWin& sw = StaleWin{},
+                                           double* lds_sum = nullptr, int* lds_cnt = nullptr)
 {
+    constexpr bool CENSUS = !std::is_same<CLS, uint2>::value;
     static_assert(!(HW && CH2), "half-wave rows have one chunk");
+    static_assert(CENSUS || TAB, "the census-free classification reads the rate table");
     const int L = A.L;
     const int sl = HW ? (lane & 31) : lane;
     constexpr int nch = CH2 ? 2 : 1;                         // chunks of 512 voxels
@@ -449,81 +445,99 @@ __device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li
     for (int m = 0; m < nch; ++m) {
         const int k0 = (m << 9) + 8 * sl;
         const bool active = jrow < L && k0 < L;
-        const int64_t trow = ((int64_t)li * L + jrow) * A.pitchT + k0;
         double v[8], ev[8];
-        uint2 own = make_uint2(0u, 0u), acc = make_uint2(0u, 0u);
         if (m == 0) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = v0[q];
         } else {
             load_vals<TAB, HW>(A, li, jrow, lane, m, v);
         }
-        if (active) {
-            // ---- census of the 8 voxels' 14 neighbours: OR of class bytes ---------------------------
-            auto ld8 = [&](const uint8_t* p) { return *reinterpret_cast<const uint2*>(p + k0); };
-            auto ld4 = [&](const uint8_t* p, int off) { return *reinterpret_cast<const unsigned*>(p + k0 + off); };
-            uint2 t;
-            acc = ld8(rowp(1, 1));
-            t = ld8(rowp(1, -1)); acc.x |= t.x; acc.y |= t.y;
-            t = ld8(rowp(-1, 1)); acc.x |= t.x; acc.y |= t.y;
-            t = ld8(rowp(-1, -1)); acc.x |= t.x; acc.y |= t.y;
-            t = ld8(rowp(2, 0)); acc.x |= t.x; acc.y |= t.y;
-            t = ld8(rowp(-2, 0)); acc.x |= t.x; acc.y |= t.y;
-            t = ld8(rowp(0, 2)); acc.x |= t.x; acc.y |= t.y;
-            t = ld8(rowp(0, -2)); acc.x |= t.x; acc.y |= t.y;
+        // ---- classification.  Bit 0 of every byte: E own voxel empty; dA atom whose table entry is its DIFF-category sum.
+        // cE / cA: the event counts (bits 7:2 of the own class byte, kept by ifc_store()) of the lane's interface voxels, empty
+        // ones / atoms.  ifc_here, diff_here (wave-uniform): some lane holds such a count / a diffusing atom.
+        uint2 own = make_uint2(0u, 0u), E, ifE, cE, cA, dA;     // (ifE: census only)
+        bool ifc_here, diff_here;
+        if constexpr (CENSUS) {
+            uint2 acc = make_uint2(0u, 0u);
+            if (active) {       // census of the 8 voxels' 14 neighbours: OR of class bytes
+                auto ld8 = [&](const uint8_t* p) { return *reinterpret_cast<const uint2*>(p + k0); };
+                auto ld4 = [&](const uint8_t* p, int off) { return *reinterpret_cast<const unsigned*>(p + k0 + off); };
+                uint2 t;
+                acc = ld8(cls(1, 1));
+                t = ld8(cls(1, -1)); acc.x |= t.x; acc.y |= t.y;
+                t = ld8(cls(-1, 1)); acc.x |= t.x; acc.y |= t.y;
+                t = ld8(cls(-1, -1)); acc.x |= t.x; acc.y |= t.y;
+                t = ld8(cls(2, 0)); acc.x |= t.x; acc.y |= t.y;
+                t = ld8(cls(-2, 0)); acc.x |= t.x; acc.y |= t.y;
+                t = ld8(cls(0, 2)); acc.x |= t.x; acc.y |= t.y;
+                t = ld8(cls(0, -2)); acc.x |= t.x; acc.y |= t.y;
 #pragma unroll
-            for (int dj = -1; dj <= 1; dj += 2) {                  // (0,dj,+-1): neighbours k-1 and k+1
-                const uint8_t* p = rowp(0, dj);
-                const unsigned Aw = ld4(p, -4), Cw = ld4(p, 8);
-                const uint2 B = ld8(p);
-                const unsigned mid = alignbyte(B.y, B.x, 1);       // bytes k0+1 .. k0+4
-                acc.x |= alignbyte(B.x, Aw, 3) | mid;
-                acc.y |= alignbyte(B.y, B.x, 3) | alignbyte(Cw, B.y, 1);
+                for (int dj = -1; dj <= 1; dj += 2) {                  // (0,dj,+-1): neighbours k-1 and k+1
+                    const uint8_t* p = cls(0, dj);
+                    const unsigned Aw = ld4(p, -4), Cw = ld4(p, 8);
+                    const uint2 B = ld8(p);
+                    const unsigned mid = alignbyte(B.y, B.x, 1);       // bytes k0+1 .. k0+4
+                    acc.x |= alignbyte(B.x, Aw, 3) | mid;
+                    acc.y |= alignbyte(B.y, B.x, 3) | alignbyte(Cw, B.y, 1);
+                }
+                const uint8_t* po = cls(0, 0);                         // own row: neighbours k-2 and k+2
+                const unsigned Aw = ld4(po, -4), Cw = ld4(po, 8);
+                own = ld8(po);
+                const unsigned mid = alignbyte(own.y, own.x, 2);       // bytes k0+2 .. k0+5
+                acc.x |= alignbyte(own.x, Aw, 2) | mid;
+                acc.y |= mid | alignbyte(Cw, own.y, 2);
             }
-            const uint8_t* po = rowp(0, 0);                        // own row: neighbours k-2 and k+2
-            const unsigned Aw = ld4(po, -4), Cw = ld4(po, 8);
-            own = ld8(po);
-            const unsigned mid = alignbyte(own.y, own.x, 2);       // bytes k0+2 .. k0+5
-            acc.x |= alignbyte(own.x, Aw, 2) | mid;
-            acc.y |= mid | alignbyte(Cw, own.y, 2);
+            // ifE empty with a W/Re/C neighbour (attachment: interface voxel); dA = W/Re/C atom with an empty neighbour
+            // (diffusion: interface voxel)
+            E = make_uint2(own.x & 0x01010101u, own.y & 0x01010101u);
+            ifE = make_uint2(E.x & (acc.x >> 1), E.y & (acc.y >> 1));
+            dA = make_uint2((own.x >> 1) & acc.x & 0x01010101u, (own.y >> 1) & acc.y & 0x01010101u);
+            if (!TAB) {         // recompute variant: the nucleation rate of every empty voxel without W/Re/C neighbours
+                const uint2 bulk = make_uint2(E.x & ~ifE.x, E.y & ~ifE.y);
+#pragma unroll
+                for (int h = 0; h < 8; ++h) {
+                    ev[h] = 0.0;
+                    if (((h < 4 ? bulk.x : bulk.y) >> (8 * (h & 3))) & 1u)
+                        ev[h] = nuc_bulk(A.T_melt, A.delta_T_c, A.kT, A.I0, A.rate_threshold, A.K0, v[h]);
+                }
+            }
+            diff_here = __any((dA.x | dA.y) != 0u);
+            ifc_here = __any((ifE.x | ifE.y | dA.x | dA.y) != 0u);
+            const uint2 c6 = make_uint2((own.x >> 2) & 0x3F3F3F3Fu, (own.y >> 2) & 0x3F3F3F3Fu);
+            cE = make_uint2(c6.x & (ifE.x * 255u), c6.y & (ifE.y * 255u));
+            cA = make_uint2(c6.x & (dA.x * 255u), c6.y & (dA.y * 255u));
+        } else {
+            own = m == 0 ? cls : load_cls8(A, li, jrow, sl, m);
+            if (!active) own = make_uint2(0u, 0u);              // (clamped addresses: whatever such a lane loaded is masked)
+            E = make_uint2(own.x & 0x01010101u, own.y & 0x01010101u);
+            const uint2 Aat = make_uint2((own.x >> 1) & 0x01010101u, (own.y >> 1) & 0x01010101u);      // own voxel a W/Re/C atom
+            const uint2 c6 = make_uint2((own.x >> 2) & 0x3F3F3F3Fu, (own.y >> 2) & 0x3F3F3F3Fu);
+            cE = make_uint2(c6.x & (E.x * 255u), c6.y & (E.y * 255u));
+            cA = make_uint2(c6.x & (Aat.x * 255u), c6.y & (Aat.y * 255u));
+            diff_here = __any((cA.x | cA.y) != 0u);
+            ifc_here = __any((cE.x | cE.y | cA.x | cA.y) != 0u);
+            dA = make_uint2(((cA.x + 0x3F3F3F3Fu) >> 6) & 0x01010101u, ((cA.y + 0x3F3F3F3Fu) >> 6) & 0x01010101u);
         }
-        // bit 0 of every byte: E own voxel empty; ifE empty with a W/Re/C neighbour (attachment: interface voxel);
-        // ifA W/Re/C atom with an empty neighbour (diffusion: interface voxel)
-        const uint2 E = make_uint2(own.x & 0x01010101u, own.y & 0x01010101u);
-        const uint2 ifE = make_uint2(E.x & (acc.x >> 1), E.y & (acc.y >> 1));
-        const uint2 ifA = make_uint2((own.x >> 1) & acc.x & 0x01010101u, (own.y >> 1) & acc.y & 0x01010101u);
-        // ---- EMPTY category ---------------------------------------------------------------------------
+        // ---- EMPTY category: the table entries of the empty voxels
         if (TAB) {
 #pragma unroll
             for (int h = 0; h < 8; ++h) ev[h] = mask_f64(v[h], h < 4 ? E.x : E.y, 8 * (h & 3));
-        } else {
-            const uint2 bulk = make_uint2(E.x & ~ifE.x, E.y & ~ifE.y);
-#pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                ev[h] = 0.0;
-                if (((h < 4 ? bulk.x : bulk.y) >> (8 * (h & 3))) & 1u)
-                    ev[h] = nuc_bulk(A.T_melt, A.delta_T_c, A.kT, A.I0, A.rate_threshold, A.K0, v[h]);
-            }
         }
-        // ---- interface voxels of the lane: event counts from bits 7:2 of their own class byte (kept by ifc_store()),
-        // no memory access.  The ballots below count an empty voxel with a non-zero EMPTY-category sum once; an
-        // interface voxel's sum is non-zero iff it owns events (every kept rate is > rate_threshold): add count - 1.
-        const uint2 iany = make_uint2(ifE.x | ifA.x, ifE.y | ifA.y);
+        // ---- interface voxels of the lane: event counts from their own class byte, no memory access.  The ballots below
+        // count an empty voxel with a non-zero EMPTY-category sum once; an interface voxel's sum is non-zero iff it owns
+        // events (every kept rate is > rate_threshold): add count - 1.
         double dv[8];
 #pragma unroll
         for (int h = 0; h < 8; ++h) dv[h] = 0.0;
-        const bool diff_here = __any((ifA.x | ifA.y) != 0u);
-        if (__any((iany.x | iany.y) != 0u)) {
+        if (ifc_here) {
             any_ifc = true;
-            const uint2 c6 = make_uint2((own.x >> 2) & 0x3F3F3F3Fu, (own.y >> 2) & 0x3F3F3F3Fu);
-            const uint2 cE = make_uint2(c6.x & (ifE.x * 255u), c6.y & (ifE.y * 255u));
-            const uint2 cA = make_uint2(c6.x & (ifA.x * 255u), c6.y & (ifA.y * 255u));
             const unsigned nz = __popc(((cE.x + 0x3F3F3F3Fu) >> 6) & 0x01010101u) + __popc(((cE.y + 0x3F3F3F3Fu) >> 6) & 0x01010101u);
             const unsigned nE = __builtin_amdgcn_sad_u8(cE.x, 0u, __builtin_amdgcn_sad_u8(cE.y, 0u, 0u)) - nz;
             const unsigned nA = __builtin_amdgcn_sad_u8(cA.x, 0u, __builtin_amdgcn_sad_u8(cA.y, 0u, 0u));
             cI += (int)(nE | (nA << 16));
-            if (!TAB) {         // recompute variant: the interface voxels' sums come from the table
-                unsigned long long bits = ((unsigned long long)iany.y << 32) | iany.x;
+            if constexpr (!TAB) {       // recompute variant: the interface voxels' sums come from the table
+                const int64_t trow = ((int64_t)li * L + jrow) * A.pitchT + k0;
+                unsigned long long bits = ((unsigned long long)(ifE.y | dA.y) << 32) | (ifE.x | dA.x);
                 const unsigned long long ebits = ((unsigned long long)ifE.y << 32) | ifE.x;
                 while (bits) {
                     const int b = __builtin_ctzll(bits);
@@ -541,7 +555,7 @@ __device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li
         }
         if (TAB && diff_here) {
 #pragma unroll
-            for (int h = 0; h < 8; ++h) dv[h] = mask_f64(v[h], h < 4 ? ifA.x : ifA.y, 8 * (h & 3));
+            for (int h = 0; h < 8; ++h) dv[h] = mask_f64(v[h], h < 4 ? dA.x : dA.y, 8 * (h & 3));
         }
         // ---- counts: scalar popcounts of ballots (bulk voxels count iff their rate is kept) -------------
 #pragma unroll
@@ -585,14 +599,18 @@ __device__ __forceinline__ void sweep_row(const StreamArgs& A, ROWP rowp, int li
         n2 += packed & 0xFFFF;
         n1 = packed >> 16;
     }
-    // SK: the test and the store offsets are worked out here, from a copy of the row index the compiler cannot see through,
-    // so nothing of them is hoisted out of the plane loop into vector registers that would live across it
+    // SK ring tiles: the test and the store offsets are worked out here, from a copy of the row index the compiler cannot see
+    // through, so nothing of them is hoisted out of the plane loop into vector registers that would live across it
     int jst = jrow;
-    if (SK) asm volatile("" : "+v"(jst));
+    if (SK && CENSUS) asm volatile("" : "+v"(jst));
     if (sl == 0 && jrow < L && !(SK && stale_row(sw, A.gi0 + lp, jst))) {
         const int64_t o = (int64_t)lp * 3 * L + jst;
         A.rowsum[o] = r0; A.rowsum[o + L] = r1; A.rowsum[o + 2 * (int64_t)L] = r2;
         A.rowcnt[o] = n0; A.rowcnt[o + L] = n1; A.rowcnt[o + 2 * (int64_t)L] = n2;
+        if (lds_sum) {
+            lds_sum[jst] = r0; lds_sum[L + jst] = r1; lds_sum[2 * L + jst] = r2;
+            lds_cnt[jst] = n0; lds_cnt[L + jst] = n1; lds_cnt[2 * L + jst] = n2;
+        }
     }
 }
 
@@ -604,7 +622,7 @@ __device__ __forceinline__ void stream_tile_of(const StreamArgs& A, int b, int& 
     if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);   // contiguous block ranges per XCD
     ibr = b / njt; jt = b - ibr * njt;
 }
-// NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682).  One tile.  SK: sweep_row()
+// NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682).  One tile.  SK: row_reduce()
 template <bool TAB, bool HW, int NPF, bool CH2, bool SK = false>
 __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, unsigned char* smem, const StaleWin& sw = StaleWin{})
 {
@@ -682,13 +700,13 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
             load_vals<TAB, HW>(A, min(li + 1, lp1 + 1), j0 + row_of(0), lane, 0, nxt);
             const int r = row_of(0);
             auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-            sweep_row<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
+            row_reduce<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
         } else {
             {
                 load_vals<TAB, HW>(A, li, j0 + row_of(1), lane, 0, nxt);
                 const int r = row_of(0);
                 auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-                sweep_row<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
+                row_reduce<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
             }
             {
 #ifdef CETKMC_NO_TAIL_PREFETCH
@@ -697,7 +715,7 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
                 load_vals<TAB, HW>(A, min(li + 1, lp1 + 1), j0 + row_of(0), lane, 0, cur);
                 const int r = row_of(1);
                 auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-                sweep_row<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, nxt, sw);
+                row_reduce<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, nxt, sw);
             }
         }
 #ifdef CETKMC_NO_TAIL_PREFETCH
@@ -728,7 +746,7 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
 //                listed empty voxel with a count);  DIFF sum = sum over atoms with a non-zero count of their entry;
 //   DEP (plane L-1) as before from dep_val.
 // No LDS ring, no halo planes or rows, no barriers: 9 B per voxel of traffic for 9 B algorithmic.  The sums, counts and
-// the summation tree are those of sweep_row() to the bit (an atom with a non-zero count is an atom with an empty neighbour
+// the summation tree are those of the census to the bit (an atom with a non-zero count is an atom with an empty neighbour
 // whose diffusion rates were kept; a listed empty voxel that lost its W/Re/C neighbours holds a count of 0 or 1).
 // A lane handles 8 consecutive voxels; HW: rows of <= 256 voxels occupy half a wave, a wave item is a pair of rows.  A wave
 // walks IPW items 4 apart (the block's four waves read 4 consecutive items at a time), values and class bytes of the next
@@ -736,16 +754,11 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
 // MEASURED: bit-identical, but not faster than k_sweep_stream -- 32.3 vs 31.3 us (sweep + reduce) at 256^3,
 // 229 vs 222 at 512^3; requesting two items ahead or fully coalesced loads make it slower.  The sweep is bound by the memory
 // system (5.6 TB/s of HBM traffic at 512^3), not by the census arithmetic.  Kept as an option and as the row kernel of the
-// incremental mode (k_rows_eval), where it saves the five-plane gather of class rows.
+// incremental mode (k_rows_eval), where it saves the five-plane gather of class rows.  (The two-ahead walker and the
+// coalesced loads were A/B-only build switches; both are gone with their measurement on record here.)
 // ----------------------------------------------------------------------------------------
-__device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow, int sl, int m)
-{
-    const int k0 = min((m << 9) + 8 * sl, A.pitchT - 8);
-    const int jr = min(jrow, A.L - 1);
-    return *reinterpret_cast<const uint2*>(A.cls + ((int64_t)li * A.RJ + (jr + 2)) * A.pitchC + KOFFC + k0);
-}
-// Whether table_row() can use any of the 8 table entries of the lane whose class bytes are `own`.  Its two uses of v[] are
-// ev[h] = mask_f64(v[h], E, ...), non-zero only where byte h has bit 0 (empty), and dv[h] = mask_f64(v[h], hasA, ...), only
+// Whether the census-free row_reduce() can use any of the 8 table entries of the lane whose class bytes are `own`.  Its two
+// uses of v[] are ev[h] = mask_f64(v[h], E, ...), non-zero only where byte h has bit 0 (empty), and dv[h] = mask_f64(v[h], dA, ...), only
 // where byte h is an atom (bit 1) with a non-zero count in bits 7:2.  A lane whose bytes are all 0x00 or 0x02 (defect, outside,
 // atom without an exposed neighbour) therefore contributes exact zeros whatever it holds in v[]: the tiles of option
 // table_lane_skip do not load its entries.  (A superset of the two masks: a count on a byte with neither bit also asks.)
@@ -763,108 +776,20 @@ __device__ __forceinline__ void pin_item_pair(uint2& ca, uint2& cb, double (&va)
     asm volatile("" : "+v"(va[0]), "+v"(va[1]), "+v"(va[2]), "+v"(va[3]), "+v"(va[4]), "+v"(va[5]), "+v"(va[6]), "+v"(va[7]),
                       "+v"(vb[0]), "+v"(vb[1]), "+v"(vb[2]), "+v"(vb[3]), "+v"(vb[4]), "+v"(vb[5]), "+v"(vb[6]), "+v"(vb[7]));
 }
-// SK (the census-free tiles of a launch that applies a pending event, sites `sw`): a stale row is not stored, as in sweep_row().
-template <bool HW, bool CH2, bool SK = false>
-__device__ __forceinline__ void table_row(const StreamArgs& A, int li, int lp, int jrow, bool top, int lane, const double (&v0)[8],
-                                          uint2 own0, double* lds_sum = nullptr, int* lds_cnt = nullptr /* [3][L] of the block's plane */,
-                                          const StaleWin& sw = StaleWin{})
+// One item of the census-free walkers (a row, HW: a pair of rows; one chunk per row or its first): "request" asks for the
+// lane's table entries and class bytes, "reduce" is row_reduce() with the census-free classification.  SK (the census-free
+// tiles of a launch that applies a pending event, sites `sw`): a stale row is not stored.
+template <bool HW>
+__device__ __forceinline__ void table_item_request(const StreamArgs& A, int lp, int jrow, int lane, double (&v)[8], uint2& c)
 {
-    static_assert(!(HW && CH2), "half-wave rows have one chunk");
-    const int L = A.L;
-    const int sl = HW ? (lane & 31) : lane;
-    constexpr int nch = CH2 ? 2 : 1;                         // chunks of 512 voxels
-    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-    int nE_a = 0, nE_b = 0, nD_a = 0, nD_b = 0;
-    int cI = 0;
-    bool any_ifc = false;
-#pragma unroll
-    for (int m = 0; m < nch; ++m) {
-        const int k0 = (m << 9) + 8 * sl;
-        const bool active = jrow < L && k0 < L;
-        double v[8], ev[8];
-        uint2 own = own0;
-        if (m == 0) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = v0[q];
-        } else {
-            load_vals<true, HW>(A, li, jrow, lane, m, v);
-            own = load_cls8(A, li, jrow, sl, m);
-        }
-        if (!active) own = make_uint2(0u, 0u);              // (clamped addresses: whatever such a lane loaded is masked)
-        // bit 0 of every byte: E own voxel empty, Aat own voxel a W/Re/C atom; c6 the count field
-        const uint2 E = make_uint2(own.x & 0x01010101u, own.y & 0x01010101u);
-        const uint2 Aat = make_uint2((own.x >> 1) & 0x01010101u, (own.y >> 1) & 0x01010101u);
-        const uint2 c6 = make_uint2((own.x >> 2) & 0x3F3F3F3Fu, (own.y >> 2) & 0x3F3F3F3Fu);
-#pragma unroll
-        for (int h = 0; h < 8; ++h) ev[h] = mask_f64(v[h], h < 4 ? E.x : E.y, 8 * (h & 3));
-        const uint2 cE = make_uint2(c6.x & (E.x * 255u), c6.y & (E.y * 255u));
-        const uint2 cA = make_uint2(c6.x & (Aat.x * 255u), c6.y & (Aat.y * 255u));
-        const bool diff_here = __any((cA.x | cA.y) != 0u);
-        double dv[8];
-#pragma unroll
-        for (int h = 0; h < 8; ++h) dv[h] = 0.0;
-        if (__any((cE.x | cE.y | cA.x | cA.y) != 0u)) {
-            any_ifc = true;
-            // a listed empty voxel with events is counted once by the ballots below (its sum is non-zero): add count - 1
-            const unsigned nz = __popc(((cE.x + 0x3F3F3F3Fu) >> 6) & 0x01010101u) + __popc(((cE.y + 0x3F3F3F3Fu) >> 6) & 0x01010101u);
-            const unsigned nE = __builtin_amdgcn_sad_u8(cE.x, 0u, __builtin_amdgcn_sad_u8(cE.y, 0u, 0u)) - nz;
-            const unsigned nA = __builtin_amdgcn_sad_u8(cA.x, 0u, __builtin_amdgcn_sad_u8(cA.y, 0u, 0u));
-            cI += (int)(nE | (nA << 16));
-        }
-        if (diff_here) {
-            const uint2 hasA = make_uint2(((cA.x + 0x3F3F3F3Fu) >> 6) & 0x01010101u, ((cA.y + 0x3F3F3F3Fu) >> 6) & 0x01010101u);
-#pragma unroll
-            for (int h = 0; h < 8; ++h) dv[h] = mask_f64(v[h], h < 4 ? hasA.x : hasA.y, 8 * (h & 3));
-        }
-#pragma unroll
-        for (int h = 0; h < 8; ++h) {
-            const unsigned long long bm = __ballot(ev[h] != 0.0);
-            if (HW) { nE_a += __popc((unsigned)bm); nE_b += __popc((unsigned)(bm >> 32)); }
-            else nE_a += __popcll(bm);
-        }
-        double s2 = wave_tree_sum_h<HW>(tree8(ev));
-        r2 = (m == 0) ? s2 : r2 + s2;
-        double s1 = 0.0;                                         // a chunk without diffusing atoms contributes +0.0
-        if (diff_here) s1 = wave_tree_sum_h<HW>(tree8(dv));
-        r1 = (m == 0) ? s1 : r1 + s1;
-        if (top) {          // nu_dep * exp(-(T_melt - T')/(kT T')) of plane L-1 by temperature (k_rate_table): kept iff finite
-            double dp[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) dp[q] = 0.0;
-            if (active) {
-                const double2* src = reinterpret_cast<const double2*>(A.dep_val + (int64_t)jrow * A.pitchT + k0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { const double2 t = src[q]; dp[2 * q] = t.x; dp[2 * q + 1] = t.y; }
-            }
-#pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                const bool keep = (((h < 4 ? E.x : E.y) >> (8 * (h & 3))) & 1u) && finite_d(dp[h]);
-                dp[h] = keep ? dp[h] : 0.0;
-                const unsigned long long bm = __ballot(keep);
-                if (HW) { nD_a += __popc((unsigned)bm); nD_b += __popc((unsigned)(bm >> 32)); }
-                else nD_a += __popcll(bm);
-            }
-            const double s0 = wave_tree_sum_h<HW>(tree8(dp));
-            r0 = (m == 0) ? s0 : r0 + s0;
-        }
-    }
-    int n2 = HW ? ((lane & 32) ? nE_b : nE_a) : nE_a;
-    const int n0 = HW ? ((lane & 32) ? nD_b : nD_a) : nD_a;
-    int n1 = 0;
-    if (any_ifc) {
-        const int packed = wave_sum_i_h<HW>(cI);
-        n2 += packed & 0xFFFF;
-        n1 = packed >> 16;
-    }
-    if (sl == 0 && jrow < L && !(SK && stale_row(sw, A.gi0 + lp, jrow))) {
-        const int64_t o = (int64_t)lp * 3 * L + jrow;
-        A.rowsum[o] = r0; A.rowsum[o + L] = r1; A.rowsum[o + 2 * (int64_t)L] = r2;
-        A.rowcnt[o] = n0; A.rowcnt[o + L] = n1; A.rowcnt[o + 2 * (int64_t)L] = n2;
-        if (lds_sum) {
-            lds_sum[jrow] = r0; lds_sum[L + jrow] = r1; lds_sum[2 * L + jrow] = r2;
-            lds_cnt[jrow] = n0; lds_cnt[L + jrow] = n1; lds_cnt[2 * L + jrow] = n2;
-        }
-    }
+    load_vals<true, HW>(A, lp + 2, jrow, lane, 0, v);
+    c = load_cls8(A, lp + 2, jrow, HW ? (lane & 31) : lane, 0);
+}
+template <bool HW, bool CH2, bool SK = false>
+__device__ __forceinline__ void table_item_reduce(const StreamArgs& A, int lp, int jrow, int lane, const double (&v)[8], uint2 c,
+                                                  const StaleWin& sw = StaleWin{}, double* lds_sum = nullptr, int* lds_cnt = nullptr)
+{
+    row_reduce<true, HW, CH2, SK>(A, c, lp + 2, lp, jrow, A.gi0 + lp == A.L - 1, lane, v, sw, lds_sum, lds_cnt);
 }
 
 #ifndef CETKMC_TABLE_IPW
@@ -897,11 +822,11 @@ __host__ __device__ constexpr int table_tile_of(int L, bool hw, int lp, int j)
     return (lp * table_tile_ipp(L, hw) + (hw ? j >> 1 : j)) / TABLE_TILE_ITEMS;
 }
 // One tile: IPW items per wave from item b * 4 * IPW on, values and class bytes of the next item requested before the current
-// one is reduced (two alternating buffers).  SK: table_row().
+// one is reduced (two alternating buffers).  SK: table_item_reduce().
 // LS (option table_lane_skip): class bytes first, table entries only for the lanes that can use them.  The wave requests the
 // class bytes of a pair of its items, then -- each item's class word at hand -- that item's table entries in the lanes where
-// lane_needs_values() holds, then reduces the two with the same table_row().  The predicate reads the very class word
-// table_row() masks with, so the row sums are those of the unconditional loads to the bit: mask_f64() zeroed a skipped lane's
+// lane_needs_values() holds, then reduces the two with the same row_reduce().  The predicate reads the very class word
+// row_reduce() masks with, so the row sums are those of the unconditional loads to the bit: mask_f64() zeroed a skipped lane's
 // entries before.  The price is one dependent round trip per pair of items; beside four other waves per SIMD it was not
 // measurable, the bytes were (131 MB per launch at 256^3 instead of 157 MB).
 // `first`: block b of the launch's nblk tile blocks runs tile first + b of the mapping above (a launch that runs a part of the
@@ -932,7 +857,7 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
             const int lpb = two ? lp2 : lp, jpb = two ? jp2 : jp;
             ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
             cb = load_cls8(A, lpb + 2, jrow_of(jpb), sl, 0);
-            // lanes that do not load hold +0.0 (whatever they held is masked by table_row(), but it must be a value); one wait
+            // lanes that do not load hold +0.0 (whatever they held is masked by row_reduce(), but it must be a value); one wait
             // for the two class words, then the two guarded requests back to back: the loads sit under the lanes' exec mask,
             // so a masked lane requests no bytes
 #pragma unroll
@@ -947,9 +872,9 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
 #endif
             if (na) load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
             if (nb) load_vals<true, HW>(A, lpb + 2, jrow_of(jpb), lane, 0, vb);
-            table_row<HW, CH2, SK>(A, lp + 2, lp, jrow_of(jp), A.gi0 + lp == L - 1, lane, va, ca, nullptr, nullptr, sw);
+            table_item_reduce<HW, CH2, SK>(A, lp, jrow_of(jp), lane, va, ca, sw);
             if (!two) break;
-            table_row<HW, CH2, SK>(A, lpb + 2, lpb, jrow_of(jpb), A.gi0 + lpb == L - 1, lane, vb, cb, nullptr, nullptr, sw);
+            table_item_reduce<HW, CH2, SK>(A, lpb, jrow_of(jpb), lane, vb, cb, sw);
             item += 8;
             if (item >= n_items) break;
             lp = lp2; jp = jp2 + 4;
@@ -957,8 +882,7 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
         }
         return;
     }
-    load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
-    ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
+    table_item_request<HW>(A, lp, jrow_of(jp), lane, va, ca);
     // one item: `cur` holds its values on entry; the next item's are requested into `nxt` first (past the wave's last item
     // the request repeats the current one: a cache hit)
     auto step = [&](double (&cur)[8], uint2& ccur, double (&nxt)[8], uint2& cnxt, bool last) {
@@ -966,9 +890,8 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
         while (jp2 >= ipp) { jp2 -= ipp; ++lp2; }
         const bool more = !last && (item + 4 < n_items);
         const int lpn = more ? lp2 : lp, jpn = more ? jp2 : jp;
-        load_vals<true, HW>(A, lpn + 2, jrow_of(jpn), lane, 0, nxt);
-        cnxt = load_cls8(A, lpn + 2, jrow_of(jpn), sl, 0);
-        table_row<HW, CH2, SK>(A, lp + 2, lp, jrow_of(jp), A.gi0 + lp == L - 1, lane, cur, ccur, nullptr, nullptr, sw);
+        table_item_request<HW>(A, lpn, jrow_of(jpn), lane, nxt, cnxt);
+        table_item_reduce<HW, CH2, SK>(A, lp, jrow_of(jp), lane, cur, ccur, sw);
         item += 4; lp = lp2; jp = jp2;
     };
 #pragma unroll 1
@@ -1000,54 +923,7 @@ template <bool HW, bool CH2>
 __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_table(StreamArgs A, const StepState* __restrict__ ss)
 {
     if (ss && ss->status) return;
-#ifdef CETKMC_TABLE_DEPTH2
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int L = A.L;
-    const int ipp = HW ? (L + 1) >> 1 : L;                       // items per plane (HW: pairs of rows)
-    const int n_items = ipp * A.nloc;
-    int b = blockIdx.x;
-    if ((gridDim.x & 7) == 0) b = (b & 7) * (int)(gridDim.x >> 3) + (b >> 3);      // contiguous item ranges per XCD
-    int item = b * 4 * TABLE_IPW + w;
-    if (item >= n_items) return;
-    int lp = item / ipp, jp = item - lp * ipp;
-    const int sl = HW ? (lane & 31) : lane;
-    auto jrow_of = [&](int jpair) { return HW ? 2 * jpair + (lane >> 5) : jpair; };
-    // A/B: requests TWO items ahead (three rotating buffers)
-    double va[8], vb[8], vc[8];
-    uint2 ca, cb, cc;
-    auto advance = [&](int& lpx, int& jpx) { jpx += 4; while (jpx >= ipp) { jpx -= ipp; ++lpx; } };
-    int lp1 = lp, jp1 = jp;
-    advance(lp1, jp1);
-    const bool has1 = item + 4 < n_items;
-    load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
-    ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
-    load_vals<true, HW>(A, (has1 ? lp1 : lp) + 2, jrow_of(has1 ? jp1 : jp), lane, 0, vb);
-    cb = load_cls8(A, (has1 ? lp1 : lp) + 2, jrow_of(has1 ? jp1 : jp), sl, 0);
-    int done = 0;
-    auto step = [&](double (&cur)[8], uint2& ccur, double (&far)[8], uint2& cfar) {
-        // request item + 8 into `far`, reduce `cur`
-        int lp2 = lp, jp2 = jp;
-        advance(lp2, jp2);
-        int lp3 = lp2, jp3 = jp2;
-        advance(lp3, jp3);
-        const bool more = (done + 2 < TABLE_IPW) && (item + 8 < n_items);
-        load_vals<true, HW>(A, (more ? lp3 : lp) + 2, jrow_of(more ? jp3 : jp), lane, 0, far);
-        cfar = load_cls8(A, (more ? lp3 : lp) + 2, jrow_of(more ? jp3 : jp), sl, 0);
-        table_row<HW, CH2>(A, lp + 2, lp, jrow_of(jp), A.gi0 + lp == L - 1, lane, cur, ccur);
-        item += 4; lp = lp2; jp = jp2; ++done;
-    };
-#pragma unroll 1
-    while (true) {
-        step(va, ca, vc, cc);
-        if (done >= TABLE_IPW || item >= n_items) break;
-        step(vb, cb, va, ca);
-        if (done >= TABLE_IPW || item >= n_items) break;
-        step(vc, cc, vb, cb);
-        if (done >= TABLE_IPW || item >= n_items) break;
-    }
-#else
     sweep_table_tile<HW, CH2, false, TABLE_IPW>(A, blockIdx.x, (int)gridDim.x);
-#endif
 }
 
 // k_sweep_plane (variant 4): k_sweep_table with one block per owned plane (16 waves; wave w takes the plane's items w, w + 16, ...),
@@ -1076,20 +952,16 @@ __global__ __launch_bounds__(1024) CETKMC_SWEEP_ATTR void k_sweep_plane(StreamAr
     const int ipp = HW ? (L + 1) >> 1 : L;                              // items per plane (HW: pairs of rows)
     int lp = blockIdx.x;
     if ((gridDim.x & 7) == 0) lp = (lp & 7) * (int)(gridDim.x >> 3) + (lp >> 3);      // contiguous plane ranges per XCD
-    const int sl = HW ? (lane & 31) : lane;
     auto jrow_of = [&](int jpair) { return HW ? 2 * jpair + (lane >> 5) : jpair; };
-    const bool top = A.gi0 + lp == L - 1;
     int jp = w;
     if (jp < ipp) {
         double va[8], vb[8];
         uint2 ca, cb;
-        load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
-        ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
+        table_item_request<HW>(A, lp, jrow_of(jp), lane, va, ca);
         auto step = [&](double (&cur)[8], uint2& ccur, double (&nxt)[8], uint2& cnxt) {
             const int jpn = (jp + 16 < ipp) ? jp + 16 : jp;             // past the wave's last item: the current one again (cache hit)
-            load_vals<true, HW>(A, lp + 2, jrow_of(jpn), lane, 0, nxt);
-            cnxt = load_cls8(A, lp + 2, jrow_of(jpn), sl, 0);
-            table_row<HW, CH2>(A, lp + 2, lp, jrow_of(jp), top, lane, cur, ccur, lds_sum, lds_cnt);
+            table_item_request<HW>(A, lp, jrow_of(jpn), lane, nxt, cnxt);
+            table_item_reduce<HW, CH2>(A, lp, jrow_of(jp), lane, cur, ccur, StaleWin{}, lds_sum, lds_cnt);
             jp += 16;
         };
 #pragma unroll 1
@@ -1122,7 +994,7 @@ __global__ __launch_bounds__(1024) CETKMC_SWEEP_ATTR void k_sweep_plane(StreamAr
 // Exact incremental stepping: between two temperature updates an event changes the rates of a few rows
 // only (those holding the changed voxel(s) or one of their 14 neighbours).  k_apply_batch records those
 // rows; this kernel re-evaluates just them -- one wave per row, class bytes read straight from global
-// memory -- with the same sweep_row() as the streaming kernel, so every row sum equals what a full sweep
+// memory -- with the same row_reduce() as the streaming kernel, so every row sum equals what a full sweep
 // would have produced.  dirty[0] = count, dirty[1..] = (global plane << 16) | row.
 constexpr int DIRTY_MAX = 63;
 template <bool TAB, bool HW, bool CH2>
@@ -1139,16 +1011,17 @@ __global__ __launch_bounds__(256) void k_rows_eval(StreamArgs A, const int* __re
     if (lp < 0 || lp >= A.nloc) return;                     // another slab's row
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (w == 0) {
-        const int li = lp + 2;
         const int jrow = (HW && lane >= 32) ? L_INACTIVE : j;       // the second half-wave idles
         double v0[8];
-        load_vals<TAB, HW>(A, li, jrow, lane, 0, v0);
-        if (TAB) {          // the census-free row reduction of k_sweep_table: same bits
-            const uint2 c0 = load_cls8(A, li, jrow, HW ? (lane & 31) : lane, 0);
-            table_row<HW, CH2>(A, li, lp, jrow, A.gi0 + lp == A.L - 1, lane, v0, c0);
+        if constexpr (TAB) {        // the census-free classification of k_sweep_table: same bits
+            uint2 c0;
+            table_item_request<HW>(A, lp, jrow, lane, v0, c0);
+            table_item_reduce<HW, CH2>(A, lp, jrow, lane, v0, c0);
         } else {
+            const int li = lp + 2;
+            load_vals<false, HW>(A, li, jrow, lane, 0, v0);
             auto rowp = [&](int d, int dj) { return A.cls + ((int64_t)(li + d) * A.RJ + (j + 2 + dj)) * A.pitchC + KOFFC; };
-            sweep_row<TAB, HW, CH2>(A, rowp, li, lp, jrow, A.gi0 + lp == A.L - 1, lane, v0);
+            row_reduce<false, HW, CH2>(A, rowp, li, lp, jrow, A.gi0 + lp == A.L - 1, lane, v0);
         }
     }
     __syncthreads();
@@ -1276,22 +1149,7 @@ __device__ __forceinline__ TreeSel tree_select(const double (&lf)[8], unsigned f
     const double q0 = p0 + p1, q1 = p2 + p3;
     double lv[7];
     lv[0] = q0 + q1;
-    lv[1] = lv[0] + dpp_f64(lv[0], 0);
-    lv[2] = lv[1] + dpp_f64(lv[1], 1);
-    lv[3] = lv[2] + dpp_f64(lv[2], 2);
-    lv[4] = lv[3] + dpp_f64(lv[3], 3);
-    {
-        const unsigned lo = __double2loint(lv[4]), hi = __double2hiint(lv[4]);
-        const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        lv[5] = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
-    {
-        const unsigned lo = __double2loint(lv[5]), hi = __double2hiint(lv[5]);
-        const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        lv[6] = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
+    wave_tree_levels(lv);
     const unsigned long long mask = __ballot(fm != 0u);
     if (lane == 0) { X.ws[w] = lv[6]; X.wm[w] = mask; }
     __syncthreads();
@@ -2270,11 +2128,12 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
     while (m) {
         int gi, j;
         stale_candidate_row(se, __builtin_ctzll(m), gi, j);
-        const int lp = gi - A.gi0, li = lp + 2;
+        const int lp = gi - A.gi0;
         const int jrow = (HW && lane >= 32) ? L_INACTIVE : j;
         double v0[8];
-        load_vals<true, HW>(A, li, jrow, lane, 0, v0);
-        table_row<HW, CH2>(A, li, lp, jrow, gi == L - 1, lane, v0, load_cls8(A, li, jrow, HW ? (lane & 31) : lane, 0));
+        uint2 c0;
+        table_item_request<HW>(A, lp, jrow, lane, v0, c0);
+        table_item_reduce<HW, CH2>(A, lp, jrow, lane, v0, c0);
         for (int k = 4; k > 0; --k) m &= m - 1;
     }
 #ifdef CETKMC_SEL_STAMPS

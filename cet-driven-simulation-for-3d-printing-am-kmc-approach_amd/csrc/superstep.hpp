@@ -301,22 +301,7 @@ __global__ __launch_bounds__(64) void k_domain_pick8(KParams P, const SlabView* 
     const double p0 = lf[0] + lf[1], p1 = lf[2] + lf[3];
     double lv[7];
     lv[0] = p0 + p1;
-    lv[1] = lv[0] + dpp_f64(lv[0], 0);
-    lv[2] = lv[1] + dpp_f64(lv[1], 1);
-    lv[3] = lv[2] + dpp_f64(lv[2], 2);
-    lv[4] = lv[3] + dpp_f64(lv[3], 3);
-    {
-        const unsigned lo = __double2loint(lv[4]), hi = __double2hiint(lv[4]);
-        const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        lv[5] = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
-    {
-        const unsigned lo = __double2loint(lv[5]), hi = __double2hiint(lv[5]);
-        const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        lv[6] = __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
-    }
+    wave_tree_levels(lv);
     const unsigned long long mask = __ballot(fm != 0u);
     const double R = lv[6];
     DomPick pk;

@@ -1,7 +1,7 @@
 """Option fused_tiles: the census-free tiles of the streaming sweep launches at 128 < L <= 256 against the ring tiles, bit for
 bit, and each against the oracle.
 
-fused_tiles 1 (default): the launch that applies a pending event (k_sweep_stream_apply) reduces its rows with table_row() --
+fused_tiles 1 (default): the launch that applies a pending event (k_sweep_stream_apply) reduces its rows with the census-free row_reduce() --
 own class byte + rate table, no neighbour census, no LDS ring -- in tiles of consecutive items; fused_tiles 2 gives the plain
 launch (k_sweep_stream: temperature-update steps, immediate steps) the same tiles; fused_tiles 0 is the ring tiles in both.
 thermal_mode 2 over two temperature updates, in two calls: fused steps, the cold plain sweep behind an update, the immediate

@@ -1,8 +1,8 @@
-"""lane_needs_values() (csrc/kernels.hpp, exported as cetkmc_lane_needs_values) against a restatement of table_row()'s two uses
+"""lane_needs_values() (csrc/kernels.hpp, exported as cetkmc_lane_needs_values) against a restatement of row_reduce()'s two uses
 of a lane's rate-table entries, on the CPU.
 
 The census-free tiles (option table_lane_skip) load a lane's 8 table entries only where the predicate holds for the lane's 8
-class bytes.  table_row() uses entry h only behind two masks: ev[h] -- byte h has bit 0 (the voxel is empty) -- and dv[h] --
+class bytes.  row_reduce() uses entry h only behind two masks: ev[h] -- byte h has bit 0 (the voxel is empty) -- and dv[h] --
 byte h has bit 1 (an atom) and a non-zero count in bits 7:2.  A lane the predicate rejects must be one whose entries no mask
 lets through; the predicate is a superset of the masks (it also fires for a count on a byte with neither bit), and it is false
 exactly for the words made of 0x00 and 0x02 bytes."""
@@ -23,7 +23,7 @@ def _bytes(w):
 
 
 def restated(w):
-    """table_row(): the lane's values are used iff some byte is empty, or is an atom with a non-zero count"""
+    """row_reduce(): the lane's values are used iff some byte is empty, or is an atom with a non-zero count"""
     return any((b & 1) or ((b & 2) and (b >> 2)) for b in _bytes(w))
 
 
