@@ -161,12 +161,16 @@ class RemeltInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("passes", "n_melted", "n_melted_last", "n_appended")]
 
 
+class SubstepInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("updates", "substeps", "launches", "blocked_launches")]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
                   "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
                   "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs,
-                  "remelt_info": RemeltInfo}
+                  "remelt_info": RemeltInfo, "substep_info": SubstepInfo}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -264,6 +268,10 @@ PROTOTYPES = {
     "cetkmc_get_remelt_info": (C.c_int, [C.c_void_p, _P(RemeltInfo)]),
     "cetkmc_ensemble_set_remelt": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "cetkmc_ensemble_remelt_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cetkmc_set_thermal_substeps": (C.c_int, [C.c_void_p, C.c_int]),
+    "cetkmc_ensemble_set_thermal_substeps": (C.c_int, [C.c_void_p, C.c_int]),
+    "cetkmc_get_substep_info": (C.c_int, [C.c_void_p, _P(SubstepInfo)]),
+    "cetkmc_time_thermal": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double)]),
 }
 
 

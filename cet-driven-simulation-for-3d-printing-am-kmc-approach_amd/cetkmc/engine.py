@@ -684,6 +684,25 @@ class Engine:
         self._ck(self.lib.cetkmc_get_remelt_info(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in _lib.RemeltInfo._fields_}
 
+    # -- sub-stepped temperature updates ------------------------------------------
+    def set_thermal_substeps(self, n):
+        """cetkmc_set_thermal_substeps: every temperature update of the handle becomes ``n`` applications of the explicit
+        step with ``dt / n`` (1: as before)."""
+        self._ck(self.lib.cetkmc_set_thermal_substeps(self.h, int(n)))
+
+    def substep_info(self):
+        """cetkmc_get_substep_info: dict(updates, substeps, launches, blocked_launches), running totals of the updates made
+        while thermal_substeps > 1."""
+        info = _lib.SubstepInfo()
+        self._ck(self.lib.cetkmc_get_substep_info(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
+
+    def time_thermal(self, n_updates, laser=False):
+        """cetkmc_time_thermal: device ms of n_updates temperature updates (dt = 1e-6 s, one hipEvent pair), measurement only."""
+        ms = C.c_double(0.0)
+        self._ck(self.lib.cetkmc_time_thermal(self.h, int(bool(laser)), int(n_updates), C.byref(ms)))
+        return ms.value
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -828,6 +847,16 @@ class Ensemble:
         replicas share)."""
         thr = float(self.params[0].T_melt if threshold is None else threshold)
         self._ck(self.lib.cetkmc_ensemble_set_remelt(self.h, int(bool(on)), thr))
+
+    def set_thermal_substeps(self, n):
+        """cetkmc_ensemble_set_thermal_substeps: one sub-step count for every replica's temperature updates in ``run``."""
+        self._ck(self.lib.cetkmc_ensemble_set_thermal_substeps(self.h, int(n)))
+
+    def substep_info(self):
+        """cetkmc_get_substep_info of the ensemble handle: dict(updates, substeps, launches, blocked_launches) of its calls."""
+        info = _lib.SubstepInfo()
+        self._ck(self.lib.cetkmc_get_substep_info(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
 
     def remelt_info(self):
         """cetkmc_ensemble_remelt_info: one dict(passes, n_melted, n_melted_last, n_appended) per replica."""

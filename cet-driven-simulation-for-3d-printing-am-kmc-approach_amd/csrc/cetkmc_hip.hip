@@ -34,6 +34,7 @@
 #include "solid.hpp"
 #include "origin.hpp"
 #include "melt.hpp"
+#include "thermal_sub.hpp"
 
 using namespace cetkmc;
 
@@ -281,6 +282,13 @@ struct Handle {
     int remelt_on = 0;           // the stepping loop melts behind every temperature update
     double remelt_threshold = 0.0;
     cetkmc_remelt_info melt_info{};      // the counters as last read (end of a stepping call, end of a direct pass)
+    // sub-stepped temperature updates (cetkmc_set_thermal_substeps, thermal_sub.hpp)
+    int thermal_substeps = 1;    // n: every update is n applications of the explicit step with dt / n
+    int substep_block = 0;       // option "substep_block": sub-steps per k_thermal_sub launch; 0 = the measured default (SUB_SDEFAULT at
+                                 // L > SUB_PLAIN_L, else the plain path), 1 = the plain path (n launches of the existing kernel) on any handle
+    int substep_planes = 0;      // option "substep_planes": planes per block of k_thermal_sub; 0 = one round of blocks on the device
+    int n_cu = 0;                // compute units of the device (read when first needed)
+    cetkmc_substep_info sub_info{};
 };
 
 // ---- cache state ------------------------------------------------------------------------------------
@@ -517,6 +525,7 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
     HIPCHK(hipMalloc((void**)&h->d_kp, sizeof(KParams)));
     HIPCHK(hipMalloc((void**)&h->d_flag, sizeof(int)));
     HIPCHK(hipMalloc((void**)&h->d_qtop, (size_t)L * L * sizeof(double)));
+    HIPCHK(hipMemset(h->d_qtop, 0, (size_t)L * L * sizeof(double)));      // cetkmc_time_thermal before any cetkmc_thermal_laser
     CHK(upload_ktab(h));
     CHK(push_views(h));
     for (auto& s : h->slabs) hipLaunchKernelGGL(k_orient, dim3(1024), dim3(256), 0, h->stream, s.v);
@@ -1081,10 +1090,11 @@ ThermalCfg thermal_cfg(Handle* h, double dt, int laser, int use_latent, int scru
     return C;
 }
 
-int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+// one application of the explicit step: a whole update (first: counted as one), or one sub-step of it
+int launch_thermal_one(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch, bool first = true)
 {
     const ThermalCfg C = thermal_cfg(h, dt, laser, use_latent, scrub);
-    ++h->cnt.thermal_updates;
+    if (first) ++h->cnt.thermal_updates;
     for (auto& sl : h->slabs) h->cnt.alg_bytes_thermal += (int64_t)16 * sl.v.nloc * h->L * h->L;   // T read + written
     const int nxt = h->cur ^ 1;
     size_t n_fused = 0;
@@ -1138,6 +1148,76 @@ int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_l
     const bool wrote_table = n_fused == h->slabs.size();      // every slab's update wrote its table as well
     invalidate(h, wrote_table ? Cause::thermal_update_wrote_table : Cause::thermal_update);
     if (wrote_table) { h->table_fresh = true; ++h->cnt.table_updates; }
+    return 0;
+}
+
+// ---- sub-stepped updates (thermal_sub.hpp) ---------------------------------------------------------
+// sub-steps per k_thermal_sub launch on this handle; 1: the plain path (several in-process slabs have only two halo planes)
+int substep_block_of(const Handle* h)
+{
+    if (h->slabs.size() != 1 || multi_rank(h) || h->thermal_variant != 1) return 1;
+    if (h->substep_block) return h->substep_block;
+    return h->L > SUB_PLAIN_L ? SUB_SDEFAULT : 1;       // the measured default (thermal_sub.hpp)
+}
+// planes per block of k_thermal_sub: as few plane groups as fill the device once (every group recomputes 2 S rim planes)
+int substep_planes_of(Handle* h, int S)
+{
+    if (h->substep_planes) return h->substep_planes;
+    if (!h->n_cu && hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->dev) != hipSuccess) { (void)hipGetLastError(); h->n_cu = 256; }
+    const int tiles = ((h->L + SUB_EK - 2 * S - 1) / (SUB_EK - 2 * S)) * ((h->L + SUB_EJ - 2 * S - 1) / (SUB_EJ - 2 * S));
+    const int groups = std::max(1, h->n_cu / tiles), nloc = h->slabs[0].v.nloc;
+    return std::max((nloc + groups - 1) / groups, std::min(nloc, 8));
+}
+template <int LASER, int S>
+void launch_sub_S(Handle* h, const SlabView& v, const double* Tin, double* Tout, const double* d_q, const ThermalCfg& C, const StepState* ssp)
+{
+    const dim3 grid((h->L + SUB_EK - 2 * S - 1) / (SUB_EK - 2 * S), (h->L + SUB_EJ - 2 * S - 1) / (SUB_EJ - 2 * S), (v.nloc + C.ni - 1) / C.ni);
+    launch(k_thermal_sub<LASER, S>, grid, dim3(SUB_THREADS), 0, h->stream, nullptr, nullptr, v, Tin, Tout, d_q, C, ssp);
+}
+// m further sub-steps of dt_s on a one-slab handle, S per launch (the last launch takes the remainder)
+int launch_thermal_sub(Handle* h, double dt_s, int laser, const double* d_q, int m, int S, bool batch)
+{
+    const StepState* ssp = batch ? h->d_ss : nullptr;
+    while (m > 0) {
+        const int s = std::min(m, S), nxt = h->cur ^ 1;
+        ThermalCfg C = thermal_cfg(h, dt_s, laser, 0, 0);
+        C.ni = substep_planes_of(h, s);
+        const SlabView v = view_of(h, 0);
+        const double* Tin = h->slabs[0].Tbuf[h->cur];
+        double* Tout = h->slabs[0].Tbuf[nxt];
+        with_flag(laser != 0, [&](auto la) {
+            static_assert(SUB_SMAX == 4, "one case per S");
+            switch (s) {
+            case 1: launch_sub_S<la.value, 1>(h, v, Tin, Tout, d_q, C, ssp); break;
+            case 2: launch_sub_S<la.value, 2>(h, v, Tin, Tout, d_q, C, ssp); break;
+            case 3: launch_sub_S<la.value, 3>(h, v, Tin, Tout, d_q, C, ssp); break;
+            default: launch_sub_S<la.value, 4>(h, v, Tin, Tout, d_q, C, ssp); break;
+            }
+        });
+        HIPCHK(hipGetLastError());
+        h->cnt.alg_bytes_thermal += (int64_t)16 * v.nloc * h->L * h->L;     // T read + written, once per launch
+        h->cur = nxt;
+        ++h->sub_info.launches; ++h->sub_info.blocked_launches;
+        m -= s;
+    }
+    invalidate(h, Cause::thermal_update);       // the table sub-step 1 may have written belongs to an intermediate field
+    return 0;
+}
+
+// a temperature update of the handle: thermal_substeps applications of the explicit step with dt / n
+int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+{
+    const int n = h->thermal_substeps;
+    if (n == 1) return launch_thermal_one(h, dt, laser, d_q, use_latent, scrub, batch);
+    const double dt_s = dt / (double)n;
+    CHK(launch_thermal_one(h, dt_s, laser, d_q, use_latent, scrub, batch));
+    ++h->sub_info.updates; h->sub_info.substeps += n; ++h->sub_info.launches;
+    const int S = substep_block_of(h);
+    if (S > 1) return launch_thermal_sub(h, dt_s, laser, d_q, n - 1, S, batch);
+    for (int q = 1; q < n; ++q) {
+        CHK(launch_thermal_one(h, dt_s, laser, d_q, 0, 0, batch, false));
+        ++h->sub_info.launches;
+    }
     return 0;
 }
 
@@ -1377,6 +1457,8 @@ struct Ens {
     MeltState* d_melt_tab = nullptr;     // cetkmc_ensemble_set_remelt: every replica's row flags and counters [R] (each replica owns its own)
     unsigned long long* d_melt_out = nullptr;      // [R][4] counters gathered at the end of a call
     int remelt_on = 0;
+    int thermal_substeps = 1;            // cetkmc_ensemble_set_thermal_substeps: one n for all replicas
+    cetkmc_substep_info sub_info{};
     double remelt_threshold = 0.0;
 };
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
@@ -1453,7 +1535,7 @@ int cetkmc_struct_size(const char* name)
     SZ("grain_rec", struct cetkmc_grain_rec);
     SZ("solid_info", struct cetkmc_solid_info); SZ("solid_args", struct cetkmc_solid_args); SZ("solid_rec", struct cetkmc_solid_rec);
     SZ("origin_rec", struct cetkmc_origin_rec); SZ("local_args", cetkmc_local_args);
-    SZ("remelt_info", struct cetkmc_remelt_info);
+    SZ("remelt_info", struct cetkmc_remelt_info); SZ("substep_info", struct cetkmc_substep_info);
 #undef SZ
     return -1;
 }
@@ -1643,7 +1725,18 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
     }
     if (!strcmp(key, "thermal_lookahead")) {
         if (value && h->remelt_on) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while remelting is on (the field computed ahead knows no melt)");
+        if (value && h->thermal_substeps > 1) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while thermal_substeps > 1 (the field computed ahead is one explicit step)");
         h->thermal_ahead = value ? 1 : 0;
+        return 0;
+    }
+    if (!strcmp(key, "substep_block")) {
+        if (value < 0 || value > SUB_SMAX) return fail("substep_block must be 0 (default), 1 (plain path: one launch per sub-step) or 2.." + std::to_string(SUB_SMAX) + " sub-steps per k_thermal_sub launch");
+        h->substep_block = (int)value;
+        return 0;
+    }
+    if (!strcmp(key, "substep_planes")) {
+        if (value < 0 || value > 4096) return fail("substep_planes must be 0 (default: one round of blocks) or 1..4096 planes per block of k_thermal_sub");
+        h->substep_planes = (int)value;
         return 0;
     }
     if (!strcmp(key, "apply_in_sweep")) { h->apply_in_sweep = value ? 1 : 0; return 0; }
@@ -2326,6 +2419,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     if (h->remelt_on) return fail("cetkmc_run_supersteps is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
+    if (h->thermal_substeps > 1) return fail("cetkmc_run_supersteps is refused while thermal_substeps > 1 (cetkmc_set_thermal_substeps): Mode B updates are not sub-stepped");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps needs a streaming sweep_variant (1 or 2)");
@@ -2424,6 +2518,7 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     if (h->remelt_on) return fail("cetkmc_run_supersteps_local is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
+    if (h->thermal_substeps > 1) return fail("cetkmc_run_supersteps_local is refused while thermal_substeps > 1 (cetkmc_set_thermal_substeps): Mode B updates are not sub-stepped");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (a->box != 8 || h->L % 8) return fail("cetkmc_run_supersteps_local: box must be 8 and divide L");
@@ -2986,7 +3081,9 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const double K0 = host_k_eff(h0->p, 0, 0);
     const SlabView v0{};
     const int latent = laser && a->use_latent ? 1 : 0;
-    const ThermalCfg tc0 = thermal_cfg(h0, a->thermal_dt, laser ? 1 : 0, latent, 1);
+    const int nsub = e->thermal_substeps;
+    const double dt_s = nsub > 1 ? a->thermal_dt / (double)nsub : a->thermal_dt;
+    const ThermalCfg tc0 = thermal_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), tc_sub = thermal_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
     const BatchCfg cfg0{};
     const dim3 g_flags((unsigned)std::min<int64_t>(((int64_t)(L + 4) * L + 255) / 256, 64), (unsigned)R);
     EnsSel sel{e->d_table, 0, (int)g_therm.z / R};
@@ -3007,8 +3104,14 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
             // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
             if (latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
             sel.rel ^= 1;
-            sel.q_off += laser ? (int64_t)L2 : 0;
             ++flips;
+            for (int q = 1; q < nsub; ++q) {       // sub-steps 2..n: the plain path, no scrub, no latent term, same plane
+                launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc_sub, nullptr, sel);
+                sel.rel ^= 1;
+                ++flips;
+            }
+            if (nsub > 1) { ++e->sub_info.updates; e->sub_info.substeps += nsub; e->sub_info.launches += nsub; }
+            sel.q_off += laser ? (int64_t)L2 : 0;
             if (e->remelt_on) {        // behind the update and its prev_state := state, in front of the table and the interface kernel
                 const SlabView& mv = e->table[0].view[0];
                 launch(k_melt_scan<EnsSel>, melt_scan_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, nullptr, MeltState{}, e->d_melt_tab,
@@ -4054,6 +4157,62 @@ int cetkmc_ensemble_remelt_info(void* handle, struct cetkmc_remelt_info* info)
     if (!e) return fail("cetkmc_ensemble_remelt_info: not an ensemble handle (cetkmc_create_ensemble)");
     for (int r = 0; r < e->R; ++r) info[r] = e->reps[(size_t)r]->melt_info;
     return 0;
+}
+
+// ---- sub-stepped temperature updates (thermal_sub.hpp) --------------------------------------------
+static int substeps_range(const char* fn, int n)
+{
+    if (n < 1) return fail(std::string(fn) + ": thermal_substeps must be >= 1 (got " + std::to_string(n) + ")");
+    if (n > CETKMC_MAX_THERMAL_SUBSTEPS)
+        return fail(std::string(fn) + ": thermal_substeps above " + std::to_string(CETKMC_MAX_THERMAL_SUBSTEPS) + " (the launch bookkeeping is int)");
+    return 0;
+}
+
+int cetkmc_set_thermal_substeps(void* handle, int n)
+{
+    if (!handle) return fail("null handle");
+    if (ens_of(handle)) return fail("cetkmc_set_thermal_substeps: an ensemble handle is set by cetkmc_ensemble_set_thermal_substeps");
+    Handle* h = (Handle*)handle;
+    CHK(substeps_range("cetkmc_set_thermal_substeps", n));
+    if (h->in_ensemble) return fail("cetkmc_set_thermal_substeps: the replicas of an ensemble share one value (cetkmc_ensemble_set_thermal_substeps)");
+    if (multi_rank(h) || h->nranks != 1) return fail("cetkmc_set_thermal_substeps is refused on a rank handle (cetkmc_create_rank*): the halo exchange carries two planes per update");
+    if (n > 1 && h->thermal_ahead) return fail("cetkmc_set_thermal_substeps: n > 1 is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
+    h->thermal_substeps = n;
+    return 0;
+}
+
+int cetkmc_ensemble_set_thermal_substeps(void* handle, int n)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("cetkmc_ensemble_set_thermal_substeps: not an ensemble handle (cetkmc_create_ensemble)");
+    CHK(substeps_range("cetkmc_ensemble_set_thermal_substeps", n));
+    e->thermal_substeps = n;
+    for (Handle* h : e->reps) h->thermal_substeps = n;      // a direct update on a replica handle follows the ensemble's value
+    return 0;
+}
+
+int cetkmc_get_substep_info(void* handle, struct cetkmc_substep_info* info)
+{
+    if (!handle || !info) return fail("null argument");
+    Ens* e = ens_of(handle);
+    *info = e ? e->sub_info : ((Handle*)handle)->sub_info;
+    return 0;
+}
+
+int cetkmc_time_thermal(void* handle, int laser, int n_updates, double* ms_total)
+{
+    if (!handle || !ms_total) return fail("null argument");
+    if (ens_of(handle)) return fail("cetkmc_time_thermal: a single handle (an ensemble's updates run inside cetkmc_run_ensemble)");
+    Handle* h = (Handle*)handle;
+    if (n_updates < 0) return fail("cetkmc_time_thermal: n_updates must be >= 0");
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    for (int u = 0; u < n_updates; ++u) CHK(launch_thermal(h, 1e-6, laser ? 1 : 0, laser ? h->d_qtop : nullptr, laser ? 1 : 0, 1, false));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *ms_total = 0.0;
+    return add_elapsed(h->ev0, h->ev1, ms_total);
 }
 
 

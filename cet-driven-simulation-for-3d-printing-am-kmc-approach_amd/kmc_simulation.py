@@ -38,7 +38,7 @@ from metrics import (compute_CET, compute_metrics, compute_metrics_device, compu
                      solid_metrics as _solid_metrics, write_solid_csv as _write_solid_csv,
                      origin_metrics as _origin_metrics, write_origin_csv as _write_origin_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
-from thermal_solver import laser_scan_planes
+from thermal_solver import laser_scan_planes, stable_substeps
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
 
 # What the last run_kmc call observed besides its return tuple (the reference's signature has no room for it):
@@ -251,6 +251,25 @@ def _remelt_threshold(remelt, where="remelt"):
     raise ValueError(f"{where} must be False, True (melt at T_MELT) or a threshold temperature")
 
 
+def _thermal_substeps(value, where="thermal_substeps"):
+    """run_kmc's ``thermal_substeps`` option as a count: an integer >= 1, or "stable" = thermal_solver.stable_substeps(1e-6)"""
+    if isinstance(value, str) and value == "stable":
+        return stable_substeps(THERMAL_DT)
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"{where} must be an integer >= 1 or 'stable' (got {value!r})")
+    return int(value)
+
+
+def _check_substeps(n_sub, mode_a, thermal_updates):
+    """what run_kmc and run_kmc_ensemble refuse of thermal_substeps > 1 (before any device call)"""
+    if n_sub == 1:
+        return
+    if not mode_a:
+        raise ValueError("thermal_substeps needs mode 'A' (the super-step engine's updates are not sub-stepped)")
+    if not thermal_updates:
+        raise ValueError("thermal_substeps needs thermal_updates=True (there is no update to split)")
+
+
 def _check_remelt(thr, mode_a, origin_metrics, thermal_updates):
     if thr is None:
         return
@@ -362,6 +381,7 @@ def run_kmc(
     solid_every: int = 20,
     origin_metrics: bool = False,
     remelt=False,
+    thermal_substeps=1,
     local_events: int = 0,
     local_horizon: float = 1.0,
 ):
@@ -471,8 +491,17 @@ def run_kmc(
     the given threshold) become empty, before that step's rates are evaluated.  Every metrics row gains, behind every other
     column, ``RemeltPasses`` and ``RemeltedVoxels`` (running totals); ``last_run_info["remelted"]`` carries the total.
     Checkpoints carry the setting and the totals (only then), and a resumed run must ask for the same threshold.  Refused
-    with ValueError: ``mode="B"``, ``origin_metrics``, ``thermal_updates=False``."""
+    with ValueError: ``mode="B"``, ``origin_metrics``, ``thermal_updates=False``.
+
+    ``thermal_substeps=n`` (or ``"stable"`` = thermal_solver.stable_substeps(1e-6) = 17; mode "A" only, with or without
+    ``laser`` and ``remelt``): every temperature update is n explicit steps of 1e-6 / n s on the device
+    (cetkmc_set_thermal_substeps) -- the reference's single step is 16 times too long for the
+    explicit scheme and turns a rough field into noise between the clip values.  ``last_run_info["thermal_substeps"]``
+    reports n.  Checkpoints carry the value only when it is not 1, and a resumed run must ask for the same.  Refused with
+    ValueError: ``mode="B"``, ``thermal_updates=False``."""
     import cetkmc
+    n_sub = _thermal_substeps(thermal_substeps)
+    _check_substeps(n_sub, mode == "A", thermal_updates)
     remelt_thr = _remelt_threshold(remelt)
     _check_remelt(remelt_thr, mode == "A", origin_metrics, thermal_updates)
     _check_solid(solid_metrics, solid_every, bool(checkpoint_every or resume_from))
@@ -528,6 +557,12 @@ def run_kmc(
             raise ValueError(f"checkpoint was written by a run with remelt={ex.get('remelt', False)}, this call asks for {remelt_thr or False}")
         remelt_off = (int(ex.get("remelt_passes", 0)), int(ex.get("remelted", 0)))
         engine.set_remelt(True, remelt_thr)
+    if ckpt and int(ckpt["extra"].get("thermal_substeps", 1)) != n_sub:
+        engine.close()
+        raise ValueError(f"checkpoint was written by a run with thermal_substeps={ckpt['extra'].get('thermal_substeps', 1)}, "
+                         f"this call asks for {n_sub}")
+    if n_sub != 1:
+        engine.set_thermal_substeps(n_sub)
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -594,6 +629,8 @@ def run_kmc(
         if remelt_thr is not None:       # (only then: the checkpoints of every other run stay as they were)
             info = engine.remelt_info()
             extra = dict(extra or {}, remelt=remelt_thr, remelt_passes=remelt_off[0] + info["passes"], remelted=remelt_off[1] + info["n_melted"])
+        if n_sub != 1:                   # (likewise)
+            extra = dict(extra or {}, thermal_substeps=n_sub)
         save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
                         engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
                         at, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected, extra=extra)
@@ -727,7 +764,7 @@ def run_kmc(
     remelted = remelt_off[1] + engine.remelt_info()["n_melted"] if remelt_thr is not None else None
     engine.close()
     last_run_info.clear()
-    last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1)
+    last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1, thermal_substeps=n_sub)
     if remelt_thr is not None:
         last_run_info.update(remelted=remelted)
     if local_events:
@@ -828,7 +865,7 @@ def _replica_prefix(cfg, L):
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
                      front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False, solid_metrics=False,
-                     solid_every=20, origin_metrics=False):
+                     solid_every=20, origin_metrics=False, thermal_substeps=1):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -855,8 +892,12 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     ``solid_every`` steps and ONE batched cetkmc_ensemble_solid_profile per metrics row.
     ``origin_metrics=True``: run_kmc's option of that name (columns, ``origin_layers.csv`` and, with ``grain_metrics``,
     ``origin_grains.csv`` of every replica): every cetkmc_run_ensemble call folds the replicas' executed events into their
-    origin maps in one launch, and every metrics row takes ONE batched cetkmc_ensemble_origin_profile and census."""
+    origin maps in one launch, and every metrics row takes ONE batched cetkmc_ensemble_origin_profile and census.
+    ``thermal_substeps``: run_kmc's option of that name, one value for all replicas (cetkmc_ensemble_set_thermal_substeps);
+    ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_substeps"]``."""
     import cetkmc
+    n_sub = _thermal_substeps(thermal_substeps)
+    _check_substeps(n_sub, rng == "reference", thermal_updates)
     _check_solid(solid_metrics, solid_every, False)
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates, origin_metrics)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
@@ -904,6 +945,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         remelt_thr = cfgs[0]["remelt"]
         if remelt_thr is not None:
             ens.set_remelt(True, remelt_thr)
+        if n_sub != 1:
+            ens.set_thermal_substeps(n_sub)
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -1051,6 +1094,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))
             last_ensemble_info.append(dict(random_state=gens[r].py, np_state=gens[r].np, executed_events=last_step[r] + 1,
                                            min_margin=min_margin[r] if rng == "reference" else None,
+                                           thermal_substeps=n_sub,
                                            **({"remelted": ri[r]["n_melted"]} if ri is not None else {})))
             print(f"[{c['output_prefix']}] completed {last_step[r] + 1} steps in {total_time[r]:.2e} s")
         return out

@@ -79,6 +79,27 @@ def laser_source_plane(L, laser_pos, laser_power, beam_radius=DEFAULT_BEAM_RADIU
 SCAN_EVERY = 20      # run_kmc's temperature update cadence (kmc_simulation.py:248)
 
 
+def stable_substeps(dt, alpha=ALPHA, dx=VOXEL_SIZE):
+    """Smallest n >= 1 for which the explicit 7-point update with dt / n is stable: alpha * (dt / n) / dx**2 <= 1/6, the
+    quotient evaluated as written (17 for the reference's dt = 1e-6 s, where alpha dt / dx^2 = 2.716).  For the
+    ``substeps`` / ``thermal_substeps`` options."""
+    dt, alpha, dx = float(dt), float(alpha), float(dx)
+    if not (dt > 0.0 and alpha > 0.0 and dx > 0.0) or not np.isfinite(alpha * dt / (dx * dx)):
+        raise ValueError("stable_substeps needs positive finite dt, alpha and dx")
+    n = max(1, int(np.floor(6.0 * alpha * dt / (dx * dx))))
+    while n > 1 and alpha * (dt / (n - 1)) / (dx * dx) <= 1.0 / 6.0:
+        n -= 1
+    while alpha * (dt / n) / (dx * dx) > 1.0 / 6.0:
+        n += 1
+    return n
+
+
+def _check_substeps(substeps):
+    if isinstance(substeps, bool) or not isinstance(substeps, (int, np.integer)) or substeps < 1:
+        raise ValueError("substeps must be an integer >= 1")
+    return int(substeps)
+
+
 def laser_scan_planes(L, laser, first_step, n_steps):
     """Source planes (n, L, L) of the temperature updates that fall in the global steps [first_step, first_step + n_steps):
     one per step g with g % 20 == 0, in step order.  ``laser`` is a dict: ``power`` [W], ``start`` (beam centre at update
@@ -99,25 +120,36 @@ def laser_scan_planes(L, laser, first_step, n_steps):
 
 
 def update_temperature(T, state, prev_state, dt, laser_pos, laser_power,
-                       beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY):
+                       beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, substeps=1):
     """Explicit Euler step with Laplacian + Gaussian surface source on i=L-1 + latent heat where
-    ``prev_state==0 & state!=0``; clipped to [T_SUB, 1.1*T_MELT] (thermal_solver.py:36-105)."""
+    ``prev_state==0 & state!=0``; clipped to [T_SUB, 1.1*T_MELT] (thermal_solver.py:36-105).  ``substeps=n`` (not in the
+    reference): n such steps of dt / n from the same source, the latent heat in the first (``stable_substeps``)."""
     L = T.shape[0]
     assert T.shape == (L, L, L)
     assert state.shape == T.shape and prev_state.shape == T.shape
+    substeps = _check_substeps(substeps)
     eng = _engine(L)
     eng.upload(state=state, T=T)
     eng.set_prev_state(prev_state)
-    eng.thermal_laser(dt, laser_source_plane(L, laser_pos, laser_power, beam_radius, absorptivity),
-                      use_latent=True, scrub_nan=False)
+    eng.set_thermal_substeps(substeps)
+    try:
+        eng.thermal_laser(dt, laser_source_plane(L, laser_pos, laser_power, beam_radius, absorptivity),
+                          use_latent=True, scrub_nan=False)
+    finally:
+        eng.set_thermal_substeps(1)        # the handle is cached
     return eng.download(state=False, theta=False, phi=False, T=True)["T"]
 
 
-def update_temperature_cet(T, state, dt=1e-6):
+def update_temperature_cet(T, state, dt=1e-6, substeps=1):
     """Diffusion-only step used by run_kmc; ``state`` is unused, as in the reference
-    (thermal_solver.py:107-117)."""
+    (thermal_solver.py:107-117).  ``substeps=n`` (not in the reference): n such steps of dt / n."""
     L = T.shape[0]
+    substeps = _check_substeps(substeps)
     eng = _engine(L)
     eng.upload(T=T)
-    eng.thermal_cet(dt, scrub_nan=False)
+    eng.set_thermal_substeps(substeps)
+    try:
+        eng.thermal_cet(dt, scrub_nan=False)
+    finally:
+        eng.set_thermal_substeps(1)
     return eng.download(state=False, theta=False, phi=False, T=True)["T"]

@@ -200,7 +200,7 @@ int cetkmc_abi_version(void);
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
- * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -851,6 +851,40 @@ int cetkmc_time_remelt(void* handle, double threshold, int n, double* ms_total);
 int cetkmc_get_remelt_info(void* handle, struct cetkmc_remelt_info* info);
 int cetkmc_ensemble_set_remelt(void* handle, int on, double threshold);
 int cetkmc_ensemble_remelt_info(void* handle, struct cetkmc_remelt_info* info);
+
+/* ---- sub-stepped temperature updates -------------------------------------------------------------
+ * The explicit update is stable only for alpha dt / dx^2 <= 1/6; the reference's dt = 1e-6 s gives 2.716.  With
+ * thermal_substeps = n >= 1 (default 1: nothing changes) EVERY temperature update the handle performs -- cetkmc_thermal_cet,
+ * cetkmc_thermal_laser, the cadence updates of cetkmc_run_steps and cetkmc_run_ensemble -- is n consecutive applications of
+ * the existing update with dt_s = dt / n (one IEEE division on the host), all from the same source plane, clipped after
+ * each.  Sub-step 1 is the existing launch: NaN scrub, latent-heat term, prev_state := state, row flags cleared.  Sub-steps
+ * 2..n have neither scrub nor latent term.  One update still consumes one source plane, counts once in
+ * cetkmc_counters.thermal_updates, and is applied or skipped as a whole (the marker of a status-2 stop, the pass-through
+ * behind a terminated batch); with remelting on, the melt pass follows the last sub-step.
+ *   cetkmc_set_thermal_substeps            a single handle (not a rank handle, not an ensemble's handles)
+ *   cetkmc_ensemble_set_thermal_substeps   an ensemble handle: one n for all replicas (they share the thermal settings)
+ *   cetkmc_get_substep_info                running totals of the handle since its creation: updates made while n > 1,
+ *                      their sub-steps, the temperature-kernel launches they took, and how many of those were the
+ *                      temporally blocked k_thermal_sub (thermal_sub.hpp) -- which proves which kernel ran.  An ensemble
+ *                      handle reports the launches of its calls (one launch steps all replicas).
+ *   cetkmc_time_thermal                    n_updates updates with dt = 1e-6 s and the scrub (laser != 0: with the handle's last
+ *                      cetkmc_thermal_laser plane, zeros before the first, and the latent-heat term) bracketed by one hipEvent pair on the
+ *                      handle's stream: measurement only (tools/thermal_substeps_timing.py).  The field moves on.
+ * On a handle with one slab sub-steps 2..n can run in k_thermal_sub, option "substep_block" sub-steps per launch: 2..4; 1 =
+ * the plain path (n launches of the existing kernel); 0 = the measured default, 3 at L > 128 and the plain path up to
+ * L = 128, where it is faster.  A handle with several in-process slabs and an ensemble take the plain path.  Option
+ * "substep_planes" sets the planes per block of k_thermal_sub (0 = chosen so that the blocks fill the device once).  Same
+ * bits either way.
+ * Refused, before anything is launched: n < 1 and n > 65536 (the launch bookkeeping is int); rank handles
+ * (cetkmc_create_rank*); n > 1 while option thermal_lookahead is on, and thermal_lookahead = 1 while n > 1;
+ * cetkmc_set_thermal_substeps on an ensemble's own handle or on its replicas; cetkmc_run_supersteps and
+ * cetkmc_run_supersteps_local while n > 1 (Mode B is out of scope). */
+#define CETKMC_MAX_THERMAL_SUBSTEPS 65536
+struct cetkmc_substep_info { int64_t updates, substeps, launches, blocked_launches; };
+int cetkmc_set_thermal_substeps(void* handle, int n);
+int cetkmc_ensemble_set_thermal_substeps(void* handle, int n);
+int cetkmc_get_substep_info(void* handle, struct cetkmc_substep_info* info);
+int cetkmc_time_thermal(void* handle, int laser, int n_updates, double* ms_total);
 
 #ifdef __cplusplus
 }
