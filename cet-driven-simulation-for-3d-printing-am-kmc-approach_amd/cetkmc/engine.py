@@ -698,7 +698,9 @@ class Engine:
         return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
 
     def time_thermal(self, n_updates, laser=False):
-        """cetkmc_time_thermal: device ms of n_updates temperature updates (dt = 1e-6 s, one hipEvent pair), measurement only."""
+        """cetkmc_time_thermal: device ms of n_updates temperature updates (dt = 1e-6 s, one hipEvent pair).  The updates are
+        real: afterwards the handle's field has advanced by ``n_updates`` updates (``laser``: with the plane of the last
+        ``thermal_laser``, zeros before the first, and the latent-heat term)."""
         ms = C.c_double(0.0)
         self._ck(self.lib.cetkmc_time_thermal(self.h, int(bool(laser)), int(n_updates), C.byref(ms)))
         return ms.value

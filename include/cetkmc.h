@@ -106,8 +106,12 @@ typedef struct cetkmc_run_args {
                                  the continuation starts at the same step0 = that step and supplies that step's plane
                                  again as q_planes[0].  It is not read a second time, but it is counted again in q_used.
                                  The handle remembers the applied update only until the next upload (of any field, a
-                                 defects-only one included) or direct temperature update: after either, a call starting
-                                 at that step applies the update like any other (CETKMC_CACHE_APPLIED) */
+                                 defects-only one included) or direct temperature update (cetkmc_thermal_cet, _thermal_laser,
+                                 the updates of cetkmc_time_thermal): after either, a call starting at that step applies
+                                 the update like any other (CETKMC_CACHE_APPLIED).  Everything else leaves the marker --
+                                 cetkmc_remelt, cetkmc_set_remelt, cetkmc_set_thermal_substeps, cetkmc_set_params,
+                                 cetkmc_time_sweeps, the read-only calls: behind them the continuation still skips that
+                                 step's update (and its melt pass, whatever the switches say by then) */
     int64_t n_q;
     int32_t use_latent;       /* thermal_mode 2: latent-heat term on/off                */
     int32_t profile;          /* 1: time every rate-sweep launch with hipEvents; 3: every 8th launch, every 4th in batches of <= 64
@@ -123,7 +127,8 @@ typedef struct cetkmc_run_result {
     int32_t status;           /* 0 ok, 1 terminated (no valid events, :260-262), 2 u_np exhausted: continue with a call
                                  whose step0 is this call's step0 + steps_done and whose u_np starts at np_used.  When
                                  that step is a temperature-update step its update has been applied already and the
-                                 continuation does not repeat it (cetkmc_run_args.q_planes says what it must supply) */
+                                 continuation does not repeat it (cetkmc_run_args.q_planes says what it must supply, and
+                                 which calls in between make the handle forget the applied update) */
     int64_t np_used;          /* doubles of u_np consumed                               */
     int64_t q_used;           /* thermal_mode 2: source planes consumed by the executed steps (and by the step a batch
                                  stopped in: its update precedes the selection); planes queued behind an early stop
@@ -818,11 +823,15 @@ int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layer
  * The voxels of the rows around a melted voxel are relisted (interface list, neighbourhood words), not evaluated.
  *   cetkmc_remelt      one pass now, behind the pending work of the handle's stream; a single handle or a replica handle.
  *                      It costs what cetkmc_apply costs (cause "apply" of cetkmc_invalidates: the row sums and the interface
- *                      sums go stale, the rate table stays valid).  info may be NULL.  On a replica that has terminated the pass
+ *                      sums go stale, the rate table stays valid).  A pass that melts nothing -- threshold +inf, or nothing hot
+ *                      enough -- leaves the lattice as it is, and is a pass all the same: it is counted and raises the same
+ *                      cause.  info may be NULL.  On a replica that has terminated the pass
  *                      may create events, but the replica stays frozen for cetkmc_run_ensemble until a lattice is uploaded
  *                      into it, as after any other change of a terminated replica.
  *   cetkmc_time_remelt n passes bracketed by one hipEvent pair on the handle's stream (ms_total; as cetkmc_time_sweeps times
- *                      sweeps), then one untimed cetkmc_remelt: measurement only (tools/remelt_timing.py).
+ *                      sweeps), then one untimed cetkmc_remelt: measurement only (tools/remelt_timing.py).  The lattice is
+ *                      what ONE pass leaves (the rule is idempotent); cetkmc_remelt_info.passes grows by n + 1 and
+ *                      n_melted_last is the untimed pass's count, 0 when n >= 1.
  *   cetkmc_set_remelt  on != 0: every temperature-update step (g % 20 == 0, thermal_mode 1 or 2) of cetkmc_run_steps runs a
  *                      pass behind the update (and behind its prev_state := state) and before that step's rate evaluation.
  *                      Nothing happens with thermal_mode 0.  Behind an early stop (status 1 or 2) the queued passes are
@@ -869,7 +878,9 @@ int cetkmc_ensemble_remelt_info(void* handle, struct cetkmc_remelt_info* info);
  *                      handle reports the launches of its calls (one launch steps all replicas).
  *   cetkmc_time_thermal                    n_updates updates with dt = 1e-6 s and the scrub (laser != 0: with the handle's last
  *                      cetkmc_thermal_laser plane, zeros before the first, and the latent-heat term) bracketed by one hipEvent pair on the
- *                      handle's stream: measurement only (tools/thermal_substeps_timing.py).  The field moves on.
+ *                      handle's stream: measurement only (tools/thermal_substeps_timing.py).  The updates are real: afterwards
+ *                      the handle's field has advanced by n_updates updates (each of thermal_substeps sub-steps; in laser
+ *                      mode prev_state := state as well), with what any direct update makes stale (cause "thermal_update").
  * On a handle with one slab sub-steps 2..n can run in k_thermal_sub, option "substep_block" sub-steps per launch: 2..4; 1 =
  * the plain path (n launches of the existing kernel); 0 = the measured default, 3 at L > 128 and the plain path up to
  * L = 128, where it is faster.  A handle with several in-process slabs and an ensemble take the plain path.  Option

@@ -63,6 +63,16 @@ class Stepper:
         self.applied_g = -1         # a call that stopped with status 2 ON an update step has applied that step's whole update
         self.stats = new_stats()
         self.melted = 0
+        self.info = dict(passes=0, n_melted=0, n_melted_last=0)      # mirrors cetkmc_remelt_info for the passes of this loop
+
+    def melt(self, g):
+        """the melt pass behind the update of global step g (a subclass may look at the lattice first)"""
+        k = remelt(self.lat, self.threshold)
+        self.melted += k
+        self.info["passes"] += 1
+        self.info["n_melted"] += k
+        self.info["n_melted_last"] = k
+        return k
 
     def run_steps(self, step0, n, defect_fraction, u_pick, u_defect, u_np, rng_mode=0, seed=0, thermal_mode=1, thermal_dt=1e-6,
                   q_planes=None, use_latent=True):
@@ -81,7 +91,7 @@ class Stepper:
                            use_latent=use_latent, scrub=True, stats=self.stats)
                     q_idx += thermal_mode == 2
                     if self.threshold is not None:
-                        self.melted += remelt(lat, self.threshold)
+                        self.melt(g)
             nxt = min(n, s + 20 - g % 20) if thermal_mode else n
             m = nxt - s
             if rng_mode == 2:

@@ -99,6 +99,91 @@ CASES = [
 @pytest.mark.parametrize("n_slabs", [1, 2])
 @pytest.mark.parametrize("case,cause,call", CASES, ids=[c[0] for c in CASES])
 def test_cause_invalidates_exactly_its_row(case, cause, call, n_slabs):
+    _check(case, cause, call, n_slabs)
+
+
+# ---- remelting, sub-stepped updates, the timers, the maps ------------------------------------------------------------------------
+MELT_AT = lo.T_MELT + 0.3          # about half of the deposition plane i = L - 1 of lo.fields lies above it
+
+
+def _remelt(e):
+    assert e.remelt(MELT_AT)["n_melted_last"] > 0, "the pass melts nothing: the case would not show what a melt makes stale"
+
+
+def _remelt_nothing(e):
+    info = e.remelt(float("inf"))
+    assert (info["passes"], info["n_melted"]) == (1, 0)
+
+
+def _time_remelt(e):
+    e.time_remelt(2, MELT_AT)
+    info = e.remelt_info()
+    assert info["passes"] == 3 and info["n_melted"] > 0 and info["n_melted_last"] == 0      # two timed passes, one untimed (cetkmc.h)
+
+
+def _set_remelt_on_and_off(e):
+    e.set_remelt(True, MELT_AT)
+    e.set_remelt(False, MELT_AT)
+
+
+def _set_substeps(e):
+    e.set_thermal_substeps(5)
+    e.set_thermal_substeps(1)
+
+
+def _substepped_cet(e):
+    e.set_thermal_substeps(5)
+    e.set_option("substep_block", 3)
+    e.thermal_cet(lo.THERMAL_DT, scrub_nan=True)
+    assert e.substep_info()["substeps"] == 5
+
+
+def _solid_cycle(e):
+    e.solid_begin()
+    try:
+        e.solid_update(1, lo.THERMAL_DT)
+        e.solid_read()
+    finally:
+        e.solid_end()
+
+
+def _origin_cycle(e):
+    e.origin_begin()
+    try:
+        e.origin_read()
+    finally:
+        e.origin_end()
+
+
+# (case, cause or None, the call, on two slabs: "refused" = the call must be refused, "may" = it may be; either way every cache
+# must then have survived)
+CASES2 = [
+    ("remelt", "apply", _remelt, "refused"),
+    ("remelt_nothing", "apply", _remelt_nothing, "refused"),        # as the code does: the pass ran, its cause is raised
+    ("time_remelt", "apply", _time_remelt, "refused"),
+    ("set_remelt_on", None, lambda e: e.set_remelt(True, MELT_AT), "refused"),
+    ("set_remelt_on_and_off", None, _set_remelt_on_and_off, "refused"),
+    ("set_thermal_substeps_5", None, lambda e: e.set_thermal_substeps(5), None),
+    ("set_thermal_substeps_5_and_1", None, _set_substeps, None),
+    ("opt_substep_block", None, _option("substep_block", 3), None),
+    ("opt_substep_planes", None, _option("substep_planes", 8), None),
+    ("thermal_cet_n5_block3", "thermal_update", _substepped_cet, None),
+    ("time_thermal", "thermal_update", lambda e: e.time_thermal(2), None),
+    ("time_thermal_laser", "thermal_update", lambda e: e.time_thermal(2, laser=True), None),
+    ("time_sweeps", None, lambda e: e.time_sweeps(3), None),
+    ("event_overhead", None, lambda e: e.event_overhead(5), None),
+    ("solid_cycle", None, _solid_cycle, "may"),
+    ("origin_cycle", None, _origin_cycle, "may"),
+]
+
+
+@pytest.mark.parametrize("n_slabs", [1, 2])
+@pytest.mark.parametrize("case,cause,call,two_slabs", CASES2, ids=[c[0] for c in CASES2])
+def test_new_cause_invalidates_exactly_its_row(case, cause, call, two_slabs, n_slabs):
+    _check(case, cause, call, n_slabs, two_slabs if n_slabs > 1 else None)
+
+
+def _check(case, cause, call, n_slabs, refusal=None):
     import cetkmc
     stale = TABLE[cause] if cause else 0
     e = cetkmc.Engine(L, impurity_c=lo.IMPURITY_C, n_slabs=n_slabs)
@@ -116,7 +201,15 @@ def test_cause_invalidates_exactly_its_row(case, cause, call, n_slabs):
         warm = e.counters()
         assert (warm["table_updates"], warm["interface_launches"]) == (before["table_updates"], before["interface_launches"]), "not warm"
 
-        call(e)
+        if refusal is None:
+            call(e)
+        else:
+            try:
+                call(e)
+                assert refusal == "may", (case, "not refused on a handle with several slabs")
+            except RuntimeError as ex:
+                assert "in one slab" in str(ex), (case, str(ex))
+                stale = 0          # refused before anything was launched: every cache survived
 
         c0 = e.counters()
         try:

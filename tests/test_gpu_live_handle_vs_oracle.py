@@ -8,7 +8,8 @@ fresh (``pairs``), walk at random over mutators, read-only calls and paths (``wa
 growing and shrinking box counts (``modes``) and step on behind a termination (``frozen``).  After every mutator and
 read-only call: all five fields and the sweep of the lattice (helpers.assert_fields_match_oracle); after every stepping call
 the whole result.  Integers, positions and fields compare with ==, rates and sums within RATE_RTOL.
-tests/test_live_ops_host.py asserts on the oracle alone that the scripts cover what they claim.
+tests/test_live_ops_host.py asserts on the oracle alone that the scripts cover what they claim.  The entry points of remelting,
+sub-stepped temperature updates, the local Mode B loop and the timers have scripts of their own at the end of this file.
 
 Pinned as the code does it today (include/cetkmc.h): the nucleation count and cetkmc_counters survive an upload of a whole
 new lattice; a staged batch survives every mutator and then steps the mutated lattice."""
@@ -112,3 +113,93 @@ def test_staged_batch_is_consumed_once_and_dropped_by_buffer_moves(oracle_mod):
         assert e.nucleation_count() == r.lat.nuc_count
     finally:
         e.close()
+
+
+# ---- the second vocabulary: remelting, sub-stepped updates, the local Mode B loop, the timers (live_ops.py) ------------------------
+CASES2 = [(L, n_slabs, name) for L, n_slabs in ((16, 1), (24, 3)) for name in lo.script_names2(L)]
+
+
+def assert_local_matches_ref(e, lat, rg, ro, rate_rtol, tag=""):
+    """One run_supersteps_local call (result rg, with want_events) against tests/local_ref.run on the oracle lattice (ro), as
+    tests/test_gpu_local_vs_ref.py compares: stop state, per-box event sequences, counts, totals, horizons, then the fields."""
+    from helpers import relerr
+    assert (rg["done"], rg["status"]) == (ro["done"], ro["status"]), (tag, rg["done"], rg["status"], ro["done"], ro["status"])
+    done, ge, oe = ro["done"], rg["events"], ro["events"]
+    assert ge.shape == oe.shape, (tag, "event log shape", ge.shape, oe.shape)
+    for f in ("type", "pos", "target", "atom"):
+        if not np.array_equal(ge[f], oe[f]):
+            bad = np.argwhere((ge[f] != oe[f]).reshape(done, ge.shape[1], ge.shape[2], -1).any(axis=3))[0]
+            raise AssertionError(f"{tag}: event field {f} differs first at super-step {bad[0]} of the call, box {bad[1]}, event {bad[2]}: "
+                                 f"engine {ge[tuple(bad)]} comparator {oe[tuple(bad)]}")
+    live = oe["type"] >= 0
+    if live.any():
+        assert relerr(ge["rate"][live], oe["rate"][live]).max() <= rate_rtol, (tag, "event rates")
+        assert np.array_equal(ge["theta"][live], oe["theta"][live]) and np.array_equal(ge["phi"][live], oe["phi"][live]), (tag, "angles")
+    assert np.array_equal(rg["n_exec"], ro["n_exec"]) and np.array_equal(rg["n_capped"], ro["n_capped"]), (tag, "n_exec, n_capped")
+    assert len(rg["totals"]) == len(ro["totals"]), (tag, "log lengths")
+    if len(ro["totals"]):
+        assert relerr(rg["totals"], ro["totals"]).max() <= rate_rtol, (tag, "totals")
+    if done:
+        fin = np.isfinite(ro["horizon"])
+        assert np.array_equal(np.isfinite(rg["horizon"]), fin) and np.array_equal(rg["horizon"][~fin], ro["horizon"][~fin]), (tag, "horizon")
+        if fin.any():
+            assert relerr(rg["horizon"][fin], ro["horizon"][fin]).max() <= rate_rtol, (tag, "horizon")
+        assert relerr(rg["dt_event"], ro["dt_event"]).max() <= rate_rtol, (tag, "dt_event")
+    assert rg["nucleation_count"] == lat.nuc_count, (tag, "nucleation_count", rg["nucleation_count"], lat.nuc_count)
+    assert_fields_match_oracle(e, lat, rate_rtol, tag)
+
+
+def _play2(oracle_mod, L, n_slabs, name, paths=None):
+    import cetkmc
+    script = lo.make_script(L, name)
+    e = cetkmc.Engine(L, impurity_c=lo.IMPURITY_C, n_slabs=n_slabs)
+    try:
+        r = lo.Runner(oracle_mod, L, paths=paths, engine=e, n_slabs=n_slabs,
+                      check_fields=lambda e, lat, tag: assert_fields_match_oracle(e, lat, RATE_RTOL, tag),
+                      check_run=lambda e, lat, rg, ro, tag: assert_call_matches_oracle(e, lat, rg, ro, RATE_RTOL, tag),
+                      check_super=lambda e, lat, rg, ro, tag: assert_supersteps_match_oracle(e, lat, rg, ro, RATE_RTOL, tag),
+                      check_local=lambda e, lat, rg, ro, tag: assert_local_matches_ref(e, lat, rg, ro, RATE_RTOL, tag))
+        results = []
+        for op, tag in zip(script, lo.tags(script, f"L={L} slabs={n_slabs} {name}")):
+            results.append((op, tag, r.do(op, tag)))
+        return r, results, e.counters(), e.substep_info()
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("L,n_slabs,name", CASES2, ids=[f"L{L}-slabs{s}-{n}" for L, s, n in CASES2])
+def test_live_handle_second_vocabulary_vs_oracle(oracle_mod, L, n_slabs, name):
+    """The scripts over remelting, sub-stepped updates, the local loop and the timers.  T behind the sub-stepped updates compares
+    bit for bit (NaN against NaN) with the rest of the fields; cetkmc_remelt_info and cetkmc_substep_info are compared behind
+    every stepping call and every direct pass (Runner._verify_info); a refused call must have changed nothing."""
+    r, results, cnt, sub = _play2(oracle_mod, L, n_slabs, name)
+    for op, tag, ro in results:
+        if ro is None:
+            continue
+        want = ((20, 2) if "cut" in op else (r.paths[op["name"]]["n"] - 20, 0)) if name == "stopped" else (r.paths[op["name"]]["n"], 0)
+        assert (ro["done"], ro["status"]) == want, tag
+    assert cnt["deferred_steps"] + r.deferred_reset == r.deferred_expected, (cnt["deferred_steps"], r.deferred_reset, r.deferred_expected)
+    if n_slabs == 1 and name.startswith("pairs2:a_") and r.sub["updates"]:
+        # block 3 with 8 planes per block on a one-slab handle: the temporally blocked kernel ran (at L = 24 in three plane groups)
+        assert sub["blocked_launches"] > 0, sub
+    if n_slabs > 1:
+        assert sub["blocked_launches"] == 0, sub          # several in-process slabs always take the plain path
+        assert lo.REFUSED_SLABS in {f for _, f in r.refusals} or not any(op["name"].startswith(("remelt", "time_remelt", "set_remelt", "local"))
+                                                                         for op, _, _ in results)
+
+
+def test_live_handle_second_vocabulary_deferred_path_vs_oracle(oracle_mod):
+    """L = 136 on the deferring path: every new mutator, setting and option once.  With n = 5 and no option set the update takes
+    the default dispatch of the temporally blocked kernel (three sub-steps, then the remainder): blocked_launches proves it."""
+    L = 136
+    oracle_mod.set_threads(min(16, os.cpu_count() or 1))
+    try:
+        r, results, cnt, sub = _play2(oracle_mod, L, 1, "pairs2_deferred", paths=lo.deferred_paths())
+    finally:
+        oracle_mod.set_threads(1)
+    for op, tag, ro in results:
+        if ro is not None:
+            assert (ro["done"], ro["status"]) == (r.paths[op["name"]]["n"], 0), tag
+    assert cnt["deferred_steps"] == r.deferred_expected > 5, (cnt["deferred_steps"], r.deferred_expected)
+    assert cnt["incremental_steps"] == 0
+    assert sub["blocked_launches"] > 0 and sub["updates"] == r.sub["updates"] > 0, (sub, r.sub)
