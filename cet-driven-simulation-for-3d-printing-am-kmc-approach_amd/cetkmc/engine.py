@@ -134,6 +134,29 @@ def device_count():
     return n.value
 
 
+THERMAL_SCHEMES = {"explicit": 0, "implicit": 1}        # CETKMC_THERMAL_EXPLICIT / _IMPLICIT
+
+
+def _scheme_value(scheme, where="set_thermal_scheme"):
+    """a scheme by name ("explicit", "implicit") or by the library's integer value (which the library checks); anything else
+    is a ValueError naming the wrapper"""
+    if isinstance(scheme, str) and scheme in THERMAL_SCHEMES:
+        return THERMAL_SCHEMES[scheme]
+    if isinstance(scheme, (int, np.integer)) and not isinstance(scheme, bool):
+        return int(scheme)
+    raise ValueError(f"{where}: the scheme must be 'explicit', 'implicit' or a CETKMC_THERMAL_* value (got {scheme!r})")
+
+
+def implicit_coeffs(L, r):
+    """cetkmc_implicit_coeffs: (inv, p), the Thomas coefficients of (I - r D) along a line of L voxels (DESIGN.md section
+    26), computed on the host in double.  Needs no GPU."""
+    lib = _lib.load()
+    inv, p = np.zeros(max(int(L), 0)), np.zeros(max(int(L), 0))
+    if lib.cetkmc_implicit_coeffs(int(L), float(r), _dptr(inv), _dptr(p)):
+        raise ValueError("cetkmc: " + lib.cetkmc_last_error().decode(errors="replace"))
+    return inv, p
+
+
 class Engine:
     """Owns a cetkmc handle.  ``n_slabs>1`` splits the lattice into axis-0 slabs on the same
     GPU (decomposition check); ``rank/nranks/unique_id`` selects the one-process-per-GPU
@@ -697,6 +720,18 @@ class Engine:
         self._ck(self.lib.cetkmc_get_substep_info(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
 
+    # -- implicit temperature updates ---------------------------------------------
+    def set_thermal_scheme(self, scheme):
+        """cetkmc_set_thermal_scheme: "explicit" (the default) or "implicit" -- every temperature update becomes
+        ``thermal_substeps`` locally one-dimensional backward-Euler steps."""
+        self._ck(self.lib.cetkmc_set_thermal_scheme(self.h, _scheme_value(scheme, "Engine.set_thermal_scheme")))
+
+    def implicit_info(self):
+        """cetkmc_get_implicit_info: dict(updates, steps, launches, coeff_uploads), running totals of the implicit updates."""
+        info = _lib.ImplicitInfo()
+        self._ck(self.lib.cetkmc_get_implicit_info(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in _lib.ImplicitInfo._fields_}
+
     def time_thermal(self, n_updates, laser=False):
         """cetkmc_time_thermal: device ms of n_updates temperature updates (dt = 1e-6 s, one hipEvent pair).  The updates are
         real: afterwards the handle's field has advanced by ``n_updates`` updates (``laser``: with the plane of the last
@@ -859,6 +894,18 @@ class Ensemble:
         info = _lib.SubstepInfo()
         self._ck(self.lib.cetkmc_get_substep_info(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
+
+    # -- implicit temperature updates ---------------------------------------------
+    def set_thermal_scheme(self, scheme):
+        """cetkmc_ensemble_set_thermal_scheme: "explicit" (the default) or "implicit" -- every replica's temperature update in ``run`` becomes
+        ``thermal_substeps`` locally one-dimensional backward-Euler steps."""
+        self._ck(self.lib.cetkmc_ensemble_set_thermal_scheme(self.h, _scheme_value(scheme, "Ensemble.set_thermal_scheme")))
+
+    def implicit_info(self):
+        """cetkmc_get_implicit_info: dict(updates, steps, launches, coeff_uploads), running totals of the implicit updates."""
+        info = _lib.ImplicitInfo()
+        self._ck(self.lib.cetkmc_get_implicit_info(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in _lib.ImplicitInfo._fields_}
 
     def remelt_info(self):
         """cetkmc_ensemble_remelt_info: one dict(passes, n_melted, n_melted_last, n_appended) per replica."""

@@ -35,6 +35,7 @@
 #include "origin.hpp"
 #include "melt.hpp"
 #include "thermal_sub.hpp"
+#include "thermal_imp.hpp"
 
 using namespace cetkmc;
 
@@ -289,6 +290,11 @@ struct Handle {
     int substep_planes = 0;      // option "substep_planes": planes per block of k_thermal_sub; 0 = one round of blocks on the device
     int n_cu = 0;                // compute units of the device (read when first needed)
     cetkmc_substep_info sub_info{};
+    // implicit temperature updates (cetkmc_set_thermal_scheme, thermal_imp.hpp)
+    int thermal_scheme = CETKMC_THERMAL_EXPLICIT;
+    double* d_imp_coef = nullptr;        // [2][L]: inv, p of imp_r (allocated by the first implicit update)
+    double imp_r = 0.0;                  // the r the device table was built for (compared by bits)
+    cetkmc_implicit_info imp_info{};
 };
 
 // ---- cache state ------------------------------------------------------------------------------------
@@ -1204,9 +1210,83 @@ int launch_thermal_sub(Handle* h, double dt_s, int laser, const double* d_q, int
     return 0;
 }
 
-// a temperature update of the handle: thermal_substeps applications of the explicit step with dt / n
+// ---- implicit updates (thermal_imp.hpp) -------------------------------------------------------------
+// the Thomas coefficients of (I - r D) at edge L, in double, exactly as include/cetkmc.h states them
+int implicit_coeffs_host(const char* fn, int L, double r, double* inv, double* p)
+{
+    const std::string f(fn);
+    if (!inv || !p) return fail(f + ": null argument");
+    if (L < 1) return fail(f + ": L must be >= 1 (got " + std::to_string(L) + ")");
+    if (!std::isfinite(r)) return fail(f + ": r is not finite");
+    if (r < 0.0) return fail(f + ": r must be >= 0");
+    inv[0] = (L == 1) ? 1.0 : 1.0 / (1.0 + r);      // L = 1: D = 0, the solve is the identity
+    p[0] = r * inv[0];
+    for (int m = 1; m < L; ++m) {
+        const double beta = ((m < L - 1) ? (1.0 + 2.0 * r) : (1.0 + r)) - r * p[m - 1];
+        inv[m] = 1.0 / beta;
+        p[m] = r * inv[m];
+    }
+    return 0;
+}
+// the device table of the handle for this r: rebuilt when r changes (a handle's L never does)
+int imp_ensure_coeffs(Handle* h, double r)
+{
+    if (h->d_imp_coef && !memcmp(&h->imp_r, &r, sizeof r)) return 0;
+    std::vector<double> tab((size_t)2 * h->L);
+    CHK(implicit_coeffs_host("implicit update", h->L, r, tab.data(), tab.data() + h->L));
+    if (!h->d_imp_coef && hipMalloc((void**)&h->d_imp_coef, tab.size() * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_imp_coef = nullptr;
+        return fail("implicit update: no device memory for " + std::to_string(tab.size() * 8) + " bytes");
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));          // launches that read the table of the previous r
+    HIPCHK(hipMemcpy(h->d_imp_coef, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    h->imp_r = r;
+    ++h->imp_info.coeff_uploads;
+    return 0;
+}
+ImpCfg imp_cfg(const Handle* h, double dt_s, int laser, int use_latent, int scrub)
+{
+    ImpCfg C{};
+    C.r = (h->p.alpha * dt_s) * h->p.inv_dx2; C.dt = dt_s; C.dF = 1.0 / (dt_s > 1e-12 ? dt_s : 1e-12);
+    C.clip_lo = h->p.T_clip_lo; C.clip_hi = h->p.T_clip_hi; C.T_nan = h->p.T_nan; C.rho_cp = h->p.rho_cp; C.latent_coef = h->p.latent_coef;
+    C.coef = h->d_imp_coef; C.laser = laser; C.use_latent = use_latent; C.scrub = scrub;
+    return C;
+}
+dim3 imp_rows_grid(int L, int nloc, int R = 1) { return dim3((unsigned)(((int64_t)nloc * L + IMP_R - 1) / IMP_R), (unsigned)R); }
+dim3 imp_lines_grid(int L, int R = 1) { return dim3((unsigned)((L + 63) / 64), (unsigned)L, (unsigned)R); }
+// a temperature update of a one-slab handle in thermal_substeps implicit steps of dt / n: three launches each, one flip each
+int launch_thermal_imp(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+{
+    const int n = h->thermal_substeps, L = h->L;
+    const double dt_s = n > 1 ? dt / (double)n : dt;
+    CHK(imp_ensure_coeffs(h, (h->p.alpha * dt_s) * h->p.inv_dx2));
+    const StepState* ssp = batch ? h->d_ss : nullptr;
+    ++h->cnt.thermal_updates;
+    for (int q = 0; q < n; ++q) {
+        const bool first = q == 0;
+        const ImpCfg C = imp_cfg(h, dt_s, laser, first ? use_latent : 0, first ? scrub : 0);
+        const int nxt = h->cur ^ 1;
+        const SlabView v = view_of(h, 0);
+        launch(k_imp_rows<>, imp_rows_grid(L, v.nloc), dim3(IMP_R), 0, h->stream, nullptr, nullptr, v, (const double*)h->slabs[0].Tbuf[h->cur],
+               h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, C, ssp);
+        launch(k_imp_lines<1>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
+        launch(k_imp_lines<0>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
+        if (first && laser && use_latent)       // k_imp_rows has brought prev_state level with state on the flagged rows
+            hipLaunchKernelGGL(k_clear_row_flags, dim3(64), dim3(256), 0, h->stream, v, ssp);
+        HIPCHK(hipGetLastError());
+        h->cnt.alg_bytes_thermal += (int64_t)96 * v.nloc * L * L;      // three passes, each: read, y written, y read, x written
+        h->cur = nxt;
+    }
+    ++h->imp_info.updates; h->imp_info.steps += n; h->imp_info.launches += 3 * (int64_t)n;
+    invalidate(h, Cause::thermal_update);
+    return 0;
+}
+
+// a temperature update of the handle: thermal_substeps applications of the explicit step with dt / n, or as many implicit steps
 int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
 {
+    if (h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return launch_thermal_imp(h, dt, laser, d_q, use_latent, scrub, batch);
     const int n = h->thermal_substeps;
     if (n == 1) return launch_thermal_one(h, dt, laser, d_q, use_latent, scrub, batch);
     const double dt_s = dt / (double)n;
@@ -1407,7 +1487,8 @@ void destroy_impl(Handle* h)
     void* ptrs[] = {h->d_views[0], h->d_views[1], h->d_views[2], h->d_views[3], h->d_blocks, h->d_events_all, h->d_ss, h->d_dirty, h->d_pend, h->d_ktab, h->d_kp, h->d_scratch,
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
-                    h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq};
+                    h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq,
+                    h->d_imp_coef};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -1459,6 +1540,8 @@ struct Ens {
     int remelt_on = 0;
     int thermal_substeps = 1;            // cetkmc_ensemble_set_thermal_substeps: one n for all replicas
     cetkmc_substep_info sub_info{};
+    int thermal_scheme = CETKMC_THERMAL_EXPLICIT;      // cetkmc_ensemble_set_thermal_scheme: one scheme for all replicas
+    cetkmc_implicit_info imp_info{};
     double remelt_threshold = 0.0;
 };
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
@@ -1536,6 +1619,7 @@ int cetkmc_struct_size(const char* name)
     SZ("solid_info", struct cetkmc_solid_info); SZ("solid_args", struct cetkmc_solid_args); SZ("solid_rec", struct cetkmc_solid_rec);
     SZ("origin_rec", struct cetkmc_origin_rec); SZ("local_args", cetkmc_local_args);
     SZ("remelt_info", struct cetkmc_remelt_info); SZ("substep_info", struct cetkmc_substep_info);
+    SZ("implicit_info", struct cetkmc_implicit_info);
 #undef SZ
     return -1;
 }
@@ -1726,6 +1810,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
     if (!strcmp(key, "thermal_lookahead")) {
         if (value && h->remelt_on) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while remelting is on (the field computed ahead knows no melt)");
         if (value && h->thermal_substeps > 1) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while thermal_substeps > 1 (the field computed ahead is one explicit step)");
+        if (value && h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while the thermal scheme is implicit (the field computed ahead is one explicit step)");
         h->thermal_ahead = value ? 1 : 0;
         return 0;
     }
@@ -2420,6 +2505,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     if (h->remelt_on) return fail("cetkmc_run_supersteps is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
     if (h->thermal_substeps > 1) return fail("cetkmc_run_supersteps is refused while thermal_substeps > 1 (cetkmc_set_thermal_substeps): Mode B updates are not sub-stepped");
+    if (h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return fail("cetkmc_run_supersteps is refused while the thermal scheme is implicit (cetkmc_set_thermal_scheme): Mode B updates are explicit");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps needs a streaming sweep_variant (1 or 2)");
@@ -2519,6 +2605,7 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     if (h->remelt_on) return fail("cetkmc_run_supersteps_local is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
     if (h->thermal_substeps > 1) return fail("cetkmc_run_supersteps_local is refused while thermal_substeps > 1 (cetkmc_set_thermal_substeps): Mode B updates are not sub-stepped");
+    if (h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return fail("cetkmc_run_supersteps_local is refused while the thermal scheme is implicit (cetkmc_set_thermal_scheme): Mode B updates are explicit");
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (a->box != 8 || h->L % 8) return fail("cetkmc_run_supersteps_local: box must be 8 and divide L");
@@ -3084,6 +3171,13 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const int nsub = e->thermal_substeps;
     const double dt_s = nsub > 1 ? a->thermal_dt / (double)nsub : a->thermal_dt;
     const ThermalCfg tc0 = thermal_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), tc_sub = thermal_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
+    const bool implicit = e->thermal_scheme == CETKMC_THERMAL_IMPLICIT;
+    if (implicit && a->thermal_mode && updates_in(a->step0, n) > 0) {      // the coefficient table of replica 0 serves every replica
+        const int64_t before = h0->imp_info.coeff_uploads;
+        CHK(imp_ensure_coeffs(h0, (h0->p.alpha * dt_s) * h0->p.inv_dx2));
+        e->imp_info.coeff_uploads += h0->imp_info.coeff_uploads - before;
+    }
+    const ImpCfg ic0 = imp_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), ic_sub = imp_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
     const BatchCfg cfg0{};
     const dim3 g_flags((unsigned)std::min<int64_t>(((int64_t)(L + 4) * L + 255) / 256, 64), (unsigned)R);
     EnsSel sel{e->d_table, 0, (int)g_therm.z / R};
@@ -3100,17 +3194,30 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     for (int64_t s = 0; s < n; ++s) {
         const int64_t g = a->step0 + s;
         if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
-            launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc0, nullptr, sel);
-            // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
-            if (latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
-            sel.rel ^= 1;
-            ++flips;
-            for (int q = 1; q < nsub; ++q) {       // sub-steps 2..n: the plain path, no scrub, no latent term, same plane
-                launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc_sub, nullptr, sel);
+            if (implicit) {        // nsub implicit steps (thermal_imp.hpp): three launches and one flip each
+                for (int q = 0; q < nsub; ++q) {
+                    launch(k_imp_rows<EnsSel>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr,
+                           q == 0 ? ic0 : ic_sub, nullptr, sel);
+                    if (q == 0 && latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
+                    sel.rel ^= 1;
+                    ++flips;
+                    launch(k_imp_lines<1, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
+                    launch(k_imp_lines<0, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
+                }
+                ++e->imp_info.updates; e->imp_info.steps += nsub; e->imp_info.launches += 3 * (int64_t)nsub;
+            } else {
+                launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc0, nullptr, sel);
+                // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
+                if (latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
                 sel.rel ^= 1;
                 ++flips;
+                for (int q = 1; q < nsub; ++q) {       // sub-steps 2..n: the plain path, no scrub, no latent term, same plane
+                    launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc_sub, nullptr, sel);
+                    sel.rel ^= 1;
+                    ++flips;
+                }
+                if (nsub > 1) { ++e->sub_info.updates; e->sub_info.substeps += nsub; e->sub_info.launches += nsub; }
             }
-            if (nsub > 1) { ++e->sub_info.updates; e->sub_info.substeps += nsub; e->sub_info.launches += nsub; }
             sel.q_off += laser ? (int64_t)L2 : 0;
             if (e->remelt_on) {        // behind the update and its prev_state := state, in front of the table and the interface kernel
                 const SlabView& mv = e->table[0].view[0];
@@ -4215,5 +4322,49 @@ int cetkmc_time_thermal(void* handle, int laser, int n_updates, double* ms_total
     return add_elapsed(h->ev0, h->ev1, ms_total);
 }
 
+// ---- implicit temperature updates (thermal_imp.hpp) ------------------------------------------------
+static int scheme_known(const char* fn, int scheme)
+{
+    if (scheme != CETKMC_THERMAL_EXPLICIT && scheme != CETKMC_THERMAL_IMPLICIT)
+        return fail(std::string(fn) + ": unknown thermal scheme " + std::to_string(scheme) + " (CETKMC_THERMAL_EXPLICIT = 0, CETKMC_THERMAL_IMPLICIT = 1)");
+    return 0;
+}
+
+int cetkmc_set_thermal_scheme(void* handle, int scheme)
+{
+    if (!handle) return fail("null handle");
+    CHK(scheme_known("cetkmc_set_thermal_scheme", scheme));
+    if (ens_of(handle)) return fail("cetkmc_set_thermal_scheme: an ensemble handle is set by cetkmc_ensemble_set_thermal_scheme");
+    Handle* h = (Handle*)handle;
+    if (h->in_ensemble) return fail("cetkmc_set_thermal_scheme: the replicas of an ensemble share one scheme (cetkmc_ensemble_set_thermal_scheme)");
+    if (scheme == CETKMC_THERMAL_IMPLICIT) {
+        if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h))
+            return fail("cetkmc_set_thermal_scheme: the implicit scheme needs the whole lattice in one slab of one process (the solve along the plane axis crosses slabs)");
+        if (h->thermal_ahead) return fail("cetkmc_set_thermal_scheme: the implicit scheme is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
+    }
+    h->thermal_scheme = scheme;
+    return 0;
+}
+
+int cetkmc_ensemble_set_thermal_scheme(void* handle, int scheme)
+{
+    if (!handle) return fail("null argument");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("cetkmc_ensemble_set_thermal_scheme: not an ensemble handle (cetkmc_create_ensemble)");
+    CHK(scheme_known("cetkmc_ensemble_set_thermal_scheme", scheme));
+    e->thermal_scheme = scheme;
+    for (Handle* h : e->reps) h->thermal_scheme = scheme;      // a direct update on a replica handle follows the ensemble's scheme
+    return 0;
+}
+
+int cetkmc_get_implicit_info(void* handle, struct cetkmc_implicit_info* info)
+{
+    if (!handle || !info) return fail("null argument");
+    Ens* e = ens_of(handle);
+    *info = e ? e->imp_info : ((Handle*)handle)->imp_info;
+    return 0;
+}
+
+int cetkmc_implicit_coeffs(int L, double r, double* inv, double* p) { return implicit_coeffs_host("cetkmc_implicit_coeffs", L, r, inv, p); }
 
 }  // extern "C"

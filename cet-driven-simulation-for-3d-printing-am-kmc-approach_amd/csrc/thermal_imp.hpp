@@ -1,0 +1,259 @@
+// thermal_imp.hpp -- implicit temperature update: locally one-dimensional backward Euler (not in the
+// reference).
+//
+// One implicit step of length dt:  b = scrub(T) + dt * (qterm + latent_coef * dF)  per voxel, then (I - r D) x = b along
+// every line of axis 2 (k), of axis 1 (j) and of axis 0 (i), in that order, r = (alpha dt) / dx^2, D the 1-D second difference
+// with the lattice edge replicated; the clip follows the third solve.  Each solve is the Thomas algorithm with the coefficient
+// table inv[m], p[m] = r inv[m] the host computed in double (cetkmc_implicit_coeffs):
+//   forward   y[0] = b[0] inv[0],   y[m] = (b[m] + r y[m - 1]) inv[m]
+//   backward  x[L - 1] = y[L - 1],  x[m] = y[m] + p[m] x[m + 1]
+// Multiplies and adds only, under -ffp-contract=off, one line strictly in order: the same bits as a sequential restatement.
+// (The right-hand side keeps thermal_voxel()'s one division, qv / rho_cp, where the source plane is not zero.)
+//
+// Three launches per implicit step, each variadic in a trailing EnsSel (the replica rides in a grid dimension):
+//
+// k_imp_rows    right-hand side and k solve; reads the current buffer, writes the other.  Lines along k are contiguous, so a
+//               one-wave block owns IMP_R = 64 consecutive rows and moves them in chunks of IMP_C = 64 columns through an LDS
+//               tile of pitch 65 doubles: global access with the lanes along k (IMP_V row segments of 512 B in flight), LDS access
+//               transposed for the sweep, where lane t owns row t (65 doubles = 130 banks of 4 B: a half-wave's 8-byte reads fall
+//               on all 64 banks).  The forward sweep writes y, the backward sweep reads it back chunk by chunk in reverse; the
+//               last chunk of the forward sweep is still in LDS when the backward sweep begins.
+//               Bytes per voxel: 8 read + 8 (y) + 8 (y again) + 8 (x) = 32, less 16 for the chunk that stays in LDS (L <= 64: 16).
+// k_imp_lines   <1>: the j solve, <0>: the i solve and the clip; in place.  A thread owns one line, the lanes run along k, so
+//               every access is a row segment.  The element index m is wave-uniform: inv[m] and p[m] are uniform loads.  The
+//               dependent chain is three fp64 operations per element; the loads do not depend on it and are issued IMP_U
+//               elements ahead (two register sets of IMP_U).  Forward writes y, backward reads it back: 32 B per voxel.
+//
+// 96 B per voxel and implicit step before cache hits (92 at L = 256: one chunk in four of k_imp_rows stays in LDS; 80 up to L = 64).
+// Behind an early stop of the batch (status != 0) k_imp_rows copies the field and k_imp_lines returns.
+#pragma once
+#include "kernels.hpp"
+
+namespace cetkmc {
+
+struct ImpCfg {
+    double r, dt, dF;            // dF: 1 / max(dt, 1e-12), the latent-heat indicator's rate (thermal_voxel), divided on the host
+    double clip_lo, clip_hi, T_nan, rho_cp, latent_coef;
+    const double* coef;          // [2][L]: inv, p
+    int laser, use_latent, scrub;
+};
+constexpr int IMP_R = 64, IMP_C = 64, IMP_PITCH = IMP_C + 1, IMP_U = 8, IMP_V = 16;   // IMP_V: rows of a chunk in flight per lane (k_imp_rows)
+
+// the scrub of this scheme: NaN -> T_nan, +-inf -> the clip values (not +-DBL_MAX, which a solve would spread over the lattice)
+__device__ __forceinline__ double imp_scrub(double x, const ImpCfg& C)
+{
+    if (!C.scrub) return x;
+    if (x != x) return C.T_nan;
+    if (__builtin_isinf(x)) return x > 0 ? C.clip_hi : C.clip_lo;
+    return x;
+}
+
+// grid: x = blocks of IMP_R rows of the owned planes, y = replica
+template <class... E>
+__global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __restrict__ Tin, double* Tout, uint8_t* __restrict__ prev_state,
+                                                    const double* __restrict__ q_top, ImpCfg C, const StepState* __restrict__ ss, E... ens)
+{
+    if constexpr (sizeof...(E) > 0) {
+        const auto& e = ens_rep(blockIdx.y, ens...);
+        const int rel = ens_rel(ens...);
+        S = e.view[rel]; Tin = e.view[rel].T; Tout = e.view[rel ^ 1].T; prev_state = e.prev; ss = e.ss;
+        q_top = C.laser ? e.q + ens_q_off(ens...) : nullptr;
+    }
+    __shared__ double tile[IMP_R * IMP_PITCH];
+    const int L = S.L, lane = threadIdx.x;
+    const int64_t nrows = (int64_t)S.nloc * L, row0 = (int64_t)blockIdx.x * IMP_R;
+    const int nr = (int)min((int64_t)IMP_R, nrows - row0);          // rows of this block (uniform)
+    const int64_t base = ((int64_t)2 * L + row0) * S.pitchT;         // T index of (row0, k = 0): local plane = owned plane + 2
+    const int pitch = S.pitchT;
+    if (ss && ss->status) {                     // a terminated batch: the update is a copy
+        for (int kc = 0; kc < L; kc += IMP_C) {
+            const int k = kc + lane;
+            if (k < L)
+                for (int q = 0; q < nr; ++q) { const int64_t c = base + (int64_t)q * pitch + k; Tout[c] = Tin[c]; }
+        }
+        return;
+    }
+    const double* __restrict__ inv = C.coef;
+    const double* __restrict__ pc = C.coef + L;
+    const double r = C.r;
+    const bool source = C.laser != 0, latent = source && C.use_latent;
+    double* mine = tile + lane * IMP_PITCH;     // the row this lane sweeps
+    const int nchunk = (L + IMP_C - 1) / IMP_C;
+    // Rows whose right-hand side needs more than the field: those of plane L - 1 (the source) and those written since the last
+    // update (latent heat), one bit per row of the block.  Every other voxel of a laser-mode update gets thermal_voxel()'s
+    // terms with qterm = dF = 0, which is + 0.0 for finite settings (it turns a -0.0 into +0.0, as the definition does).
+    unsigned long long need = 0;
+    double zero_term = 0.0;
+    if (source) {
+        zero_term = C.dt * (0.0 + C.latent_coef * 0.0);
+        bool nd = false;
+        if (lane < nr) {
+            const int64_t row = row0 + lane;
+            const int lp = (int)(row / L), j = (int)(row - (int64_t)lp * L);
+            nd = (S.gi0 + lp == L - 1) || (latent && S.row_chg[(int64_t)(lp + 2) * L + j]);
+        }
+        need = __ballot(nd);
+    }
+    // global <-> tile, the lanes along k.  A load clamps its row and column into the block (no predicates: what lands in the
+    // tile beyond the block's rows and the lattice's columns is never swept into a stored value); a store is predicated.
+    auto load_rows = [&](const double* __restrict__ g, int kc, int q0, double (&v)[IMP_V]) {
+        const double* p = g + base + min(kc + lane, L - 1);
+#pragma unroll
+        for (int u = 0; u < IMP_V; ++u) v[u] = p[min(q0 + u, nr - 1) * pitch];
+    };
+    auto store_chunk = [&](int kc) {
+        if (kc + lane < L) {
+            double* p = Tout + base + kc + lane;
+#pragma unroll 8
+            for (int q = 0; q < nr; ++q) p[q * pitch] = tile[q * IMP_PITCH + lane];
+        }
+    };
+    // ---- forward: right-hand side in, y out ----
+    double y = 0.0;
+#pragma unroll 1
+    for (int ch = 0; ch < nchunk; ++ch) {
+        const int kc = ch * IMP_C, k = kc + lane, cn = min(IMP_C, L - kc);
+#pragma unroll 1
+        for (int q0 = 0; q0 < IMP_R; q0 += IMP_V) {
+            double v[IMP_V];
+            load_rows(Tin, kc, q0, v);
+#pragma unroll
+            for (int u = 0; u < IMP_V; ++u) {
+                double b = imp_scrub(v[u], C);
+                if (source && !((need >> (q0 + u)) & 1ull)) b = b + zero_term;
+                tile[(q0 + u) * IMP_PITCH + lane] = b;
+            }
+        }
+        if (k < L) {                // the rows with a source or a flag: thermal_voxel()'s terms in full (a lane's own tile entries)
+            unsigned long long w = need;
+#pragma unroll 1
+            while (w) {
+                const int q = __ffsll(w) - 1;
+                w &= w - 1;
+                const int64_t row = row0 + q;
+                const int lp = (int)(row / L), j = (int)(row - (int64_t)lp * L), li = lp + 2;
+                const double qv = (S.gi0 + lp == L - 1) ? q_top[(int64_t)j * L + k] : 0.0;
+                const double qterm = (qv != 0.0) ? qv / C.rho_cp : 0.0;
+                double dF = 0.0;
+                if (latent && S.row_chg[(int64_t)li * L + j]) {      // only rows written since the last update can differ
+                    const int64_t sc = S.sidx(li, j, k);
+                    const int st = S.state[sc], pv = prev_state[sc];
+                    if (pv == 0 && st != 0) dF = C.dF;
+                    if (pv != st) prev_state[sc] = (uint8_t)st;
+                }
+                tile[q * IMP_PITCH + lane] = tile[q * IMP_PITCH + lane] + C.dt * (qterm + C.latent_coef * dF);
+            }
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int c = 0; c < cn; ++c) {
+            const int m = kc + c;
+            const double b = mine[c];
+            const double a = (m == 0) ? b : b + r * y;
+            y = a * inv[m];
+            mine[c] = y;
+        }
+        __syncthreads();
+        if (ch + 1 < nchunk) {                  // (the last chunk stays in LDS for the backward sweep)
+            store_chunk(kc);
+            __syncthreads();
+        }
+    }
+    // ---- backward: y in, x out ----
+    double x = 0.0;
+#pragma unroll 1
+    for (int ch = nchunk - 1; ch >= 0; --ch) {
+        const int kc = ch * IMP_C, cn = min(IMP_C, L - kc);
+        if (ch + 1 < nchunk) {
+#pragma unroll 1
+            for (int q0 = 0; q0 < IMP_R; q0 += IMP_V) {
+                double v[IMP_V];
+                load_rows(Tout, kc, q0, v);
+#pragma unroll
+                for (int u = 0; u < IMP_V; ++u) tile[(q0 + u) * IMP_PITCH + lane] = v[u];
+            }
+            __syncthreads();
+        }
+#pragma unroll 8
+        for (int c = cn - 1; c >= 0; --c) {
+            const int m = kc + c;
+            const double yv = mine[c];
+            x = (m == L - 1) ? yv : yv + pc[m] * x;
+            mine[c] = x;
+        }
+        __syncthreads();
+        store_chunk(kc);
+        __syncthreads();
+    }
+}
+
+// AXIS 1: lines along j, grid y = owned plane; AXIS 0: lines along i (the whole lattice in one slab), grid y = j, and the clip.
+// grid: x = segments of 64 k, z = replica
+template <int AXIS, class... E>
+__global__ __launch_bounds__(64) void k_imp_lines(SlabView S, double* T, ImpCfg C, const StepState* __restrict__ ss, E... ens)
+{
+    if constexpr (sizeof...(E) > 0) {
+        const auto& e = ens_rep(blockIdx.z, ens...);
+        S = e.view[ens_rel(ens...)]; T = S.T; ss = e.ss;
+    }
+    if (ss && ss->status) return;
+    const int L = S.L, k = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (k >= L) return;
+    const int64_t plane = (int64_t)L * S.pitchT;
+    const int64_t ls = AXIS == 1 ? (int64_t)S.pitchT : plane;                            // from element m to m + 1 of the line
+    double* p0 = T + 2 * plane + (int64_t)blockIdx.y * (AXIS == 1 ? plane : (int64_t)S.pitchT) + k;
+    const double* __restrict__ inv = C.coef;
+    const double* __restrict__ pc = C.coef + L;
+    const double r = C.r;
+    auto clip = [&](double v) {
+        if constexpr (AXIS == 0) { v = v < C.clip_lo ? C.clip_lo : v; v = v > C.clip_hi ? C.clip_hi : v; }
+        return v;
+    };
+    double cur[IMP_U], nxt[IMP_U];
+    // ---- forward ----
+    double y = p0[0] * inv[0];
+    if (L > 1) p0[0] = y;
+    auto load_up = [&](int m0, double (&d)[IMP_U]) {
+#pragma unroll
+        for (int u = 0; u < IMP_U; ++u) d[u] = (m0 + u < L) ? p0[(int64_t)(m0 + u) * ls] : 0.0;
+    };
+    load_up(1, cur);
+#pragma unroll 1
+    for (int m0 = 1; m0 < L; m0 += IMP_U) {
+        load_up(m0 + IMP_U, nxt);
+#pragma unroll
+        for (int u = 0; u < IMP_U; ++u) {
+            const int m = m0 + u;
+            if (m < L) {
+                y = (cur[u] + r * y) * inv[m];
+                if (m < L - 1) p0[(int64_t)m * ls] = y;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < IMP_U; ++u) cur[u] = nxt[u];
+    }
+    // ---- backward: x[L - 1] = y[L - 1] is in the register ----
+    double x = y;
+    p0[(int64_t)(L - 1) * ls] = clip(x);
+    auto load_down = [&](int m0, double (&d)[IMP_U]) {
+#pragma unroll
+        for (int u = 0; u < IMP_U; ++u) d[u] = (m0 - u >= 0) ? p0[(int64_t)(m0 - u) * ls] : 0.0;
+    };
+    load_down(L - 2, cur);
+#pragma unroll 1
+    for (int m0 = L - 2; m0 >= 0; m0 -= IMP_U) {
+        load_down(m0 - IMP_U, nxt);
+#pragma unroll
+        for (int u = 0; u < IMP_U; ++u) {
+            const int m = m0 - u;
+            if (m >= 0) {
+                x = cur[u] + pc[m] * x;
+                p0[(int64_t)m * ls] = clip(x);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < IMP_U; ++u) cur[u] = nxt[u];
+    }
+}
+
+}  // namespace cetkmc

@@ -9,7 +9,7 @@ collects the CET classification of the last metrics row of every run into ``outp
     python gv_sweep.py [--L 30] [--steps 2000] [--temps 2800 3100 3400] [--nu-dep 2e12 2e13 2e14] [--carbon 0.2]
                        [--mode B --box 8 [--local-events K --local-horizon X]] [--seeds K] [--ensemble [--rng counter]]
                        [--laser-power P1,P2,... --scan-speed V1,V2,... [--laser-start J0]] [--front] [--layers] [--texture]
-                       [--grains] [--solid] [--origin] [--remelt [T]] [--thermal-substeps N|stable]
+                       [--grains] [--solid] [--origin] [--remelt [T]] [--thermal-substeps N|stable] [--thermal-scheme implicit]
 
 ``--seeds K`` runs every point with the seeds RANDOM_SEED .. RANDOM_SEED + K - 1 (one gv_map.csv row per point and seed, with
 a ``seed`` column when K > 1); ``--ensemble`` runs all of them as one replica ensemble (run_kmc_ensemble): with the default
@@ -84,8 +84,9 @@ def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_p
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
              laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, texture=False,
-             grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1, **run_kw):
+             grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1, thermal_scheme="explicit", **run_kw):
     """``thermal_substeps`` (N or "stable"): every run with run_kmc's option of that name (mode "A"; one value for an ensemble).
+    ``thermal_scheme`` ("explicit" or "implicit"): likewise.
     ``remelt`` (True or a threshold temperature): every run with run_kmc's ``remelt`` option (mode "A"; in an ensemble the
     shared ``remelt`` key of the configs).  ``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
     engine (same metrics.csv columns; n_steps stays the number of executed events).  ``seeds=K`` runs every point with the
@@ -120,7 +121,8 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
     opt = dict(**({"front_metrics": True} if front else {}), **({"layer_metrics": True} if layers else {}),
                **({"texture_metrics": True} if texture else {}), **({"grain_metrics": True} if grains else {}),
                **({"solid_metrics": True} if solid else {}), **({"origin_metrics": True} if origin else {}),
-               **({"thermal_substeps": thermal_substeps} if thermal_substeps != 1 else {}))
+               **({"thermal_substeps": thermal_substeps} if thermal_substeps != 1 else {}),
+               **({"thermal_scheme": thermal_scheme} if thermal_scheme != "explicit" else {}))
     if ensemble:
         run_kmc_ensemble(cfg, L, n_steps, rng=rng, **opt)
     else:
@@ -198,6 +200,9 @@ if __name__ == "__main__":
     ap.add_argument("--thermal-substeps", type=lambda s: s if s == "stable" else int(s), default=1, metavar="N|stable",
                     help="every temperature update as N explicit steps of dt / N on the device ('stable': the smallest stable N, 17; "
                          "run_kmc thermal_substeps, mode A)")
+    ap.add_argument("--thermal-scheme", choices=("explicit", "implicit"), default="explicit",
+                    help="every temperature update as locally one-dimensional backward-Euler steps on the device, stable at any dt "
+                         "(run_kmc thermal_scheme, mode A)")
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
@@ -208,4 +213,4 @@ if __name__ == "__main__":
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
                    layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt,
-                   thermal_substeps=a.thermal_substeps, **kw).to_string(index=False))
+                   thermal_substeps=a.thermal_substeps, thermal_scheme=a.thermal_scheme, **kw).to_string(index=False))

@@ -270,6 +270,19 @@ def _check_substeps(n_sub, mode_a, thermal_updates):
         raise ValueError("thermal_substeps needs thermal_updates=True (there is no update to split)")
 
 
+def _check_scheme(scheme, mode_a, thermal_updates, where="thermal_scheme", needs="mode 'A' (the super-step engine's updates are explicit)"):
+    """what run_kmc and run_kmc_ensemble refuse of thermal_scheme (before any device call); ``needs``: what ``mode_a`` stands
+    for in the caller's terms"""
+    if scheme not in ("explicit", "implicit"):
+        raise ValueError(f"{where} must be 'explicit' or 'implicit' (got {scheme!r})")
+    if scheme == "explicit":
+        return
+    if not mode_a:
+        raise ValueError(f"thermal_scheme='implicit' needs {needs}")
+    if not thermal_updates:
+        raise ValueError("thermal_scheme='implicit' needs thermal_updates=True (there is no update to make implicit)")
+
+
 def _check_remelt(thr, mode_a, origin_metrics, thermal_updates):
     if thr is None:
         return
@@ -382,6 +395,7 @@ def run_kmc(
     origin_metrics: bool = False,
     remelt=False,
     thermal_substeps=1,
+    thermal_scheme="explicit",
     local_events: int = 0,
     local_horizon: float = 1.0,
 ):
@@ -498,10 +512,17 @@ def run_kmc(
     (cetkmc_set_thermal_substeps) -- the reference's single step is 16 times too long for the
     explicit scheme and turns a rough field into noise between the clip values.  ``last_run_info["thermal_substeps"]``
     reports n.  Checkpoints carry the value only when it is not 1, and a resumed run must ask for the same.  Refused with
+    ValueError: ``mode="B"``, ``thermal_updates=False``.
+
+    ``thermal_scheme="implicit"`` (mode "A" only, with or without ``laser``, ``remelt`` and ``thermal_substeps``): every
+    temperature update is ``thermal_substeps`` locally one-dimensional backward-Euler steps on the device
+    (cetkmc_set_thermal_scheme), stable at any dt.  ``last_run_info["thermal_scheme"]`` reports it.
+    Checkpoints carry the value only when it is not "explicit", and a resumed run must ask for the same.  Refused with
     ValueError: ``mode="B"``, ``thermal_updates=False``."""
     import cetkmc
     n_sub = _thermal_substeps(thermal_substeps)
     _check_substeps(n_sub, mode == "A", thermal_updates)
+    _check_scheme(thermal_scheme, mode == "A", thermal_updates)
     remelt_thr = _remelt_threshold(remelt)
     _check_remelt(remelt_thr, mode == "A", origin_metrics, thermal_updates)
     _check_solid(solid_metrics, solid_every, bool(checkpoint_every or resume_from))
@@ -563,6 +584,12 @@ def run_kmc(
                          f"this call asks for {n_sub}")
     if n_sub != 1:
         engine.set_thermal_substeps(n_sub)
+    if ckpt and ckpt["extra"].get("thermal_scheme", "explicit") != thermal_scheme:
+        engine.close()
+        raise ValueError(f"checkpoint was written by a run with thermal_scheme={ckpt['extra'].get('thermal_scheme', 'explicit')!r}, "
+                         f"this call asks for {thermal_scheme!r}")
+    if thermal_scheme != "explicit":
+        engine.set_thermal_scheme(thermal_scheme)
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -631,6 +658,8 @@ def run_kmc(
             extra = dict(extra or {}, remelt=remelt_thr, remelt_passes=remelt_off[0] + info["passes"], remelted=remelt_off[1] + info["n_melted"])
         if n_sub != 1:                   # (likewise)
             extra = dict(extra or {}, thermal_substeps=n_sub)
+        if thermal_scheme != "explicit": # (likewise)
+            extra = dict(extra or {}, thermal_scheme=thermal_scheme)
         save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
                         engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
                         at, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected, extra=extra)
@@ -764,7 +793,8 @@ def run_kmc(
     remelted = remelt_off[1] + engine.remelt_info()["n_melted"] if remelt_thr is not None else None
     engine.close()
     last_run_info.clear()
-    last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1, thermal_substeps=n_sub)
+    last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1, thermal_substeps=n_sub,
+                         thermal_scheme=thermal_scheme)
     if remelt_thr is not None:
         last_run_info.update(remelted=remelted)
     if local_events:
@@ -865,7 +895,7 @@ def _replica_prefix(cfg, L):
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
                      front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False, solid_metrics=False,
-                     solid_every=20, origin_metrics=False, thermal_substeps=1):
+                     solid_every=20, origin_metrics=False, thermal_substeps=1, thermal_scheme="explicit"):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -894,10 +924,14 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     ``origin_grains.csv`` of every replica): every cetkmc_run_ensemble call folds the replicas' executed events into their
     origin maps in one launch, and every metrics row takes ONE batched cetkmc_ensemble_origin_profile and census.
     ``thermal_substeps``: run_kmc's option of that name, one value for all replicas (cetkmc_ensemble_set_thermal_substeps);
-    ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_substeps"]``."""
+    ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_substeps"]``.
+    ``thermal_scheme``: run_kmc's option of that name, one value for all replicas (cetkmc_ensemble_set_thermal_scheme);
+    ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_scheme"]``."""
     import cetkmc
     n_sub = _thermal_substeps(thermal_substeps)
     _check_substeps(n_sub, rng == "reference", thermal_updates)
+    _check_scheme(thermal_scheme, rng == "reference", thermal_updates,
+                  needs="rng='reference' (the counter mode steps through the super-step engine, whose updates are explicit)")
     _check_solid(solid_metrics, solid_every, False)
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates, origin_metrics)
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
@@ -947,6 +981,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             ens.set_remelt(True, remelt_thr)
         if n_sub != 1:
             ens.set_thermal_substeps(n_sub)
+        if thermal_scheme != "explicit":
+            ens.set_thermal_scheme(thermal_scheme)
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -1094,7 +1130,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))
             last_ensemble_info.append(dict(random_state=gens[r].py, np_state=gens[r].np, executed_events=last_step[r] + 1,
                                            min_margin=min_margin[r] if rng == "reference" else None,
-                                           thermal_substeps=n_sub,
+                                           thermal_substeps=n_sub, thermal_scheme=thermal_scheme,
                                            **({"remelted": ri[r]["n_melted"]} if ri is not None else {})))
             print(f"[{c['output_prefix']}] completed {last_step[r] + 1} steps in {total_time[r]:.2e} s")
         return out

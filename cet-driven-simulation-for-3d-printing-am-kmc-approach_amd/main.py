@@ -14,6 +14,7 @@ outside the accelerated path and are not part of this package.
     python main.py --solid                        # solidification columns in every metrics.csv and a solid_layers.csv per level (run_kmc solid_metrics)
     python main.py --remelt [T]                   # remelting on the device: solid at or above T_MELT (or T) turns liquid (run_kmc remelt)
     python main.py --thermal-substeps N|stable    # sub-stepped temperature updates (run_kmc thermal_substeps; 'stable' = 17)
+    python main.py --thermal-scheme implicit      # implicit temperature updates (run_kmc thermal_scheme)
     python main.py --origin                       # origin columns in every metrics.csv and an origin_layers.csv per level (run_kmc origin_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
@@ -52,7 +53,7 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
          layers=False, texture=False, grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1,
-         **run_kw):
+         thermal_scheme="explicit", **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     rm = {"remelt": remelt} if remelt is not False and remelt is not None else {}      # --remelt: run_kmc's option / config key
     print("Starting KMC simulation for microstructure control...")
@@ -62,6 +63,8 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
     fm = {"front_metrics": True} if front else {}     # --front: measured front columns in every metrics.csv (run_kmc)
     if thermal_substeps != 1:                         # --thermal-substeps: run_kmc's / run_kmc_ensemble's option of that name
         fm["thermal_substeps"] = thermal_substeps
+    if thermal_scheme != "explicit":                  # --thermal-scheme: run_kmc's / run_kmc_ensemble's option of that name
+        fm["thermal_scheme"] = thermal_scheme
     if layers:                                        # --layers: layer columns and layers.csv (run_kmc layer_metrics)
         fm["layer_metrics"] = True
     if texture:                                       # --texture: texture columns and texture.csv (run_kmc texture_metrics)
@@ -151,6 +154,9 @@ if __name__ == "__main__":
     ap.add_argument("--thermal-substeps", type=lambda s: s if s == "stable" else int(s), default=1, metavar="N|stable",
                     help="every temperature update as N explicit steps of dt / N on the device ('stable': the smallest stable N, 17; "
                          "run_kmc thermal_substeps, mode A)")
+    ap.add_argument("--thermal-scheme", choices=("explicit", "implicit"), default="explicit",
+                    help="every temperature update as locally one-dimensional backward-Euler steps on the device, stable at any dt "
+                         "(run_kmc thermal_scheme, mode A)")
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
@@ -159,4 +165,5 @@ if __name__ == "__main__":
     if a.local_events:
         kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
-         grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt, thermal_substeps=a.thermal_substeps, **kw)
+         grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt, thermal_substeps=a.thermal_substeps,
+         thermal_scheme=a.thermal_scheme, **kw)

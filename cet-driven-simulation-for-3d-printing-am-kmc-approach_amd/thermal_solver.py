@@ -100,6 +100,15 @@ def _check_substeps(substeps):
     return int(substeps)
 
 
+THERMAL_SCHEMES = ("explicit", "implicit")
+
+
+def _check_scheme(scheme, where="scheme"):
+    if scheme not in THERMAL_SCHEMES:
+        raise ValueError(f"{where} must be 'explicit' or 'implicit' (got {scheme!r})")
+    return scheme
+
+
 def laser_scan_planes(L, laser, first_step, n_steps):
     """Source planes (n, L, L) of the temperature updates that fall in the global steps [first_step, first_step + n_steps):
     one per step g with g % 20 == 0, in step order.  ``laser`` is a dict: ``power`` [W], ``start`` (beam centre at update
@@ -120,36 +129,45 @@ def laser_scan_planes(L, laser, first_step, n_steps):
 
 
 def update_temperature(T, state, prev_state, dt, laser_pos, laser_power,
-                       beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, substeps=1):
+                       beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, substeps=1, scheme="explicit"):
     """Explicit Euler step with Laplacian + Gaussian surface source on i=L-1 + latent heat where
     ``prev_state==0 & state!=0``; clipped to [T_SUB, 1.1*T_MELT] (thermal_solver.py:36-105).  ``substeps=n`` (not in the
-    reference): n such steps of dt / n from the same source, the latent heat in the first (``stable_substeps``)."""
+    reference): n such steps of dt / n from the same source, the latent heat in the first (``stable_substeps``).
+    ``scheme="implicit"`` (not in the reference): the steps are locally one-dimensional backward-Euler steps, stable at any dt
+    (DESIGN.md section 26)."""
     L = T.shape[0]
     assert T.shape == (L, L, L)
     assert state.shape == T.shape and prev_state.shape == T.shape
     substeps = _check_substeps(substeps)
+    _check_scheme(scheme)
     eng = _engine(L)
     eng.upload(state=state, T=T)
     eng.set_prev_state(prev_state)
     eng.set_thermal_substeps(substeps)
     try:
+        eng.set_thermal_scheme(scheme)
         eng.thermal_laser(dt, laser_source_plane(L, laser_pos, laser_power, beam_radius, absorptivity),
                           use_latent=True, scrub_nan=False)
     finally:
         eng.set_thermal_substeps(1)        # the handle is cached
+        eng.set_thermal_scheme("explicit")
     return eng.download(state=False, theta=False, phi=False, T=True)["T"]
 
 
-def update_temperature_cet(T, state, dt=1e-6, substeps=1):
+def update_temperature_cet(T, state, dt=1e-6, substeps=1, scheme="explicit"):
     """Diffusion-only step used by run_kmc; ``state`` is unused, as in the reference
-    (thermal_solver.py:107-117).  ``substeps=n`` (not in the reference): n such steps of dt / n."""
+    (thermal_solver.py:107-117).  ``substeps=n`` (not in the reference): n such steps of dt / n; ``scheme="implicit"`` (not in
+    the reference): implicit steps."""
     L = T.shape[0]
     substeps = _check_substeps(substeps)
+    _check_scheme(scheme)
     eng = _engine(L)
     eng.upload(T=T)
     eng.set_thermal_substeps(substeps)
     try:
+        eng.set_thermal_scheme(scheme)
         eng.thermal_cet(dt, scrub_nan=False)
     finally:
         eng.set_thermal_substeps(1)
+        eng.set_thermal_scheme("explicit")
     return eng.download(state=False, theta=False, phi=False, T=True)["T"]

@@ -109,7 +109,7 @@ typedef struct cetkmc_run_args {
                                  defects-only one included) or direct temperature update (cetkmc_thermal_cet, _thermal_laser,
                                  the updates of cetkmc_time_thermal): after either, a call starting at that step applies
                                  the update like any other (CETKMC_CACHE_APPLIED).  Everything else leaves the marker --
-                                 cetkmc_remelt, cetkmc_set_remelt, cetkmc_set_thermal_substeps, cetkmc_set_params,
+                                 cetkmc_remelt, cetkmc_set_remelt, cetkmc_set_thermal_substeps, cetkmc_set_thermal_scheme, cetkmc_set_params,
                                  cetkmc_time_sweeps, the read-only calls: behind them the continuation still skips that
                                  step's update (and its melt pass, whatever the switches say by then) */
     int64_t n_q;
@@ -205,7 +205,7 @@ int cetkmc_abi_version(void);
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
- * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info", "implicit_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -896,6 +896,40 @@ int cetkmc_set_thermal_substeps(void* handle, int n);
 int cetkmc_ensemble_set_thermal_substeps(void* handle, int n);
 int cetkmc_get_substep_info(void* handle, struct cetkmc_substep_info* info);
 int cetkmc_time_thermal(void* handle, int laser, int n_updates, double* ms_total);
+
+/* ---- implicit temperature updates ------------------------------------------------------------------
+ * An opt-in, unconditionally stable scheme for EVERY temperature update the handle performs (the direct calls, the cadence
+ * updates of cetkmc_run_steps and cetkmc_run_ensemble, cetkmc_time_thermal): a locally one-dimensional backward-Euler step.
+ * With the scheme CETKMC_THERMAL_EXPLICIT (the default) nothing changes.  One implicit step of length dt:
+ *   1. b = tc + dt * (qterm + latent_coef * dF) per voxel, thermal_voxel()'s terms without the Laplacian; tc = scrub(T), where
+ *      the scrub of this scheme maps NaN -> T_nan, +inf -> T_clip_hi, -inf -> T_clip_lo and leaves finite values alone;
+ *   2. (I - r D) x = b along every line of axis 2, then of axis 1, then of axis 0; r = (alpha * dt) * inv_dx2; D the 1-D second
+ *      difference with the lattice edge replicated (diagonal 1 + r at both ends, 1 + 2 r inside, off-diagonals -r; L = 1: the
+ *      identity).  Thomas algorithm with the coefficients of cetkmc_implicit_coeffs:
+ *        inv[0] = 1 / (1 + r) (L = 1: 1), p[0] = r * inv[0];  beta = ((m < L - 1) ? (1 + 2 r) : (1 + r)) - r * p[m - 1],
+ *        inv[m] = 1 / beta, p[m] = r * inv[m];
+ *        y[0] = b[0] * inv[0], y[m] = (b[m] + r * y[m - 1]) * inv[m];  x[L - 1] = y[L - 1], x[m] = y[m] + p[m] * x[m + 1];
+ *   3. the clip to [T_clip_lo, T_clip_hi], once, after the third solve;
+ *   4. with the latent term on: prev_state := state, row flags cleared.
+ * thermal_substeps = n composes: an update is n implicit steps of dt / n; step 1 carries the scrub and the latent term, all
+ * use the same source plane; one update consumes one plane, counts once, and is applied or skipped as a whole.
+ *   cetkmc_set_thermal_scheme            a single handle; leaves every cache and the applied-update marker alone
+ *   cetkmc_ensemble_set_thermal_scheme   an ensemble handle: one scheme for all replicas
+ *   cetkmc_get_implicit_info             running totals: implicit updates, their steps, their kernel launches (three per step:
+ *                      k_imp_rows, k_imp_lines<1>, k_imp_lines<0>, thermal_imp.hpp), and rebuilds of the device's coefficient
+ *                      table (one per change of r).  cetkmc_substep_info counts explicit updates only.
+ *   cetkmc_implicit_coeffs               the host routine that fills the table; needs no device.  Refuses L < 1, a non-finite r
+ *                      and r < 0.
+ * Refused, before anything is allocated or launched: an unknown scheme; cetkmc_set_thermal_scheme on an ensemble's handle or on
+ * its replicas; the implicit scheme on a handle with several slabs and on rank handles (the solve along axis 0 crosses slabs);
+ * the implicit scheme while option thermal_lookahead is on, and thermal_lookahead = 1 while the scheme is implicit;
+ * cetkmc_run_supersteps and cetkmc_run_supersteps_local while the scheme is implicit (Mode B is out of scope). */
+enum { CETKMC_THERMAL_EXPLICIT = 0, CETKMC_THERMAL_IMPLICIT = 1 };
+struct cetkmc_implicit_info { int64_t updates, steps, launches, coeff_uploads; };
+int cetkmc_set_thermal_scheme(void* handle, int scheme);
+int cetkmc_ensemble_set_thermal_scheme(void* handle, int scheme);
+int cetkmc_get_implicit_info(void* handle, struct cetkmc_implicit_info* info);
+int cetkmc_implicit_coeffs(int L, double r, double* inv, double* p);
 
 #ifdef __cplusplus
 }
