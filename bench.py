@@ -3,14 +3,21 @@
 lattice; achieved HBM GB/s).
 
   python bench.py --gpus 1 --steps K --warmup W          (N=1: config 3, 256^3, one MI355X)
+  python bench.py --gpus 1 --steps K --warmup W --full   (the same, then every other measurement and check)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
 
 A "step" is ONE exact KMC step (Mode A): full-lattice rate sweep (every candidate event's rate
 looked up / evaluated and reduced), cumulative-rate event pick, lattice update, plus the melt-pool
 temperature update, rate-table refresh and interface-list evaluation every 20 steps.
 `value` = EXECUTED events per second of that loop (= steps/s: one event per sweep, exactly like the
-reference).  The candidate-event rate (entries of get_event_rates' list per second), the exact
-incremental loop and Mode B (several events per sweep) are reported beside it under their own names.
+reference), with the candidate-event rate (entries of get_event_rates' list per second) beside it.
+
+A plain run does only what that figure needs: set-up, the lead-in and warm-up steps, the K timed steps, `--dump-outputs`,
+the result line (with the sweep launches' roofline from the timed steps' own hipEvents).  `--full` adds every other
+measurement and check, each under its own name in the same line (EXTRAS below): the CPU oracle on the first steps (speed and
+parity), the sweep kernel's memory traffic under rocprofv3, the per-phase table, the recompute sweep variant, the exact
+incremental loop, Mode B (several events per sweep), the 512^3 sweep, the PCIe-inclusive rate.  The `--no-...` options
+switch single ones of those off again.  The timed steps are the same steps of the same trajectory either way.
 `--dump-outputs DIR` writes what the timed steps computed as DIR/<name>.npy (dump_outputs), so that two builds can be
 compared output for output: the inputs depend only on the arguments.
 
@@ -193,8 +200,34 @@ def live_traffic(L, steps=20, timeout=90):
          "launches, 2 x FETCH_SIZE + WRITE_SIZE (KB); Infinity-Cache hits are included (memory-side requests of the L2)")
 
 
-def main():
+LEAD_IN_STEPS = 40             # stepped before the warm-up at N = 1; a --full run compares them with the CPU oracle
+
+# --full: what a run measures or checks besides its headline figure, and the option that switches each off again
+EXTRAS = {"live_traffic": "no_live_traffic", "cpu_baseline": "no_cpu_baseline", "phases": "no_phases",
+          "sweep_recompute": "no_recompute", "incremental_exact": "no_incremental", "mode_b": "no_mode_b", "hbm_512": "no_512",
+          "event_overhead": None, "pcie_inclusive": None}
+
+
+def extras(a, N, world, L, config5):
+    """The extra measurements of this run (names of EXTRAS): none without --full; with it, those that fit the
+    configuration and were not switched off."""
+    if not a.full:
+        return set()
+    fits = {"live_traffic": N == 1 and world == 1 and not config5 and not a.force_dist,
+            "cpu_baseline": N == 1 and not config5,
+            "sweep_recompute": N == 1,
+            "incremental_exact": N == 1 or a.extras_multi,
+            "mode_b": L % 8 == 0 and (L // N) % 8 == 0,
+            "hbm_512": N == 1 and L == 256 and not config5}
+    return {name for name, off in EXTRAS.items() if fits.get(name, True) and not (off and getattr(a, off))}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run every other measurement and check (CPU oracle baseline and parity, "
+                         "live memory traffic, phases, recompute variant, incremental loop, Mode B, 512^3 sweep, PCIe-inclusive "
+                         "rate); off by default, the --no-... options below narrow it")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
@@ -222,7 +255,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed (event log, totals, seeded lattice sample; rank 0) "
                          "as DIR/<name>.npy, at most 64 MB")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    a = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -243,14 +280,16 @@ def main():
     else:
         cfg_name, scaling = "config3-weak", "weak"
 
+    todo = extras(a, N, world, L, config5)
+
     # memory traffic of the dominant kernel, measured now (child runs under rocprofv3 --pmc) -- before this process owns the GPU
     live_bytes, live_src = (None, "not requested")
-    if N == 1 and world == 1 and not a.no_live_traffic and not config5 and not a.force_dist:
+    if "live_traffic" in todo:
         live_bytes, live_src = live_traffic(L)
         if live_bytes is None:
             print(f"bench: live traffic measurement skipped ({live_src})", file=sys.stderr)
     live512_bytes, live512_src = (None, "not requested")
-    if live_bytes is not None and L == 256 and not a.no_512:      # the cache-free leg's traffic too (hbm_512 below)
+    if live_bytes is not None and "hbm_512" in todo:              # the cache-free leg's traffic too (hbm_512 below)
         live512_bytes, live512_src = live_traffic(512, steps=6)
 
     # Libraries chat on stdout (gloo's "[Gloo] Rank ..." line, RCCL's version banner under NCCL_DEBUG): keep fd 1 for
@@ -396,13 +435,14 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    # ---- parity sample + CPU baseline (rank 0, N=1): GPU and oracle run the same first steps
+    # ---- lead-in steps (N=1): with or without --full the timed steps are the same steps of the trajectory.  --full: parity
+    # sample + CPU baseline, the oracle runs the same first steps
     step = 0
     base = None
     if N == 1 and not a.no_cpu_baseline and not config5:
-        n_chk = 40
-        r = run(0, n_chk)
+        r = run(0, LEAD_IN_STEPS)
         step = r["done"]
+    if "cpu_baseline" in todo:
         base = cpu_baseline(L, (state, theta, phi, T, defects), r["n_events"], a.cpu_budget)
         k = base["steps"]
         same = all(np.array_equal(r["events"][f][:k], base["events"][f][:k]) for f in ("type", "pos", "target", "atom"))
@@ -480,7 +520,7 @@ def main():
                                "records); thermal / rate table / interface list averaged over their 1-in-20 cadence")
         return phases
 
-    phases = guarded("phases", do_phases) if not a.no_phases else None       # at N > 1 this is where comm_us_per_step comes from
+    phases = guarded("phases", do_phases) if "phases" in todo else None       # at N > 1 this is where comm_us_per_step comes from
 
     # ---- the recompute variant of the sweep kernel (nucleation rates evaluated in every sweep instead of looked up)
     def do_recompute():
@@ -507,7 +547,7 @@ def main():
                                  "test_sweep_variants_bit_identical); steps_per_s includes the hipEvent records"}
         return recompute
 
-    recompute = guarded("sweep_recompute", do_recompute) if (not a.no_recompute and N == 1) else None
+    recompute = guarded("sweep_recompute", do_recompute) if "sweep_recompute" in todo else None
 
     # ---- the same loop in exact incremental mode (reported beside `value`, never as it)
     def do_incremental():
@@ -528,7 +568,7 @@ def main():
                            "(tests/test_gpu_parity.py::test_incremental_mode_bit_identical); not part of `value`"}
         return inc
 
-    inc = guarded("incremental_exact", do_incremental) if (not a.no_incremental and (N == 1 or a.extras_multi)) else None
+    inc = guarded("incremental_exact", do_incremental) if "incremental_exact" in todo else None
 
     # ---- Mode B (super-steps over 8^3 boxes; not the reference's trajectory, own CPU comparator): executed events/s
     def do_mode_b(null_events, const_T=None):
@@ -601,13 +641,13 @@ def main():
                 break
     except Exception:
         pass
-    mode_b_ok = not a.no_mode_b and L % 8 == 0 and (L // N) % 8 == 0
+    mode_b_ok = "mode_b" in todo
     mode_b = guarded("mode_b", lambda: do_mode_b(False)) if mode_b_ok else None
     mode_b_null = guarded("mode_b_null_events", lambda: do_mode_b(True)) if mode_b_ok else None
     # (last: it replaces the temperature field)
     mode_b_null_ct = guarded("mode_b_null_events_stationary_T", lambda: do_mode_b(True, const_T=3000.0)) if mode_b_ok else None
 
-    ev_over_ms = guarded("event_overhead", lambda: eng.event_overhead(50))
+    ev_over_ms = guarded("event_overhead", lambda: eng.event_overhead(50)) if "event_overhead" in todo else None
 
     # ---- what the boundary costs when it hands over host buffers: the lattice up before and down after a job
     def do_pcie():
@@ -624,7 +664,7 @@ def main():
                 "note": "rank 0's slab (+halo on the way up) in the plane API's types (u8 state/defects, f64 theta/phi/T) from and to "
                         "pageable NumPy arrays; the timed region itself starts with everything resident in HBM, so these rates "
                         "are context, never `value`"}
-    pcie = guarded("pcie_inclusive", do_pcie)
+    pcie = guarded("pcie_inclusive", do_pcie) if "pcie_inclusive" in todo else None
     cand = float(np.sum(r["n_events"].astype(np.float64)))     # identical on every rank (global counts)
     steps_per_s = a.steps / dt
     sweep_ms = r["sweep_ms_total"] / max(r["sweep_launches"], 1)
@@ -692,7 +732,7 @@ def main():
         finally:
             e5.close()
 
-    hbm_512 = guarded("hbm_512", do_hbm_512) if (N == 1 and L == 256 and not a.no_512 and not config5) else None
+    hbm_512 = guarded("hbm_512", do_hbm_512) if "hbm_512" in todo else None
 
     workloads = {
         "config3": f"config 3: {L}^3 voxel lattice, one MI355X",
@@ -705,6 +745,7 @@ def main():
         "metric": "kmc_events_per_sec", "value": steps_per_s, "unit": "executed events/s",
         "n_gpus": N, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "full": bool(a.full), "extras": sorted(todo),
         "config": {
             "workload": workloads[cfg_name] + "; k<L/4 pre-filled W/Re/C, moving Gaussian melt-pool T-field "
                         "(update_temperature every 20 steps), exact Mode A: 1 executed event per full rate sweep",
