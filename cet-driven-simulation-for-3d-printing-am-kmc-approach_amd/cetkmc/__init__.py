@@ -5,4 +5,4 @@ thermal_solver.py, ...) keep the reference's names and call signatures and are b
 :class:`cetkmc.engine.Engine`.  There is no CPU fallback: loading fails loudly when the
 shared library is missing, and every compute call fails when no GPU is present.
 """
-from .engine import Engine, Ensemble, Event, default_params, device_count, build_library, library_path, implicit_coeffs  # noqa: F401
+from .engine import Engine, Ensemble, Event, default_params, device_count, build_library, library_path, implicit_coeffs, implicit_coeffs_bc  # noqa: F401

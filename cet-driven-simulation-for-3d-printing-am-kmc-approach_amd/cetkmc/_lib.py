@@ -169,12 +169,21 @@ class ImplicitInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("updates", "steps", "launches", "coeff_uploads")]
 
 
+class ThermalBoundary(C.Structure):
+    _fields_ = [(n, C.c_double * 6) for n in ("beta", "T_ext", "ramp")]
+
+
+class BoundaryInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("updates", "steps", "launches", "coeff_uploads")]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
                   "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
                   "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs,
-                  "remelt_info": RemeltInfo, "substep_info": SubstepInfo, "implicit_info": ImplicitInfo}
+                  "remelt_info": RemeltInfo, "substep_info": SubstepInfo, "implicit_info": ImplicitInfo,
+                  "thermal_boundary": ThermalBoundary, "boundary_info": BoundaryInfo}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -280,6 +289,10 @@ PROTOTYPES = {
     "cetkmc_ensemble_set_thermal_scheme": (C.c_int, [C.c_void_p, C.c_int]),
     "cetkmc_get_implicit_info": (C.c_int, [C.c_void_p, _P(ImplicitInfo)]),
     "cetkmc_implicit_coeffs": (C.c_int, [C.c_int, C.c_double, _P(C.c_double), _P(C.c_double)]),
+    "cetkmc_set_thermal_boundary": (C.c_int, [C.c_void_p, _P(ThermalBoundary)]),
+    "cetkmc_ensemble_set_thermal_boundary": (C.c_int, [C.c_void_p, _P(ThermalBoundary)]),
+    "cetkmc_get_thermal_boundary": (C.c_int, [C.c_void_p, _P(ThermalBoundary), _P(BoundaryInfo)]),
+    "cetkmc_implicit_coeffs_bc": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, _P(C.c_double), _P(C.c_double)]),
 }
 
 

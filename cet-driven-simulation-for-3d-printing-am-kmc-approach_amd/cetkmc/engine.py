@@ -157,6 +157,45 @@ def implicit_coeffs(L, r):
     return inv, p
 
 
+FACES = ("i_lo", "i_hi", "j_lo", "j_hi", "k_lo", "k_hi")        # CETKMC_FACE_*: i_lo the substrate side, i_hi the top
+
+
+def implicit_coeffs_bc(L, r, beta_lo, beta_hi):
+    """cetkmc_implicit_coeffs_bc: (inv, p) of one axis whose two faces carry beta_lo, beta_hi; both 0:
+    the bits of ``implicit_coeffs``.  Needs no GPU."""
+    lib = _lib.load()
+    inv, p = np.zeros(max(int(L), 0)), np.zeros(max(int(L), 0))
+    if lib.cetkmc_implicit_coeffs_bc(int(L), float(r), float(beta_lo), float(beta_hi), _dptr(inv), _dptr(p)):
+        raise ValueError("cetkmc: " + lib.cetkmc_last_error().decode(errors="replace"))
+    return inv, p
+
+
+def _boundary_struct(boundary, where):
+    """None (adiabatic), a _lib.ThermalBoundary, or a mapping with ``beta`` and optionally ``T_ext``, ``ramp`` (six values each,
+    in the order of FACES) -> a pointer argument for the setters; the library checks the values"""
+    if boundary is None:
+        return None
+    if isinstance(boundary, _lib.ThermalBoundary):
+        return C.byref(boundary)
+    try:
+        cols = [np.asarray(boundary.get(n, np.zeros(6)) if n != "beta" else boundary["beta"], np.float64).reshape(6)
+                for n in ("beta", "T_ext", "ramp")]
+    except (AttributeError, KeyError, TypeError, ValueError):
+        raise ValueError(f"{where}: the boundary must be None or a mapping with six 'beta' (and 'T_ext', 'ramp') values in the "
+                         f"order {FACES} (got {boundary!r})") from None
+    b = _lib.ThermalBoundary()
+    for n, col in zip(("beta", "T_ext", "ramp"), cols):
+        getattr(b, n)[:] = [float(x) for x in col]
+    return C.byref(b)
+
+
+def _boundary_get(lib, ck, h):
+    b, info = _lib.ThermalBoundary(), _lib.BoundaryInfo()
+    ck(lib.cetkmc_get_thermal_boundary(h, C.byref(b), C.byref(info)))
+    return ({n: [float(x) for x in getattr(b, n)] for n, _ in _lib.ThermalBoundary._fields_},
+            {n: int(getattr(info, n)) for n, _ in _lib.BoundaryInfo._fields_})
+
+
 class Engine:
     """Owns a cetkmc handle.  ``n_slabs>1`` splits the lattice into axis-0 slabs on the same
     GPU (decomposition check); ``rank/nranks/unique_id`` selects the one-process-per-GPU
@@ -732,6 +771,20 @@ class Engine:
         self._ck(self.lib.cetkmc_get_implicit_info(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in _lib.ImplicitInfo._fields_}
 
+    # -- thermal boundary conditions ----------------------------------------------
+    def set_thermal_boundary(self, boundary):
+        """cetkmc_set_thermal_boundary: None (adiabatic) or dict(beta=, T_ext=, ramp=), six values each in the order of
+        ``cetkmc.engine.FACES``; needs the implicit scheme unless every beta is 0."""
+        self._ck(self.lib.cetkmc_set_thermal_boundary(self.h, _boundary_struct(boundary, "Engine.set_thermal_boundary")))
+
+    def thermal_boundary(self):
+        """the boundary as set: dict(beta, T_ext, ramp) of six floats each (all zero: adiabatic)"""
+        return _boundary_get(self.lib, self._ck, self.h)[0]
+
+    def boundary_info(self):
+        """dict(updates, steps, launches, coeff_uploads): running totals of the updates made with a non-adiabatic boundary"""
+        return _boundary_get(self.lib, self._ck, self.h)[1]
+
     def time_thermal(self, n_updates, laser=False):
         """cetkmc_time_thermal: device ms of n_updates temperature updates (dt = 1e-6 s, one hipEvent pair).  The updates are
         real: afterwards the handle's field has advanced by ``n_updates`` updates (``laser``: with the plane of the last
@@ -906,6 +959,20 @@ class Ensemble:
         info = _lib.ImplicitInfo()
         self._ck(self.lib.cetkmc_get_implicit_info(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in _lib.ImplicitInfo._fields_}
+
+    # -- thermal boundary conditions ----------------------------------------------
+    def set_thermal_boundary(self, boundary):
+        """cetkmc_ensemble_set_thermal_boundary: one boundary for all replicas; None (adiabatic) or dict(beta=, T_ext=, ramp=), six values each in the order of
+        ``cetkmc.engine.FACES``; needs the implicit scheme unless every beta is 0."""
+        self._ck(self.lib.cetkmc_ensemble_set_thermal_boundary(self.h, _boundary_struct(boundary, "Ensemble.set_thermal_boundary")))
+
+    def thermal_boundary(self):
+        """the boundary as set: dict(beta, T_ext, ramp) of six floats each (all zero: adiabatic)"""
+        return _boundary_get(self.lib, self._ck, self.h)[0]
+
+    def boundary_info(self):
+        """dict(updates, steps, launches, coeff_uploads): running totals of the updates made with a non-adiabatic boundary"""
+        return _boundary_get(self.lib, self._ck, self.h)[1]
 
     def remelt_info(self):
         """cetkmc_ensemble_remelt_info: one dict(passes, n_melted, n_melted_last, n_appended) per replica."""

@@ -295,6 +295,13 @@ struct Handle {
     double* d_imp_coef = nullptr;        // [2][L]: inv, p of imp_r (allocated by the first implicit update)
     double imp_r = 0.0;                  // the r the device table was built for (compared by bits)
     cetkmc_implicit_info imp_info{};
+    // thermal boundary conditions of the implicit updates (cetkmc_set_thermal_boundary)
+    cetkmc_thermal_boundary bc{};        // as set; every beta 0: adiabatic, the launches and the table of section 26
+    bool bc_on = false;                  // some beta != 0
+    double* d_bc_coef = nullptr;         // [3][2][L]: inv, p per axis for bc_r and bc_beta (allocated by the first boundary update)
+    double bc_r = 0.0, bc_beta[6] = {};  // what the device table was built for (compared by bits)
+    int64_t bc_u = 0;                    // the update ordinal g / 20 of the stepping call's update being queued
+    cetkmc_boundary_info bc_info{};
 };
 
 // ---- cache state ------------------------------------------------------------------------------------
@@ -1253,6 +1260,88 @@ ImpCfg imp_cfg(const Handle* h, double dt_s, int laser, int use_latent, int scru
     C.coef = h->d_imp_coef; C.laser = laser; C.use_latent = use_latent; C.scrub = scrub;
     return C;
 }
+// ---- thermal boundary conditions ---------------------------------------------------------------------
+// the Thomas coefficients of one axis whose faces carry beta_lo, beta_hi, exactly as include/cetkmc.h states them; both 0: the
+// bits of implicit_coeffs_host
+int implicit_coeffs_bc_host(const char* fn, int L, double r, double beta_lo, double beta_hi, double* inv, double* p)
+{
+    const std::string f(fn);
+    if (!inv || !p) return fail(f + ": null argument");
+    if (L < 1) return fail(f + ": L must be >= 1 (got " + std::to_string(L) + ")");
+    if (!std::isfinite(r)) return fail(f + ": r is not finite");
+    if (r < 0.0) return fail(f + ": r must be >= 0");
+    if (!std::isfinite(beta_lo) || !std::isfinite(beta_hi)) return fail(f + ": beta is not finite");
+    if (beta_lo < 0.0 || beta_hi < 0.0) return fail(f + ": beta must be >= 0");
+    inv[0] = 1.0 / ((L == 1) ? 1.0 + r * (beta_lo + beta_hi) : 1.0 + r * (1.0 + beta_lo));
+    p[0] = r * inv[0];
+    for (int m = 1; m < L; ++m) {
+        const double diag = (m < L - 1) ? (1.0 + 2.0 * r) : (1.0 + r * (1.0 + beta_hi));
+        inv[m] = 1.0 / (diag - r * p[m - 1]);
+        p[m] = r * inv[m];
+    }
+    return 0;
+}
+// what both boundary setters refuse of the values, before anything changes
+int boundary_values_ok(const char* fn, const cetkmc_thermal_boundary& b)
+{
+    const std::string f(fn);
+    for (int k = 0; k < 6; ++k) {
+        const std::string face = " of face " + std::to_string(k);
+        if (!std::isfinite(b.beta[k])) return fail(f + ": beta" + face + " is not finite");
+        if (b.beta[k] < 0.0) return fail(f + ": beta" + face + " is negative");
+        if (!std::isfinite(b.T_ext[k])) return fail(f + ": T_ext" + face + " is not finite");
+        if (!std::isfinite(b.ramp[k])) return fail(f + ": ramp" + face + " is not finite");
+    }
+    return 0;
+}
+bool boundary_active(const cetkmc_thermal_boundary& b)
+{
+    for (int k = 0; k < 6; ++k) if (b.beta[k] != 0.0) return true;
+    return false;
+}
+// the face temperature of update ordinal u: one multiply, one add
+double boundary_T(const cetkmc_thermal_boundary& b, int k, int64_t u) { return b.T_ext[k] + b.ramp[k] * (double)u; }
+// a stepping call's own updates (global steps g in [step0, step0 + n), g % 20 == 0, ordinal g / 20) must all have finite T_f
+int boundary_steps_ok(const char* fn, const cetkmc_thermal_boundary& b, int64_t step0, int64_t n)
+{
+    for (int64_t g = (step0 + 19) / 20 * 20; g < step0 + n; g += 20)
+        for (int k = 0; k < 6; ++k)
+            if (b.beta[k] != 0.0 && !std::isfinite(boundary_T(b, k, g / 20)))
+                return fail(std::string(fn) + ": the thermal boundary's temperature of face " + std::to_string(k) + " is not finite at the update of step " +
+                            std::to_string(g) + " (T_ext + ramp * " + std::to_string(g / 20) + ")");
+    return 0;
+}
+// the device table [3][2][L] of the handle for this r and the boundary's six beta: rebuilt when any of them changes
+int bc_ensure_coeffs(Handle* h, double r, const cetkmc_thermal_boundary& b, cetkmc_boundary_info* info)
+{
+    if (h->d_bc_coef && !memcmp(&h->bc_r, &r, sizeof r) && !memcmp(h->bc_beta, b.beta, sizeof h->bc_beta)) return 0;
+    const size_t L = (size_t)h->L;
+    std::vector<double> tab(6 * L);
+    for (int ax = 0; ax < 3; ++ax)
+        CHK(implicit_coeffs_bc_host("implicit update", h->L, r, b.beta[2 * ax], b.beta[2 * ax + 1], tab.data() + 2 * ax * L, tab.data() + (2 * ax + 1) * L));
+    if (!h->d_bc_coef && hipMalloc((void**)&h->d_bc_coef, tab.size() * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_bc_coef = nullptr;
+        return fail("implicit update: no device memory for " + std::to_string(tab.size() * 8) + " bytes");
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));          // launches that read the previous table
+    HIPCHK(hipMemcpy(h->d_bc_coef, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    h->bc_r = r;
+    memcpy(h->bc_beta, b.beta, sizeof h->bc_beta);
+    ++info->coeff_uploads;
+    return 0;
+}
+// the by-value boundary of one implicit step at ratio r, update ordinal u: c_f = (r * beta_f) * T_f where beta_f != 0
+ImpBc imp_bc(const cetkmc_thermal_boundary& b, double r, int64_t u)
+{
+    ImpBc B{};
+    for (int k = 0; k < 6; ++k)
+        if (b.beta[k] != 0.0) {
+            B.c[k] = (r * b.beta[k]) * boundary_T(b, k, u);
+            B.on |= 1 << k;
+        }
+    return B;
+}
 dim3 imp_rows_grid(int L, int nloc, int R = 1) { return dim3((unsigned)(((int64_t)nloc * L + IMP_R - 1) / IMP_R), (unsigned)R); }
 dim3 imp_lines_grid(int L, int R = 1) { return dim3((unsigned)((L + 63) / 64), (unsigned)L, (unsigned)R); }
 // a temperature update of a one-slab handle in thermal_substeps implicit steps of dt / n: three launches each, one flip each
@@ -1260,18 +1349,30 @@ int launch_thermal_imp(Handle* h, double dt, int laser, const double* d_q, int u
 {
     const int n = h->thermal_substeps, L = h->L;
     const double dt_s = n > 1 ? dt / (double)n : dt;
-    CHK(imp_ensure_coeffs(h, (h->p.alpha * dt_s) * h->p.inv_dx2));
+    const double r = (h->p.alpha * dt_s) * h->p.inv_dx2;
+    const bool bc = h->bc_on;       // the boundary form (section 27): its own table, the six addends by value; a direct call is update 0
+    if (bc) CHK(bc_ensure_coeffs(h, r, h->bc, &h->bc_info));
+    else CHK(imp_ensure_coeffs(h, r));
+    const ImpBc B = bc ? imp_bc(h->bc, r, batch ? h->bc_u : 0) : ImpBc{};
     const StepState* ssp = batch ? h->d_ss : nullptr;
     ++h->cnt.thermal_updates;
     for (int q = 0; q < n; ++q) {
         const bool first = q == 0;
-        const ImpCfg C = imp_cfg(h, dt_s, laser, first ? use_latent : 0, first ? scrub : 0);
+        ImpCfg C = imp_cfg(h, dt_s, laser, first ? use_latent : 0, first ? scrub : 0);
         const int nxt = h->cur ^ 1;
         const SlabView v = view_of(h, 0);
-        launch(k_imp_rows<>, imp_rows_grid(L, v.nloc), dim3(IMP_R), 0, h->stream, nullptr, nullptr, v, (const double*)h->slabs[0].Tbuf[h->cur],
-               h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, C, ssp);
-        launch(k_imp_lines<1>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
-        launch(k_imp_lines<0>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
+        if (bc) {
+            C.coef = h->d_bc_coef;
+            launch(k_imp_rows<ImpBc>, imp_rows_grid(L, v.nloc), dim3(IMP_R), 0, h->stream, nullptr, nullptr, v, (const double*)h->slabs[0].Tbuf[h->cur],
+                   h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, C, ssp, B);
+            launch(k_imp_lines<1, ImpBc>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp, B);
+            launch(k_imp_lines<0, ImpBc>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp, B);
+        } else {
+            launch(k_imp_rows<>, imp_rows_grid(L, v.nloc), dim3(IMP_R), 0, h->stream, nullptr, nullptr, v, (const double*)h->slabs[0].Tbuf[h->cur],
+                   h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, C, ssp);
+            launch(k_imp_lines<1>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
+            launch(k_imp_lines<0>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
+        }
         if (first && laser && use_latent)       // k_imp_rows has brought prev_state level with state on the flagged rows
             hipLaunchKernelGGL(k_clear_row_flags, dim3(64), dim3(256), 0, h->stream, v, ssp);
         HIPCHK(hipGetLastError());
@@ -1279,6 +1380,7 @@ int launch_thermal_imp(Handle* h, double dt, int laser, const double* d_q, int u
         h->cur = nxt;
     }
     ++h->imp_info.updates; h->imp_info.steps += n; h->imp_info.launches += 3 * (int64_t)n;
+    if (bc) { ++h->bc_info.updates; h->bc_info.steps += n; h->bc_info.launches += 3 * (int64_t)n; }
     invalidate(h, Cause::thermal_update);
     return 0;
 }
@@ -1335,6 +1437,7 @@ int thermal_step(Handle* h, int64_t g, double dt, int laser, const double* d_q, 
     Handle::Spec& sp = h->spec;
     if (!(sp.valid && sp.g == g && sp.laser == laser && sp.use_latent == use_latent && sp.scrub == scrub && sp.dt == dt && sp.d_q == d_q)) {
         if (sp.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); sp.valid = false; }     // a stale look-ahead still owns the other buffers
+        h->bc_u = g / 20;       // a thermal boundary's face temperatures follow the global step (section 27)
         return launch_thermal(h, dt, laser, d_q, use_latent, scrub, true);
     }
     sp.valid = false;
@@ -1488,7 +1591,7 @@ void destroy_impl(Handle* h)
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
                     h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq,
-                    h->d_imp_coef};
+                    h->d_imp_coef, h->d_bc_coef};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -1542,6 +1645,9 @@ struct Ens {
     cetkmc_substep_info sub_info{};
     int thermal_scheme = CETKMC_THERMAL_EXPLICIT;      // cetkmc_ensemble_set_thermal_scheme: one scheme for all replicas
     cetkmc_implicit_info imp_info{};
+    cetkmc_thermal_boundary bc{};        // cetkmc_ensemble_set_thermal_boundary: one boundary for all replicas
+    bool bc_on = false;
+    cetkmc_boundary_info bc_info{};
     double remelt_threshold = 0.0;
 };
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
@@ -1620,6 +1726,8 @@ int cetkmc_struct_size(const char* name)
     SZ("origin_rec", struct cetkmc_origin_rec); SZ("local_args", cetkmc_local_args);
     SZ("remelt_info", struct cetkmc_remelt_info); SZ("substep_info", struct cetkmc_substep_info);
     SZ("implicit_info", struct cetkmc_implicit_info);
+    SZ("thermal_boundary", struct cetkmc_thermal_boundary);
+    SZ("boundary_info", struct cetkmc_boundary_info);
 #undef SZ
     return -1;
 }
@@ -2338,6 +2446,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     const int64_t n = a->n_steps;
     CHK(origin_room(h, n, "cetkmc_run_steps"));
+    if (h->bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_steps", h->bc, a->step0, n));
     CHK(stage_run(h, a));
     // reset the batch part of the step state (nucleation_count persists): a one-thread kernel, no host round trip
     hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
@@ -3080,6 +3189,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     // temperature updates of the call: the cadence is shared, so every replica's u-th update is the same global step
     const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     const bool laser = a->thermal_mode == 2;
+    if (e->bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_ensemble", e->bc, a->step0, n));
     if (laser) {       // everything about the plane sets is checked before anything is copied or launched
         if (a->n_q < n_therm) return fail("thermal_mode 2 needs one q plane per temperature update of the call in every plane set (n_q too small)");
         if (n_therm > 0 && !a->q_planes) return fail("thermal_mode 2: q_planes[n_sets][n_q][L*L] required (the call holds a temperature update)");
@@ -3172,12 +3282,19 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const double dt_s = nsub > 1 ? a->thermal_dt / (double)nsub : a->thermal_dt;
     const ThermalCfg tc0 = thermal_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), tc_sub = thermal_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
     const bool implicit = e->thermal_scheme == CETKMC_THERMAL_IMPLICIT;
+    const bool bc = implicit && e->bc_on;       // the boundary form (section 27): one boundary, one table for every replica
+    const double imp_r = (h0->p.alpha * dt_s) * h0->p.inv_dx2;
     if (implicit && a->thermal_mode && updates_in(a->step0, n) > 0) {      // the coefficient table of replica 0 serves every replica
-        const int64_t before = h0->imp_info.coeff_uploads;
-        CHK(imp_ensure_coeffs(h0, (h0->p.alpha * dt_s) * h0->p.inv_dx2));
-        e->imp_info.coeff_uploads += h0->imp_info.coeff_uploads - before;
+        if (bc) {
+            CHK(bc_ensure_coeffs(h0, imp_r, e->bc, &e->bc_info));
+        } else {
+            const int64_t before = h0->imp_info.coeff_uploads;
+            CHK(imp_ensure_coeffs(h0, imp_r));
+            e->imp_info.coeff_uploads += h0->imp_info.coeff_uploads - before;
+        }
     }
-    const ImpCfg ic0 = imp_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), ic_sub = imp_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
+    ImpCfg ic0 = imp_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), ic_sub = imp_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
+    if (bc) ic0.coef = ic_sub.coef = h0->d_bc_coef;
     const BatchCfg cfg0{};
     const dim3 g_flags((unsigned)std::min<int64_t>(((int64_t)(L + 4) * L + 255) / 256, 64), (unsigned)R);
     EnsSel sel{e->d_table, 0, (int)g_therm.z / R};
@@ -3195,16 +3312,27 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         const int64_t g = a->step0 + s;
         if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
             if (implicit) {        // nsub implicit steps (thermal_imp.hpp): three launches and one flip each
+                const ImpBc B = bc ? imp_bc(e->bc, imp_r, g / 20) : ImpBc{};
                 for (int q = 0; q < nsub; ++q) {
-                    launch(k_imp_rows<EnsSel>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr,
-                           q == 0 ? ic0 : ic_sub, nullptr, sel);
+                    if (bc)
+                        launch(k_imp_rows<ImpBc, EnsSel>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr,
+                               q == 0 ? ic0 : ic_sub, nullptr, B, sel);
+                    else
+                        launch(k_imp_rows<EnsSel>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr,
+                               q == 0 ? ic0 : ic_sub, nullptr, sel);
                     if (q == 0 && latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
                     sel.rel ^= 1;
                     ++flips;
-                    launch(k_imp_lines<1, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
-                    launch(k_imp_lines<0, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
+                    if (bc) {
+                        launch(k_imp_lines<1, ImpBc, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, B, sel);
+                        launch(k_imp_lines<0, ImpBc, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, B, sel);
+                    } else {
+                        launch(k_imp_lines<1, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
+                        launch(k_imp_lines<0, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
+                    }
                 }
                 ++e->imp_info.updates; e->imp_info.steps += nsub; e->imp_info.launches += 3 * (int64_t)nsub;
+                if (bc) { ++e->bc_info.updates; e->bc_info.steps += nsub; e->bc_info.launches += 3 * (int64_t)nsub; }
             } else {
                 launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc0, nullptr, sel);
                 // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
@@ -4342,6 +4470,8 @@ int cetkmc_set_thermal_scheme(void* handle, int scheme)
             return fail("cetkmc_set_thermal_scheme: the implicit scheme needs the whole lattice in one slab of one process (the solve along the plane axis crosses slabs)");
         if (h->thermal_ahead) return fail("cetkmc_set_thermal_scheme: the implicit scheme is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
     }
+    if (scheme == CETKMC_THERMAL_EXPLICIT && h->bc_on)
+        return fail("cetkmc_set_thermal_scheme: the explicit scheme is refused while a thermal boundary is set (cetkmc_set_thermal_boundary(handle, NULL) first)");
     h->thermal_scheme = scheme;
     return 0;
 }
@@ -4352,6 +4482,8 @@ int cetkmc_ensemble_set_thermal_scheme(void* handle, int scheme)
     Ens* e = ens_of(handle);
     if (!e) return fail("cetkmc_ensemble_set_thermal_scheme: not an ensemble handle (cetkmc_create_ensemble)");
     CHK(scheme_known("cetkmc_ensemble_set_thermal_scheme", scheme));
+    if (scheme == CETKMC_THERMAL_EXPLICIT && e->bc_on)
+        return fail("cetkmc_ensemble_set_thermal_scheme: the explicit scheme is refused while a thermal boundary is set (cetkmc_ensemble_set_thermal_boundary(handle, NULL) first)");
     e->thermal_scheme = scheme;
     for (Handle* h : e->reps) h->thermal_scheme = scheme;      // a direct update on a replica handle follows the ensemble's scheme
     return 0;
@@ -4366,5 +4498,50 @@ int cetkmc_get_implicit_info(void* handle, struct cetkmc_implicit_info* info)
 }
 
 int cetkmc_implicit_coeffs(int L, double r, double* inv, double* p) { return implicit_coeffs_host("cetkmc_implicit_coeffs", L, r, inv, p); }
+
+// ---- thermal boundary conditions (thermal_imp.hpp) --------------------------------------------------
+int cetkmc_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b)
+{
+    if (!handle) return fail("cetkmc_set_thermal_boundary: null handle");
+    if (ens_of(handle)) return fail("cetkmc_set_thermal_boundary: an ensemble handle is set by cetkmc_ensemble_set_thermal_boundary");
+    Handle* h = (Handle*)handle;
+    if (h->in_ensemble) return fail("cetkmc_set_thermal_boundary: the replicas of an ensemble share one boundary (cetkmc_ensemble_set_thermal_boundary)");
+    const cetkmc_thermal_boundary v = b ? *b : cetkmc_thermal_boundary{};
+    CHK(boundary_values_ok("cetkmc_set_thermal_boundary", v));
+    const bool on = boundary_active(v);
+    if (on && h->thermal_scheme != CETKMC_THERMAL_IMPLICIT)
+        return fail("cetkmc_set_thermal_boundary: a thermal boundary needs the implicit scheme (cetkmc_set_thermal_scheme); the explicit kernels are adiabatic");
+    h->bc = v; h->bc_on = on;
+    return 0;
+}
+
+int cetkmc_ensemble_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b)
+{
+    if (!handle) return fail("cetkmc_ensemble_set_thermal_boundary: null handle");
+    Ens* e = ens_of(handle);
+    if (!e) return fail("cetkmc_ensemble_set_thermal_boundary: not an ensemble handle (cetkmc_create_ensemble)");
+    const cetkmc_thermal_boundary v = b ? *b : cetkmc_thermal_boundary{};
+    CHK(boundary_values_ok("cetkmc_ensemble_set_thermal_boundary", v));
+    const bool on = boundary_active(v);
+    if (on && e->thermal_scheme != CETKMC_THERMAL_IMPLICIT)
+        return fail("cetkmc_ensemble_set_thermal_boundary: a thermal boundary needs the implicit scheme (cetkmc_ensemble_set_thermal_scheme); the explicit kernels are adiabatic");
+    e->bc = v; e->bc_on = on;
+    for (Handle* h : e->reps) { h->bc = v; h->bc_on = on; }      // a direct update on a replica handle follows the ensemble's boundary
+    return 0;
+}
+
+int cetkmc_get_thermal_boundary(void* handle, struct cetkmc_thermal_boundary* b, struct cetkmc_boundary_info* info)
+{
+    if (!handle) return fail("cetkmc_get_thermal_boundary: null handle");
+    Ens* e = ens_of(handle);
+    if (b) *b = e ? e->bc : ((Handle*)handle)->bc;
+    if (info) *info = e ? e->bc_info : ((Handle*)handle)->bc_info;
+    return 0;
+}
+
+int cetkmc_implicit_coeffs_bc(int L, double r, double beta_lo, double beta_hi, double* inv, double* p)
+{
+    return implicit_coeffs_bc_host("cetkmc_implicit_coeffs_bc", L, r, beta_lo, beta_hi, inv, p);
+}
 
 }  // extern "C"

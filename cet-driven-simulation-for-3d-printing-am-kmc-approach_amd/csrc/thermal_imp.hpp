@@ -26,6 +26,14 @@
 //
 // 96 B per voxel and implicit step before cache hits (92 at L = 256: one chunk in four of k_imp_rows stays in LDS; 80 up to L = 64).
 // Behind an early stop of the batch (status != 0) k_imp_rows copies the field and k_imp_lines returns.
+//
+// Boundary form: the instantiations whose trailing pack BEGINS with an ImpBc, k_imp_rows<ImpBc>,
+// k_imp_lines<AXIS, ImpBc> and the same with EnsSel behind it.  A face f with beta_f != 0 sees a ghost node x + beta_f (T_f - x):
+// the end diagonals change (the host's table, [3][2][L]: one inv, p pair per axis) and the right-hand side of the end row gains
+// the wave-uniform addend c_f = (r beta_f) T_f in front of everything else that row adds: y[0] = (b[0] + c_lo) inv[0],
+// y[L - 1] = ((b[L - 1] + c_hi) + r y[L - 2]) inv[L - 1].  An adiabatic face adds nothing (not even + 0.0).  Every boundary
+// statement stands under if constexpr: the instantiations without an ImpBc are the kernels of section 26, instruction for
+// instruction.
 #pragma once
 #include "kernels.hpp"
 
@@ -37,6 +45,19 @@ struct ImpCfg {
     const double* coef;          // [2][L]: inv, p
     int laser, use_latent, scrub;
 };
+// the boundary of one implicit step: the six addends, faces in the order i_lo, i_hi, j_lo, j_hi, k_lo, k_hi (face 2 * axis + hi),
+// and one bit per face with beta != 0.  With a boundary ImpCfg::coef is [3][2][L]: inv, p of axis 0, of axis 1, of axis 2.
+struct ImpBc {
+    double c[6];
+    int on;
+};
+template <class... E> struct imp_pack { static constexpr bool bc = false; static constexpr int n_ens = (int)sizeof...(E); };
+template <class... E> struct imp_pack<ImpBc, E...> { static constexpr bool bc = true; static constexpr int n_ens = (int)sizeof...(E); };
+template <class... E> __device__ __forceinline__ const ImpBc& imp_bc_of(const ImpBc& B, const E&...) { return B; }
+// the replica selection of a boundary-form ensemble launch stands behind the ImpBc
+template <class S> __device__ __forceinline__ const auto& ens_rep(unsigned r, const ImpBc&, const S& sel) { return ens_rep(r, sel); }
+template <class S> __device__ __forceinline__ int ens_rel(const ImpBc&, const S& sel) { return ens_rel(sel); }
+template <class S> __device__ __forceinline__ int64_t ens_q_off(const ImpBc&, const S& sel) { return ens_q_off(sel); }
 constexpr int IMP_R = 64, IMP_C = 64, IMP_PITCH = IMP_C + 1, IMP_U = 8, IMP_V = 16;   // IMP_V: rows of a chunk in flight per lane (k_imp_rows)
 
 // the scrub of this scheme: NaN -> T_nan, +-inf -> the clip values (not +-DBL_MAX, which a solve would spread over the lattice)
@@ -53,7 +74,8 @@ template <class... E>
 __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __restrict__ Tin, double* Tout, uint8_t* __restrict__ prev_state,
                                                     const double* __restrict__ q_top, ImpCfg C, const StepState* __restrict__ ss, E... ens)
 {
-    if constexpr (sizeof...(E) > 0) {
+    constexpr bool BC = imp_pack<E...>::bc;
+    if constexpr (imp_pack<E...>::n_ens > 0) {
         const auto& e = ens_rep(blockIdx.y, ens...);
         const int rel = ens_rel(ens...);
         S = e.view[rel]; Tin = e.view[rel].T; Tout = e.view[rel ^ 1].T; prev_state = e.prev; ss = e.ss;
@@ -73,8 +95,8 @@ __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __
         }
         return;
     }
-    const double* __restrict__ inv = C.coef;
-    const double* __restrict__ pc = C.coef + L;
+    const double* __restrict__ inv = C.coef + (BC ? 4 * L : 0);       // BC: the pair of axis 2
+    const double* __restrict__ pc = inv + L;
     const double r = C.r;
     const bool source = C.laser != 0, latent = source && C.use_latent;
     double* mine = tile + lane * IMP_PITCH;     // the row this lane sweeps
@@ -145,6 +167,11 @@ __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __
             }
         }
         __syncthreads();
+        if constexpr (BC) {         // the end addends of faces k_lo, k_hi, on the lane's own row (L = 1: (b + c_lo) + c_hi)
+            const ImpBc& B = imp_bc_of(ens...);
+            if (ch == 0 && (B.on & 16)) mine[0] = mine[0] + B.c[4];
+            if (ch + 1 == nchunk && (B.on & 32)) mine[cn - 1] = mine[cn - 1] + B.c[5];
+        }
 #pragma unroll 8
         for (int c = 0; c < cn; ++c) {
             const int m = kc + c;
@@ -192,7 +219,8 @@ __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __
 template <int AXIS, class... E>
 __global__ __launch_bounds__(64) void k_imp_lines(SlabView S, double* T, ImpCfg C, const StepState* __restrict__ ss, E... ens)
 {
-    if constexpr (sizeof...(E) > 0) {
+    constexpr bool BC = imp_pack<E...>::bc;
+    if constexpr (imp_pack<E...>::n_ens > 0) {
         const auto& e = ens_rep(blockIdx.z, ens...);
         S = e.view[ens_rel(ens...)]; T = S.T; ss = e.ss;
     }
@@ -202,16 +230,31 @@ __global__ __launch_bounds__(64) void k_imp_lines(SlabView S, double* T, ImpCfg 
     const int64_t plane = (int64_t)L * S.pitchT;
     const int64_t ls = AXIS == 1 ? (int64_t)S.pitchT : plane;                            // from element m to m + 1 of the line
     double* p0 = T + 2 * plane + (int64_t)blockIdx.y * (AXIS == 1 ? plane : (int64_t)S.pitchT) + k;
-    const double* __restrict__ inv = C.coef;
-    const double* __restrict__ pc = C.coef + L;
+    const double* __restrict__ inv = C.coef + (BC ? 2 * AXIS * L : 0);       // BC: the pair of this axis
+    const double* __restrict__ pc = inv + L;
     const double r = C.r;
+    bool lo_on = false, hi_on = false;             // wave-uniform
+    double c_lo = 0.0, c_hi = 0.0;
+    if constexpr (BC) {
+        const ImpBc& B = imp_bc_of(ens...);
+        lo_on = (B.on >> (2 * AXIS)) & 1; hi_on = (B.on >> (2 * AXIS + 1)) & 1;
+        c_lo = B.c[2 * AXIS]; c_hi = B.c[2 * AXIS + 1];
+    }
     auto clip = [&](double v) {
         if constexpr (AXIS == 0) { v = v < C.clip_lo ? C.clip_lo : v; v = v > C.clip_hi ? C.clip_hi : v; }
         return v;
     };
     double cur[IMP_U], nxt[IMP_U];
     // ---- forward ----
-    double y = p0[0] * inv[0];
+    double y;
+    if constexpr (BC) {         // L = 1: (b + c_lo) + c_hi
+        y = p0[0];
+        if (lo_on) y = y + c_lo;
+        if (hi_on && L == 1) y = y + c_hi;
+        y = y * inv[0];
+    } else {
+        y = p0[0] * inv[0];
+    }
     if (L > 1) p0[0] = y;
     auto load_up = [&](int m0, double (&d)[IMP_U]) {
 #pragma unroll
@@ -225,6 +268,7 @@ __global__ __launch_bounds__(64) void k_imp_lines(SlabView S, double* T, ImpCfg 
         for (int u = 0; u < IMP_U; ++u) {
             const int m = m0 + u;
             if (m < L) {
+                if constexpr (BC) { if (hi_on && m == L - 1) cur[u] = cur[u] + c_hi; }
                 y = (cur[u] + r * y) * inv[m];
                 if (m < L - 1) p0[(int64_t)m * ls] = y;
             }

@@ -57,7 +57,7 @@ import os
 import pandas as pd
 
 from constants import ATOMIC_SPACING_W, DEFECT_PROB, N_SEEDS, RANDOM_SEED, T_MELT, VOXEL_SIZE
-from kmc_simulation import run_kmc, run_kmc_ensemble
+from kmc_simulation import run_gradient_boundary, run_kmc, run_kmc_ensemble
 
 
 def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers=None, scan_speeds=None):
@@ -84,8 +84,12 @@ def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_p
 def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 2e13, 2e14), carbon=0.2,
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
              laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, texture=False,
-             grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1, thermal_scheme="explicit", **run_kw):
-    """``thermal_substeps`` (N or "stable"): every run with run_kmc's option of that name (mode "A"; one value for an ensemble).
+             grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1, thermal_scheme="explicit", hold_gradient=False,
+             cooling_rate=0.0, **run_kw):
+    """``hold_gradient=True`` (with ``thermal_scheme="implicit"``): every run with run_kmc's ``thermal_boundary`` set to the
+    boundary that holds its own initial ramp (``kmc_simulation.run_gradient_boundary``), lowered by ``cooling_rate`` [K/s];
+    gv_map.csv gains ``CoolingRate_K_per_s`` behind ``G_over_V``.  An ensemble shares one boundary, so it needs one temperature.
+    ``thermal_substeps`` (N or "stable"): every run with run_kmc's option of that name (mode "A"; one value for an ensemble).
     ``thermal_scheme`` ("explicit" or "implicit"): likewise.
     ``remelt`` (True or a threshold temperature): every run with run_kmc's ``remelt`` option (mode "A"; in an ensemble the
     shared ``remelt`` key of the configs).  ``run_kw`` goes to run_kmc unchanged -- e.g. ``mode="B", box=8`` runs every point of the map through the super-step
@@ -123,11 +127,18 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
                **({"solid_metrics": True} if solid else {}), **({"origin_metrics": True} if origin else {}),
                **({"thermal_substeps": thermal_substeps} if thermal_substeps != 1 else {}),
                **({"thermal_scheme": thermal_scheme} if thermal_scheme != "explicit" else {}))
+    if cooling_rate and not hold_gradient:
+        raise ValueError("cooling_rate needs hold_gradient=True (it lowers the held faces)")
+    if hold_gradient and ensemble and len(set(temps)) != 1:
+        raise ValueError("hold_gradient with ensemble=True needs one temperature (the replicas share one boundary)")
+
+    def held(T_sub):
+        return {"thermal_boundary": run_gradient_boundary(L, T_sub, cooling_rate)} if hold_gradient else {}
     if ensemble:
-        run_kmc_ensemble(cfg, L, n_steps, rng=rng, **opt)
+        run_kmc_ensemble(cfg, L, n_steps, rng=rng, **opt, **held(temps[0]))
     else:
         for c in cfg:
-            run_kmc(L=L, n_steps=n_steps, **c, **run_kw, **opt)
+            run_kmc(L=L, n_steps=n_steps, **c, **run_kw, **opt, **held(c["temp"]))
     rows = []
     for T_sub, nu_dep, seed, prefix, beam in runs:
         last = pd.read_csv(f"outputs/{prefix}/metrics.csv").iloc[-1]
@@ -139,6 +150,7 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
         if seeds > 1:
             row["seed"] = seed
         row.update({"G_K_per_m": G, "V_m_per_s": V, "G_over_V": G / V,
+                    **({"CoolingRate_K_per_s": float(cooling_rate)} if hold_gradient else {}),
                     "AspectRatio": last["AspectRatio"], "EquiaxedFraction": last["EquiaxedFraction"],
                     "GrainCount": last["GrainCount"], "NucleationCount": last["NucleationCount"],
                     "CET_Class": last["CET_Class"], "CET_Detected": last["CET_Detected"]})
@@ -203,6 +215,11 @@ if __name__ == "__main__":
     ap.add_argument("--thermal-scheme", choices=("explicit", "implicit"), default="explicit",
                     help="every temperature update as locally one-dimensional backward-Euler steps on the device, stable at any dt "
                          "(run_kmc thermal_scheme, mode A)")
+    ap.add_argument("--hold-gradient", action="store_true",
+                    help="with --thermal-scheme implicit: fixed faces at the next values of each run's initial ramp, so the imposed G "
+                         "lasts through the run (run_kmc thermal_boundary)")
+    ap.add_argument("--cooling-rate", type=float, default=0.0, metavar="K_PER_S",
+                    help="--hold-gradient: the held faces fall by this rate; recorded beside G and V in gv_map.csv")
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
@@ -213,4 +230,5 @@ if __name__ == "__main__":
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
                    layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt,
-                   thermal_substeps=a.thermal_substeps, thermal_scheme=a.thermal_scheme, **kw).to_string(index=False))
+                   thermal_substeps=a.thermal_substeps, thermal_scheme=a.thermal_scheme, hold_gradient=a.hold_gradient,
+                   cooling_rate=a.cooling_rate, **kw).to_string(index=False))

@@ -283,6 +283,38 @@ def _check_scheme(scheme, mode_a, thermal_updates, where="thermal_scheme", needs
         raise ValueError("thermal_scheme='implicit' needs thermal_updates=True (there is no update to make implicit)")
 
 
+def run_gradient_boundary(L, temp=T_SUB, cooling_rate=0.0):
+    """The boundary that holds the field a run starts from: ``initialize_lattice`` ramps T along axis 2 with the slope
+    (T_MELT - temp) / L, so the two k faces are fixed at the ramp's next values, T(-1) and T(L); every other face adiabatic.
+    (thermal_solver.gradient_boundary does the same for ``build_temperature_field``'s ramp along axis 0.)"""
+    slope = (T_MELT - float(temp)) / L
+    return dict(beta=[0.0, 0.0, 0.0, 0.0, 1.0, 1.0], T_ext=[0.0, 0.0, 0.0, 0.0, float(temp) - slope, float(temp) + slope * L],
+                ramp=[0.0] * 4 + [-float(cooling_rate) * THERMAL_DT] * 2)
+
+
+def _thermal_boundary(value, L, temp, mode_a, scheme, thermal_updates, needs="mode 'A' (the super-step engine's updates are explicit)"):
+    """run_kmc's and run_kmc_ensemble's ``thermal_boundary`` option as dict(beta, T_ext, ramp) of six floats each, or None;
+    what they refuse of it (before any device call)"""
+    if value is None:
+        return None
+    if not mode_a:
+        raise ValueError(f"thermal_boundary needs {needs}")
+    if scheme != "implicit":
+        raise ValueError("thermal_boundary needs thermal_scheme='implicit' (the explicit update is adiabatic)")
+    if not thermal_updates:
+        raise ValueError("thermal_boundary needs thermal_updates=True (there is no update to bound)")
+    if isinstance(value, str) and value == "gradient":
+        return run_gradient_boundary(L, temp)
+    try:
+        out = {k: [float(x) for x in value.get(k, [0.0] * 6)] if k != "beta" else [float(x) for x in value["beta"]] for k in ("beta", "T_ext", "ramp")}
+        if all(len(v) == 6 for v in out.values()):
+            return out
+    except (AttributeError, KeyError, TypeError, ValueError):
+        pass
+    raise ValueError(f"thermal_boundary must be None, 'gradient' or a dict of six beta, T_ext and ramp values "
+                     f"(thermal_solver.thermal_boundary); got {value!r}")
+
+
 def _check_remelt(thr, mode_a, origin_metrics, thermal_updates):
     if thr is None:
         return
@@ -396,6 +428,7 @@ def run_kmc(
     remelt=False,
     thermal_substeps=1,
     thermal_scheme="explicit",
+    thermal_boundary=None,
     local_events: int = 0,
     local_horizon: float = 1.0,
 ):
@@ -518,11 +551,19 @@ def run_kmc(
     temperature update is ``thermal_substeps`` locally one-dimensional backward-Euler steps on the device
     (cetkmc_set_thermal_scheme), stable at any dt.  ``last_run_info["thermal_scheme"]`` reports it.
     Checkpoints carry the value only when it is not "explicit", and a resumed run must ask for the same.  Refused with
-    ValueError: ``mode="B"``, ``thermal_updates=False``."""
+    ValueError: ``mode="B"``, ``thermal_updates=False``.
+
+    ``thermal_boundary`` (mode "A" with ``thermal_scheme="implicit"`` only): ``"gradient"`` holds the imposed gradient -- the two
+    faces across the initial ramp are fixed at the ramp's next values (``run_gradient_boundary``), so the ramp is a fixed point
+    of the update -- or a dict from ``thermal_solver.thermal_boundary`` (a substrate sink, convective faces, a cooling rate);
+    cetkmc_set_thermal_boundary, DESIGN.md section 27.  ``last_run_info["thermal_boundary"]`` reports the dict (None without).
+    Checkpoints carry it (``extra["thermal_bc"]``) only when it is set, and a resumed run must ask for the same.  Refused with
+    ValueError: ``mode="B"``, any other ``thermal_scheme``, ``thermal_updates=False``."""
     import cetkmc
     n_sub = _thermal_substeps(thermal_substeps)
     _check_substeps(n_sub, mode == "A", thermal_updates)
     _check_scheme(thermal_scheme, mode == "A", thermal_updates)
+    face_bc = _thermal_boundary(thermal_boundary, L, temp, mode == "A", thermal_scheme, thermal_updates)
     remelt_thr = _remelt_threshold(remelt)
     _check_remelt(remelt_thr, mode == "A", origin_metrics, thermal_updates)
     _check_solid(solid_metrics, solid_every, bool(checkpoint_every or resume_from))
@@ -590,6 +631,12 @@ def run_kmc(
                          f"this call asks for {thermal_scheme!r}")
     if thermal_scheme != "explicit":
         engine.set_thermal_scheme(thermal_scheme)
+    if ckpt and ckpt["extra"].get("thermal_bc") != face_bc:
+        engine.close()
+        raise ValueError(f"checkpoint was written by a run with thermal_boundary={ckpt['extra'].get('thermal_bc')!r}, "
+                         f"this call asks for {face_bc!r}")
+    if face_bc is not None:
+        engine.set_thermal_boundary(face_bc)
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -660,6 +707,8 @@ def run_kmc(
             extra = dict(extra or {}, thermal_substeps=n_sub)
         if thermal_scheme != "explicit": # (likewise)
             extra = dict(extra or {}, thermal_scheme=thermal_scheme)
+        if face_bc is not None:          # (likewise)
+            extra = dict(extra or {}, thermal_bc=face_bc)
         save_checkpoint(os.path.join(output_dir, "checkpoint.npz"), engine.download(),
                         engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
                         at, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected, extra=extra)
@@ -794,7 +843,7 @@ def run_kmc(
     engine.close()
     last_run_info.clear()
     last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1, thermal_substeps=n_sub,
-                         thermal_scheme=thermal_scheme)
+                         thermal_scheme=thermal_scheme, thermal_boundary=face_bc)
     if remelt_thr is not None:
         last_run_info.update(remelted=remelted)
     if local_events:
@@ -895,7 +944,7 @@ def _replica_prefix(cfg, L):
 
 def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METRIC_UPDATE_STEP, thermal_updates=True,
                      front_metrics=False, layer_metrics=False, texture_metrics=False, grain_metrics=False, solid_metrics=False,
-                     solid_every=20, origin_metrics=False, thermal_substeps=1, thermal_scheme="explicit"):
+                     solid_every=20, origin_metrics=False, thermal_substeps=1, thermal_scheme="explicit", thermal_boundary=None):
     """Many independent run_kmc calls of the same L and n_steps stepped together on one GPU (cetkmc.Ensemble).
 
     ``configs``: one dict per replica with run_kmc's per-run arguments (temp, defect_fraction, n_seeds, impurity_c,
@@ -926,7 +975,9 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
     ``thermal_substeps``: run_kmc's option of that name, one value for all replicas (cetkmc_ensemble_set_thermal_substeps);
     ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_substeps"]``.
     ``thermal_scheme``: run_kmc's option of that name, one value for all replicas (cetkmc_ensemble_set_thermal_scheme);
-    ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_scheme"]``."""
+    ``rng="reference"`` only; ``last_ensemble_info[r]["thermal_scheme"]``.
+    ``thermal_boundary``: run_kmc's option of that name, one value for all replicas (cetkmc_ensemble_set_thermal_boundary);
+    ``"gradient"`` needs one ``temp`` for all; ``last_ensemble_info[r]["thermal_boundary"]``."""
     import cetkmc
     n_sub = _thermal_substeps(thermal_substeps)
     _check_substeps(n_sub, rng == "reference", thermal_updates)
@@ -934,6 +985,10 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                   needs="rng='reference' (the counter mode steps through the super-step engine, whose updates are explicit)")
     _check_solid(solid_metrics, solid_every, False)
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates, origin_metrics)
+    if thermal_boundary == "gradient" and len({float(c["temp"]) for c in cfgs}) != 1:
+        raise ValueError("thermal_boundary='gradient' needs one temp for all replicas (the ensemble shares one boundary)")
+    boundary = _thermal_boundary(thermal_boundary, int(L), cfgs[0]["temp"], rng == "reference", thermal_scheme, thermal_updates,
+                                 needs="rng='reference' (the counter mode steps through the super-step engine, whose updates are explicit)")
     L, n_steps, me, R = int(L), int(n_steps), int(metrics_every), len(cfgs)
     caller_py, caller_np = random.getstate(), np.random.get_state()
     ens = None
@@ -983,6 +1038,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             ens.set_thermal_substeps(n_sub)
         if thermal_scheme != "explicit":
             ens.set_thermal_scheme(thermal_scheme)
+        if boundary is not None:
+            ens.set_thermal_boundary(boundary)
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True
@@ -1130,7 +1187,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
             out.append((state, state.copy(), total_time[r], fields["theta"], fields["phi"]))
             last_ensemble_info.append(dict(random_state=gens[r].py, np_state=gens[r].np, executed_events=last_step[r] + 1,
                                            min_margin=min_margin[r] if rng == "reference" else None,
-                                           thermal_substeps=n_sub, thermal_scheme=thermal_scheme,
+                                           thermal_substeps=n_sub, thermal_scheme=thermal_scheme, thermal_boundary=boundary,
                                            **({"remelted": ri[r]["n_melted"]} if ri is not None else {})))
             print(f"[{c['output_prefix']}] completed {last_step[r] + 1} steps in {total_time[r]:.2e} s")
         return out

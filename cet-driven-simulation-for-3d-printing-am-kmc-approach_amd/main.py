@@ -15,6 +15,7 @@ outside the accelerated path and are not part of this package.
     python main.py --remelt [T]                   # remelting on the device: solid at or above T_MELT (or T) turns liquid (run_kmc remelt)
     python main.py --thermal-substeps N|stable    # sub-stepped temperature updates (run_kmc thermal_substeps; 'stable' = 17)
     python main.py --thermal-scheme implicit      # implicit temperature updates (run_kmc thermal_scheme)
+    python main.py --thermal-scheme implicit --thermal-boundary gradient|sink    # held gradient / substrate sink (run_kmc thermal_boundary)
     python main.py --origin                       # origin columns in every metrics.csv and an origin_layers.csv per level (run_kmc origin_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
@@ -53,7 +54,7 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
          layers=False, texture=False, grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1,
-         thermal_scheme="explicit", **run_kw):
+         thermal_scheme="explicit", thermal_boundary=None, **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
     rm = {"remelt": remelt} if remelt is not False and remelt is not None else {}      # --remelt: run_kmc's option / config key
     print("Starting KMC simulation for microstructure control...")
@@ -65,6 +66,9 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
         fm["thermal_substeps"] = thermal_substeps
     if thermal_scheme != "explicit":                  # --thermal-scheme: run_kmc's / run_kmc_ensemble's option of that name
         fm["thermal_scheme"] = thermal_scheme
+    if thermal_boundary is not None:                  # --thermal-boundary: run_kmc's / run_kmc_ensemble's option of that name
+        from thermal_solver import thermal_boundary as build_boundary
+        fm["thermal_boundary"] = build_boundary(bottom=("fixed", T_SUB)) if thermal_boundary == "sink" else thermal_boundary
     if layers:                                        # --layers: layer columns and layers.csv (run_kmc layer_metrics)
         fm["layer_metrics"] = True
     if texture:                                       # --texture: texture columns and texture.csv (run_kmc texture_metrics)
@@ -157,6 +161,9 @@ if __name__ == "__main__":
     ap.add_argument("--thermal-scheme", choices=("explicit", "implicit"), default="explicit",
                     help="every temperature update as locally one-dimensional backward-Euler steps on the device, stable at any dt "
                          "(run_kmc thermal_scheme, mode A)")
+    ap.add_argument("--thermal-boundary", choices=("gradient", "sink"), default=None,
+                    help="with --thermal-scheme implicit: 'gradient' holds the imposed ramp (fixed faces at its next values), 'sink' "
+                         "fixes T_SUB under the substrate face; every other face adiabatic (run_kmc thermal_boundary, mode A)")
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
@@ -166,4 +173,4 @@ if __name__ == "__main__":
         kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
          grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt, thermal_substeps=a.thermal_substeps,
-         thermal_scheme=a.thermal_scheme, **kw)
+         thermal_scheme=a.thermal_scheme, thermal_boundary=a.thermal_boundary, **kw)

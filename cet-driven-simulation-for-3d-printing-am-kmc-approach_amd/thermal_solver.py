@@ -109,6 +109,47 @@ def _check_scheme(scheme, where="scheme"):
     return scheme
 
 
+FACES = ("i_lo", "i_hi", "j_lo", "j_hi", "k_lo", "k_hi")        # cetkmc's face order: i_lo the substrate side, i_hi the top
+
+
+def _face_group(spec, where):
+    """(beta, T, fixed) of "adiabatic", ("fixed", T) or ("convective", h [W/m^2-K], T_ambient)"""
+    if spec is None or spec == "adiabatic":
+        return 0.0, 0.0, False
+    try:
+        kind = spec[0]
+        if kind == "fixed" and len(spec) == 2:
+            return 1.0, float(spec[1]), True
+        if kind == "convective" and len(spec) == 3:
+            return float(spec[1]) * VOXEL_SIZE / K, float(spec[2]), False
+    except (TypeError, IndexError, ValueError):
+        pass
+    raise ValueError(f"thermal_boundary: {where} must be 'adiabatic', ('fixed', T) or ('convective', h, T_ambient) (got {spec!r})")
+
+
+def thermal_boundary(bottom="adiabatic", top="adiabatic", sides="adiabatic", cooling_rate=0.0, dt=1e-6):
+    """The boundary of the implicit temperature updates (not in the reference) as
+    dict(beta=, T_ext=, ramp=), six values each in the order FACES.  ``bottom`` is face i_lo, ``top`` face i_hi, ``sides`` the
+    four j and k faces; each "adiabatic", ("fixed", T [K]) or ("convective", h [W/m^2-K], T_ambient [K]) with
+    beta = h * VOXEL_SIZE / K.  ``cooling_rate`` [K/s] lowers the fixed faces by cooling_rate * dt per temperature update."""
+    groups = [_face_group(bottom, "bottom"), _face_group(top, "top")] + [_face_group(sides, "sides")] * 4
+    return dict(beta=[g[0] for g in groups], T_ext=[g[1] for g in groups],
+                ramp=[-float(cooling_rate) * float(dt) if g[2] else 0.0 for g in groups])
+
+
+def gradient_boundary(L, T_bottom=T_SUB, T_top=T_MELT, cooling_rate=0.0, dt=1e-6):
+    """The two fixed i faces whose ghost temperatures extend ``build_temperature_field``'s ramp by one voxel, so that the ramp
+    is a fixed point of the implicit update; every other face adiabatic."""
+    slope = (T_top - T_bottom) / (L - 1) if L > 1 else 0.0
+    return thermal_boundary(bottom=("fixed", T_bottom - slope), top=("fixed", T_top + slope), cooling_rate=cooling_rate, dt=dt)
+
+
+def _check_boundary(boundary, scheme, where):
+    if boundary is not None and scheme != "implicit":
+        raise ValueError(f"{where}: boundary= needs scheme='implicit' (the explicit update is adiabatic)")
+    return boundary
+
+
 def laser_scan_planes(L, laser, first_step, n_steps):
     """Source planes (n, L, L) of the temperature updates that fall in the global steps [first_step, first_step + n_steps):
     one per step g with g % 20 == 0, in step order.  ``laser`` is a dict: ``power`` [W], ``start`` (beam centre at update
@@ -129,45 +170,51 @@ def laser_scan_planes(L, laser, first_step, n_steps):
 
 
 def update_temperature(T, state, prev_state, dt, laser_pos, laser_power,
-                       beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, substeps=1, scheme="explicit"):
+                       beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, substeps=1, scheme="explicit", boundary=None):
     """Explicit Euler step with Laplacian + Gaussian surface source on i=L-1 + latent heat where
     ``prev_state==0 & state!=0``; clipped to [T_SUB, 1.1*T_MELT] (thermal_solver.py:36-105).  ``substeps=n`` (not in the
     reference): n such steps of dt / n from the same source, the latent heat in the first (``stable_substeps``).
     ``scheme="implicit"`` (not in the reference): the steps are locally one-dimensional backward-Euler steps, stable at any dt
-    (DESIGN.md section 26)."""
+    (DESIGN.md section 26); ``boundary`` (``thermal_boundary``; implicit only): its faces, at update 0 (section 27)."""
     L = T.shape[0]
     assert T.shape == (L, L, L)
     assert state.shape == T.shape and prev_state.shape == T.shape
     substeps = _check_substeps(substeps)
-    _check_scheme(scheme)
+    _check_boundary(boundary, _check_scheme(scheme), "update_temperature")
     eng = _engine(L)
     eng.upload(state=state, T=T)
     eng.set_prev_state(prev_state)
     eng.set_thermal_substeps(substeps)
     try:
         eng.set_thermal_scheme(scheme)
+        if boundary is not None:
+            eng.set_thermal_boundary(boundary)
         eng.thermal_laser(dt, laser_source_plane(L, laser_pos, laser_power, beam_radius, absorptivity),
                           use_latent=True, scrub_nan=False)
     finally:
         eng.set_thermal_substeps(1)        # the handle is cached
+        eng.set_thermal_boundary(None)
         eng.set_thermal_scheme("explicit")
     return eng.download(state=False, theta=False, phi=False, T=True)["T"]
 
 
-def update_temperature_cet(T, state, dt=1e-6, substeps=1, scheme="explicit"):
+def update_temperature_cet(T, state, dt=1e-6, substeps=1, scheme="explicit", boundary=None):
     """Diffusion-only step used by run_kmc; ``state`` is unused, as in the reference
     (thermal_solver.py:107-117).  ``substeps=n`` (not in the reference): n such steps of dt / n; ``scheme="implicit"`` (not in
-    the reference): implicit steps."""
+    the reference): implicit steps; ``boundary``: as in ``update_temperature``."""
     L = T.shape[0]
     substeps = _check_substeps(substeps)
-    _check_scheme(scheme)
+    _check_boundary(boundary, _check_scheme(scheme), "update_temperature_cet")
     eng = _engine(L)
     eng.upload(T=T)
     eng.set_thermal_substeps(substeps)
     try:
         eng.set_thermal_scheme(scheme)
+        if boundary is not None:
+            eng.set_thermal_boundary(boundary)
         eng.thermal_cet(dt, scrub_nan=False)
     finally:
         eng.set_thermal_substeps(1)
+        eng.set_thermal_boundary(None)
         eng.set_thermal_scheme("explicit")
     return eng.download(state=False, theta=False, phi=False, T=True)["T"]

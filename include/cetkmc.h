@@ -205,7 +205,8 @@ int cetkmc_abi_version(void);
 const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
- * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info", "implicit_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info", "implicit_info",
+ * "thermal_boundary", "boundary_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -930,6 +931,41 @@ int cetkmc_set_thermal_scheme(void* handle, int scheme);
 int cetkmc_ensemble_set_thermal_scheme(void* handle, int scheme);
 int cetkmc_get_implicit_info(void* handle, struct cetkmc_implicit_info* info);
 int cetkmc_implicit_coeffs(int L, double r, double* inv, double* p);
+
+/* ---- thermal boundary conditions of the implicit scheme ----------------------------------------------
+ * Opt-in; with no boundary set (or every beta 0) every update is section 26's, launch for launch.  Six faces, in the order of the
+ * enum: i_lo is the substrate side, i_hi the top (plane L - 1).  Face f carries beta[f] >= 0, T_ext[f] and ramp[f]; the voxel on
+ * the face sees a ghost node of value x + beta * (T_f - x): beta = 0 adiabatic, 1 a fixed temperature at the ghost node,
+ * h dx / k a convective face, any finite beta >= 0 allowed.  One implicit step is section 26's with the 1-D operator of an
+ * axis with faces (lo, hi) changed at its two ends only:
+ *   diagonal     row 0: 1 + r (1 + beta_lo), row L - 1: 1 + r (1 + beta_hi), L = 1: 1 + r (beta_lo + beta_hi); inside 1 + 2 r;
+ *   coefficients inv[0] = 1 / diag_0, p[0] = r inv[0], inv[m] = 1 / (diag_m - r p[m - 1]), p[m] = r inv[m]
+ *                (cetkmc_implicit_coeffs_bc; both beta 0: the bits of cetkmc_implicit_coeffs);
+ *   right side   c_f = (r * beta_f) * T_f, in double on the host; y[0] = (b[0] + c_lo) inv[0], and for L > 1
+ *                y[L - 1] = ((b[L - 1] + c_hi) + r y[L - 2]) inv[L - 1]; L = 1: ((b + c_lo) + c_hi) inv[0].  An addend is applied
+ *                only where beta_f != 0: an adiabatic face keeps section 26's arithmetic, -0.0 included.
+ * The face temperature of an update: T_f = T_ext[f] + ramp[f] * (double)u, u = g / 20 for the update a stepping call makes at
+ * global step g (independent of how a run is cut into calls), u = 0 for a direct update and for cetkmc_time_thermal.  T_f is
+ * not clipped.  thermal_substeps = n: n steps with the r of dt / n and the same T_f.  Remelting follows the update as before.
+ *   cetkmc_set_thermal_boundary            a single handle; NULL = adiabatic.  Invalidates nothing, leaves the applied-update marker
+ *   cetkmc_ensemble_set_thermal_boundary   an ensemble handle: one boundary for all replicas
+ *   cetkmc_get_thermal_boundary            the boundary as set (b) and running totals (info) of the updates made with a
+ *                      non-adiabatic boundary: updates, their steps, their launches (three per step: the boundary
+ *                      instantiations of k_imp_rows, k_imp_lines<1>, k_imp_lines<0>) and rebuilds of the device's [3][2][L] table (one per change of r or
+ *                      of a beta; a changed T_ext or ramp travels in the launch).  Either pointer may be NULL.
+ *                      cetkmc_get_implicit_info goes on counting every implicit update.
+ *   cetkmc_implicit_coeffs_bc              the host routine behind the table; needs no device
+ * Refused, before anything is allocated or launched: a negative or non-finite beta; a non-finite T_ext or ramp; a non-adiabatic
+ * boundary while the scheme is explicit, and the explicit scheme while a non-adiabatic boundary is set; the per-handle setter on
+ * an ensemble's handle or on its replicas; a stepping call one of whose own updates would have a non-finite T_f on a face with
+ * beta != 0; cetkmc_implicit_coeffs_bc with L < 1, a non-finite or negative r or beta. */
+enum { CETKMC_FACE_I_LO = 0, CETKMC_FACE_I_HI, CETKMC_FACE_J_LO, CETKMC_FACE_J_HI, CETKMC_FACE_K_LO, CETKMC_FACE_K_HI };
+struct cetkmc_thermal_boundary { double beta[6], T_ext[6], ramp[6]; };
+struct cetkmc_boundary_info { int64_t updates, steps, launches, coeff_uploads; };
+int cetkmc_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b);
+int cetkmc_ensemble_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b);
+int cetkmc_get_thermal_boundary(void* handle, struct cetkmc_thermal_boundary* b, struct cetkmc_boundary_info* info);
+int cetkmc_implicit_coeffs_bc(int L, double r, double beta_lo, double beta_hi, double* inv, double* p);
 
 #ifdef __cplusplus
 }
