@@ -189,17 +189,74 @@ def _boundary_struct(boundary, where):
     return C.byref(b)
 
 
-def _boundary_get(lib, ck, h):
-    b, info = _lib.ThermalBoundary(), _lib.BoundaryInfo()
-    ck(lib.cetkmc_get_thermal_boundary(h, C.byref(b), C.byref(info)))
-    return ({n: [float(x) for x in getattr(b, n)] for n, _ in _lib.ThermalBoundary._fields_},
-            {n: int(getattr(info, n)) for n, _ in _lib.BoundaryInfo._fields_})
+def _info_dict(info):
+    """an info record of the library (a ctypes structure of integers) as a dict"""
+    return {n: int(getattr(info, n)) for n, _ in info._fields_}
 
 
-class Engine:
+class _ThermalSettings:
+    """How a temperature update is made (DESIGN.md sections 25-27): the setters and info records that :class:`Engine` and
+    :class:`Ensemble` share.  The class names the symbol prefix of its setters (``_SET``) and itself (``_WHO``, which the
+    ValueErrors of a wrapper carry); the getters are the same symbols for both."""
+
+    def _set(self, name, value):
+        self._ck(getattr(self.lib, self._SET + name)(self.h, value))
+
+    def _get_info(self, name, record):
+        info = record()
+        self._ck(getattr(self.lib, name)(self.h, C.byref(info)))
+        return _info_dict(info)
+
+    def _boundary_get(self):
+        b, info = _lib.ThermalBoundary(), _lib.BoundaryInfo()
+        self._ck(self.lib.cetkmc_get_thermal_boundary(self.h, C.byref(b), C.byref(info)))
+        return {n: [float(x) for x in getattr(b, n)] for n, _ in b._fields_}, _info_dict(info)
+
+    # -- sub-stepped temperature updates (DESIGN.md section 25) ------------------------------------------
+    def set_thermal_substeps(self, n):
+        """cetkmc_set_thermal_substeps: every temperature update of the handle becomes ``n`` applications of the explicit
+        step with ``dt / n`` (1: as before).  Ensemble (cetkmc_ensemble_set_thermal_substeps): one sub-step count for every
+        replica's temperature updates in ``run``."""
+        self._set("set_thermal_substeps", int(n))
+
+    def substep_info(self):
+        """cetkmc_get_substep_info: dict(updates, substeps, launches, blocked_launches), running totals of the updates made
+        while thermal_substeps > 1.  Ensemble: of the ensemble handle, the totals of its calls."""
+        return self._get_info("cetkmc_get_substep_info", _lib.SubstepInfo)
+
+    # -- implicit temperature updates (DESIGN.md section 26) ---------------------------------------------
+    def set_thermal_scheme(self, scheme):
+        """cetkmc_set_thermal_scheme: "explicit" (the default) or "implicit" -- every temperature update becomes
+        ``thermal_substeps`` locally one-dimensional backward-Euler steps.  Ensemble (cetkmc_ensemble_set_thermal_scheme):
+        every replica's temperature update in ``run``."""
+        self._set("set_thermal_scheme", _scheme_value(scheme, self._WHO + ".set_thermal_scheme"))
+
+    def implicit_info(self):
+        """cetkmc_get_implicit_info: dict(updates, steps, launches, coeff_uploads), running totals of the implicit updates."""
+        return self._get_info("cetkmc_get_implicit_info", _lib.ImplicitInfo)
+
+    # -- thermal boundary conditions (DESIGN.md section 27) ----------------------------------------------
+    def set_thermal_boundary(self, boundary):
+        """cetkmc_set_thermal_boundary: None (adiabatic) or dict(beta=, T_ext=, ramp=), six values each in the order of
+        ``cetkmc.engine.FACES``; needs the implicit scheme unless every beta is 0.  Ensemble
+        (cetkmc_ensemble_set_thermal_boundary): one boundary for all replicas."""
+        self._set("set_thermal_boundary", _boundary_struct(boundary, self._WHO + ".set_thermal_boundary"))
+
+    def thermal_boundary(self):
+        """the boundary as set: dict(beta, T_ext, ramp) of six floats each (all zero: adiabatic)"""
+        return self._boundary_get()[0]
+
+    def boundary_info(self):
+        """dict(updates, steps, launches, coeff_uploads): running totals of the updates made with a non-adiabatic boundary"""
+        return self._boundary_get()[1]
+
+
+class Engine(_ThermalSettings):
     """Owns a cetkmc handle.  ``n_slabs>1`` splits the lattice into axis-0 slabs on the same
     GPU (decomposition check); ``rank/nranks/unique_id`` selects the one-process-per-GPU
     RCCL mode."""
+
+    _SET, _WHO = "cetkmc_", "Engine"
 
     def __init__(self, L, impurity_c=0.0, params=None, n_slabs=1, device=0, rank=None, nranks=None, unique_id=None,
                  host_comm=None):
@@ -731,7 +788,7 @@ class Engine:
         """cetkmc_remelt: one pass now.  Returns the counters as ``remelt_info`` does."""
         info = _lib.RemeltInfo()
         self._ck(self.lib.cetkmc_remelt(self.h, float(self.params.T_melt if threshold is None else threshold), C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in _lib.RemeltInfo._fields_}
+        return _info_dict(info)
 
     def time_remelt(self, n, threshold=None):
         """cetkmc_time_remelt: device ms of n passes (one hipEvent pair), measurement only."""
@@ -744,46 +801,7 @@ class Engine:
         at the end of the last stepping call or direct pass."""
         info = _lib.RemeltInfo()
         self._ck(self.lib.cetkmc_get_remelt_info(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in _lib.RemeltInfo._fields_}
-
-    # -- sub-stepped temperature updates (DESIGN.md section 25) ------------------------------------------
-    def set_thermal_substeps(self, n):
-        """cetkmc_set_thermal_substeps: every temperature update of the handle becomes ``n`` applications of the explicit
-        step with ``dt / n`` (1: as before)."""
-        self._ck(self.lib.cetkmc_set_thermal_substeps(self.h, int(n)))
-
-    def substep_info(self):
-        """cetkmc_get_substep_info: dict(updates, substeps, launches, blocked_launches), running totals of the updates made
-        while thermal_substeps > 1."""
-        info = _lib.SubstepInfo()
-        self._ck(self.lib.cetkmc_get_substep_info(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
-
-    # -- implicit temperature updates (DESIGN.md section 26) ---------------------------------------------
-    def set_thermal_scheme(self, scheme):
-        """cetkmc_set_thermal_scheme: "explicit" (the default) or "implicit" -- every temperature update becomes
-        ``thermal_substeps`` locally one-dimensional backward-Euler steps."""
-        self._ck(self.lib.cetkmc_set_thermal_scheme(self.h, _scheme_value(scheme, "Engine.set_thermal_scheme")))
-
-    def implicit_info(self):
-        """cetkmc_get_implicit_info: dict(updates, steps, launches, coeff_uploads), running totals of the implicit updates."""
-        info = _lib.ImplicitInfo()
-        self._ck(self.lib.cetkmc_get_implicit_info(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in _lib.ImplicitInfo._fields_}
-
-    # -- thermal boundary conditions (DESIGN.md section 27) ----------------------------------------------
-    def set_thermal_boundary(self, boundary):
-        """cetkmc_set_thermal_boundary: None (adiabatic) or dict(beta=, T_ext=, ramp=), six values each in the order of
-        ``cetkmc.engine.FACES``; needs the implicit scheme unless every beta is 0."""
-        self._ck(self.lib.cetkmc_set_thermal_boundary(self.h, _boundary_struct(boundary, "Engine.set_thermal_boundary")))
-
-    def thermal_boundary(self):
-        """the boundary as set: dict(beta, T_ext, ramp) of six floats each (all zero: adiabatic)"""
-        return _boundary_get(self.lib, self._ck, self.h)[0]
-
-    def boundary_info(self):
-        """dict(updates, steps, launches, coeff_uploads): running totals of the updates made with a non-adiabatic boundary"""
-        return _boundary_get(self.lib, self._ck, self.h)[1]
+        return _info_dict(info)
 
     def time_thermal(self, n_updates, laser=False):
         """cetkmc_time_thermal: device ms of n_updates temperature updates (dt = 1e-6 s, one hipEvent pair).  The updates are
@@ -840,11 +858,13 @@ class _Replica(Engine):
         self.h = None
 
 
-class Ensemble:
+class Ensemble(_ThermalSettings):
     """R independent lattices of edge L (1 <= L <= 128) on one GPU, stepped together (cetkmc_create_ensemble /
     cetkmc_run_ensemble).  ``params`` is one cetkmc_params per replica (they may differ in
     impurity_c and nu_dep only); ``replica(r)`` is an :class:`Engine` view of lattice r for uploads, downloads and the
     analysis calls."""
+
+    _SET, _WHO = "cetkmc_ensemble_", "Ensemble"
 
     def __init__(self, L, params, device=0):
         self.lib = _lib.load()
@@ -938,47 +958,11 @@ class Ensemble:
         thr = float(self.params[0].T_melt if threshold is None else threshold)
         self._ck(self.lib.cetkmc_ensemble_set_remelt(self.h, int(bool(on)), thr))
 
-    def set_thermal_substeps(self, n):
-        """cetkmc_ensemble_set_thermal_substeps: one sub-step count for every replica's temperature updates in ``run``."""
-        self._ck(self.lib.cetkmc_ensemble_set_thermal_substeps(self.h, int(n)))
-
-    def substep_info(self):
-        """cetkmc_get_substep_info of the ensemble handle: dict(updates, substeps, launches, blocked_launches) of its calls."""
-        info = _lib.SubstepInfo()
-        self._ck(self.lib.cetkmc_get_substep_info(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in _lib.SubstepInfo._fields_}
-
-    # -- implicit temperature updates (DESIGN.md section 26) ---------------------------------------------
-    def set_thermal_scheme(self, scheme):
-        """cetkmc_ensemble_set_thermal_scheme: "explicit" (the default) or "implicit" -- every replica's temperature update in ``run`` becomes
-        ``thermal_substeps`` locally one-dimensional backward-Euler steps."""
-        self._ck(self.lib.cetkmc_ensemble_set_thermal_scheme(self.h, _scheme_value(scheme, "Ensemble.set_thermal_scheme")))
-
-    def implicit_info(self):
-        """cetkmc_get_implicit_info: dict(updates, steps, launches, coeff_uploads), running totals of the implicit updates."""
-        info = _lib.ImplicitInfo()
-        self._ck(self.lib.cetkmc_get_implicit_info(self.h, C.byref(info)))
-        return {n: int(getattr(info, n)) for n, _ in _lib.ImplicitInfo._fields_}
-
-    # -- thermal boundary conditions (DESIGN.md section 27) ----------------------------------------------
-    def set_thermal_boundary(self, boundary):
-        """cetkmc_ensemble_set_thermal_boundary: one boundary for all replicas; None (adiabatic) or dict(beta=, T_ext=, ramp=), six values each in the order of
-        ``cetkmc.engine.FACES``; needs the implicit scheme unless every beta is 0."""
-        self._ck(self.lib.cetkmc_ensemble_set_thermal_boundary(self.h, _boundary_struct(boundary, "Ensemble.set_thermal_boundary")))
-
-    def thermal_boundary(self):
-        """the boundary as set: dict(beta, T_ext, ramp) of six floats each (all zero: adiabatic)"""
-        return _boundary_get(self.lib, self._ck, self.h)[0]
-
-    def boundary_info(self):
-        """dict(updates, steps, launches, coeff_uploads): running totals of the updates made with a non-adiabatic boundary"""
-        return _boundary_get(self.lib, self._ck, self.h)[1]
-
     def remelt_info(self):
         """cetkmc_ensemble_remelt_info: one dict(passes, n_melted, n_melted_last, n_appended) per replica."""
         buf = (_lib.RemeltInfo * max(self.R, 1))()
         self._ck(self.lib.cetkmc_ensemble_remelt_info(self.h, buf))
-        return [{n: int(getattr(buf[r], n)) for n, _ in _lib.RemeltInfo._fields_} for r in range(self.R)]
+        return [_info_dict(buf[r]) for r in range(self.R)]
 
     def analyze(self, threshold=0.5, species=-1, labels=True):
         """Clustering, species counts, nucleation counts and (species >= 0) the sorted (index, T) gather of every replica,

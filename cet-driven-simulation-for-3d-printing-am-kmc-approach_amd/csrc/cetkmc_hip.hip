@@ -70,11 +70,13 @@ void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t shmem, hipStream
 }
 
 // Run-time flags -> template arguments: f is called once, with std::true_type / std::false_type values, for exactly the
-// combinations the kernels are built for.  with_source: (LASER, LATENT) of the temperature tiles.
+// combinations the kernels are built for.  with_source: (LASER, LATENT) of the temperature tiles.  with_boundary: the ImpBc that
+// leads the trailing pack of the implicit kernels' boundary form, or nothing.
 using Yes = std::true_type;
 using No = std::false_type;
 template <class F> void with_flag(bool on, F&& f) { if (on) f(Yes{}); else f(No{}); }
 template <class F> void with_source(int laser, int latent, F&& f) { if (laser && latent) f(Yes{}, Yes{}); else if (laser) f(Yes{}, No{}); else f(No{}, No{}); }
+template <class F> void with_boundary(bool on, const ImpBc& B, F&& f) { if (on) f(B); else f(); }
 
 // 20-step temperature updates (kmc_simulation.py:248) among the global steps [step0, step0 + n): multiples of 20 below
 // step0 + n less those below step0
@@ -129,6 +131,22 @@ int load_rccl()
     } while (0)
 
 // ---- handle ---------------------------------------------------------------------------
+// How temperature updates are made (DESIGN.md sections 24 to 27), as the setters leave it.  A handle holds one; an ensemble holds
+// one for all its replicas and hands it to each (share_thermal), so a direct update on a replica handle follows the ensemble.
+struct ThermalSettings {
+    int substeps = 1;                    // n: every update is n steps of dt / n (thermal_sub.hpp)
+    int scheme = CETKMC_THERMAL_EXPLICIT;        // or _IMPLICIT (thermal_imp.hpp)
+    cetkmc_thermal_boundary bc{};        // as set; every beta 0: adiabatic, the launches and the table of section 26
+    bool bc_on = false;                  // some beta != 0
+    int remelt_on = 0;                   // the stepping loop melts behind every temperature update (melt.hpp)
+    double remelt_threshold = 0.0;
+};
+// what the updates made so far add up to: a handle's by its own calls, an ensemble's by cetkmc_run_ensemble
+struct ThermalInfo { cetkmc_substep_info sub{}; cetkmc_implicit_info imp{}; cetkmc_boundary_info bc{}; };
+// A device table of Thomas coefficients and what it was built for (compared by bits): [2][L], inv and p of r (section 26), or
+// [3][2][L], inv and p per axis of r and the six beta (section 27).  Allocated by the first update that reads it.
+struct CoefTable { double* d = nullptr; double r = 0.0, beta[6] = {}; };
+
 struct Slab {
     SlabView v{};
     uint8_t* prev = nullptr;
@@ -280,28 +298,15 @@ struct Handle {
     // is first used
     MeltState melt{};
     void* d_melt_block = nullptr;
-    int remelt_on = 0;           // the stepping loop melts behind every temperature update
-    double remelt_threshold = 0.0;
     cetkmc_remelt_info melt_info{};      // the counters as last read (end of a stepping call, end of a direct pass)
-    // sub-stepped temperature updates (cetkmc_set_thermal_substeps, thermal_sub.hpp)
-    int thermal_substeps = 1;    // n: every update is n applications of the explicit step with dt / n
+    ThermalSettings ts{};        // cetkmc_set_remelt / _thermal_substeps / _thermal_scheme / _thermal_boundary
+    ThermalInfo ti{};
+    CoefTable coef{}, coef_bc{}; // of the implicit updates without / with a boundary (two: clearing a boundary uploads nothing)
+    // sub-stepped temperature updates (thermal_sub.hpp)
     int substep_block = 0;       // option "substep_block": sub-steps per k_thermal_sub launch; 0 = the measured default (SUB_SDEFAULT at
                                  // L > SUB_PLAIN_L, else the plain path), 1 = the plain path (n launches of the existing kernel) on any handle
     int substep_planes = 0;      // option "substep_planes": planes per block of k_thermal_sub; 0 = one round of blocks on the device
     int n_cu = 0;                // compute units of the device (read when first needed)
-    cetkmc_substep_info sub_info{};
-    // implicit temperature updates (cetkmc_set_thermal_scheme, thermal_imp.hpp)
-    int thermal_scheme = CETKMC_THERMAL_EXPLICIT;
-    double* d_imp_coef = nullptr;        // [2][L]: inv, p of imp_r (allocated by the first implicit update)
-    double imp_r = 0.0;                  // the r the device table was built for (compared by bits)
-    cetkmc_implicit_info imp_info{};
-    // thermal boundary conditions of the implicit updates (cetkmc_set_thermal_boundary)
-    cetkmc_thermal_boundary bc{};        // as set; every beta 0: adiabatic, the launches and the table of section 26
-    bool bc_on = false;                  // some beta != 0
-    double* d_bc_coef = nullptr;         // [3][2][L]: inv, p per axis for bc_r and bc_beta (allocated by the first boundary update)
-    double bc_r = 0.0, bc_beta[6] = {};  // what the device table was built for (compared by bits)
-    int64_t bc_u = 0;                    // the update ordinal g / 20 of the stepping call's update being queued
-    cetkmc_boundary_info bc_info{};
 };
 
 // ---- cache state ------------------------------------------------------------------------------------
@@ -814,6 +819,28 @@ int refresh_ifc_grid(Handle* h)
 
 // ---- collectives: RCCL on the stream, or relayed through host callbacks (bring-up / test transport) ------
 inline bool multi_rank(const Handle* h) { return h->comm != nullptr || h->hc.allgather != nullptr; }
+// refused by `who` (a function, or a function and what of it) unless the handle is one slab in one process; why: " (...)" or ""
+int one_slab_only(const Handle* h, const std::string& who, const char* why)
+{
+    if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h)) return fail(who + " needs the whole lattice in one slab of one process" + why);
+    return 0;
+}
+// What a thermal setting rules out elsewhere, one row per setting: Mode B stepping (fn: the driver) and, its mirror image, the
+// look-ahead option (fn null).  The first setting that is on refuses.
+int thermal_exclusions(const ThermalSettings& s, const char* fn)
+{
+    const struct { bool on; const char *what, *setter, *mode_b, *ahead; } rows[] = {
+        {s.remelt_on != 0, "remelting is on", "cetkmc_set_remelt", "Mode B has no melt", "the field computed ahead knows no melt"},
+        {s.substeps > 1, "thermal_substeps > 1", "cetkmc_set_thermal_substeps", "Mode B updates are not sub-stepped", "the field computed ahead is one explicit step"},
+        {s.scheme == CETKMC_THERMAL_IMPLICIT, "the thermal scheme is implicit", "cetkmc_set_thermal_scheme", "Mode B updates are explicit", "the field computed ahead is one explicit step"},
+    };
+    for (const auto& r : rows) {
+        if (!r.on) continue;
+        if (fn) return fail(std::string(fn) + " is refused while " + r.what + " (" + r.setter + "): " + r.mode_b);
+        return fail(std::string("cetkmc_set_option: thermal_lookahead = 1 is refused while ") + r.what + " (" + r.ahead + ")");
+    }
+    return 0;
+}
 
 // profile 2: one more hipEvent of the batch's collective timers, recorded on the stream now (nullptr when not timing)
 int comm_stamp(Handle* h)
@@ -1210,59 +1237,16 @@ int launch_thermal_sub(Handle* h, double dt_s, int laser, const double* d_q, int
         HIPCHK(hipGetLastError());
         h->cnt.alg_bytes_thermal += (int64_t)16 * v.nloc * h->L * h->L;     // T read + written, once per launch
         h->cur = nxt;
-        ++h->sub_info.launches; ++h->sub_info.blocked_launches;
+        ++h->ti.sub.launches; ++h->ti.sub.blocked_launches;
         m -= s;
     }
     invalidate(h, Cause::thermal_update);       // the table sub-step 1 may have written belongs to an intermediate field
     return 0;
 }
 
-// ---- implicit updates (thermal_imp.hpp) -------------------------------------------------------------
-// the Thomas coefficients of (I - r D) at edge L, in double, exactly as include/cetkmc.h states them
-int implicit_coeffs_host(const char* fn, int L, double r, double* inv, double* p)
-{
-    const std::string f(fn);
-    if (!inv || !p) return fail(f + ": null argument");
-    if (L < 1) return fail(f + ": L must be >= 1 (got " + std::to_string(L) + ")");
-    if (!std::isfinite(r)) return fail(f + ": r is not finite");
-    if (r < 0.0) return fail(f + ": r must be >= 0");
-    inv[0] = (L == 1) ? 1.0 : 1.0 / (1.0 + r);      // L = 1: D = 0, the solve is the identity
-    p[0] = r * inv[0];
-    for (int m = 1; m < L; ++m) {
-        const double beta = ((m < L - 1) ? (1.0 + 2.0 * r) : (1.0 + r)) - r * p[m - 1];
-        inv[m] = 1.0 / beta;
-        p[m] = r * inv[m];
-    }
-    return 0;
-}
-// the device table of the handle for this r: rebuilt when r changes (a handle's L never does)
-int imp_ensure_coeffs(Handle* h, double r)
-{
-    if (h->d_imp_coef && !memcmp(&h->imp_r, &r, sizeof r)) return 0;
-    std::vector<double> tab((size_t)2 * h->L);
-    CHK(implicit_coeffs_host("implicit update", h->L, r, tab.data(), tab.data() + h->L));
-    if (!h->d_imp_coef && hipMalloc((void**)&h->d_imp_coef, tab.size() * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_imp_coef = nullptr;
-        return fail("implicit update: no device memory for " + std::to_string(tab.size() * 8) + " bytes");
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));          // launches that read the table of the previous r
-    HIPCHK(hipMemcpy(h->d_imp_coef, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    h->imp_r = r;
-    ++h->imp_info.coeff_uploads;
-    return 0;
-}
-ImpCfg imp_cfg(const Handle* h, double dt_s, int laser, int use_latent, int scrub)
-{
-    ImpCfg C{};
-    C.r = (h->p.alpha * dt_s) * h->p.inv_dx2; C.dt = dt_s; C.dF = 1.0 / (dt_s > 1e-12 ? dt_s : 1e-12);
-    C.clip_lo = h->p.T_clip_lo; C.clip_hi = h->p.T_clip_hi; C.T_nan = h->p.T_nan; C.rho_cp = h->p.rho_cp; C.latent_coef = h->p.latent_coef;
-    C.coef = h->d_imp_coef; C.laser = laser; C.use_latent = use_latent; C.scrub = scrub;
-    return C;
-}
-// ---- thermal boundary conditions ---------------------------------------------------------------------
-// the Thomas coefficients of one axis whose faces carry beta_lo, beta_hi, exactly as include/cetkmc.h states them; both 0: the
-// bits of implicit_coeffs_host
+// ---- implicit updates and their boundary conditions (thermal_imp.hpp, DESIGN.md sections 26 and 27) -------------------------
+// the Thomas coefficients of one axis whose faces carry beta_lo, beta_hi, exactly as include/cetkmc.h states them; both 0: those
+// of (I - r D) between insulated walls (L = 1: D = 0, the solve is the identity), bit for bit as cetkmc_implicit_coeffs states them
 int implicit_coeffs_bc_host(const char* fn, int L, double r, double beta_lo, double beta_hi, double* inv, double* p)
 {
     const std::string f(fn);
@@ -1311,24 +1295,27 @@ int boundary_steps_ok(const char* fn, const cetkmc_thermal_boundary& b, int64_t 
                             std::to_string(g) + " (T_ext + ramp * " + std::to_string(g / 20) + ")");
     return 0;
 }
-// the device table [3][2][L] of the handle for this r and the boundary's six beta: rebuilt when any of them changes
-int bc_ensure_coeffs(Handle* h, double r, const cetkmc_thermal_boundary& b, cetkmc_boundary_info* info)
+// a device table of the handle for this r (beta null: [2][L]) or for this r and a boundary's six beta ([3][2][L]): rebuilt when
+// any of them changes (a handle's L never does), the upload counted where the caller says
+int ensure_coeffs(Handle* h, CoefTable& t, double r, const double* beta, int64_t* uploads)
 {
-    if (h->d_bc_coef && !memcmp(&h->bc_r, &r, sizeof r) && !memcmp(h->bc_beta, b.beta, sizeof h->bc_beta)) return 0;
-    const size_t L = (size_t)h->L;
-    std::vector<double> tab(6 * L);
-    for (int ax = 0; ax < 3; ++ax)
-        CHK(implicit_coeffs_bc_host("implicit update", h->L, r, b.beta[2 * ax], b.beta[2 * ax + 1], tab.data() + 2 * ax * L, tab.data() + (2 * ax + 1) * L));
-    if (!h->d_bc_coef && hipMalloc((void**)&h->d_bc_coef, tab.size() * 8) != hipSuccess) {
+    const double none[6] = {};
+    const size_t L = (size_t)h->L, axes = beta ? 3 : 1;
+    if (!beta) beta = none;
+    if (t.d && !memcmp(&t.r, &r, sizeof r) && !memcmp(t.beta, beta, sizeof t.beta)) return 0;
+    std::vector<double> tab(2 * axes * L);
+    for (size_t ax = 0; ax < axes; ++ax)
+        CHK(implicit_coeffs_bc_host("implicit update", h->L, r, beta[2 * ax], beta[2 * ax + 1], tab.data() + 2 * ax * L, tab.data() + (2 * ax + 1) * L));
+    if (!t.d && hipMalloc((void**)&t.d, tab.size() * 8) != hipSuccess) {
         (void)hipGetLastError();
-        h->d_bc_coef = nullptr;
+        t.d = nullptr;
         return fail("implicit update: no device memory for " + std::to_string(tab.size() * 8) + " bytes");
     }
     HIPCHK(hipStreamSynchronize(h->stream));          // launches that read the previous table
-    HIPCHK(hipMemcpy(h->d_bc_coef, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    h->bc_r = r;
-    memcpy(h->bc_beta, b.beta, sizeof h->bc_beta);
-    ++info->coeff_uploads;
+    HIPCHK(hipMemcpy(t.d, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    t.r = r;
+    memcpy(t.beta, beta, sizeof t.beta);
+    ++*uploads;
     return 0;
 }
 // the by-value boundary of one implicit step at ratio r, update ordinal u: c_f = (r * beta_f) * T_f where beta_f != 0
@@ -1342,64 +1329,101 @@ ImpBc imp_bc(const cetkmc_thermal_boundary& b, double r, int64_t u)
         }
     return B;
 }
+// ---- one plan per update ------------------------------------------------------------------------------------------------------
+// What the settings make of one temperature update of dt, update ordinal u (0 in a direct call, g / 20 at global step g of a
+// stepping call: a boundary's face temperatures follow it): n steps of dt_s at ratio r, explicit or implicit, the latter between
+// insulated walls or (bc) with the six addends B by value.  A handle's update and an ensemble's are launched and counted from it.
+struct UpdatePlan { int n; double dt_s, r; bool implicit, bc; ImpBc B; };
+UpdatePlan plan_update(const ThermalSettings& s, const cetkmc_params& p, double dt, int64_t u)
+{
+    UpdatePlan P{};
+    P.n = s.substeps;
+    P.dt_s = P.n > 1 ? dt / (double)P.n : dt;
+    P.r = (p.alpha * P.dt_s) * p.inv_dx2;
+    P.implicit = s.scheme == CETKMC_THERMAL_IMPLICIT;
+    P.bc = P.implicit && s.bc_on;
+    if (P.bc) P.B = imp_bc(s.bc, P.r, u);
+    return P;
+}
+// the update joins the running totals: the implicit records, or the sub-step record while n > 1; launches: the blocked
+// sub-step path issues fewer than n and counts its own
+void count_update(ThermalInfo& ti, const UpdatePlan& P, int64_t launches)
+{
+    if (P.implicit) {
+        ++ti.imp.updates; ti.imp.steps += P.n; ti.imp.launches += launches;
+        if (P.bc) { ++ti.bc.updates; ti.bc.steps += P.n; ti.bc.launches += launches; }
+    } else if (P.n > 1) {
+        ++ti.sub.updates; ti.sub.substeps += P.n; ti.sub.launches += launches;
+    }
+}
+// the table an implicit plan's launches read, on handle h (an ensemble's: replica 0, for every replica), uploads counted in ti
+int plan_coeffs(Handle* h, const ThermalSettings& s, const UpdatePlan& P, ThermalInfo& ti, const double** coef)
+{
+    CoefTable& t = P.bc ? h->coef_bc : h->coef;
+    CHK(ensure_coeffs(h, t, P.r, P.bc ? s.bc.beta : nullptr, P.bc ? &ti.bc.coeff_uploads : &ti.imp.coeff_uploads));
+    *coef = t.d;
+    return 0;
+}
+ImpCfg imp_cfg(const cetkmc_params& p, const UpdatePlan& P, const double* coef, int laser, int use_latent, int scrub)
+{
+    ImpCfg C{};
+    C.r = P.r; C.dt = P.dt_s; C.dF = 1.0 / (P.dt_s > 1e-12 ? P.dt_s : 1e-12);
+    C.clip_lo = p.T_clip_lo; C.clip_hi = p.T_clip_hi; C.T_nan = p.T_nan; C.rho_cp = p.rho_cp; C.latent_coef = p.latent_coef;
+    C.coef = coef; C.laser = laser; C.use_latent = use_latent; C.scrub = scrub;
+    return C;
+}
 dim3 imp_rows_grid(int L, int nloc, int R = 1) { return dim3((unsigned)(((int64_t)nloc * L + IMP_R - 1) / IMP_R), (unsigned)R); }
 dim3 imp_lines_grid(int L, int R = 1) { return dim3((unsigned)((L + 63) / 64), (unsigned)L, (unsigned)R); }
-// a temperature update of a one-slab handle in thermal_substeps implicit steps of dt / n: three launches each, one flip each
-int launch_thermal_imp(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+// One implicit step, three launches: of a one-slab handle (its view and pointers, R = 1, no tail) or of every replica of an
+// ensemble (SlabView{}, null pointers, the replica selection as the tail).  between(): what the caller queues between the row
+// pass and the line passes; the tail is taken by reference, so the line passes see a flip made there.
+template <class Between, class... E>
+void launch_imp_step(hipStream_t st, int L, int R, const UpdatePlan& P, const ImpCfg& C, const SlabView& v, const double* Tin, double* Tout,
+                     uint8_t* prev, const double* d_q, const StepState* ssp, Between&& between, E&... e)
 {
-    const int n = h->thermal_substeps, L = h->L;
-    const double dt_s = n > 1 ? dt / (double)n : dt;
-    const double r = (h->p.alpha * dt_s) * h->p.inv_dx2;
-    const bool bc = h->bc_on;       // the boundary form (section 27): its own table, the six addends by value; a direct call is update 0
-    if (bc) CHK(bc_ensure_coeffs(h, r, h->bc, &h->bc_info));
-    else CHK(imp_ensure_coeffs(h, r));
-    const ImpBc B = bc ? imp_bc(h->bc, r, batch ? h->bc_u : 0) : ImpBc{};
+    with_boundary(P.bc, P.B, [&](auto... b) {
+        launch(k_imp_rows<decltype(b)..., E...>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v, Tin, Tout, prev, d_q, C, ssp, b..., e...);
+        between();
+        launch(k_imp_lines<1, decltype(b)..., E...>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v, Tout, C, ssp, b..., e...);
+        launch(k_imp_lines<0, decltype(b)..., E...>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v, Tout, C, ssp, b..., e...);
+    });
+}
+// a temperature update of a one-slab handle in P.n implicit steps: three launches each, one flip each
+int launch_thermal_imp(Handle* h, const UpdatePlan& P, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+{
+    const int L = h->L;
+    const double* coef = nullptr;
+    CHK(plan_coeffs(h, h->ts, P, h->ti, &coef));
     const StepState* ssp = batch ? h->d_ss : nullptr;
     ++h->cnt.thermal_updates;
-    for (int q = 0; q < n; ++q) {
+    for (int q = 0; q < P.n; ++q) {
         const bool first = q == 0;
-        ImpCfg C = imp_cfg(h, dt_s, laser, first ? use_latent : 0, first ? scrub : 0);
+        const ImpCfg C = imp_cfg(h->p, P, coef, laser, first ? use_latent : 0, first ? scrub : 0);
         const int nxt = h->cur ^ 1;
         const SlabView v = view_of(h, 0);
-        if (bc) {
-            C.coef = h->d_bc_coef;
-            launch(k_imp_rows<ImpBc>, imp_rows_grid(L, v.nloc), dim3(IMP_R), 0, h->stream, nullptr, nullptr, v, (const double*)h->slabs[0].Tbuf[h->cur],
-                   h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, C, ssp, B);
-            launch(k_imp_lines<1, ImpBc>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp, B);
-            launch(k_imp_lines<0, ImpBc>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp, B);
-        } else {
-            launch(k_imp_rows<>, imp_rows_grid(L, v.nloc), dim3(IMP_R), 0, h->stream, nullptr, nullptr, v, (const double*)h->slabs[0].Tbuf[h->cur],
-                   h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, C, ssp);
-            launch(k_imp_lines<1>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
-            launch(k_imp_lines<0>, imp_lines_grid(L), dim3(64), 0, h->stream, nullptr, nullptr, v, h->slabs[0].Tbuf[nxt], C, ssp);
-        }
+        launch_imp_step(h->stream, L, 1, P, C, v, h->slabs[0].Tbuf[h->cur], h->slabs[0].Tbuf[nxt], h->slabs[0].prev, d_q, ssp, [] {});
         if (first && laser && use_latent)       // k_imp_rows has brought prev_state level with state on the flagged rows
             hipLaunchKernelGGL(k_clear_row_flags, dim3(64), dim3(256), 0, h->stream, v, ssp);
         HIPCHK(hipGetLastError());
         h->cnt.alg_bytes_thermal += (int64_t)96 * v.nloc * L * L;      // three passes, each: read, y written, y read, x written
         h->cur = nxt;
     }
-    ++h->imp_info.updates; h->imp_info.steps += n; h->imp_info.launches += 3 * (int64_t)n;
-    if (bc) { ++h->bc_info.updates; h->bc_info.steps += n; h->bc_info.launches += 3 * (int64_t)n; }
+    count_update(h->ti, P, 3 * (int64_t)P.n);
     invalidate(h, Cause::thermal_update);
     return 0;
 }
 
-// a temperature update of the handle: thermal_substeps applications of the explicit step with dt / n, or as many implicit steps
-int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch)
+// a temperature update of the handle, update ordinal u: P.n applications of the explicit step with dt / n, or as many implicit steps
+int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch, int64_t u = 0)
 {
-    if (h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return launch_thermal_imp(h, dt, laser, d_q, use_latent, scrub, batch);
-    const int n = h->thermal_substeps;
-    if (n == 1) return launch_thermal_one(h, dt, laser, d_q, use_latent, scrub, batch);
-    const double dt_s = dt / (double)n;
-    CHK(launch_thermal_one(h, dt_s, laser, d_q, use_latent, scrub, batch));
-    ++h->sub_info.updates; h->sub_info.substeps += n; ++h->sub_info.launches;
+    const UpdatePlan P = plan_update(h->ts, h->p, dt, u);
+    if (P.implicit) return launch_thermal_imp(h, P, laser, d_q, use_latent, scrub, batch);
+    CHK(launch_thermal_one(h, P.dt_s, laser, d_q, use_latent, scrub, batch));
+    if (P.n == 1) return 0;
     const int S = substep_block_of(h);
-    if (S > 1) return launch_thermal_sub(h, dt_s, laser, d_q, n - 1, S, batch);
-    for (int q = 1; q < n; ++q) {
-        CHK(launch_thermal_one(h, dt_s, laser, d_q, 0, 0, batch, false));
-        ++h->sub_info.launches;
-    }
+    count_update(h->ti, P, S > 1 ? 1 : P.n);
+    if (S > 1) return launch_thermal_sub(h, P.dt_s, laser, d_q, P.n - 1, S, batch);
+    for (int q = 1; q < P.n; ++q) CHK(launch_thermal_one(h, P.dt_s, laser, d_q, 0, 0, batch, false));
     return 0;
 }
 
@@ -1437,8 +1461,7 @@ int thermal_step(Handle* h, int64_t g, double dt, int laser, const double* d_q, 
     Handle::Spec& sp = h->spec;
     if (!(sp.valid && sp.g == g && sp.laser == laser && sp.use_latent == use_latent && sp.scrub == scrub && sp.dt == dt && sp.d_q == d_q)) {
         if (sp.valid) { HIPCHK(hipStreamSynchronize(h->stream2)); sp.valid = false; }     // a stale look-ahead still owns the other buffers
-        h->bc_u = g / 20;       // a thermal boundary's face temperatures follow the global step (section 27)
-        return launch_thermal(h, dt, laser, d_q, use_latent, scrub, true);
+        return launch_thermal(h, dt, laser, d_q, use_latent, scrub, true, g / 20);       // a thermal boundary's face temperatures follow the global step (section 27)
     }
     sp.valid = false;
     const ThermalCfg C = thermal_cfg(h, dt, laser, use_latent, scrub);
@@ -1468,11 +1491,8 @@ int thermal_step(Handle* h, int64_t g, double dt, int laser, const double* d_q, 
 // what every remelt entry point refuses of a handle, before anything is allocated or launched
 int melt_refusals(const Handle* h, const char* fn, double threshold)
 {
-    const std::string f(fn);
-    if (std::isnan(threshold)) return fail(f + ": the threshold is NaN");
-    if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h))
-        return fail(f + " needs the whole lattice in one slab of one process (a melt in a halo plane would need the neighbour's field)");
-    return 0;
+    if (std::isnan(threshold)) return fail(std::string(fn) + ": the threshold is NaN");
+    return one_slab_only(h, fn, " (a melt in a halo plane would need the neighbour's field)");
 }
 // row flags and counters of this lattice, zero, on first use
 int melt_ensure(Handle* h)
@@ -1492,14 +1512,21 @@ int melt_ensure(Handle* h)
 dim3 melt_scan_grid(const SlabView& v, int R = 1) { return dim3((unsigned)(((int64_t)v.nloc * v.L * (v.pitchT / 4) + MELT_QPB - 1) / MELT_QPB), (unsigned)R); }
 dim3 melt_touch_grid(const SlabView& v, int R = 1) { return dim3((unsigned)(((int64_t)v.nloc * v.L * ((v.L + 63) / 64) + 3) / 4), (unsigned)R); }
 dim3 melt_close_grid(const SlabView& v, int R = 1) { return dim3((unsigned)std::min<int64_t>(((int64_t)(v.nloc + 4) * v.L + 255) / 256, 64), (unsigned)R); }
+// One melt pass, three launches with grids of shape's size: over a one-slab handle's lattice (its view, prev_state and MeltState,
+// R = 1, no tail) or over every replica of an ensemble (SlabView{}, null, MeltState{}, the replicas' table, the selection as tail)
+template <class... E>
+void launch_melt_pass(hipStream_t st, const SlabView& shape, int R, const SlabView& v, uint8_t* prev, const MeltState& M, const MeltState* tab,
+                      double threshold, const StepState* ss, const E&... e)
+{
+    launch(k_melt_scan<E...>, melt_scan_grid(shape, R), dim3(256), 0, st, nullptr, nullptr, v, prev, M, tab, threshold, ss, e...);
+    launch(k_melt_touch<E...>, melt_touch_grid(shape, R), dim3(256), 0, st, nullptr, nullptr, v, M, tab, ss, e...);
+    launch(k_melt_close<E...>, melt_close_grid(shape, R), dim3(256), 0, st, nullptr, nullptr, v, M, tab, ss, e...);
+}
 // one pass over the lattice of a single-slab handle, on its stream; batch: a pass-through behind an early stop
 int launch_melt(Handle* h, double threshold, bool batch)
 {
     const SlabView v = view_of(h, 0);
-    const StepState* ss = batch ? h->d_ss : nullptr;
-    launch(k_melt_scan<>, melt_scan_grid(v), dim3(256), 0, h->stream, nullptr, nullptr, v, h->slabs[0].prev, h->melt, nullptr, threshold, ss);
-    launch(k_melt_touch<>, melt_touch_grid(v), dim3(256), 0, h->stream, nullptr, nullptr, v, h->melt, nullptr, ss);
-    launch(k_melt_close<>, melt_close_grid(v), dim3(256), 0, h->stream, nullptr, nullptr, v, h->melt, nullptr, ss);
+    launch_melt_pass(h->stream, v, 1, v, h->slabs[0].prev, h->melt, nullptr, threshold, batch ? h->d_ss : nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1591,7 +1618,7 @@ void destroy_impl(Handle* h)
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
                     h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq,
-                    h->d_imp_coef, h->d_bc_coef};
+                    h->coef.d, h->coef_bc.d};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -1640,16 +1667,11 @@ struct Ens {
     std::vector<OriginRun> origin_runs;  // host copy of the run table of the last stepping call
     MeltState* d_melt_tab = nullptr;     // cetkmc_ensemble_set_remelt: every replica's row flags and counters [R] (each replica owns its own)
     unsigned long long* d_melt_out = nullptr;      // [R][4] counters gathered at the end of a call
-    int remelt_on = 0;
-    int thermal_substeps = 1;            // cetkmc_ensemble_set_thermal_substeps: one n for all replicas
-    cetkmc_substep_info sub_info{};
-    int thermal_scheme = CETKMC_THERMAL_EXPLICIT;      // cetkmc_ensemble_set_thermal_scheme: one scheme for all replicas
-    cetkmc_implicit_info imp_info{};
-    cetkmc_thermal_boundary bc{};        // cetkmc_ensemble_set_thermal_boundary: one boundary for all replicas
-    bool bc_on = false;
-    cetkmc_boundary_info bc_info{};
-    double remelt_threshold = 0.0;
+    ThermalSettings ts{};                // cetkmc_ensemble_set_remelt / _thermal_substeps / _thermal_scheme / _thermal_boundary: one for all replicas
+    ThermalInfo ti{};                    // of the updates cetkmc_run_ensemble made
 };
+// the ensemble's settings reach every replica: a direct update on a replica handle follows the ensemble
+void share_thermal(Ens* e) { for (Handle* h : e->reps) h->ts = e->ts; }
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
 bool shared_params_equal(cetkmc_params a, cetkmc_params b)
 {
@@ -1916,9 +1938,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         return 0;
     }
     if (!strcmp(key, "thermal_lookahead")) {
-        if (value && h->remelt_on) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while remelting is on (the field computed ahead knows no melt)");
-        if (value && h->thermal_substeps > 1) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while thermal_substeps > 1 (the field computed ahead is one explicit step)");
-        if (value && h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return fail("cetkmc_set_option: thermal_lookahead = 1 is refused while the thermal scheme is implicit (the field computed ahead is one explicit step)");
+        if (value) CHK(thermal_exclusions(h->ts, nullptr));
         h->thermal_ahead = value ? 1 : 0;
         return 0;
     }
@@ -1962,7 +1982,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         CHK(grow(&h->d_u_np, &h->cap_np, 2 * n + 2 + (size_t)h->L * h->L));
         CHK(grow(&h->d_q, &h->cap_q, (n / 20 + 2) * (size_t)h->L * h->L));
         CHK(grow_pinned(&h->pin_in, &h->pin_in_cap, 2 * n * 8 + (2 * n + 2) * 8 + std::min<size_t>(PIN_SMALL_MAX, (n / 20 + 2) * (size_t)h->L * h->L * 8)));
-        CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, 64 + n * (16 + sizeof(cetkmc_event)) + h->slabs.size() * sizeof(int) + (h->remelt_on ? 8 + 4 * 8 : 0)));
+        CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, 64 + n * (16 + sizeof(cetkmc_event)) + h->slabs.size() * sizeof(int) + (h->ts.remelt_on ? 8 + 4 * 8 : 0)));
         // events: the per-phase mode (7 per step) is used on short batches only; the sampled modes need 2 per (8th) step
         return reserve_events(h, std::max<int64_t>(7 * std::min<int64_t>(value, 256), value <= 64 ? 2 * value : 2 * (value / 8 + 1)));
     }
@@ -2369,7 +2389,7 @@ static int enqueue_steps(Handle* h, const cetkmc_run_args* a, const BatchCfg& cf
             // remelting: behind the update and its prev_state := state, in front of this step's table / interface / sweep (no
             // event is pending here: a step before an update step is never deferred); the touched voxels are relisted and the
             // interface kernel, which follows every update, evaluates them
-            if (h->remelt_on) { CHK(launch_melt(h, h->remelt_threshold, true)); invalidate(h, Cause::apply); }
+            if (h->ts.remelt_on) { CHK(launch_melt(h, h->ts.remelt_threshold, true)); invalidate(h, Cause::apply); }
             if (pe.mode == 2) pe.was_thermal[s] = 1;
         }
         const int rc_sw = launch_sweep(h, true, pe.sweep(s, 0), pe.sweep(s, 1), false, pe.phase(s, 1), pe.phase(s, 4));
@@ -2396,8 +2416,8 @@ static int download_run(Handle* h, int64_t n, StepState* ss, double* totals, cet
     const size_t o_tot = 64, o_ev = o_tot + (size_t)n * 8, o_nev = o_ev + (size_t)n * sizeof(cetkmc_event), o_len = o_nev + (size_t)n * 8;
     const size_t o_melt = (o_len + nsl * sizeof(int) + 7) & ~(size_t)7;        // the remelt counters, if the handle has any
     static_assert(sizeof(StepState) <= 64, "StepState grew: move the log offsets");
-    CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, o_melt + (h->remelt_on ? 4 * 8 : 0)));
-    const bool melt_read = h->remelt_on && h->d_melt_block;      // only a loop that may have run a pass reads the counters
+    CHK(grow_pinned(&h->pin_out, &h->pin_out_cap, o_melt + (h->ts.remelt_on ? 4 * 8 : 0)));
+    const bool melt_read = h->ts.remelt_on && h->d_melt_block;      // only a loop that may have run a pass reads the counters
     if (melt_read) HIPCHK(hipMemcpyAsync(h->pin_out + o_melt, h->melt.cnt, 4 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(h->pin_out, h->d_ss, sizeof *ss, hipMemcpyDeviceToHost, h->stream));
     if (totals && n > 0) HIPCHK(hipMemcpyAsync(h->pin_out + o_tot, h->d_log_total, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2446,7 +2466,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
     const int64_t n = a->n_steps;
     CHK(origin_room(h, n, "cetkmc_run_steps"));
-    if (h->bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_steps", h->bc, a->step0, n));
+    if (h->ts.bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_steps", h->ts.bc, a->step0, n));
     CHK(stage_run(h, a));
     // reset the batch part of the step state (nucleation_count persists): a one-thread kernel, no host round trip
     hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
@@ -2612,9 +2632,7 @@ int cetkmc_run_supersteps(void* handle, const cetkmc_super_args* a, cetkmc_run_r
     Handle* h = (Handle*)handle;
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
-    if (h->remelt_on) return fail("cetkmc_run_supersteps is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
-    if (h->thermal_substeps > 1) return fail("cetkmc_run_supersteps is refused while thermal_substeps > 1 (cetkmc_set_thermal_substeps): Mode B updates are not sub-stepped");
-    if (h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return fail("cetkmc_run_supersteps is refused while the thermal scheme is implicit (cetkmc_set_thermal_scheme): Mode B updates are explicit");
+    CHK(thermal_exclusions(h->ts, "cetkmc_run_supersteps"));
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps needs a streaming sweep_variant (1 or 2)");
@@ -2712,9 +2730,7 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     Handle* h = (Handle*)handle;
     if (!h || !a || !res) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
-    if (h->remelt_on) return fail("cetkmc_run_supersteps_local is refused while remelting is on (cetkmc_set_remelt): Mode B has no melt");
-    if (h->thermal_substeps > 1) return fail("cetkmc_run_supersteps_local is refused while thermal_substeps > 1 (cetkmc_set_thermal_substeps): Mode B updates are not sub-stepped");
-    if (h->thermal_scheme == CETKMC_THERMAL_IMPLICIT) return fail("cetkmc_run_supersteps_local is refused while the thermal scheme is implicit (cetkmc_set_thermal_scheme): Mode B updates are explicit");
+    CHK(thermal_exclusions(h->ts, "cetkmc_run_supersteps_local"));
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
     if (a->box != 8 || h->L % 8) return fail("cetkmc_run_supersteps_local: box must be 8 and divide L");
@@ -2722,8 +2738,7 @@ int cetkmc_run_supersteps_local(void* handle, const cetkmc_local_args* a, cetkmc
     if (!(a->horizon_events > 0.0)) return fail("cetkmc_run_supersteps_local: horizon_events must be > 0 (it may be +inf)");
     if (a->thermal_mode == 2) return fail("cetkmc_run_supersteps_local: thermal_mode 2 (laser) is not supported in this mode");
     if (a->thermal_mode != 0 && a->thermal_mode != 1) return fail("cetkmc_run_supersteps_local: thermal_mode must be 0 or 1");
-    if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h))
-        return fail("cetkmc_run_supersteps_local needs the whole lattice in one slab of one process");
+    CHK(one_slab_only(h, "cetkmc_run_supersteps_local", ""));
     if (h->sweep_variant < 1) return fail("cetkmc_run_supersteps_local needs a streaming sweep_variant (1 or 2)");
     CHK(origin_room(h, n, "cetkmc_run_supersteps_local"));
     HIPCHK(hipSetDevice(h->dev));
@@ -3189,7 +3204,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     // temperature updates of the call: the cadence is shared, so every replica's u-th update is the same global step
     const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     const bool laser = a->thermal_mode == 2;
-    if (e->bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_ensemble", e->bc, a->step0, n));
+    if (e->ts.bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_ensemble", e->ts.bc, a->step0, n));
     if (laser) {       // everything about the plane sets is checked before anything is copied or launched
         if (a->n_q < n_therm) return fail("thermal_mode 2 needs one q plane per temperature update of the call in every plane set (n_q too small)");
         if (n_therm > 0 && !a->q_planes) return fail("thermal_mode 2: q_planes[n_sets][n_q][L*L] required (the call holds a temperature update)");
@@ -3278,23 +3293,12 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const double K0 = host_k_eff(h0->p, 0, 0);
     const SlabView v0{};
     const int latent = laser && a->use_latent ? 1 : 0;
-    const int nsub = e->thermal_substeps;
-    const double dt_s = nsub > 1 ? a->thermal_dt / (double)nsub : a->thermal_dt;
-    const ThermalCfg tc0 = thermal_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), tc_sub = thermal_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
-    const bool implicit = e->thermal_scheme == CETKMC_THERMAL_IMPLICIT;
-    const bool bc = implicit && e->bc_on;       // the boundary form (section 27): one boundary, one table for every replica
-    const double imp_r = (h0->p.alpha * dt_s) * h0->p.inv_dx2;
-    if (implicit && a->thermal_mode && updates_in(a->step0, n) > 0) {      // the coefficient table of replica 0 serves every replica
-        if (bc) {
-            CHK(bc_ensure_coeffs(h0, imp_r, e->bc, &e->bc_info));
-        } else {
-            const int64_t before = h0->imp_info.coeff_uploads;
-            CHK(imp_ensure_coeffs(h0, imp_r));
-            e->imp_info.coeff_uploads += h0->imp_info.coeff_uploads - before;
-        }
-    }
-    ImpCfg ic0 = imp_cfg(h0, dt_s, laser ? 1 : 0, latent, 1), ic_sub = imp_cfg(h0, dt_s, laser ? 1 : 0, 0, 0);
-    if (bc) ic0.coef = ic_sub.coef = h0->d_bc_coef;
+    // every update of the call is made alike (one n, one scheme, one boundary for every replica) but for the update ordinal
+    const UpdatePlan P0 = plan_update(e->ts, h0->p, a->thermal_dt, 0);
+    const ThermalCfg tc0 = thermal_cfg(h0, P0.dt_s, laser ? 1 : 0, latent, 1), tc_sub = thermal_cfg(h0, P0.dt_s, laser ? 1 : 0, 0, 0);
+    const double* coef = nullptr;       // the coefficient table of replica 0 serves every replica
+    if (P0.implicit && n_therm > 0) CHK(plan_coeffs(h0, e->ts, P0, e->ti, &coef));
+    const ImpCfg ic0 = imp_cfg(h0->p, P0, coef, laser ? 1 : 0, latent, 1), ic_sub = imp_cfg(h0->p, P0, coef, laser ? 1 : 0, 0, 0);
     const BatchCfg cfg0{};
     const dim3 g_flags((unsigned)std::min<int64_t>(((int64_t)(L + 4) * L + 255) / 256, 64), (unsigned)R);
     EnsSel sel{e->d_table, 0, (int)g_therm.z / R};
@@ -3308,52 +3312,29 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     // have left them stale; recomputing fresh ones gives the same values) -- unless the first step's update does it
     if (!(a->thermal_mode && n > 0 && a->step0 % 20 == 0)) table_and_interface();
     int flips = 0;
+    // the kernel that wrote the other buffer pair has also brought prev_state level with state on the flagged rows: the first step
+    // of a latent update drops the flags (live replicas); from here on the other pair is the current one
+    auto flip = [&](bool first) {
+        if (first && latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
+        sel.rel ^= 1;
+        ++flips;
+    };
     for (int64_t s = 0; s < n; ++s) {
         const int64_t g = a->step0 + s;
         if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
-            if (implicit) {        // nsub implicit steps (thermal_imp.hpp): three launches and one flip each
-                const ImpBc B = bc ? imp_bc(e->bc, imp_r, g / 20) : ImpBc{};
-                for (int q = 0; q < nsub; ++q) {
-                    if (bc)
-                        launch(k_imp_rows<ImpBc, EnsSel>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr,
-                               q == 0 ? ic0 : ic_sub, nullptr, B, sel);
-                    else
-                        launch(k_imp_rows<EnsSel>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr,
-                               q == 0 ? ic0 : ic_sub, nullptr, sel);
-                    if (q == 0 && latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
-                    sel.rel ^= 1;
-                    ++flips;
-                    if (bc) {
-                        launch(k_imp_lines<1, ImpBc, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, B, sel);
-                        launch(k_imp_lines<0, ImpBc, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, B, sel);
-                    } else {
-                        launch(k_imp_lines<1, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
-                        launch(k_imp_lines<0, EnsSel>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v0, nullptr, ic_sub, nullptr, sel);
-                    }
+            const UpdatePlan P = plan_update(e->ts, h0->p, a->thermal_dt, g / 20);
+            for (int q = 0; q < P.n; ++q) {        // steps 2..n: no scrub, no latent term, same plane
+                // an implicit step (thermal_imp.hpp): three launches, the flip behind the row pass (the line passes work in place)
+                if (P.implicit) launch_imp_step(st, L, R, P, q == 0 ? ic0 : ic_sub, v0, nullptr, nullptr, nullptr, nullptr, nullptr, [&] { flip(q == 0); }, sel);
+                else {
+                    launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, q == 0 ? tc0 : tc_sub, nullptr, sel);
+                    flip(q == 0);
                 }
-                ++e->imp_info.updates; e->imp_info.steps += nsub; e->imp_info.launches += 3 * (int64_t)nsub;
-                if (bc) { ++e->bc_info.updates; e->bc_info.steps += nsub; e->bc_info.launches += 3 * (int64_t)nsub; }
-            } else {
-                launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc0, nullptr, sel);
-                // the marching kernel has brought prev_state level with state on the flagged rows: drop the flags (live replicas)
-                if (latent) hipLaunchKernelGGL(k_ens_clear_row_flags, g_flags, dim3(256), 0, st, (const EnsRep*)e->d_table);
-                sel.rel ^= 1;
-                ++flips;
-                for (int q = 1; q < nsub; ++q) {       // sub-steps 2..n: the plain path, no scrub, no latent term, same plane
-                    launch(k_thermal_march<EnsSel>, g_therm, dim3(256), 0, st, nullptr, nullptr, v0, nullptr, nullptr, nullptr, nullptr, tc_sub, nullptr, sel);
-                    sel.rel ^= 1;
-                    ++flips;
-                }
-                if (nsub > 1) { ++e->sub_info.updates; e->sub_info.substeps += nsub; e->sub_info.launches += nsub; }
             }
+            count_update(e->ti, P, (P.implicit ? 3 : 1) * (int64_t)P.n);
             sel.q_off += laser ? (int64_t)L2 : 0;
-            if (e->remelt_on) {        // behind the update and its prev_state := state, in front of the table and the interface kernel
-                const SlabView& mv = e->table[0].view[0];
-                launch(k_melt_scan<EnsSel>, melt_scan_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, nullptr, MeltState{}, e->d_melt_tab,
-                       e->remelt_threshold, nullptr, sel);
-                launch(k_melt_touch<EnsSel>, melt_touch_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, MeltState{}, e->d_melt_tab, nullptr, sel);
-                launch(k_melt_close<EnsSel>, melt_close_grid(mv, R), dim3(256), 0, st, nullptr, nullptr, v0, MeltState{}, e->d_melt_tab, nullptr, sel);
-            }
+            if (e->ts.remelt_on)       // behind the update and its prev_state := state, in front of the table and the interface kernel
+                launch_melt_pass(st, e->table[0].view[0], R, v0, nullptr, MeltState{}, e->d_melt_tab, e->ts.remelt_threshold, nullptr, sel);
             table_and_interface();
         }
         launch(k_sweep_plane<true, false, EnsSel>, g_sweep, dim3(1024), plane_shmem(L), st, nullptr, nullptr, sa0, nullptr, nullptr, sel);
@@ -3364,7 +3345,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     HIPCHK(hipEventRecord(e->ev1, st));
     hipLaunchKernelGGL(k_ens_collect, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, st, (const EnsRep*)e->d_table, R, e->d_ss_out, e->d_n_out);
     HIPCHK(hipGetLastError());
-    const bool melt_read = e->remelt_on && e->d_melt_tab;       // only a call that may have run a pass gathers the counters
+    const bool melt_read = e->ts.remelt_on && e->d_melt_tab;       // only a call that may have run a pass gathers the counters
     std::vector<unsigned long long> melt_cnt(melt_read ? (size_t)R * 4 : 0);       // the remelt counters travel with the results
     if (melt_read) {
         launch(k_melt_collect, dim3((unsigned)((4 * R + 255) / 256)), dim3(256), 0, st, nullptr, nullptr, e->d_melt_tab, R, e->d_melt_out);
@@ -4142,7 +4123,7 @@ static int origin_begin(const char* fn, void* handle, bool ens, int max_L)
     Lattices A;
     CHK(lattices(fn, handle, ens, OWNER | ORIGIN, &A));
     for (Handle* h : A.hs)
-        if (h->remelt_on) return fail(std::string(fn) + " is refused while remelting is on: the event log the origin map folds holds no melts");
+        if (h->ts.remelt_on) return fail(std::string(fn) + " is refused while remelting is on: the event log the origin map folds holds no melts");
     if (A.L > max_L) return fail(std::string(fn) + ": L > " + std::to_string(max_L) + " (the profile packs a voxel's linear index into 24 bits)");
     void** block = A.e ? &A.e->d_origin_block : &A.h0->d_origin_block;
     const size_t R = (size_t)A.R;
@@ -4293,20 +4274,64 @@ int cetkmc_ensemble_origin_profile(void* handle, struct cetkmc_origin_rec* layer
 }
 
 // ---- remelting (melt.hpp) -----------------------------------------------------------------------
-int cetkmc_set_remelt(void* handle, int on, double threshold)
+// The setters of ThermalSettings, each written once for a single handle (cetkmc_set_X) and for an ensemble (ens,
+// cetkmc_ensemble_set_X; its handle is replica 0's).  fn names the entry point, prefix_of(ens) + "set_Y" a setter for the same
+// kind of handle, other_kind(fn, ens) the entry point's counterpart.
+static std::string prefix_of(bool ens) { return ens ? "cetkmc_ensemble_" : "cetkmc_"; }
+static std::string other_kind(const char* fn, bool ens) { return prefix_of(!ens) + (fn + prefix_of(ens).size()); }
+// how the setters but cetkmc_set_remelt open: the ensemble of an ensemble handle, and the handle kind the entry point is not for
+static int setter_ensemble(const char* fn, void* handle, bool ens, Ens** e)
 {
-    Handle* h = (Handle*)handle;
-    if (!h) return fail("null handle");
-    CHK(melt_refusals(h, "cetkmc_set_remelt", threshold));
-    if (h->in_ensemble) return fail("cetkmc_set_remelt: the replicas of an ensemble are switched by cetkmc_ensemble_set_remelt");
-    if (on && h->origin_on) return fail("cetkmc_set_remelt is refused while an origin map is attached: the event log it folds holds no melts");
-    if (on && h->thermal_ahead) return fail("cetkmc_set_remelt is refused with option thermal_lookahead on (the field computed ahead knows no melt)");
-    HIPCHK(hipSetDevice(h->dev));
-    if (on) CHK(melt_ensure(h));
-    h->remelt_on = on ? 1 : 0;
-    h->remelt_threshold = threshold;
+    *e = ens_of(handle);
+    if (ens && !*e) return fail(std::string(fn) + ": not an ensemble handle (cetkmc_create_ensemble)");
+    if (!ens && *e) return fail(std::string(fn) + ": an ensemble handle is set by " + other_kind(fn, ens));
     return 0;
 }
+// the record a setter writes: the ensemble's (handed on to every replica by share_thermal), or the handle's own
+static ThermalSettings& settings_of(Handle* h, Ens* e) { return e ? e->ts : h->ts; }
+
+// every replica's row flags and counters, and the device table that names them [R]
+static int ens_melt_ensure(Ens* e, const char* fn)
+{
+    const size_t R = (size_t)e->R;
+    Handle* h0 = e->reps[0];
+    for (Handle* h : e->reps) CHK(melt_ensure(h));
+    if (e->d_melt_tab) return 0;
+    if (hipMalloc((void**)&e->d_melt_tab, R * sizeof(MeltState)) != hipSuccess || hipMalloc((void**)&e->d_melt_out, R * 4 * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        if (e->d_melt_tab) (void)hipFree(e->d_melt_tab);
+        e->d_melt_tab = nullptr; e->d_melt_out = nullptr;
+        return fail(std::string(fn) + ": no device memory for the replica table");
+    }
+    std::vector<MeltState> tab(R);
+    for (size_t r = 0; r < R; ++r) tab[r] = e->reps[r]->melt;
+    HIPCHK(hipMemcpyAsync(e->d_melt_tab, tab.data(), R * sizeof(MeltState), hipMemcpyHostToDevice, h0->stream));
+    HIPCHK(hipStreamSynchronize(h0->stream));       // the table is copied from this frame
+    return 0;
+}
+static int set_remelt(const char* fn, void* handle, bool ens, int on, double threshold)
+{
+    const std::string f(fn);
+    if (!handle) return fail(ens ? "null argument" : "null handle");
+    Ens* e = ens ? ens_of(handle) : nullptr;
+    if (ens && !e) return fail(f + ": not an ensemble handle (cetkmc_create_ensemble)");
+    Handle* h = (Handle*)handle;
+    CHK(melt_refusals(h, fn, threshold));
+    if (!ens && h->in_ensemble) return fail(f + ": the replicas of an ensemble are switched by " + other_kind(fn, ens));
+    if (on && h->origin_on)
+        return fail(f + (ens ? " is refused while the origin maps are attached: the event log they fold holds no melts"
+                             : " is refused while an origin map is attached: the event log it folds holds no melts"));
+    if (!ens && on && h->thermal_ahead) return fail(f + " is refused with option thermal_lookahead on (the field computed ahead knows no melt)");
+    HIPCHK(hipSetDevice(h->dev));
+    if (on) CHK(ens ? ens_melt_ensure(e, fn) : melt_ensure(h));
+    ThermalSettings& s = settings_of(h, e);
+    s.remelt_on = on ? 1 : 0;
+    s.remelt_threshold = threshold;
+    if (e) share_thermal(e);
+    return 0;
+}
+int cetkmc_set_remelt(void* handle, int on, double threshold) { return set_remelt("cetkmc_set_remelt", handle, false, on, threshold); }
+int cetkmc_ensemble_set_remelt(void* handle, int on, double threshold) { return set_remelt("cetkmc_ensemble_set_remelt", handle, true, on, threshold); }
 
 int cetkmc_remelt(void* handle, double threshold, struct cetkmc_remelt_info* info)
 {
@@ -4354,37 +4379,6 @@ int cetkmc_get_remelt_info(void* handle, struct cetkmc_remelt_info* info)
     return 0;
 }
 
-int cetkmc_ensemble_set_remelt(void* handle, int on, double threshold)
-{
-    if (!handle) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("cetkmc_ensemble_set_remelt: not an ensemble handle (cetkmc_create_ensemble)");
-    Handle* h0 = e->reps[0];
-    CHK(melt_refusals(h0, "cetkmc_ensemble_set_remelt", threshold));
-    if (on && h0->origin_on) return fail("cetkmc_ensemble_set_remelt is refused while the origin maps are attached: the event log they fold holds no melts");
-    HIPCHK(hipSetDevice(h0->dev));
-    if (on) {
-        const size_t R = (size_t)e->R;
-        for (Handle* h : e->reps) CHK(melt_ensure(h));
-        if (!e->d_melt_tab) {
-            if (hipMalloc((void**)&e->d_melt_tab, R * sizeof(MeltState)) != hipSuccess || hipMalloc((void**)&e->d_melt_out, R * 4 * 8) != hipSuccess) {
-                (void)hipGetLastError();
-                if (e->d_melt_tab) (void)hipFree(e->d_melt_tab);
-                e->d_melt_tab = nullptr; e->d_melt_out = nullptr;
-                return fail("cetkmc_ensemble_set_remelt: no device memory for the replica table");
-            }
-            std::vector<MeltState> tab(R);
-            for (size_t r = 0; r < R; ++r) tab[r] = e->reps[r]->melt;
-            HIPCHK(hipMemcpyAsync(e->d_melt_tab, tab.data(), R * sizeof(MeltState), hipMemcpyHostToDevice, h0->stream));
-            HIPCHK(hipStreamSynchronize(h0->stream));       // the table is copied from this frame
-        }
-    }
-    e->remelt_on = on ? 1 : 0;
-    e->remelt_threshold = threshold;
-    for (Handle* h : e->reps) { h->remelt_on = e->remelt_on; h->remelt_threshold = threshold; }
-    return 0;
-}
-
 int cetkmc_ensemble_remelt_info(void* handle, struct cetkmc_remelt_info* info)
 {
     if (!handle || !info) return fail("null argument");
@@ -4403,35 +4397,36 @@ static int substeps_range(const char* fn, int n)
     return 0;
 }
 
-int cetkmc_set_thermal_substeps(void* handle, int n)
+static int set_thermal_substeps(const char* fn, void* handle, bool ens, int n)
 {
-    if (!handle) return fail("null handle");
-    if (ens_of(handle)) return fail("cetkmc_set_thermal_substeps: an ensemble handle is set by cetkmc_ensemble_set_thermal_substeps");
+    const std::string f(fn);
+    if (!handle) return fail(ens ? "null argument" : "null handle");
+    Ens* e = nullptr;
+    CHK(setter_ensemble(fn, handle, ens, &e));
     Handle* h = (Handle*)handle;
-    CHK(substeps_range("cetkmc_set_thermal_substeps", n));
-    if (h->in_ensemble) return fail("cetkmc_set_thermal_substeps: the replicas of an ensemble share one value (cetkmc_ensemble_set_thermal_substeps)");
-    if (multi_rank(h) || h->nranks != 1) return fail("cetkmc_set_thermal_substeps is refused on a rank handle (cetkmc_create_rank*): the halo exchange carries two planes per update");
-    if (n > 1 && h->thermal_ahead) return fail("cetkmc_set_thermal_substeps: n > 1 is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
-    h->thermal_substeps = n;
+    CHK(substeps_range(fn, n));
+    if (!ens) {
+        if (h->in_ensemble) return fail(f + ": the replicas of an ensemble share one value (" + other_kind(fn, ens) + ")");
+        if (multi_rank(h) || h->nranks != 1) return fail(f + " is refused on a rank handle (cetkmc_create_rank*): the halo exchange carries two planes per update");
+        if (n > 1 && h->thermal_ahead) return fail(f + ": n > 1 is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
+    }
+    settings_of(h, e).substeps = n;
+    if (e) share_thermal(e);
     return 0;
 }
+int cetkmc_set_thermal_substeps(void* handle, int n) { return set_thermal_substeps("cetkmc_set_thermal_substeps", handle, false, n); }
+int cetkmc_ensemble_set_thermal_substeps(void* handle, int n) { return set_thermal_substeps("cetkmc_ensemble_set_thermal_substeps", handle, true, n); }
 
-int cetkmc_ensemble_set_thermal_substeps(void* handle, int n)
+// the records of an ensemble handle are the ensemble's (replica 0's own cannot be read), any other handle's are its own
+static const ThermalInfo& thermal_info_of(void* handle)
 {
-    if (!handle) return fail("null argument");
     Ens* e = ens_of(handle);
-    if (!e) return fail("cetkmc_ensemble_set_thermal_substeps: not an ensemble handle (cetkmc_create_ensemble)");
-    CHK(substeps_range("cetkmc_ensemble_set_thermal_substeps", n));
-    e->thermal_substeps = n;
-    for (Handle* h : e->reps) h->thermal_substeps = n;      // a direct update on a replica handle follows the ensemble's value
-    return 0;
+    return e ? e->ti : ((Handle*)handle)->ti;
 }
-
 int cetkmc_get_substep_info(void* handle, struct cetkmc_substep_info* info)
 {
     if (!handle || !info) return fail("null argument");
-    Ens* e = ens_of(handle);
-    *info = e ? e->sub_info : ((Handle*)handle)->sub_info;
+    *info = thermal_info_of(handle).sub;
     return 0;
 }
 
@@ -4458,84 +4453,72 @@ static int scheme_known(const char* fn, int scheme)
     return 0;
 }
 
-int cetkmc_set_thermal_scheme(void* handle, int scheme)
+static int set_thermal_scheme(const char* fn, void* handle, bool ens, int scheme)
 {
-    if (!handle) return fail("null handle");
-    CHK(scheme_known("cetkmc_set_thermal_scheme", scheme));
-    if (ens_of(handle)) return fail("cetkmc_set_thermal_scheme: an ensemble handle is set by cetkmc_ensemble_set_thermal_scheme");
+    const std::string f(fn), pre = prefix_of(ens);
+    if (!handle) return fail(ens ? "null argument" : "null handle");
+    Ens* e = nullptr;
+    if (!ens) CHK(scheme_known(fn, scheme));        // (a single handle hears of an unknown scheme first, an ensemble of its handle)
+    CHK(setter_ensemble(fn, handle, ens, &e));
+    if (ens) CHK(scheme_known(fn, scheme));
     Handle* h = (Handle*)handle;
-    if (h->in_ensemble) return fail("cetkmc_set_thermal_scheme: the replicas of an ensemble share one scheme (cetkmc_ensemble_set_thermal_scheme)");
-    if (scheme == CETKMC_THERMAL_IMPLICIT) {
-        if (h->slabs.size() != 1 || h->nranks != 1 || multi_rank(h))
-            return fail("cetkmc_set_thermal_scheme: the implicit scheme needs the whole lattice in one slab of one process (the solve along the plane axis crosses slabs)");
-        if (h->thermal_ahead) return fail("cetkmc_set_thermal_scheme: the implicit scheme is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
+    if (!ens) {
+        if (h->in_ensemble) return fail(f + ": the replicas of an ensemble share one scheme (" + other_kind(fn, ens) + ")");
+        if (scheme == CETKMC_THERMAL_IMPLICIT) {
+            CHK(one_slab_only(h, f + ": the implicit scheme", " (the solve along the plane axis crosses slabs)"));
+            if (h->thermal_ahead) return fail(f + ": the implicit scheme is refused with option thermal_lookahead on (the field computed ahead is one explicit step)");
+        }
     }
-    if (scheme == CETKMC_THERMAL_EXPLICIT && h->bc_on)
-        return fail("cetkmc_set_thermal_scheme: the explicit scheme is refused while a thermal boundary is set (cetkmc_set_thermal_boundary(handle, NULL) first)");
-    h->thermal_scheme = scheme;
+    ThermalSettings& s = settings_of(h, e);
+    if (scheme == CETKMC_THERMAL_EXPLICIT && s.bc_on)
+        return fail(f + ": the explicit scheme is refused while a thermal boundary is set (" + pre + "set_thermal_boundary(handle, NULL) first)");
+    s.scheme = scheme;
+    if (e) share_thermal(e);
     return 0;
 }
-
-int cetkmc_ensemble_set_thermal_scheme(void* handle, int scheme)
-{
-    if (!handle) return fail("null argument");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("cetkmc_ensemble_set_thermal_scheme: not an ensemble handle (cetkmc_create_ensemble)");
-    CHK(scheme_known("cetkmc_ensemble_set_thermal_scheme", scheme));
-    if (scheme == CETKMC_THERMAL_EXPLICIT && e->bc_on)
-        return fail("cetkmc_ensemble_set_thermal_scheme: the explicit scheme is refused while a thermal boundary is set (cetkmc_ensemble_set_thermal_boundary(handle, NULL) first)");
-    e->thermal_scheme = scheme;
-    for (Handle* h : e->reps) h->thermal_scheme = scheme;      // a direct update on a replica handle follows the ensemble's scheme
-    return 0;
-}
+int cetkmc_set_thermal_scheme(void* handle, int scheme) { return set_thermal_scheme("cetkmc_set_thermal_scheme", handle, false, scheme); }
+int cetkmc_ensemble_set_thermal_scheme(void* handle, int scheme) { return set_thermal_scheme("cetkmc_ensemble_set_thermal_scheme", handle, true, scheme); }
 
 int cetkmc_get_implicit_info(void* handle, struct cetkmc_implicit_info* info)
 {
     if (!handle || !info) return fail("null argument");
-    Ens* e = ens_of(handle);
-    *info = e ? e->imp_info : ((Handle*)handle)->imp_info;
+    *info = thermal_info_of(handle).imp;
     return 0;
 }
 
-int cetkmc_implicit_coeffs(int L, double r, double* inv, double* p) { return implicit_coeffs_host("cetkmc_implicit_coeffs", L, r, inv, p); }
+int cetkmc_implicit_coeffs(int L, double r, double* inv, double* p) { return implicit_coeffs_bc_host("cetkmc_implicit_coeffs", L, r, 0.0, 0.0, inv, p); }
 
 // ---- thermal boundary conditions (thermal_imp.hpp) --------------------------------------------------
-int cetkmc_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b)
+static int set_thermal_boundary(const char* fn, void* handle, bool ens, const cetkmc_thermal_boundary* b)
 {
-    if (!handle) return fail("cetkmc_set_thermal_boundary: null handle");
-    if (ens_of(handle)) return fail("cetkmc_set_thermal_boundary: an ensemble handle is set by cetkmc_ensemble_set_thermal_boundary");
+    const std::string f(fn), pre = prefix_of(ens);
+    if (!handle) return fail(f + ": null handle");
+    Ens* e = nullptr;
+    CHK(setter_ensemble(fn, handle, ens, &e));
     Handle* h = (Handle*)handle;
-    if (h->in_ensemble) return fail("cetkmc_set_thermal_boundary: the replicas of an ensemble share one boundary (cetkmc_ensemble_set_thermal_boundary)");
+    if (!ens && h->in_ensemble) return fail(f + ": the replicas of an ensemble share one boundary (" + other_kind(fn, ens) + ")");
     const cetkmc_thermal_boundary v = b ? *b : cetkmc_thermal_boundary{};
-    CHK(boundary_values_ok("cetkmc_set_thermal_boundary", v));
+    CHK(boundary_values_ok(fn, v));
     const bool on = boundary_active(v);
-    if (on && h->thermal_scheme != CETKMC_THERMAL_IMPLICIT)
-        return fail("cetkmc_set_thermal_boundary: a thermal boundary needs the implicit scheme (cetkmc_set_thermal_scheme); the explicit kernels are adiabatic");
-    h->bc = v; h->bc_on = on;
+    ThermalSettings& s = settings_of(h, e);
+    if (on && s.scheme != CETKMC_THERMAL_IMPLICIT)
+        return fail(f + ": a thermal boundary needs the implicit scheme (" + pre + "set_thermal_scheme); the explicit kernels are adiabatic");
+    s.bc = v; s.bc_on = on;
+    if (e) share_thermal(e);
     return 0;
 }
-
+int cetkmc_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b) { return set_thermal_boundary("cetkmc_set_thermal_boundary", handle, false, b); }
 int cetkmc_ensemble_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b)
 {
-    if (!handle) return fail("cetkmc_ensemble_set_thermal_boundary: null handle");
-    Ens* e = ens_of(handle);
-    if (!e) return fail("cetkmc_ensemble_set_thermal_boundary: not an ensemble handle (cetkmc_create_ensemble)");
-    const cetkmc_thermal_boundary v = b ? *b : cetkmc_thermal_boundary{};
-    CHK(boundary_values_ok("cetkmc_ensemble_set_thermal_boundary", v));
-    const bool on = boundary_active(v);
-    if (on && e->thermal_scheme != CETKMC_THERMAL_IMPLICIT)
-        return fail("cetkmc_ensemble_set_thermal_boundary: a thermal boundary needs the implicit scheme (cetkmc_ensemble_set_thermal_scheme); the explicit kernels are adiabatic");
-    e->bc = v; e->bc_on = on;
-    for (Handle* h : e->reps) { h->bc = v; h->bc_on = on; }      // a direct update on a replica handle follows the ensemble's boundary
-    return 0;
+    return set_thermal_boundary("cetkmc_ensemble_set_thermal_boundary", handle, true, b);
 }
 
 int cetkmc_get_thermal_boundary(void* handle, struct cetkmc_thermal_boundary* b, struct cetkmc_boundary_info* info)
 {
     if (!handle) return fail("cetkmc_get_thermal_boundary: null handle");
     Ens* e = ens_of(handle);
-    if (b) *b = e ? e->bc : ((Handle*)handle)->bc;
-    if (info) *info = e ? e->bc_info : ((Handle*)handle)->bc_info;
+    if (b) *b = settings_of((Handle*)handle, e).bc;
+    if (info) *info = (e ? e->ti : ((Handle*)handle)->ti).bc;
     return 0;
 }
 

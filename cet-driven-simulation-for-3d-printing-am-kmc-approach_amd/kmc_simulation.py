@@ -260,6 +260,18 @@ def _thermal_substeps(value, where="thermal_substeps"):
     return int(value)
 
 
+def _apply_thermal_options(target, n_sub, scheme, boundary, remelt_thr):
+    """the four thermal options of run_kmc / run_kmc_ensemble on their Engine / Ensemble; a default stays unset"""
+    if remelt_thr is not None:
+        target.set_remelt(True, remelt_thr)
+    if n_sub != 1:
+        target.set_thermal_substeps(n_sub)
+    if scheme != "explicit":
+        target.set_thermal_scheme(scheme)
+    if boundary is not None:
+        target.set_thermal_boundary(boundary)
+
+
 def _check_substeps(n_sub, mode_a, thermal_updates):
     """what run_kmc and run_kmc_ensemble refuse of thermal_substeps > 1 (before any device call)"""
     if n_sub == 1:
@@ -618,25 +630,19 @@ def run_kmc(
             engine.close()
             raise ValueError(f"checkpoint was written by a run with remelt={ex.get('remelt', False)}, this call asks for {remelt_thr or False}")
         remelt_off = (int(ex.get("remelt_passes", 0)), int(ex.get("remelted", 0)))
-        engine.set_remelt(True, remelt_thr)
     if ckpt and int(ckpt["extra"].get("thermal_substeps", 1)) != n_sub:
         engine.close()
         raise ValueError(f"checkpoint was written by a run with thermal_substeps={ckpt['extra'].get('thermal_substeps', 1)}, "
                          f"this call asks for {n_sub}")
-    if n_sub != 1:
-        engine.set_thermal_substeps(n_sub)
     if ckpt and ckpt["extra"].get("thermal_scheme", "explicit") != thermal_scheme:
         engine.close()
         raise ValueError(f"checkpoint was written by a run with thermal_scheme={ckpt['extra'].get('thermal_scheme', 'explicit')!r}, "
                          f"this call asks for {thermal_scheme!r}")
-    if thermal_scheme != "explicit":
-        engine.set_thermal_scheme(thermal_scheme)
     if ckpt and ckpt["extra"].get("thermal_bc") != face_bc:
         engine.close()
         raise ValueError(f"checkpoint was written by a run with thermal_boundary={ckpt['extra'].get('thermal_bc')!r}, "
                          f"this call asks for {face_bc!r}")
-    if face_bc is not None:
-        engine.set_thermal_boundary(face_bc)
+    _apply_thermal_options(engine, n_sub, thermal_scheme, face_bc, remelt_thr)
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -1032,14 +1038,7 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
         if origin_metrics:
             ens.origin_begin()
         remelt_thr = cfgs[0]["remelt"]
-        if remelt_thr is not None:
-            ens.set_remelt(True, remelt_thr)
-        if n_sub != 1:
-            ens.set_thermal_substeps(n_sub)
-        if thermal_scheme != "explicit":
-            ens.set_thermal_scheme(thermal_scheme)
-        if boundary is not None:
-            ens.set_thermal_boundary(boundary)
+        _apply_thermal_options(ens, n_sub, thermal_scheme, boundary, remelt_thr)
         thermal_mode = 1 if thermal_updates else 0
         # laser configs: replicas with equal scans (the seeds of one map point) share a plane set
         scans, q_set, use_latent = [], None, True

@@ -34,10 +34,12 @@ def lattices(L, R):
     return out
 
 
-def one(L, R, mode, steps, seq_cap):
+def one(L, R, mode, steps, seq_cap, scheme="explicit", n_sub=1):
     lat = lattices(L, R)
     params = [cetkmc.default_params(0.1 * (r % 3)) for r in range(R)]
     ens = cetkmc.Ensemble(L, params)
+    ens.set_thermal_substeps(n_sub)
+    ens.set_thermal_scheme(scheme)
     for r, (st, th, ph, T) in enumerate(lat):
         ens.replica(r).upload(st, th, ph, T, np.zeros_like(st))
     per_step = L * L + 2
@@ -72,6 +74,8 @@ def one(L, R, mode, steps, seq_cap):
     t_seq, ev_seq = 0.0, 0
     for r in range(k):
         e = cetkmc.Engine(L, params=params[r])
+        e.set_thermal_substeps(n_sub)
+        e.set_thermal_scheme(scheme)
         st, th, ph, T = lat[r]
         e.upload(st, th, ph, T, np.zeros_like(st))
         if mode == "counter":
@@ -90,7 +94,8 @@ def one(L, R, mode, steps, seq_cap):
         e.close()
     seq_rate = ev_seq / t_seq if t_seq > 0 else 0.0
     ens_rate = events / wall
-    return dict(L=L, R=R, rng=mode, steps_per_call=n, events_per_s=round(ens_rate, 1), device_us_per_step=round(step_us, 2),
+    return dict(L=L, R=R, rng=mode, thermal_scheme=scheme, thermal_substeps=n_sub, steps_per_call=n,
+                events_per_s=round(ens_rate, 1), device_us_per_step=round(step_us, 2),
                 host_ms_per_call=round(wall * 1e3 / calls, 3), host_draw_ms_per_call=round(draw * 1e3 / calls, 3),
                 sequential_events_per_s=round(seq_rate, 1), sequential_replicas_timed=k,
                 speedup=round(ens_rate / seq_rate, 2) if seq_rate else None,
@@ -135,8 +140,10 @@ def main():
     ap.add_argument("--e2e-steps", type=int, default=1000, help="end-to-end rows (L = 30, R = 16 / 64); 0: none")
     ap.add_argument("--modes", nargs="*", default=["counter", "reference"])
     ap.add_argument("--seq-cap", type=int, default=8)
+    ap.add_argument("--thermal-scheme", default="explicit", choices=["explicit", "implicit"], help="of the `rows` (ensemble and baseline)")
+    ap.add_argument("--thermal-substeps", type=int, default=1, help="of the `rows` (ensemble and baseline)")
     a = ap.parse_args()
-    rows = [one(L, R, m, a.steps, a.seq_cap) for L in a.L for R in a.R for m in a.modes]
+    rows = [one(L, R, m, a.steps, a.seq_cap, a.thermal_scheme, a.thermal_substeps) for L in a.L for R in a.R for m in a.modes]
     e2e = [end_to_end(30, R, m, a.e2e_steps, 4) for R in (16, 64) for m in a.modes] if a.e2e_steps > 0 else []
     print(json.dumps(dict(tool="ensemble_throughput", rows=rows, end_to_end=e2e)))
 
