@@ -177,13 +177,23 @@ class BoundaryInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("updates", "steps", "launches", "coeff_uploads")]
 
 
+class Beam(C.Structure):
+    _fields_ = [("u0", C.c_int64), ("n_u", C.c_int32), ("depth", C.c_int32), ("amp", C.POINTER(C.c_double)),
+                ("gj", C.POINTER(C.c_double)), ("gk", C.POINTER(C.c_double)), ("fi", C.POINTER(C.c_double))]
+
+
+class BeamInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("updates", "steps", "launches", "table_uploads")]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
                   "texture_args": TextureArgs, "grain_rec": GrainRec, "solid_info": SolidInfo, "solid_args": SolidArgs,
                   "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs,
                   "remelt_info": RemeltInfo, "substep_info": SubstepInfo, "implicit_info": ImplicitInfo,
-                  "thermal_boundary": ThermalBoundary, "boundary_info": BoundaryInfo}
+                  "thermal_boundary": ThermalBoundary, "boundary_info": BoundaryInfo,
+                  "beam": Beam, "beam_info": BeamInfo}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -292,6 +302,10 @@ PROTOTYPES = {
     "cetkmc_set_thermal_boundary": (C.c_int, [C.c_void_p, _P(ThermalBoundary)]),
     "cetkmc_ensemble_set_thermal_boundary": (C.c_int, [C.c_void_p, _P(ThermalBoundary)]),
     "cetkmc_get_thermal_boundary": (C.c_int, [C.c_void_p, _P(ThermalBoundary), _P(BoundaryInfo)]),
+    "cetkmc_set_beam": (C.c_int, [C.c_void_p, _P(Beam)]),
+    "cetkmc_ensemble_set_beam": (C.c_int, [C.c_void_p, C.c_int, _P(Beam), _P(C.c_int32)]),
+    "cetkmc_get_beam_info": (C.c_int, [C.c_void_p, _P(BeamInfo)]),
+    "cetkmc_thermal_beam": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, C.c_int, C.c_int]),
     "cetkmc_implicit_coeffs_bc": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, _P(C.c_double), _P(C.c_double)]),
 }
 

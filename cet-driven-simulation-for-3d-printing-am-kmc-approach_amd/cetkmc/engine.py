@@ -189,13 +189,33 @@ def _boundary_struct(boundary, where):
     return C.byref(b)
 
 
+def _beam_struct(table, L, where, keep):
+    """a beam table -- a mapping with ``u0``, ``amp`` (n_u), ``gj`` and ``gk`` (n_u, L), ``fi`` (depth),
+    as thermal_solver.beam_table returns it -- as a _lib.Beam; the arrays it points to are appended to ``keep``.  Shapes are
+    checked here, values by the library."""
+    try:
+        amp = np.ascontiguousarray(table["amp"], np.float64).reshape(-1)
+        gj, gk = (np.ascontiguousarray(table[n], np.float64) for n in ("gj", "gk"))
+        fi = np.ascontiguousarray(table["fi"], np.float64).reshape(-1)
+        u0 = int(table.get("u0", 0))
+    except (AttributeError, KeyError, TypeError, ValueError):
+        raise ValueError(f"{where}: a beam table is a mapping with 'u0', 'amp', 'gj', 'gk' and 'fi' (got {table!r})") from None
+    if gj.shape != (amp.size, L) or gk.shape != (amp.size, L):
+        raise ValueError(f"{where}: gj and gk must have the shape (n_u, L) = ({amp.size}, {L}) (got {gj.shape}, {gk.shape})")
+    keep += [amp, gj, gk, fi]
+    b = _lib.Beam()
+    b.u0, b.n_u, b.depth = u0, amp.size, fi.size
+    b.amp, b.gj, b.gk, b.fi = _dptr(amp), _dptr(gj), _dptr(gk), _dptr(fi)
+    return b
+
+
 def _info_dict(info):
     """an info record of the library (a ctypes structure of integers) as a dict"""
     return {n: int(getattr(info, n)) for n, _ in info._fields_}
 
 
 class _ThermalSettings:
-    """How a temperature update is made (DESIGN.md sections 25-27): the setters and info records that :class:`Engine` and
+    """How a temperature update is made (DESIGN.md sections 25-28): the setters and info records that :class:`Engine` and
     :class:`Ensemble` share.  The class names the symbol prefix of its setters (``_SET``) and itself (``_WHO``, which the
     ValueErrors of a wrapper carry); the getters are the same symbols for both."""
 
@@ -249,6 +269,12 @@ class _ThermalSettings:
     def boundary_info(self):
         """dict(updates, steps, launches, coeff_uploads): running totals of the updates made with a non-adiabatic boundary"""
         return self._boundary_get()[1]
+
+    # -- beam tables (DESIGN.md section 28) ----------------------------------------------------------------
+    def beam_info(self):
+        """cetkmc_get_beam_info: dict(updates, steps, launches, table_uploads), running totals of the updates whose source was
+        a row of a beam table.  Ensemble: the totals of its calls."""
+        return self._get_info("cetkmc_get_beam_info", _lib.BeamInfo)
 
 
 class Engine(_ThermalSettings):
@@ -415,6 +441,20 @@ class Engine(_ThermalSettings):
         q = np.ascontiguousarray(q_top, dtype=np.float64)
         assert q.shape == (self.L, self.L)
         self._ck(self.lib.cetkmc_thermal_laser(self.h, float(dt), _ptr(q), int(bool(use_latent)), int(bool(scrub_nan))))
+
+    def set_beam(self, table):
+        """cetkmc_set_beam: the source of every laser-mode update becomes a row of ``table`` (thermal_solver.beam_table: u0,
+        amp, gj, gk, fi); None removes the beam.  Needs the implicit scheme.  The table is copied to the device."""
+        if table is None:
+            self._ck(self.lib.cetkmc_set_beam(self.h, None))
+            return
+        keep = []
+        b = _beam_struct(table, self.L, "Engine.set_beam", keep)
+        self._ck(self.lib.cetkmc_set_beam(self.h, C.byref(b)))
+
+    def thermal_beam(self, dt, u, use_latent=True, scrub_nan=False):
+        """cetkmc_thermal_beam: one update now from the beam table's row of update ordinal ``u``"""
+        self._ck(self.lib.cetkmc_thermal_beam(self.h, float(dt), int(u), int(bool(use_latent)), int(bool(scrub_nan))))
 
     # -- single-step primitives -----------------------------------------------------------
     def rate_sweep(self):
@@ -906,6 +946,19 @@ class Ensemble(_ThermalSettings):
             self.close()
         except Exception:
             pass
+
+    def set_beam(self, tables, set_of=None):
+        """cetkmc_ensemble_set_beam: ``tables`` is a sequence of beam tables (thermal_solver.beam_table) that share u0, n_u and
+        depth; replica r reads table ``set_of[r]`` (None: table r, one per replica).  None removes the beam."""
+        if tables is None:
+            self._ck(self.lib.cetkmc_ensemble_set_beam(self.h, 0, None, None))
+            return
+        keep = []
+        arr = (_lib.Beam * max(len(tables), 1))(*[_beam_struct(t, self.L, "Ensemble.set_beam", keep) for t in tables])
+        so = None if set_of is None else np.ascontiguousarray(np.asarray(set_of, dtype=np.int32).reshape(-1))
+        if so is not None and so.size != self.R:
+            raise ValueError(f"Ensemble.set_beam: set_of needs one entry per replica ({self.R}), got {so.size}")
+        self._ck(self.lib.cetkmc_ensemble_set_beam(self.h, len(tables), arr, None if so is None else so.ctypes.data_as(C.POINTER(C.c_int32))))
 
     def run(self, step0, n, defect_fraction, u_pick=None, u_defect=None, u_np=None, rng_mode=0, seeds=None, thermal_mode=1,
             thermal_dt=1e-6, q_planes=None, q_set=None, use_latent=True):

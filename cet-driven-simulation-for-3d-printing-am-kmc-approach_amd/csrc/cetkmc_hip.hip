@@ -77,6 +77,7 @@ using No = std::false_type;
 template <class F> void with_flag(bool on, F&& f) { if (on) f(Yes{}); else f(No{}); }
 template <class F> void with_source(int laser, int latent, F&& f) { if (laser && latent) f(Yes{}, Yes{}); else if (laser) f(Yes{}, No{}); else f(No{}, No{}); }
 template <class F> void with_boundary(bool on, const ImpBc& B, F&& f) { if (on) f(B); else f(); }
+template <class F> void with_beam(bool on, const ImpBeam& M, F&& f) { if (on) f(M); else f(); }
 
 // 20-step temperature updates (kmc_simulation.py:248) among the global steps [step0, step0 + n): multiples of 20 below
 // step0 + n less those below step0
@@ -131,7 +132,18 @@ int load_rccl()
     } while (0)
 
 // ---- handle ---------------------------------------------------------------------------
-// How temperature updates are made (DESIGN.md sections 24 to 27), as the setters leave it.  A handle holds one; an ensemble holds
+// A beam table on the device as the settings name it; the memory belongs to the handle or the ensemble
+// that was given the table (Handle::d_beam, Ens::d_beam).  One set is set_stride doubles: amp[n_u], gj[n_u][L], gk[n_u][L],
+// fi[depth].  base: where the set of this handle begins (a replica: set_of[r] * set_stride); set_of: the ensemble's device
+// array [R], read by the ensemble's own launches alone.
+struct BeamView {
+    bool on = false;
+    const double* d = nullptr;
+    const int32_t* set_of = nullptr;
+    int64_t u0 = 0, set_stride = 0, base = 0;
+    int n_u = 0, depth = 0, L = 0;
+};
+// How temperature updates are made (DESIGN.md sections 24 to 28), as the setters leave it.  A handle holds one; an ensemble holds
 // one for all its replicas and hands it to each (share_thermal), so a direct update on a replica handle follows the ensemble.
 struct ThermalSettings {
     int substeps = 1;                    // n: every update is n steps of dt / n (thermal_sub.hpp)
@@ -140,9 +152,10 @@ struct ThermalSettings {
     bool bc_on = false;                  // some beta != 0
     int remelt_on = 0;                   // the stepping loop melts behind every temperature update (melt.hpp)
     double remelt_threshold = 0.0;
+    BeamView beam{};                     // on: the source of every laser-mode update is a row of this table, not a plane
 };
 // what the updates made so far add up to: a handle's by its own calls, an ensemble's by cetkmc_run_ensemble
-struct ThermalInfo { cetkmc_substep_info sub{}; cetkmc_implicit_info imp{}; cetkmc_boundary_info bc{}; };
+struct ThermalInfo { cetkmc_substep_info sub{}; cetkmc_implicit_info imp{}; cetkmc_boundary_info bc{}; cetkmc_beam_info beam{}; };
 // A device table of Thomas coefficients and what it was built for (compared by bits): [2][L], inv and p of r (section 26), or
 // [3][2][L], inv and p per axis of r and the six beta (section 27).  Allocated by the first update that reads it.
 struct CoefTable { double* d = nullptr; double r = 0.0, beta[6] = {}; };
@@ -299,9 +312,10 @@ struct Handle {
     MeltState melt{};
     void* d_melt_block = nullptr;
     cetkmc_remelt_info melt_info{};      // the counters as last read (end of a stepping call, end of a direct pass)
-    ThermalSettings ts{};        // cetkmc_set_remelt / _thermal_substeps / _thermal_scheme / _thermal_boundary
+    ThermalSettings ts{};        // cetkmc_set_remelt / _thermal_substeps / _thermal_scheme / _thermal_boundary / _beam
     ThermalInfo ti{};
     CoefTable coef{}, coef_bc{}; // of the implicit updates without / with a boundary (two: clearing a boundary uploads nothing)
+    double* d_beam = nullptr;    // cetkmc_set_beam: the table ts.beam names
     // sub-stepped temperature updates (thermal_sub.hpp)
     int substep_block = 0;       // option "substep_block": sub-steps per k_thermal_sub launch; 0 = the measured default (SUB_SDEFAULT at
                                  // L > SUB_PLAIN_L, else the plain path), 1 = the plain path (n launches of the existing kernel) on any handle
@@ -1329,12 +1343,41 @@ ImpBc imp_bc(const cetkmc_thermal_boundary& b, double r, int64_t u)
         }
     return B;
 }
+// the by-value beam of one update: row x of the table (of the handle's own set; an ensemble's launches add the replica's)
+ImpBeam imp_beam(const BeamView& b, int64_t x)
+{
+    const int64_t L = b.L, nu = b.n_u;
+    const double* d = b.d + b.base;
+    ImpBeam M{};
+    M.amp = d + x; M.gj = d + nu + x * L; M.gk = d + nu + nu * L + x * L; M.fi = d + nu * (1 + 2 * L);
+    M.set_of = b.set_of; M.set_stride = b.set_stride; M.depth = b.depth;
+    return M;
+}
+// the update ordinals of a stepping call (or of one direct update: step0 = 20 u, n = 1) lie inside the beam table
+int beam_steps_ok(const char* fn, const BeamView& b, int64_t step0, int64_t n)
+{
+    const int64_t k = updates_in(step0, n);
+    if (k <= 0) return 0;
+    const int64_t first = (step0 > 0 ? step0 + 19 : step0) / 20, last = first + k - 1;
+    if (first < b.u0 || last >= b.u0 + b.n_u)
+        return fail(std::string(fn) + ": the temperature updates of the call, ordinals " + std::to_string(first) + " to " + std::to_string(last) +
+                    ", leave the beam table's rows [" + std::to_string(b.u0) + ", " + std::to_string(b.u0 + b.n_u) + ")");
+    return 0;
+}
+// a stepping call's source arguments while a beam is set: no planes, every update inside the table
+int beam_args_ok(const char* fn, const BeamView& b, const double* q_planes, int64_t n_q, int64_t step0, int64_t n)
+{
+    if (q_planes || n_q)
+        return fail(std::string(fn) + ": a beam is set, so the updates' sources are rows of its table: q_planes must be NULL and n_q 0");
+    return beam_steps_ok(fn, b, step0, n);
+}
 // ---- one plan per update ------------------------------------------------------------------------------------------------------
 // What the settings make of one temperature update of dt, update ordinal u (0 in a direct call, g / 20 at global step g of a
 // stepping call: a boundary's face temperatures follow it): n steps of dt_s at ratio r, explicit or implicit, the latter between
 // insulated walls or (bc) with the six addends B by value.  A handle's update and an ensemble's are launched and counted from it.
-struct UpdatePlan { int n; double dt_s, r; bool implicit, bc; ImpBc B; };
-UpdatePlan plan_update(const ThermalSettings& s, const cetkmc_params& p, double dt, int64_t u)
+// source: a laser-mode update; with a beam set it reads row u - u0 of the table (M by value) instead of a plane.
+struct UpdatePlan { int n; double dt_s, r; bool implicit, bc; ImpBc B; bool beam; int64_t row; ImpBeam M; };
+UpdatePlan plan_update(const ThermalSettings& s, const cetkmc_params& p, double dt, int64_t u, bool source = false)
 {
     UpdatePlan P{};
     P.n = s.substeps;
@@ -1343,6 +1386,11 @@ UpdatePlan plan_update(const ThermalSettings& s, const cetkmc_params& p, double 
     P.implicit = s.scheme == CETKMC_THERMAL_IMPLICIT;
     P.bc = P.implicit && s.bc_on;
     if (P.bc) P.B = imp_bc(s.bc, P.r, u);
+    P.beam = P.implicit && s.beam.on && source;
+    if (P.beam) {
+        P.row = u - s.beam.u0;
+        if (P.row >= 0 && P.row < s.beam.n_u) P.M = imp_beam(s.beam, P.row);       // (the callers refuse any other row before they launch)
+    }
     return P;
 }
 // the update joins the running totals: the implicit records, or the sub-step record while n > 1; launches: the blocked
@@ -1352,6 +1400,7 @@ void count_update(ThermalInfo& ti, const UpdatePlan& P, int64_t launches)
     if (P.implicit) {
         ++ti.imp.updates; ti.imp.steps += P.n; ti.imp.launches += launches;
         if (P.bc) { ++ti.bc.updates; ti.bc.steps += P.n; ti.bc.launches += launches; }
+        if (P.beam) { ++ti.beam.updates; ti.beam.steps += P.n; ti.beam.launches += launches; }
     } else if (P.n > 1) {
         ++ti.sub.updates; ti.sub.substeps += P.n; ti.sub.launches += launches;
     }
@@ -1382,7 +1431,9 @@ void launch_imp_step(hipStream_t st, int L, int R, const UpdatePlan& P, const Im
                      uint8_t* prev, const double* d_q, const StepState* ssp, Between&& between, E&... e)
 {
     with_boundary(P.bc, P.B, [&](auto... b) {
-        launch(k_imp_rows<decltype(b)..., E...>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v, Tin, Tout, prev, d_q, C, ssp, b..., e...);
+        with_beam(P.beam, P.M, [&](auto... m) {         // the beam rides behind the boundary, in the row pass alone
+            launch(k_imp_rows<decltype(b)..., decltype(m)..., E...>, imp_rows_grid(L, L, R), dim3(IMP_R), 0, st, nullptr, nullptr, v, Tin, Tout, prev, d_q, C, ssp, b..., m..., e...);
+        });
         between();
         launch(k_imp_lines<1, decltype(b)..., E...>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v, Tout, C, ssp, b..., e...);
         launch(k_imp_lines<0, decltype(b)..., E...>, imp_lines_grid(L, R), dim3(64), 0, st, nullptr, nullptr, v, Tout, C, ssp, b..., e...);
@@ -1393,6 +1444,8 @@ int launch_thermal_imp(Handle* h, const UpdatePlan& P, int laser, const double* 
 {
     const int L = h->L;
     const double* coef = nullptr;
+    if (P.beam && (P.row < 0 || P.row >= h->ts.beam.n_u)) return fail("implicit update: update ordinal outside the beam table");
+    if (P.beam) d_q = nullptr;
     CHK(plan_coeffs(h, h->ts, P, h->ti, &coef));
     const StepState* ssp = batch ? h->d_ss : nullptr;
     ++h->cnt.thermal_updates;
@@ -1416,7 +1469,7 @@ int launch_thermal_imp(Handle* h, const UpdatePlan& P, int laser, const double* 
 // a temperature update of the handle, update ordinal u: P.n applications of the explicit step with dt / n, or as many implicit steps
 int launch_thermal(Handle* h, double dt, int laser, const double* d_q, int use_latent, int scrub, bool batch, int64_t u = 0)
 {
-    const UpdatePlan P = plan_update(h->ts, h->p, dt, u);
+    const UpdatePlan P = plan_update(h->ts, h->p, dt, u, laser != 0);
     if (P.implicit) return launch_thermal_imp(h, P, laser, d_q, use_latent, scrub, batch);
     CHK(launch_thermal_one(h, P.dt_s, laser, d_q, use_latent, scrub, batch));
     if (P.n == 1) return 0;
@@ -1541,10 +1594,11 @@ int batch_thermal(Handle* h, int64_t g, int64_t end, int thermal_mode, double dt
 {
     const size_t L2 = (size_t)h->L * h->L;
     const int laser = thermal_mode == 2 ? 1 : 0, latent = laser ? use_latent : 0;
-    CHK(thermal_step(h, g, dt, laser, laser ? h->d_q + (size_t)*q_idx * L2 : nullptr, latent, 1));
+    const bool planes = laser && !h->ts.beam.on;        // a beam: the update's source is the table row of g / 20
+    CHK(thermal_step(h, g, dt, laser, planes ? h->d_q + (size_t)*q_idx * L2 : nullptr, latent, 1));
     *q_idx += laser;
     if (g + 20 < end)      // the next update lies inside this batch (its source plane is on the device): look ahead
-        CHK(launch_thermal_ahead(h, g + 20, dt, laser, laser ? h->d_q + (size_t)*q_idx * L2 : nullptr, latent, 1));
+        CHK(launch_thermal_ahead(h, g + 20, dt, laser, planes ? h->d_q + (size_t)*q_idx * L2 : nullptr, latent, 1));
     return 0;
 }
 
@@ -1618,7 +1672,7 @@ void destroy_impl(Handle* h)
                     h->d_flag, h->d_qtop, h->d_u_pick, h->d_u_defect, h->d_u_np, h->d_q, h->d_log_total,
                     h->d_log_event, h->d_log_nev, h->d_sup_dom, h->d_sup_picks, h->d_sup_cnt, h->d_sup_log, h->d_sup_rmax,
                     h->d_loc_horizon, h->d_loc_capped, h->d_front_part, h->d_front_out, h->d_layer_part, h->d_layer_out, h->d_layer_eq,
-                    h->coef.d, h->coef_bc.d};
+                    h->coef.d, h->coef_bc.d, h->d_beam};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
@@ -1669,9 +1723,19 @@ struct Ens {
     unsigned long long* d_melt_out = nullptr;      // [R][4] counters gathered at the end of a call
     ThermalSettings ts{};                // cetkmc_ensemble_set_remelt / _thermal_substeps / _thermal_scheme / _thermal_boundary: one for all replicas
     ThermalInfo ti{};                    // of the updates cetkmc_run_ensemble made
+    double* d_beam = nullptr;            // cetkmc_ensemble_set_beam: every set of the table ts.beam names, and the replicas' sets [R]
+    int32_t* d_beam_set_of = nullptr;
+    std::vector<int32_t> beam_set_of;
 };
-// the ensemble's settings reach every replica: a direct update on a replica handle follows the ensemble
-void share_thermal(Ens* e) { for (Handle* h : e->reps) h->ts = e->ts; }
+// the ensemble's settings reach every replica: a direct update on a replica handle follows the ensemble (a beam: from the replica's set)
+void share_thermal(Ens* e)
+{
+    for (size_t r = 0; r < e->reps.size(); ++r) {
+        ThermalSettings& s = e->reps[r]->ts;
+        s = e->ts;
+        if (s.beam.on) { s.beam.base = (int64_t)e->beam_set_of[r] * s.beam.set_stride; s.beam.set_of = nullptr; }
+    }
+}
 // every field of cetkmc_params but impurity_c / nu_dep is shared by the replicas (kernels.hpp)
 bool shared_params_equal(cetkmc_params a, cetkmc_params b)
 {
@@ -1698,7 +1762,7 @@ void destroy_ens(Ens* e)
     void* ptrs[] = {e->d_table, e->d_u_pick, e->d_u_defect, e->d_u_np, e->d_log_total, e->d_log_event, e->d_log_nev, e->d_q,
                     e->d_ss_out, e->d_n_out, e->d_cc_parent, e->d_cc_cid, e->d_cc_roots, e->d_cc_labels, e->d_cc_n, e->d_cc_stats,
                     e->d_cc_offs, e->d_sc_offs, e->d_sc_idx, e->d_g_idx, e->d_g_T, e->d_counts, e->d_g_n, e->d_solid_block,
-                    e->d_origin_block, e->d_melt_tab, e->d_melt_out};
+                    e->d_origin_block, e->d_melt_tab, e->d_melt_out, e->d_beam, e->d_beam_set_of};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -1750,6 +1814,7 @@ int cetkmc_struct_size(const char* name)
     SZ("implicit_info", struct cetkmc_implicit_info);
     SZ("thermal_boundary", struct cetkmc_thermal_boundary);
     SZ("boundary_info", struct cetkmc_boundary_info);
+    SZ("beam", struct cetkmc_beam); SZ("beam_info", struct cetkmc_beam_info);
 #undef SZ
     return -1;
 }
@@ -2103,6 +2168,7 @@ int cetkmc_thermal_laser(void* handle, double dt, const double* q_top, int use_l
 {
     Handle* h = (Handle*)handle;
     if (!h || !q_top) return fail("null argument");
+    if (h->ts.beam.on) return fail("cetkmc_thermal_laser: a beam is set; cetkmc_thermal_beam makes an update from its table (or cetkmc_set_beam(handle, NULL) first)");
     HIPCHK(hipSetDevice(h->dev));
     HIPCHK(hipMemcpyAsync(h->d_qtop, q_top, (size_t)h->L * h->L * sizeof(double), hipMemcpyHostToDevice, h->stream));
     CHK(launch_thermal(h, dt, 1, h->d_qtop, use_latent, scrub_nan, false));
@@ -2224,7 +2290,7 @@ int cetkmc_enumerate_events(void* handle, cetkmc_event* buf, int64_t cap, int64_
 
 // argument checks / host inputs of a batch -> the handle's device buffers (grown as needed); shared by cetkmc_stage_inputs /
 // cetkmc_run_steps
-static int check_run_args(const cetkmc_run_args* a, bool need_ptrs)
+static int check_run_args(const cetkmc_run_args* a, bool need_ptrs, bool beam)
 {
     const int64_t n = a->n_steps;
     if (n < 0) return fail("n_steps < 0");
@@ -2234,7 +2300,7 @@ static int check_run_args(const cetkmc_run_args* a, bool need_ptrs)
     if (need_ptrs && streams && a->defect_fraction > 0.0 && n > 0 && !a->u_defect) return fail("u_defect required when defect_fraction > 0");
     if (need_ptrs && streams && a->np_cap > 0 && !a->u_np) return fail("u_np required");
     const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
-    if (a->thermal_mode == 2 && (n_therm > a->n_q || (need_ptrs && n_therm > 0 && !a->q_planes)))
+    if (a->thermal_mode == 2 && !beam && (n_therm > a->n_q || (need_ptrs && n_therm > 0 && !a->q_planes)))
         return fail("thermal_mode 2 needs one q plane per thermal update in the batch");
     return 0;
 }
@@ -2245,14 +2311,15 @@ static int upload_run_inputs(Handle* h, const cetkmc_run_args* a)
     const size_t L2 = (size_t)h->L * h->L;
     CHK(reserve_steps(h, (size_t)n));
     CHK(grow(&h->d_u_np, &h->cap_np, (size_t)std::max<int64_t>(a->np_cap, 2)));
-    if (a->thermal_mode == 2) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
+    const bool planes = a->thermal_mode == 2 && !h->ts.beam.on;        // a beam: no plane travels
+    if (planes) CHK(grow(&h->d_q, &h->cap_q, (size_t)std::max<int64_t>(n_therm, 1) * L2));
     // the small arrays travel through the page-locked staging buffer (queued copies); a large one goes directly
     struct Part { void* dst; const void* src; size_t bytes; };
     const bool streams = a->rng_mode != 2;
     const Part parts[4] = {{h->d_u_pick, a->u_pick, (streams && n > 0 && a->u_pick) ? (size_t)n * 8 : 0},
                            {h->d_u_defect, a->u_defect, (streams && n > 0 && a->u_defect) ? (size_t)n * 8 : 0},
                            {h->d_u_np, a->u_np, (streams && a->np_cap > 0 && a->u_np) ? (size_t)a->np_cap * 8 : 0},
-                           {h->d_q, a->q_planes, (a->thermal_mode == 2 && n_therm > 0) ? (size_t)n_therm * L2 * 8 : 0}};
+                           {h->d_q, a->q_planes, (planes && n_therm > 0) ? (size_t)n_therm * L2 * 8 : 0}};
     size_t small = 0;
     for (const Part& q : parts) if (q.bytes && q.bytes <= PIN_SMALL_MAX) small += q.bytes;
     // the staging buffer may still feed the copies of the previous call: they are complete (every stepping call ends with a
@@ -2270,7 +2337,7 @@ static int upload_run_inputs(Handle* h, const cetkmc_run_args* a)
         }
     }
     h->cnt.bytes_h2d += (n > 0 ? n * 8 : 0) + (n > 0 && a->u_defect ? n * 8 : 0) + std::max<int64_t>(a->np_cap, 0) * 8 +
-                        (a->thermal_mode == 2 ? n_therm * (int64_t)L2 * 8 : 0);
+                        (planes ? n_therm * (int64_t)L2 * 8 : 0);
     return 0;
 }
 
@@ -2279,8 +2346,9 @@ int cetkmc_stage_inputs(void* handle, const cetkmc_run_args* a)
     Handle* h = (Handle*)handle;
     if (!h || !a) return fail("null argument");
     if (h->in_ensemble) return fail("an ensemble replica is stepped by cetkmc_run_ensemble");
+    if (h->ts.beam.on && a->thermal_mode == 2) CHK(beam_args_ok("cetkmc_stage_inputs", h->ts.beam, a->q_planes, a->n_q, a->step0, a->n_steps));
     invalidate(h, Cause::batch_begin);
-    CHK(check_run_args(a, true));
+    CHK(check_run_args(a, true, h->ts.beam.on));
     HIPCHK(hipSetDevice(h->dev));
     CHK(upload_run_inputs(h, a));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2334,7 +2402,7 @@ static int stage_run(Handle* h, const cetkmc_run_args* a)
     const int64_t n = a->n_steps;
     // all input pointers NULL: the batch's inputs were put on the device by cetkmc_stage_inputs (same batch shape)
     const bool staged = n > 0 && a->rng_mode != 2 && !a->u_pick && !a->u_defect && !a->u_np && !a->q_planes;
-    CHK(check_run_args(a, !staged));
+    CHK(check_run_args(a, !staged, h->ts.beam.on));
     const auto g = h->staged;
     invalidate(h, Cause::batch_begin);      // a staged batch is consumed (or dropped) by the next stepping call
     if (staged) {
@@ -2467,6 +2535,7 @@ int cetkmc_run_steps(void* handle, const cetkmc_run_args* a, cetkmc_run_result* 
     const int64_t n = a->n_steps;
     CHK(origin_room(h, n, "cetkmc_run_steps"));
     if (h->ts.bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_steps", h->ts.bc, a->step0, n));
+    if (h->ts.beam.on && a->thermal_mode == 2) CHK(beam_args_ok("cetkmc_run_steps", h->ts.beam, a->q_planes, a->n_q, a->step0, n));
     CHK(stage_run(h, a));
     // reset the batch part of the step state (nucleation_count persists): a one-thread kernel, no host round trip
     hipLaunchKernelGGL(k_batch_reset, dim3(1), dim3(1), 0, h->stream, h->d_ss);
@@ -3205,7 +3274,9 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     const int64_t n_therm = a->thermal_mode ? updates_in(a->step0, n) : 0;
     const bool laser = a->thermal_mode == 2;
     if (e->ts.bc_on && a->thermal_mode) CHK(boundary_steps_ok("cetkmc_run_ensemble", e->ts.bc, a->step0, n));
-    if (laser) {       // everything about the plane sets is checked before anything is copied or launched
+    const bool beam = laser && e->ts.beam.on;       // the sources are rows of the ensemble's beam table: no plane sets
+    if (beam) CHK(beam_args_ok("cetkmc_run_ensemble", e->ts.beam, a->q_planes, a->n_q, a->step0, n));
+    if (laser && !beam) {       // everything about the plane sets is checked before anything is copied or launched
         if (a->n_q < n_therm) return fail("thermal_mode 2 needs one q plane per temperature update of the call in every plane set (n_q too small)");
         if (n_therm > 0 && !a->q_planes) return fail("thermal_mode 2: q_planes[n_sets][n_q][L*L] required (the call holds a temperature update)");
         if (!a->q_set && a->n_sets != R) return fail("thermal_mode 2: q_set NULL means plane set r for replica r, so n_sets must equal R");
@@ -3250,7 +3321,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         }
     }
     const size_t L2 = (size_t)L * L;
-    if (laser && n_therm > 0) {      // the first n_therm planes of every set, once per call: [n_sets][n_therm][L*L] on the device
+    if (laser && !beam && n_therm > 0) {      // the first n_therm planes of every set, once per call: [n_sets][n_therm][L*L] on the device
         CHK(grow(&e->d_q, &e->cap_q, (size_t)a->n_sets * (size_t)n_therm * L2));
         HIPCHK(hipMemcpy2DAsync(e->d_q, (size_t)n_therm * L2 * 8, a->q_planes, (size_t)a->n_q * L2 * 8, (size_t)n_therm * L2 * 8,
                                 (size_t)a->n_sets, hipMemcpyHostToDevice, st));
@@ -3279,7 +3350,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
         t.u_np = streams ? e->d_u_np + (size_t)r * stride : nullptr;
         t.log_total = e->d_log_total + (size_t)r * nn; t.log_event = e->d_log_event + (size_t)r * nn; t.log_nev = e->d_log_nev + (size_t)r * nn;
         t.active = e->frozen[(size_t)r] ? 0 : 1;
-        t.q = (laser && n_therm > 0) ? e->d_q + (size_t)(a->q_set ? a->q_set[r] : r) * (size_t)n_therm * L2 : nullptr;
+        t.q = (laser && !beam && n_therm > 0) ? e->d_q + (size_t)(a->q_set ? a->q_set[r] : r) * (size_t)n_therm * L2 : nullptr;
     }
     HIPCHK(hipMemcpyAsync(e->d_table, e->table.data(), (size_t)R * sizeof(EnsRep), hipMemcpyHostToDevice, st));
     // the replica rides in y (in z, times the plane groups, for the temperature kernel)
@@ -3322,7 +3393,7 @@ int cetkmc_run_ensemble(void* handle, const cetkmc_ens_args* a, cetkmc_run_resul
     for (int64_t s = 0; s < n; ++s) {
         const int64_t g = a->step0 + s;
         if (a->thermal_mode && g % 20 == 0) {          // kmc_simulation.py:248-250, shared cadence
-            const UpdatePlan P = plan_update(e->ts, h0->p, a->thermal_dt, g / 20);
+            const UpdatePlan P = plan_update(e->ts, h0->p, a->thermal_dt, g / 20, laser);
             for (int q = 0; q < P.n; ++q) {        // steps 2..n: no scrub, no latent term, same plane
                 // an implicit step (thermal_imp.hpp): three launches, the flip behind the row pass (the line passes work in place)
                 if (P.implicit) launch_imp_step(st, L, R, P, q == 0 ? ic0 : ic_sub, v0, nullptr, nullptr, nullptr, nullptr, nullptr, [&] { flip(q == 0); }, sel);
@@ -4438,7 +4509,9 @@ int cetkmc_time_thermal(void* handle, int laser, int n_updates, double* ms_total
     if (n_updates < 0) return fail("cetkmc_time_thermal: n_updates must be >= 0");
     HIPCHK(hipSetDevice(h->dev));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int u = 0; u < n_updates; ++u) CHK(launch_thermal(h, 1e-6, laser ? 1 : 0, laser ? h->d_qtop : nullptr, laser ? 1 : 0, 1, false));
+    const bool beam = laser && h->ts.beam.on;       // a beam: row 0 of its table, update ordinal u0
+    for (int u = 0; u < n_updates; ++u)
+        CHK(launch_thermal(h, 1e-6, laser ? 1 : 0, laser && !beam ? h->d_qtop : nullptr, laser ? 1 : 0, 1, false, beam ? h->ts.beam.u0 : 0));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *ms_total = 0.0;
@@ -4472,6 +4545,8 @@ static int set_thermal_scheme(const char* fn, void* handle, bool ens, int scheme
     ThermalSettings& s = settings_of(h, e);
     if (scheme == CETKMC_THERMAL_EXPLICIT && s.bc_on)
         return fail(f + ": the explicit scheme is refused while a thermal boundary is set (" + pre + "set_thermal_boundary(handle, NULL) first)");
+    if (scheme == CETKMC_THERMAL_EXPLICIT && s.beam.on)
+        return fail(f + ": the explicit scheme is refused while a beam is set (" + pre + "set_beam with NULL first); the explicit kernels read a source plane");
     s.scheme = scheme;
     if (e) share_thermal(e);
     return 0;
@@ -4525,6 +4600,141 @@ int cetkmc_get_thermal_boundary(void* handle, struct cetkmc_thermal_boundary* b,
 int cetkmc_implicit_coeffs_bc(int L, double r, double beta_lo, double beta_hi, double* inv, double* p)
 {
     return implicit_coeffs_bc_host("cetkmc_implicit_coeffs_bc", L, r, beta_lo, beta_hi, inv, p);
+}
+
+// ---- beam tables: laser scan paths and a volumetric source (thermal_imp.hpp) --------------------------
+static int beam_table_ok(const std::string& f, const cetkmc_beam& t, int L, const std::string& which)
+{
+    if (t.n_u < 1) return fail(f + ": " + which + "n_u must be >= 1 (got " + std::to_string(t.n_u) + ")");
+    if (t.depth < 1 || t.depth > L) return fail(f + ": " + which + "depth must be in 1.." + std::to_string(L) + " (got " + std::to_string(t.depth) + ")");
+    if (!t.amp || !t.gj || !t.gk || !t.fi) return fail(f + ": " + which + "amp, gj, gk and fi are required");
+    struct Arr { const char* name; const double* p; int64_t n; };
+    const Arr arrs[4] = {{"amp", t.amp, t.n_u}, {"gj", t.gj, (int64_t)t.n_u * L}, {"gk", t.gk, (int64_t)t.n_u * L}, {"fi", t.fi, t.depth}};
+    for (const Arr& a : arrs)
+        for (int64_t q = 0; q < a.n; ++q)
+            if (!(a.p[q] >= 0.0) || !std::isfinite(a.p[q]))
+                return fail(f + ": " + which + a.name + "[" + std::to_string(q) + "] is negative or not finite");
+    return 0;
+}
+// one set behind the other in the layout BeamView names
+static void beam_pack(const cetkmc_beam& t, int L, double* out)
+{
+    const size_t nu = (size_t)t.n_u, nl = nu * (size_t)L;
+    memcpy(out, t.amp, nu * 8); memcpy(out + nu, t.gj, nl * 8); memcpy(out + nu + nl, t.gk, nl * 8); memcpy(out + nu + 2 * nl, t.fi, (size_t)t.depth * 8);
+}
+static int64_t beam_stride(const cetkmc_beam& t, int L) { return (int64_t)t.n_u * (1 + 2 * (int64_t)L) + t.depth; }
+// the packed sets (and an ensemble's set_of) replace the table *d_tab / *d_set names; the launches that read the old one are awaited
+static int beam_upload(const std::string& f, Handle* h, const std::vector<double>& tab, const int32_t* set_of, int R, double** d_tab, int32_t** d_set)
+{
+    HIPCHK(hipSetDevice(h->dev));
+    double* nd = nullptr;
+    int32_t* ns = nullptr;
+    if (hipMalloc((void**)&nd, tab.size() * 8) != hipSuccess || (set_of && hipMalloc((void**)&ns, (size_t)R * 4) != hipSuccess)) {
+        (void)hipGetLastError();
+        if (nd) (void)hipFree(nd);
+        return fail(f + ": no device memory for " + std::to_string(tab.size() * 8) + " bytes");
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(nd, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    if (set_of) HIPCHK(hipMemcpy(ns, set_of, (size_t)R * 4, hipMemcpyHostToDevice));
+    if (*d_tab) (void)hipFree(*d_tab);
+    *d_tab = nd;
+    if (d_set) { if (*d_set) (void)hipFree(*d_set); *d_set = ns; }
+    return 0;
+}
+static int beam_drop(Handle* h, double** d_tab, int32_t** d_set)
+{
+    if (!*d_tab) return 0;
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    (void)hipFree(*d_tab); *d_tab = nullptr;
+    if (d_set && *d_set) { (void)hipFree(*d_set); *d_set = nullptr; }
+    return 0;
+}
+
+int cetkmc_set_beam(void* handle, const struct cetkmc_beam* t)
+{
+    const std::string f = "cetkmc_set_beam";
+    if (!handle) return fail(f + ": null handle");
+    Ens* e = nullptr;
+    CHK(setter_ensemble(f.c_str(), handle, false, &e));
+    Handle* h = (Handle*)handle;
+    if (h->in_ensemble) return fail(f + ": the replicas of an ensemble read the ensemble's table (cetkmc_ensemble_set_beam)");
+    if (!t) {
+        h->ts.beam = BeamView{};
+        return beam_drop(h, &h->d_beam, nullptr);
+    }
+    CHK(beam_table_ok(f, *t, h->L, ""));
+    if (h->ts.scheme != CETKMC_THERMAL_IMPLICIT)
+        return fail(f + ": a beam needs the implicit scheme (cetkmc_set_thermal_scheme); the explicit kernels read a source plane");
+    std::vector<double> tab((size_t)beam_stride(*t, h->L));
+    beam_pack(*t, h->L, tab.data());
+    CHK(beam_upload(f, h, tab, nullptr, 0, &h->d_beam, nullptr));
+    BeamView& b = h->ts.beam;
+    b = BeamView{};
+    b.on = true; b.d = h->d_beam; b.u0 = t->u0; b.n_u = t->n_u; b.depth = t->depth; b.L = h->L; b.set_stride = (int64_t)tab.size();
+    ++h->ti.beam.table_uploads;
+    return 0;
+}
+
+int cetkmc_ensemble_set_beam(void* handle, int n_sets, const struct cetkmc_beam* sets, const int32_t* set_of)
+{
+    const std::string f = "cetkmc_ensemble_set_beam";
+    if (!handle) return fail(f + ": null handle");
+    Ens* e = nullptr;
+    CHK(setter_ensemble(f.c_str(), handle, true, &e));
+    Handle* h0 = e->reps[0];
+    if (!sets) {
+        e->ts.beam = BeamView{};
+        share_thermal(e);
+        return beam_drop(h0, &e->d_beam, &e->d_beam_set_of);
+    }
+    if (n_sets < 1) return fail(f + ": n_sets must be >= 1");
+    for (int q = 0; q < n_sets; ++q) CHK(beam_table_ok(f, sets[q], e->L, "set " + std::to_string(q) + ": "));
+    for (int q = 1; q < n_sets; ++q)
+        if (sets[q].u0 != sets[0].u0 || sets[q].n_u != sets[0].n_u || sets[q].depth != sets[0].depth)
+            return fail(f + ": set " + std::to_string(q) + " differs from set 0 in u0, n_u or depth (the sets share them)");
+    if (!set_of && n_sets != e->R) return fail(f + ": set_of NULL means set r for replica r, so n_sets must equal R");
+    std::vector<int32_t> so((size_t)e->R);
+    for (int r = 0; r < e->R; ++r) {
+        so[(size_t)r] = set_of ? set_of[r] : r;
+        if (so[(size_t)r] < 0 || so[(size_t)r] >= n_sets) return fail(f + ": set_of[" + std::to_string(r) + "] is outside [0, n_sets)");
+    }
+    if (e->ts.scheme != CETKMC_THERMAL_IMPLICIT)
+        return fail(f + ": a beam needs the implicit scheme (cetkmc_ensemble_set_thermal_scheme); the explicit kernels read a source plane");
+    const int64_t stride = beam_stride(sets[0], e->L);
+    std::vector<double> tab((size_t)stride * (size_t)n_sets);
+    for (int q = 0; q < n_sets; ++q) beam_pack(sets[q], e->L, tab.data() + (size_t)q * (size_t)stride);
+    CHK(beam_upload(f, h0, tab, so.data(), e->R, &e->d_beam, &e->d_beam_set_of));
+    e->beam_set_of = so;
+    BeamView& b = e->ts.beam;
+    b = BeamView{};
+    b.on = true; b.d = e->d_beam; b.set_of = e->d_beam_set_of; b.u0 = sets[0].u0; b.n_u = sets[0].n_u; b.depth = sets[0].depth; b.L = e->L; b.set_stride = stride;
+    share_thermal(e);
+    ++e->ti.beam.table_uploads;
+    return 0;
+}
+
+int cetkmc_get_beam_info(void* handle, struct cetkmc_beam_info* info)
+{
+    if (!handle || !info) return fail("cetkmc_get_beam_info: null argument");
+    *info = thermal_info_of(handle).beam;
+    return 0;
+}
+
+int cetkmc_thermal_beam(void* handle, double dt, int64_t u, int use_latent, int scrub_nan)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return fail("cetkmc_thermal_beam: null handle");
+    if (!h->ts.beam.on) return fail("cetkmc_thermal_beam: no beam is set (cetkmc_set_beam)");
+    if (u < h->ts.beam.u0 || u >= h->ts.beam.u0 + h->ts.beam.n_u)
+        return fail("cetkmc_thermal_beam: update ordinal " + std::to_string(u) + " is outside the beam table's rows [" + std::to_string(h->ts.beam.u0) + ", " +
+                    std::to_string(h->ts.beam.u0 + h->ts.beam.n_u) + ")");
+    if (h->ts.bc_on) CHK(boundary_steps_ok("cetkmc_thermal_beam", h->ts.bc, 20 * u, 1));
+    HIPCHK(hipSetDevice(h->dev));
+    CHK(launch_thermal(h, dt, 1, nullptr, use_latent, scrub_nan, false, u));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 }  // extern "C"

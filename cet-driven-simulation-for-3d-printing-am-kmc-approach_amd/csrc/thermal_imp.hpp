@@ -34,6 +34,14 @@
 // y[L - 1] = ((b[L - 1] + c_hi) + r y[L - 2]) inv[L - 1].  An adiabatic face adds nothing (not even + 0.0).  Every boundary
 // statement stands under if constexpr: the instantiations without an ImpBc are the kernels of section 26, instruction for
 // instruction.
+//
+// Beam form: the instantiations of k_imp_rows whose trailing pack holds an ImpBeam, behind the optional
+// ImpBc and in front of the optional EnsSel.  The source is no plane but a product of factors the host tabulated:
+// qv = (amp * fi[d]) * (gj[j] * gk[k]) for depth d = L - 1 - i < D, else 0: three multiplies in this order, under
+// -ffp-contract=off the bits of a sequential restatement.  amp * fi[d] and gj[j] are wave-uniform; the lane's gk[k] is loaded once
+// per chunk of columns, ahead of the row loop, which issues no load for the source.  A row whose uniform factors give zero gets
+// the term of an unheated row, so the ballot of rows with full terms is the beam's footprint.  q_top is null.  Every beam
+// statement stands under if constexpr; k_imp_lines knows no beam.
 #pragma once
 #include "kernels.hpp"
 
@@ -51,13 +59,34 @@ struct ImpBc {
     double c[6];
     int on;
 };
-template <class... E> struct imp_pack { static constexpr bool bc = false; static constexpr int n_ens = (int)sizeof...(E); };
-template <class... E> struct imp_pack<ImpBc, E...> { static constexpr bool bc = true; static constexpr int n_ens = (int)sizeof...(E); };
+// the source of one update in the beam form: the current row of the handle's beam table (device pointers).  An ensemble's table
+// holds its sets one behind the other, set_stride doubles apart; replica r reads set set_of[r] (a single handle: set_of null, the
+// pointers are those of its own set).
+struct ImpBeam {
+    const double* amp;           // [1]
+    const double* gj;            // [L]
+    const double* gk;            // [L]
+    const double* fi;            // [depth]
+    const int32_t* set_of;       // [R], ensemble launches only
+    int64_t set_stride;
+    int depth;
+};
+template <class... E> struct imp_pack { static constexpr bool bc = false, beam = false; static constexpr int n_ens = (int)sizeof...(E); };
+template <class... E> struct imp_pack<ImpBc, E...> { static constexpr bool bc = true, beam = false; static constexpr int n_ens = (int)sizeof...(E); };
+template <class... E> struct imp_pack<ImpBeam, E...> { static constexpr bool bc = false, beam = true; static constexpr int n_ens = (int)sizeof...(E); };
+template <class... E> struct imp_pack<ImpBc, ImpBeam, E...> { static constexpr bool bc = true, beam = true; static constexpr int n_ens = (int)sizeof...(E); };
 template <class... E> __device__ __forceinline__ const ImpBc& imp_bc_of(const ImpBc& B, const E&...) { return B; }
 // the replica selection of a boundary-form ensemble launch stands behind the ImpBc
 template <class S> __device__ __forceinline__ const auto& ens_rep(unsigned r, const ImpBc&, const S& sel) { return ens_rep(r, sel); }
 template <class S> __device__ __forceinline__ int ens_rel(const ImpBc&, const S& sel) { return ens_rel(sel); }
 template <class S> __device__ __forceinline__ int64_t ens_q_off(const ImpBc&, const S& sel) { return ens_q_off(sel); }
+// the beam of a beam-form launch, and its replica selection behind the ImpBeam
+template <class... E> __device__ __forceinline__ const ImpBeam& imp_beam_of(const ImpBeam& M, const E&...) { return M; }
+template <class... E> __device__ __forceinline__ const ImpBeam& imp_beam_of(const ImpBc&, const ImpBeam& M, const E&...) { return M; }
+template <class S> __device__ __forceinline__ const auto& ens_rep(unsigned r, const ImpBeam&, const S& sel) { return ens_rep(r, sel); }
+template <class S> __device__ __forceinline__ int ens_rel(const ImpBeam&, const S& sel) { return ens_rel(sel); }
+template <class S> __device__ __forceinline__ const auto& ens_rep(unsigned r, const ImpBc&, const ImpBeam&, const S& sel) { return ens_rep(r, sel); }
+template <class S> __device__ __forceinline__ int ens_rel(const ImpBc&, const ImpBeam&, const S& sel) { return ens_rel(sel); }
 constexpr int IMP_R = 64, IMP_C = 64, IMP_PITCH = IMP_C + 1, IMP_U = 8, IMP_V = 16;   // IMP_V: rows of a chunk in flight per lane (k_imp_rows)
 
 // the scrub of this scheme: NaN -> T_nan, +-inf -> the clip values (not +-DBL_MAX, which a solve would spread over the lattice)
@@ -74,12 +103,13 @@ template <class... E>
 __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __restrict__ Tin, double* Tout, uint8_t* __restrict__ prev_state,
                                                     const double* __restrict__ q_top, ImpCfg C, const StepState* __restrict__ ss, E... ens)
 {
-    constexpr bool BC = imp_pack<E...>::bc;
+    constexpr bool BC = imp_pack<E...>::bc, BEAM = imp_pack<E...>::beam;
     if constexpr (imp_pack<E...>::n_ens > 0) {
         const auto& e = ens_rep(blockIdx.y, ens...);
         const int rel = ens_rel(ens...);
         S = e.view[rel]; Tin = e.view[rel].T; Tout = e.view[rel ^ 1].T; prev_state = e.prev; ss = e.ss;
-        q_top = C.laser ? e.q + ens_q_off(ens...) : nullptr;
+        if constexpr (BEAM) q_top = nullptr;
+        else q_top = C.laser ? e.q + ens_q_off(ens...) : nullptr;
     }
     __shared__ double tile[IMP_R * IMP_PITCH];
     const int L = S.L, lane = threadIdx.x;
@@ -101,6 +131,19 @@ __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __
     const bool source = C.laser != 0, latent = source && C.use_latent;
     double* mine = tile + lane * IMP_PITCH;     // the row this lane sweeps
     const int nchunk = (L + IMP_C - 1) / IMP_C;
+    // beam form: this replica's set of the table; amp is read only by an update with a source (wave-uniform, as gj and fi are)
+    [[maybe_unused]] const double* __restrict__ bgj = nullptr;
+    [[maybe_unused]] const double* __restrict__ bgk = nullptr;
+    [[maybe_unused]] const double* __restrict__ bfi = nullptr;
+    [[maybe_unused]] double bamp = 0.0;
+    [[maybe_unused]] int bD = 0;
+    if constexpr (BEAM) {
+        const ImpBeam& M = imp_beam_of(ens...);
+        int64_t off = 0;
+        if constexpr (imp_pack<E...>::n_ens > 0) off = (int64_t)M.set_of[blockIdx.y] * M.set_stride;
+        bgj = M.gj + off; bgk = M.gk + off; bfi = M.fi + off; bD = M.depth;
+        if (source) bamp = M.amp[off];
+    }
     // Rows whose right-hand side needs more than the field: those of plane L - 1 (the source) and those written since the last
     // update (latent heat), one bit per row of the block.  Every other voxel of a laser-mode update gets thermal_voxel()'s
     // terms with qterm = dF = 0, which is + 0.0 for finite settings (it turns a -0.0 into +0.0, as the definition does).
@@ -112,7 +155,12 @@ __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __
         if (lane < nr) {
             const int64_t row = row0 + lane;
             const int lp = (int)(row / L), j = (int)(row - (int64_t)lp * L);
-            nd = (S.gi0 + lp == L - 1) || (latent && S.row_chg[(int64_t)(lp + 2) * L + j]);
+            if constexpr (BEAM) {       // the beam's footprint: planes L - D .. L - 1, rows with non-zero uniform factors
+                const int d = L - 1 - (S.gi0 + lp);
+                nd = (d < bD && bamp * bfi[d] != 0.0 && bgj[j] != 0.0) || (latent && S.row_chg[(int64_t)(lp + 2) * L + j]);
+            } else {
+                nd = (S.gi0 + lp == L - 1) || (latent && S.row_chg[(int64_t)(lp + 2) * L + j]);
+            }
         }
         need = __ballot(nd);
     }
@@ -148,13 +196,21 @@ __global__ __launch_bounds__(IMP_R) void k_imp_rows(SlabView S, const double* __
         }
         if (k < L) {                // the rows with a source or a flag: thermal_voxel()'s terms in full (a lane's own tile entries)
             unsigned long long w = need;
+            [[maybe_unused]] double gkv = 0.0;
+            if constexpr (BEAM) { if (w) gkv = bgk[k]; }      // the lane's column factor, once per chunk
 #pragma unroll 1
             while (w) {
                 const int q = __ffsll(w) - 1;
                 w &= w - 1;
                 const int64_t row = row0 + q;
                 const int lp = (int)(row / L), j = (int)(row - (int64_t)lp * L), li = lp + 2;
-                const double qv = (S.gi0 + lp == L - 1) ? q_top[(int64_t)j * L + k] : 0.0;
+                double qv;
+                if constexpr (BEAM) {
+                    const int d = L - 1 - (S.gi0 + lp);
+                    qv = d < bD ? (bamp * bfi[d]) * (bgj[j] * gkv) : 0.0;
+                } else {
+                    qv = (S.gi0 + lp == L - 1) ? q_top[(int64_t)j * L + k] : 0.0;
+                }
                 const double qterm = (qv != 0.0) ? qv / C.rho_cp : 0.0;
                 double dF = 0.0;
                 if (latent && S.row_chg[(int64_t)li * L + j]) {      // only rows written since the last update can differ

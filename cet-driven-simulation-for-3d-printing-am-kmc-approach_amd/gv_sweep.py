@@ -57,7 +57,7 @@ import os
 import pandas as pd
 
 from constants import ATOMIC_SPACING_W, DEFECT_PROB, N_SEEDS, RANDOM_SEED, T_MELT, VOXEL_SIZE
-from kmc_simulation import run_gradient_boundary, run_kmc, run_kmc_ensemble
+from kmc_simulation import beam_laser, run_gradient_boundary, run_kmc, run_kmc_ensemble
 
 
 def check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers=None, scan_speeds=None):
@@ -85,8 +85,11 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
              defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, out_dir="outputs/gv_sweep", seeds=1, ensemble=False, rng="reference",
              laser_powers=None, scan_speeds=None, laser_start=0.0, front=False, layers=False, texture=False,
              grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1, thermal_scheme="explicit", hold_gradient=False,
-             cooling_rate=0.0, **run_kw):
-    """``hold_gradient=True`` (with ``thermal_scheme="implicit"``): every run with run_kmc's ``thermal_boundary`` set to the
+             cooling_rate=0.0, scan=None, hatch=None, beam_depth=1, penetration=None, **run_kw):
+    """``scan`` (a thermal_solver.scan_path pattern; with the laser axes and ``thermal_scheme="implicit"``): every point's laser
+    follows that path with ``hatch`` voxels between tracks, absorbed over ``beam_depth`` planes (``penetration`` [m]: e-folding
+    depth; None: uniform) -- run_kmc's laser option with a path, the source built on the device (``laser_start`` is not used).
+    ``hold_gradient=True`` (with ``thermal_scheme="implicit"``): every run with run_kmc's ``thermal_boundary`` set to the
     boundary that holds its own initial ramp (``kmc_simulation.run_gradient_boundary``), lowered by ``cooling_rate`` [K/s];
     gv_map.csv gains ``CoolingRate_K_per_s`` behind ``G_over_V``.  An ensemble shares one boundary, so it needs one temperature.
     ``thermal_substeps`` (N or "stable"): every run with run_kmc's option of that name (mode "A"; one value for an ensemble).
@@ -107,7 +110,16 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
     run with ``origin_metrics=True``; gv_map.csv gains ``Nucleated_grain_volume_frac`` and ``Nucleated_voxel_frac`` of each
     run's last row behind those."""
     check_args(L, n_steps, temps, nu_deps, seeds, ensemble, rng, run_kw, laser_powers, scan_speeds)
+    if scan is None and (hatch is not None or beam_depth != 1 or penetration is not None):
+        raise ValueError("--hatch, --beam-depth and --penetration describe a --scan")
+    if scan is not None and not laser_powers:
+        raise ValueError("--scan needs the laser axes (--laser-power and --scan-speed)")
     seeds = int(seeds)
+
+    def laser_of(beam):
+        if scan is not None:
+            return beam_laser(beam[0], scan, beam[1], hatch, beam_depth, penetration)
+        return dict(power=float(beam[0]), start=float(laser_start), speed=float(beam[1]))
     beams = [(p, v) for p in laser_powers for v in scan_speeds] if laser_powers else [None]
     runs = []
     for T_sub in temps:
@@ -119,7 +131,7 @@ def gv_sweep(L=30, n_steps=2000, temps=(2800.0, 3100.0, 3400.0), nu_deps=(2e12, 
                     runs.append((T_sub, nu_dep, RANDOM_SEED + s, prefix, beam))
     cfg = [dict(temp=T_sub, defect_fraction=defect_fraction, n_seeds=n_seeds, impurity_c=carbon, output_prefix=prefix,
                 nu_dep=nu_dep, **({"seed": seed} if seeds > 1 else {}),
-                **({"laser": dict(power=float(beam[0]), start=float(laser_start), speed=float(beam[1]))} if beam else {}),
+                **({"laser": laser_of(beam)} if beam else {}),
                 **({"remelt": remelt} if remelt is not False and remelt is not None else {}))
            for T_sub, nu_dep, seed, prefix, beam in runs]
     opt = dict(**({"front_metrics": True} if front else {}), **({"layer_metrics": True} if layers else {}),
@@ -193,6 +205,13 @@ if __name__ == "__main__":
     ap.add_argument("--laser-power", type=floats, default=None, help="P1,P2,... [W]: laser axis of the map (with --scan-speed)")
     ap.add_argument("--scan-speed", type=floats, default=None, help="V1,V2,... [voxels per temperature update]")
     ap.add_argument("--laser-start", type=float, default=0.0, help="beam centre at the first temperature update [voxels]")
+    ap.add_argument("--scan", choices=("diagonal", "line", "raster", "serpentine"), default=None,
+                    help="with the laser axes and --thermal-scheme implicit: the laser follows this scan path, its source built on "
+                         "the device from a beam table (run_kmc laser with a path)")
+    ap.add_argument("--hatch", type=float, default=None, metavar="H", help="--scan raster|serpentine: voxels between tracks")
+    ap.add_argument("--beam-depth", type=int, default=1, metavar="D", help="--scan: planes from the top that absorb the beam")
+    ap.add_argument("--penetration", type=float, default=None, metavar="M",
+                    help="--beam-depth D > 1: e-folding depth of the absorption [m] (default: uniform over the D planes)")
     ap.add_argument("--front", action="store_true",
                     help="measure G and V at the growth front on the device: front columns in every metrics.csv and gv_map.csv")
     ap.add_argument("--layers", action="store_true",
@@ -231,4 +250,5 @@ if __name__ == "__main__":
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
                    layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt,
                    thermal_substeps=a.thermal_substeps, thermal_scheme=a.thermal_scheme, hold_gradient=a.hold_gradient,
-                   cooling_rate=a.cooling_rate, **kw).to_string(index=False))
+                   cooling_rate=a.cooling_rate, scan=a.scan, hatch=a.hatch, beam_depth=a.beam_depth, penetration=a.penetration,
+                   **kw).to_string(index=False))

@@ -38,7 +38,7 @@ from metrics import (compute_CET, compute_metrics, compute_metrics_device, compu
                      solid_metrics as _solid_metrics, write_solid_csv as _write_solid_csv,
                      origin_metrics as _origin_metrics, write_origin_csv as _write_origin_csv)
 from constants import CET_AR_THRESHOLD, CET_EQ_THRESHOLD
-from thermal_solver import laser_scan_planes, stable_substeps
+from thermal_solver import SCAN_PATTERNS, beam_table, laser_scan_planes, scan_path, stable_substeps
 from thermal_solver import update_temperature_cet as update_temperature  # noqa: F401
 
 # What the last run_kmc call observed besides its return tuple (the reference's signature has no room for it):
@@ -57,15 +57,53 @@ _MAX_STREAM_DOUBLES = 1 << 25   # host staging cap for the pre-drawn NumPy strea
 LASER_KEYS = ("power", "start", "speed", "beam_radius", "absorptivity", "latent")
 
 
+BEAM_KEYS = ("power", "path", "beam_radius", "absorptivity", "latent", "depth", "penetration", "cutoff")
+PATH_KEYS = ("pattern", "speed", "hatch", "start", "margin")
+
+
 def _check_laser(laser, where="laser"):
-    """A laser scan description (thermal_solver.laser_scan_planes): dict with power, start, speed and optionally
-    beam_radius, absorptivity, latent.  Returns a copy."""
+    """A laser scan description.  Without ``path``: the plane route (thermal_solver.laser_scan_planes), dict with power, start,
+    speed and optionally beam_radius, absorptivity, latent.  With ``path`` (dict with pattern, speed and optionally hatch, start,
+    margin: thermal_solver.scan_path): the beam route, optionally depth, penetration, cutoff
+    (thermal_solver.beam_table).  Returns a copy."""
+    if isinstance(laser, dict) and "path" in laser:
+        path = laser["path"]
+        bad, missing = set(laser) - set(BEAM_KEYS), {"power", "path"} - set(laser)
+        if bad or missing:
+            raise ValueError(f"{where}: unknown keys {sorted(bad)}, missing keys {sorted(missing)} (allowed beside 'path': {', '.join(BEAM_KEYS)})")
+        if not isinstance(path, dict) or set(path) - set(PATH_KEYS) or {"pattern", "speed"} - set(path):
+            raise ValueError(f"{where}['path'] must be a dict with keys pattern, speed[, hatch, start, margin] (got {path!r})")
+        if path["pattern"] not in SCAN_PATTERNS:
+            raise ValueError(f"{where}['path']['pattern'] must be one of {SCAN_PATTERNS} (got {path['pattern']!r})")
+        return dict(laser, path=dict(path))
     if not isinstance(laser, dict):
         raise ValueError(f"{where} must be a dict with keys power, start, speed[, beam_radius, absorptivity, latent]")
     bad, missing = set(laser) - set(LASER_KEYS), {"power", "start", "speed"} - set(laser)
     if bad or missing:
         raise ValueError(f"{where}: unknown keys {sorted(bad)}, missing keys {sorted(missing)} (allowed: {', '.join(LASER_KEYS)})")
     return dict(laser)
+
+
+def beam_laser(power, pattern, speed, hatch=None, depth=1, penetration=None):
+    """run_kmc's ``laser`` dict of the beam route, as the drivers' --scan / --hatch / --beam-depth / --penetration flags build it"""
+    path = dict(pattern=pattern, speed=float(speed), **({"hatch": float(hatch)} if hatch is not None else {}))
+    return dict(power=float(power), path=path, depth=int(depth), **({"penetration": float(penetration)} if penetration is not None else {}))
+
+
+def _beam_table_of(laser, L, n_steps):
+    """the beam table of a laser dict with a ``path`` for the updates of global steps [0, n_steps): ordinals 0 .. ceil(n / 20) - 1"""
+    kw = {k: laser[k] for k in ("beam_radius", "absorptivity", "depth", "penetration", "cutoff") if k in laser}
+    return beam_table(L, scan_path(L, **laser["path"]), 0, max(1, -(-int(n_steps) // THERMAL_EVERY)), laser["power"], **kw)
+
+
+def _check_beam_route(laser, scheme, L):
+    """a laser with a path needs the implicit scheme (the explicit kernels read a source plane), and a path and a depth profile
+    that thermal_solver accepts for this L (checked on a one-row table, before any device call)"""
+    if laser is None or "path" not in laser:
+        return
+    if scheme != "implicit":
+        raise ValueError("a laser with a 'path' takes the beam route, which needs thermal_scheme='implicit'")
+    _beam_table_of(laser, L, 1)
 
 
 def _draw_uniforms(per, n, per_step):
@@ -131,7 +169,7 @@ def _advance_to(engine, first, last, L, defect_fraction, rng_mode=0, seed=0, inc
             per_step = 2
         n = max(1, min(n, _MAX_STREAM_DOUBLES // per_step))
         saved, draws, u_np = _draw_uniforms(per, n, per_step)
-        q = laser_scan_planes(L, laser, step, n) if laser is not None else None
+        q = laser_scan_planes(L, laser, step, n) if laser is not None and "path" not in laser else None       # (a path: the handle's beam table)
         res = engine.run_steps(step, n, defect_fraction, draws[:, 0], draws[:, 1] if per == 3 else None, u_np,
                                rng_mode=rng_mode, seed=seed, thermal_mode=2 if laser is not None else thermal_mode,
                                thermal_dt=THERMAL_DT, incremental=incremental, q_planes=q if q is not None and len(q) else None,
@@ -487,6 +525,13 @@ def run_kmc(
     update -- instead of update_temperature_cet.  A dict ``power``, ``start`` (beam centre at update 0, voxels), ``speed``
     (voxels per update) and optionally ``beam_radius``, ``absorptivity``, ``latent`` (thermal_solver.laser_scan_planes).
     prev_state lives on the device: the initial upload snapshots it and every update brings it level with state.
+    A laser dict with a ``path`` (dict with pattern, speed and optionally hatch, start, margin: thermal_solver.scan_path) instead of
+    ``start`` / ``speed`` takes the beam route: the scan follows the path ("diagonal", "line", "raster",
+    "serpentine"), ``depth`` planes absorb the beam (``penetration`` [m]: e-folding depth; None: uniform), factors beyond
+    ``cutoff`` radii are zero, and the device builds every update's source from one beam table copied once
+    (cetkmc_set_beam); no plane crosses to the device.  It needs ``thermal_scheme="implicit"`` (ValueError otherwise) and composes
+    with ``remelt``, ``thermal_substeps``, ``thermal_boundary`` and the diagnostics; ``last_run_info["beam"]`` reports the path,
+    the depth and cetkmc_get_beam_info's totals.  A dict without ``path`` is the plane route, as before.
     Refused with ValueError: ``laser`` with ``mode="B"``; with ``checkpoint_every`` / ``resume_from`` (a checkpoint does not
     carry prev_state); with ``thermal_updates=False``.
 
@@ -590,6 +635,7 @@ def run_kmc(
             raise ValueError("laser cannot be combined with checkpoint_every / resume_from (a checkpoint does not carry prev_state)")
         if not thermal_updates:
             raise ValueError("laser needs thermal_updates=True (the source acts through the temperature update)")
+        _check_beam_route(laser, thermal_scheme, L)
     if thermal_cadence not in ("events", "supersteps"):
         raise ValueError("thermal_cadence must be 'events' or 'supersteps'")
     local_events = int(local_events)
@@ -643,6 +689,9 @@ def run_kmc(
         raise ValueError(f"checkpoint was written by a run with thermal_boundary={ckpt['extra'].get('thermal_bc')!r}, "
                          f"this call asks for {face_bc!r}")
     _apply_thermal_options(engine, n_sub, thermal_scheme, face_bc, remelt_thr)
+    beam = laser is not None and "path" in laser
+    if beam:
+        engine.set_beam(_beam_table_of(laser, L, n_steps))
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -846,12 +895,15 @@ def run_kmc(
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
     atom_type = state.copy()
     remelted = remelt_off[1] + engine.remelt_info()["n_melted"] if remelt_thr is not None else None
+    beam_report = dict(engine.beam_info(), path=dict(laser["path"]), depth=int(laser.get("depth", 1))) if beam else None
     engine.close()
     last_run_info.clear()
     last_run_info.update(mode=mode, min_margin=min_margin if mode == "A" else None, executed_events=step + 1, thermal_substeps=n_sub,
                          thermal_scheme=thermal_scheme, thermal_boundary=face_bc)
     if remelt_thr is not None:
         last_run_info.update(remelted=remelted)
+    if beam:
+        last_run_info.update(beam=beam_report)
     if local_events:
         last_run_info.update(horizon_time=horizon_time, capped_boxes=capped_boxes)
     if mode == "A" and min_margin < MARGIN_WARN:
@@ -909,6 +961,10 @@ def _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates=T
             raise ValueError("laser needs thermal_updates=True (the source acts through the temperature update)")
         if len({bool(d["laser"].get("latent", True)) for d in out}) != 1:
             raise ValueError("the lasers' 'latent' setting must be the same in every config (it is shared by the ensemble)")
+        if len({"path" in d["laser"] for d in out}) != 1:
+            raise ValueError("either every laser has a 'path' (the beam route) or none has (the route is shared by the ensemble)")
+        if len({int(d["laser"].get("depth", 1)) for d in out}) != 1:
+            raise ValueError("the lasers' 'depth' must be the same in every config (the ensemble's beam tables share it)")
     if rng == "reference" and len(out) * (int(L) * int(L) + 2) > _MAX_STREAM_DOUBLES:
         raise ValueError(f"rng='reference': R * (L*L + 2) must stay within {_MAX_STREAM_DOUBLES} pre-drawn doubles per step "
                          "(split the ensemble)")
@@ -991,6 +1047,8 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                   needs="rng='reference' (the counter mode steps through the super-step engine, whose updates are explicit)")
     _check_solid(solid_metrics, solid_every, False)
     cfgs = _ensemble_configs(configs, L, n_steps, rng, metrics_every, thermal_updates, origin_metrics)
+    for c in cfgs:
+        _check_beam_route(c["laser"], thermal_scheme, int(L))
     if thermal_boundary == "gradient" and len({float(c["temp"]) for c in cfgs}) != 1:
         raise ValueError("thermal_boundary='gradient' needs one temp for all replicas (the ensemble shares one boundary)")
     boundary = _thermal_boundary(thermal_boundary, int(L), cfgs[0]["temp"], rng == "reference", thermal_scheme, thermal_updates,
@@ -1049,10 +1107,15 @@ def run_kmc_ensemble(configs, L, n_steps, *, rng="reference", metrics_every=METR
                 if c["laser"] not in scans:
                     scans.append(c["laser"])
                 q_set[r] = scans.index(c["laser"])
+        beam = bool(scans) and "path" in scans[0]
+        if beam:                # one table per distinct laser dict, on the device for the whole run
+            ens.set_beam([_beam_table_of(z, L, n_steps) for z in scans], q_set)
 
         def laser_kw(s0, n):
             if not scans:
                 return {}
+            if beam:
+                return dict(use_latent=use_latent)
             q = np.stack([laser_scan_planes(L, z, s0, n) for z in scans])
             return dict(q_planes=q if q.shape[1] else None, q_set=q_set, use_latent=use_latent)
         cap = _MAX_STREAM_DOUBLES // (R * per_step) if rng == "reference" else 4096

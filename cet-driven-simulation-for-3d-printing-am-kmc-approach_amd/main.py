@@ -16,6 +16,8 @@ outside the accelerated path and are not part of this package.
     python main.py --thermal-substeps N|stable    # sub-stepped temperature updates (run_kmc thermal_substeps; 'stable' = 17)
     python main.py --thermal-scheme implicit      # implicit temperature updates (run_kmc thermal_scheme)
     python main.py --thermal-scheme implicit --thermal-boundary gradient|sink    # held gradient / substrate sink (run_kmc thermal_boundary)
+    python main.py --thermal-scheme implicit --laser-power P --scan raster|serpentine|line|diagonal [--scan-speed V] [--hatch H]
+                   [--beam-depth D] [--penetration M]      # a laser scan path with a volumetric beam (run_kmc laser with a path)
     python main.py --origin                       # origin columns in every metrics.csv and an origin_layers.csv per level (run_kmc origin_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
@@ -29,7 +31,7 @@ import numpy as np
 import pandas as pd
 
 from constants import DEFECT_PROB, LATTICE_SIZE, N_SEEDS, N_STEPS, T_SUB
-from kmc_simulation import run_kmc, run_kmc_ensemble
+from kmc_simulation import beam_laser, run_kmc, run_kmc_ensemble
 from lattice_init import initialize_lattice, save_lattice
 from metrics import detect_CET_transition
 
@@ -54,8 +56,15 @@ def check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw):
 
 def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=False, ensemble=False, rng="reference", front=False,
          layers=False, texture=False, grains=False, solid=False, origin=False, remelt=False, thermal_substeps=1,
-         thermal_scheme="explicit", thermal_boundary=None, **run_kw):
+         thermal_scheme="explicit", thermal_boundary=None, scan=None, laser_power=None, scan_speed=1.0, hatch=None, beam_depth=1,
+         penetration=None, **run_kw):
     check_args(L, n_steps, carbon_levels, ensemble, rng, run_kw)
+    if scan is None and (hatch is not None or beam_depth != 1 or penetration is not None):
+        raise ValueError("--hatch, --beam-depth and --penetration describe a --scan")
+    if scan is not None and laser_power is None:
+        raise ValueError("--scan needs --laser-power")
+    # --scan: run_kmc's laser option with a path (the beam route; needs --thermal-scheme implicit), in every run / config
+    lz = {"laser": beam_laser(laser_power, scan, scan_speed, hatch, beam_depth, penetration)} if scan is not None else {}
     rm = {"remelt": remelt} if remelt is not False and remelt is not None else {}      # --remelt: run_kmc's option / config key
     print("Starting KMC simulation for microstructure control...")
     t_start = time.time()
@@ -87,7 +96,7 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
             save_lattice(*init[:4], init[4], prefix=f"outputs/{prefix}/init")
         t0 = time.time()
         ens_out = run_kmc_ensemble([dict(temp=T_SUB, defect_fraction=DEFECT_PROB, n_seeds=N_SEEDS, impurity_c=c,
-                                         output_prefix=f"impurity_c_{int(c * 100)}", **rm) for c in carbon_levels], L, n_steps, rng=rng,
+                                         output_prefix=f"impurity_c_{int(c * 100)}", **rm, **lz) for c in carbon_levels], L, n_steps, rng=rng,
                                    **fm)
         ens_t = time.time() - t0
     for q, c in enumerate(carbon_levels):
@@ -102,7 +111,7 @@ def main(L=LATTICE_SIZE, n_steps=N_STEPS, carbon_levels=(0.0, 0.1, 0.2), plots=F
             save_lattice(*init[:4], init[4], prefix=f"{out_dir}/init")
             t0 = time.time()
             state, atom_type, total_time, theta, phi = run_kmc(L=L, n_steps=n_steps, temp=T_SUB, defect_fraction=DEFECT_PROB,
-                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw, **fm, **rm)
+                                                               n_seeds=N_SEEDS, impurity_c=c, output_prefix=prefix, **run_kw, **fm, **rm, **lz)
         else:
             state, atom_type, total_time, theta, phi = ens_out[q]
             t0 -= ens_t / len(carbon_levels)
@@ -164,6 +173,15 @@ if __name__ == "__main__":
     ap.add_argument("--thermal-boundary", choices=("gradient", "sink"), default=None,
                     help="with --thermal-scheme implicit: 'gradient' holds the imposed ramp (fixed faces at its next values), 'sink' "
                          "fixes T_SUB under the substrate face; every other face adiabatic (run_kmc thermal_boundary, mode A)")
+    ap.add_argument("--scan", choices=("diagonal", "line", "raster", "serpentine"), default=None,
+                    help="with --thermal-scheme implicit and --laser-power: the laser follows this scan path, its source built on the "
+                         "device from a beam table (run_kmc laser with a path, mode A)")
+    ap.add_argument("--laser-power", type=float, default=None, metavar="W", help="--scan: the beam's power [W]")
+    ap.add_argument("--scan-speed", type=float, default=1.0, metavar="V", help="--scan: voxels per temperature update along a track")
+    ap.add_argument("--hatch", type=float, default=None, metavar="H", help="--scan raster|serpentine: voxels between tracks")
+    ap.add_argument("--beam-depth", type=int, default=1, metavar="D", help="--scan: planes from the top that absorb the beam")
+    ap.add_argument("--penetration", type=float, default=None, metavar="M",
+                    help="--beam-depth D > 1: e-folding depth of the absorption [m] (default: uniform over the D planes)")
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
@@ -173,4 +191,5 @@ if __name__ == "__main__":
         kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
          grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt, thermal_substeps=a.thermal_substeps,
-         thermal_scheme=a.thermal_scheme, thermal_boundary=a.thermal_boundary, **kw)
+         thermal_scheme=a.thermal_scheme, thermal_boundary=a.thermal_boundary, scan=a.scan, laser_power=a.laser_power,
+         scan_speed=a.scan_speed, hatch=a.hatch, beam_depth=a.beam_depth, penetration=a.penetration, **kw)

@@ -169,6 +169,87 @@ def laser_scan_planes(L, laser, first_step, n_steps):
     return out
 
 
+SCAN_PATTERNS = ("diagonal", "line", "raster", "serpentine")
+
+
+def scan_path(L, pattern, speed, hatch=None, start=None, margin=0.0):
+    """A scan strategy (not in the reference): a function u -> (cj, ck, on) of the update ordinal
+    u = g // 20 -- the beam centre in voxels along j and k, and whether the beam is on.  Pure in u, so adjacent ranges of
+    updates concatenate and a resumed range gets the same rows (as ``laser_scan_planes``' planes do).
+      "diagonal"    cj = ck = start + speed * u (``laser_scan_planes``' path; start defaults to 0); always on
+      "line"        one track along +k at j = start (default: the middle, (L - 1) / 2); off behind its end
+      "raster"      tracks along +k at j = start + hatch * t (start defaults to margin), each from k = margin; the beam
+                    jumps back between tracks
+      "serpentine"  as "raster", every odd track along -k from k = L - 1 - margin
+    A track of length len = L - 1 - 2 * margin voxels takes n_t = floor(len / speed) + 1 updates; track t = u // n_t,
+    position s = u % n_t, ck = margin + speed * s (or L - 1 - margin - speed * s); off once cj passes L - 1 - margin."""
+    L, speed, margin = int(L), float(speed), float(margin)
+    if pattern not in SCAN_PATTERNS:
+        raise ValueError(f"scan_path: pattern must be one of {SCAN_PATTERNS} (got {pattern!r})")
+    if not (np.isfinite(speed) and speed > 0.0):
+        raise ValueError("scan_path: speed must be positive and finite (voxels per update)")
+    if pattern == "diagonal":
+        s0 = 0.0 if start is None else float(start)
+        return lambda u: (s0 + speed * int(u), s0 + speed * int(u), True)
+    length = L - 1 - 2.0 * margin
+    if not (margin >= 0.0 and length >= 0.0):
+        raise ValueError("scan_path: margin must be >= 0 and leave a track (L - 1 - 2 * margin >= 0)")
+    if pattern == "line":
+        hatch_v, j0 = 0.0, ((L - 1) / 2.0 if start is None else float(start))
+    else:
+        if hatch is None or not (np.isfinite(float(hatch)) and float(hatch) > 0.0):
+            raise ValueError(f"scan_path: pattern {pattern!r} needs a positive hatch spacing (voxels)")
+        hatch_v, j0 = float(hatch), (margin if start is None else float(start))
+    n_t = int(np.floor(length / speed)) + 1
+    k_lo, k_hi = margin, L - 1 - margin
+
+    def path(u):
+        u = int(u)
+        if u < 0:
+            return j0, k_lo, False
+        t, s = divmod(u, n_t)
+        cj = j0 + hatch_v * t
+        back = pattern == "serpentine" and t % 2 == 1
+        ck = k_hi - speed * s if back else k_lo + speed * s
+        on = cj <= k_hi and (pattern != "line" or t == 0)
+        return cj, ck, bool(on)
+    return path
+
+
+def beam_table(L, path, u0, n_u, power, beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, depth=1,
+               penetration=None, cutoff=3.0):
+    """The beam table of update ordinals u0 .. u0 + n_u - 1 of ``path`` (``scan_path``) for cetkmc's set_beam (DESIGN.md
+    section 28): dict(u0, amp (n_u), gj (n_u, L), gk (n_u, L), fi (depth)).  The Gaussian beam is separable,
+    exp(-(dj^2 + dk^2) / r_b^2) = gj[j] * gk[k]: the host's exp runs over 2 L values per update and the device multiplies.
+      gj[x][j] = exp(-((j - cj) dx)^2 / r_b^2), exactly 0 where |j - cj| dx > cutoff * r_b; gk likewise
+      amp[x]   = power * absorptivity / (pi r_b^2) / dx, 0 where the path is off
+      fi       = w / w.sum(), w[d] = exp(-d dx / penetration) over the ``depth`` planes from the top down (uniform for
+                 penetration=None, [1.0] for depth 1): the absorbed power is spread over the planes, not multiplied."""
+    L, u0, n_u, depth = int(L), int(u0), int(n_u), int(depth)
+    if n_u < 1 or not 1 <= depth <= L:
+        raise ValueError("beam_table: n_u >= 1 and 1 <= depth <= L")
+    r_b, cutoff = float(beam_radius), float(cutoff)
+    if not (r_b > 0.0 and np.isfinite(r_b) and cutoff > 0.0):
+        raise ValueError("beam_table: a positive finite beam_radius and a positive cutoff")
+    axis = np.arange(L, dtype=np.float64)
+    amp, gj, gk = np.zeros(n_u), np.zeros((n_u, L)), np.zeros((n_u, L))
+    peak = float(power) * float(absorptivity) / (np.pi * r_b * r_b) / VOXEL_SIZE
+    for x in range(n_u):
+        cj, ck, on = path(u0 + x)
+        for g, c in ((gj, cj), (gk, ck)):
+            r_m = (axis - c) * VOXEL_SIZE
+            g[x] = np.where(np.abs(r_m) > cutoff * r_b, 0.0, np.exp(-(r_m ** 2) / (r_b ** 2)))
+        amp[x] = peak if on else 0.0
+    if depth == 1:
+        fi = np.ones(1)
+    else:
+        if penetration is not None and not (float(penetration) > 0.0 and np.isfinite(float(penetration))):
+            raise ValueError("beam_table: penetration must be positive and finite (metres), or None")
+        w = np.ones(depth) if penetration is None else np.exp(-np.arange(depth, dtype=np.float64) * VOXEL_SIZE / float(penetration))
+        fi = w / w.sum()
+    return dict(u0=u0, amp=amp, gj=gj, gk=gk, fi=fi)
+
+
 def update_temperature(T, state, prev_state, dt, laser_pos, laser_power,
                        beam_radius=DEFAULT_BEAM_RADIUS, absorptivity=DEFAULT_ABSORPTIVITY, substeps=1, scheme="explicit", boundary=None):
     """Explicit Euler step with Laplacian + Gaussian surface source on i=L-1 + latent heat where

@@ -206,7 +206,7 @@ const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
  * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info", "implicit_info",
- * "thermal_boundary", "boundary_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "thermal_boundary", "boundary_info", "beam", "beam_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -966,6 +966,47 @@ int cetkmc_set_thermal_boundary(void* handle, const struct cetkmc_thermal_bounda
 int cetkmc_ensemble_set_thermal_boundary(void* handle, const struct cetkmc_thermal_boundary* b);
 int cetkmc_get_thermal_boundary(void* handle, struct cetkmc_thermal_boundary* b, struct cetkmc_boundary_info* info);
 int cetkmc_implicit_coeffs_bc(int L, double r, double beta_lo, double beta_hi, double* inv, double* p);
+
+/* ---- beam tables: laser scan paths and a volumetric source, built on the device -----------------------
+ * Opt-in; with no beam set every kernel, launch, counter and byte is what it was.  A Gaussian beam is separable, so the source of a
+ * laser-mode update need not cross to the device as an L * L plane: a beam table holds, for the update ordinals u0 .. u0 + n_u - 1
+ * (u = g / 20 for the update a stepping call makes at global step g), one row of factors each, and a depth profile:
+ *   amp[n_u], gj[n_u][L], gk[n_u][L], fi[depth], all finite and >= 0, 1 <= depth <= L.
+ * The source of update u is row x = u - u0.  Voxel (i, j, k) at depth d = L - 1 - i receives
+ *   qv    = d < depth ? (amp[x] * fi[d]) * (gj[x][j] * gk[x][k]) : 0.0        three multiplies in this order, no contraction
+ *   qterm = qv != 0.0 ? qv / rho_cp : 0.0
+ * and everything else is the implicit step of section 26 (with the boundary of section 27 when one is set): scrub, b = T + dt *
+ * (qterm + latent_coef * dF), the solves along k, j, i, the clip, prev_state := state, thermal_substeps = n steps of dt / n from
+ * the same row, the melt pass behind the update.  With depth 1 and fi = {1.0} an update equals section 26's from the plane
+ * q[j][k] = (amp[x] * 1.0) * (gj[x][j] * gk[x][k]) in every bit.  The device forms the products (the beam instantiations of
+ * k_imp_rows); no plane is built, copied or stored.
+ *   cetkmc_set_beam            a single handle: copies the table to the device (the caller's arrays are free after the return);
+ *                              NULL removes the beam.  Invalidates nothing, leaves the applied-update marker alone.
+ *   cetkmc_ensemble_set_beam   an ensemble handle: n_sets tables that share u0, n_u and depth; replica r reads set set_of[r]
+ *                              (set_of NULL: set r, and n_sets must equal R).  sets NULL removes the beam.
+ *   cetkmc_get_beam_info       running totals of the updates made from a table: updates, their steps, their launches (three per
+ *                              step), and the tables copied to the device.  An ensemble handle: of cetkmc_run_ensemble's updates.
+ *   cetkmc_thermal_beam        one update now from row u - u0: the twin of cetkmc_thermal_laser.  u is the update ordinal in every
+ *                              respect: a thermal boundary's face temperatures are those of u as well.
+ * While a beam is set, a stepping call with thermal_mode 2 (cetkmc_run_steps, cetkmc_stage_inputs, cetkmc_run_ensemble) takes every
+ * update's source from the row of its global ordinal g / 20: q_planes must be NULL and n_q 0; q_used counts as before.  A call
+ * that continues a batch stopped with status 2 on an update step needs nothing supplied again.  cetkmc_time_thermal(laser != 0)
+ * reads row 0 (update ordinal u0).  thermal_mode 1 updates have no source, with or without a beam.
+ * Refused, before anything is allocated or launched, each naming its entry point: n_u < 1; depth outside 1..L; a null array; a
+ * negative or non-finite value; a beam while the scheme is explicit, and the explicit scheme while a beam is set; the per-handle
+ * setter on an ensemble's handle or on its replicas; sets that differ in u0, n_u or depth; a set_of entry outside [0, n_sets); a
+ * stepping call with a beam and a non-null q_planes or a non-zero n_q; a stepping call, or cetkmc_thermal_beam, one of whose own
+ * updates falls outside [u0, u0 + n_u) (computed from step0 and n_steps); cetkmc_thermal_laser while a beam is set. */
+struct cetkmc_beam {
+    int64_t u0;
+    int32_t n_u, depth;
+    const double *amp, *gj, *gk, *fi;
+};
+struct cetkmc_beam_info { int64_t updates, steps, launches, table_uploads; };
+int cetkmc_set_beam(void* handle, const struct cetkmc_beam* beam);
+int cetkmc_ensemble_set_beam(void* handle, int n_sets, const struct cetkmc_beam* sets, const int32_t* set_of);
+int cetkmc_get_beam_info(void* handle, struct cetkmc_beam_info* info);
+int cetkmc_thermal_beam(void* handle, double dt, int64_t u, int use_latent, int scrub_nan);
 
 #ifdef __cplusplus
 }
