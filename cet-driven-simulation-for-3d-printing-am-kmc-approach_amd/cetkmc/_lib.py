@@ -68,6 +68,10 @@ class LocalArgs(C.Structure):
     ]
 
 
+class LaneTableInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("fresh", "chunks", "usable", "poisoned", "builds")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("steps", "sweeps", "incremental_steps", "thermal_updates", "supersteps", "bytes_h2d",
                                          "bytes_d2h", "alg_bytes_sweep", "alg_bytes_thermal", "profiled_steps")] + \
@@ -208,6 +212,8 @@ PROTOTYPES = {
     "cetkmc_table_tile_of": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "cetkmc_early_tile_row": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "cetkmc_lane_needs_values": (C.c_int, [C.c_uint64]),
+    "cetkmc_lane_request": (C.c_int, [C.c_uint64, C.c_int]),
+    "cetkmc_lane_table": (C.c_int, [C.c_void_p, _P(LaneTableInfo)]),
     "cetkmc_invalidates": (C.c_int, [C.c_char_p]),
     "cetkmc_device_count": (C.c_int, [_P(C.c_int)]),
     "cetkmc_create": (C.c_int, [_P(Params), C.c_int, C.c_int, _P(C.c_int), _P(C.c_void_p)]),

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Counters, EnsAnalysis, EnsArgs, Event, LocalArgs, Params, RunArgs, RunResult, SuperArgs, SweepInfo, build_library  # noqa: F401
+from ._lib import Counters, EnsAnalysis, EnsArgs, Event, LaneTableInfo, LocalArgs, Params, RunArgs, RunResult, SuperArgs, SweepInfo, build_library  # noqa: F401
 
 EVENT_DTYPE = np.dtype([("type", "<i4"), ("pos", "<i4", 3), ("target", "<i4", 3), ("atom", "<i4"),
                         ("rate", "<f8"), ("dep_rank", "<i8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
@@ -537,6 +537,12 @@ class Engine(_ThermalSettings):
         c = Counters()
         self._ck(self.lib.cetkmc_get_counters(self.h, C.byref(c), int(bool(reset))))
         return {n: getattr(c, n) for n, _ in Counters._fields_}
+
+    def lane_table(self):
+        """cetkmc_lane_table as a dict (tests): fresh, chunks, usable, poisoned, builds."""
+        info = LaneTableInfo()
+        self._ck(self.lib.cetkmc_lane_table(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in LaneTableInfo._fields_}
 
     # -- Mode B: synchronous super-steps over (L/box)^3 boxes (not in the reference; include/cetkmc.h) --------
     def run_supersteps(self, step0, n, box, defect_fraction, seed, thermal_mode=1, thermal_dt=1e-6, q_planes=None,

@@ -195,6 +195,8 @@ struct Handle {
                                  // (sweep_table_tile) at 128 < L <= 256, 2 = the plain launch at that shape as well, 0 = ring tiles
     int table_lane_skip = 1;     // option "table_lane_skip": 1 = those tiles request the class bytes first and the table entries only in
                                  // the lanes that can use them (lane_needs_values()), 0 = every lane's entries; same bits
+    int lane_sums = 1;           // option "lane_sums": 1 = the skipping tiles of the deferred launches request the 8 B lane sum of a pristine
+                                 // chunk instead of its 64 B of entries while the lane table is fresh (kernels.hpp, "lane sums"); 0 = entries
     int early_tiles = -1;        // option "early_tiles": tiles of the next step's sweep that a deferred step's selection launch runs
                                  // (k_select_pend_tiles, into the other row-sum pair); 0 = k_select_pend and one pair; -1 (default) =
                                  // a quarter of the tile range, 1024 of 4096 at 256^3, where it was measured
@@ -202,6 +204,7 @@ struct Handle {
                                  // CU, four tiles each at 256^3); 0 = one per tile
     int poison_alt_rows = 0;     // option "poison_alt_rows" (tests): the pair about to be written is filled with 0xFF first
     bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
+    int64_t cnt_lane_builds = 0; // plain launches that built the lane table (cetkmc_lane_table)
     int pend_early = 0;          // ... and leaves out its first pend_early tiles, which the selection launch ran
     BatchCfg pend_cfg{};         // ... with this batch configuration
     double* d_ktab = nullptr;
@@ -231,6 +234,8 @@ struct Handle {
                                // recomputed per sweep, 3 census-free table sweep (same bits, measured no faster: DESIGN.md section 13)
     bool table_fresh = false;  // vval / dep_val match the current T and parameters (k_rate_table)
     bool ifc_fresh = false;    // vval / event count (class byte) of every listed voxel match the current lattice, T, defects and parameters
+    bool lanes_fresh = false;  // the lane table (Slab::v.lanesum / lanecnt) was built from the current table and every write of an entry
+                               // since then went through ifc_store(); follows TABLE and IFC: whatever clears either clears it
     int ifc_every_step = 0;    // 1: k_interface before every full sweep (round-1 behaviour, A/B); 0: only when stale --
                                // between temperature updates the apply kernel re-evaluates the <= 30 listed voxels an event touches
     int thermal_variant = 1;   // 1 = plane-marching LDS kernel, 0 = one thread per voxel
@@ -389,6 +394,10 @@ void invalidate(Handle* h, Cause c)
     if (stale & SWEEP) h->swept = false;
     if (stale & TABLE) h->table_fresh = false;
     if (stale & IFC) h->ifc_fresh = false;
+    // the lane table is a digest of the rate table and of the class bytes as the batched apply keeps them: every cause that
+    // rewrites the table, leaves listed voxels' entries to be rewritten or changes the lattice outside the batched apply
+    // carries TABLE or IFC
+    if (stale & (TABLE | IFC)) h->lanes_fresh = false;
     if (stale & APPLIED) h->therm_applied_g = -1;
     if (stale & STAGED) h->staged.valid = false;
 }
@@ -525,6 +534,12 @@ int create_common(const cetkmc_params* p, int L, const std::vector<std::pair<int
             HIPCHK(hipMemsetAsync(s.depbuf[b], 0, (size_t)L * h->pitchT * sizeof(double), h->stream));
         }
         s.v.vval = s.vvalbuf[0]; s.v.dep_val = s.depbuf[0];
+        if (ranges.size() == 1 && L > 128 && h->Pk <= 256) {      // the shape of table_tiles(): one copy, the table's indexing / 8
+            HIPCHK(hipMalloc((void**)&s.v.lanesum, s.nT / 8 * sizeof(double)));
+            HIPCHK(hipMalloc((void**)&s.v.lanecnt, s.nT / 8));
+            HIPCHK(hipMemsetAsync(s.v.lanesum, 0, s.nT / 8 * sizeof(double), h->stream));
+            HIPCHK(hipMemsetAsync(s.v.lanecnt, (int)LANE_POISON, s.nT / 8, h->stream));
+        }
         HIPCHK(hipMalloc((void**)&s.v.ifc_in, s.nT));
         HIPCHK(hipMalloc((void**)&s.v.ifc_code, s.nT * sizeof(uint32_t)));
         HIPCHK(hipMemsetAsync(s.v.ifc_code, 0xFF, s.nT * sizeof(uint32_t), h->stream));
@@ -806,6 +821,7 @@ StreamArgs stream_args(Handle* h, const SlabView& v)
     sa.rate_threshold = h->kp.rate_threshold; sa.K0 = host_k_eff(h->p, 0, 0);
     sa.L = v.L; sa.gi0 = v.gi0; sa.nloc = v.nloc; sa.RJ = v.RJ; sa.pitchC = v.pitchC; sa.pitchT = v.pitchT; sa.Pk = v.Pk;
     sa.cls = v.cls; sa.T = v.T; sa.vval = v.vval; sa.dep_val = v.dep_val; sa.rowsum = v.rowsum; sa.rowcnt = v.rowcnt;
+    sa.lanesum = v.lanesum; sa.lanecnt = v.lanecnt;
     sa.group_first = 0; sa.group_count = (v.nloc + STREAM_NI - 1) / STREAM_NI;
     return sa;
 }
@@ -922,6 +938,14 @@ bool table_tiles(const Handle* h, int level)
     return h->fused_tiles >= level && h->slabs.size() == 1 && !multi_rank(h) && h->L > 128 && row_shape(h).hw;
 }
 size_t apply_shmem() { return APPLY_SHMEM; }
+// Lane sums (option lane_sums): where the skipping census-free tiles run the deferred launches.  The look-ahead's k_thermal_fix
+// writes table entries beside the loop without going through ifc_store(): with thermal_lookahead on there are no lane sums.
+bool lane_table_on(const Handle* h)
+{
+    return h->lane_sums && h->table_lane_skip && !h->thermal_ahead && h->sweep_variant == 1 && table_tiles(h, 1) && h->slabs[0].v.lanecnt;
+}
+// the deferred launches read lane sums only while the table is fresh
+bool lane_table_use(const Handle* h) { return lane_table_on(h) && h->lanes_fresh; }
 
 // One full-lattice rate sweep: (rate table, if T changed) -> (interface kernel, if the listed voxels' sums are stale)
 // -> sweep kernel -> block sums (+ all-gather across ranks).  ev_pre | table + interface | ev_a | sweep | ev_b |
@@ -978,18 +1002,29 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
             if (table_tiles(h, 1))      // LDS: the apply block's KParams + SlabView + PendRec copy alone; the tiles the selection
                                         // launch has not run (launch_select_pend)
                 with_flag(h->table_lane_skip != 0, [&](auto ls) {
-                    const int late = table_tile_count(h->L, v.nloc, true) - h->pend_early;
-                    launch(k_sweep_stream_apply<true, 1, false, true, ls.value>, dim3(late + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X, h->pend_early);
+                    with_flag(lane_table_use(h), [&](auto lu) {
+                        const int late = table_tile_count(h->L, v.nloc, true) - h->pend_early;
+                        launch(k_sweep_stream_apply<true, 1, false, true, ls.value, ls.value && lu.value>, dim3(late + 1), dim3(256), apply_shmem(), h->stream, xa, xb, sa, h->d_ss, X, h->pend_early);
+                    });
                 });
             else
                 launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X, 0);
         } else if (h->sweep_variant == 1 && table_tiles(h, 2)) {
+            // (a plain launch where the lane table is stale builds it: the table, the interface kernel and the lattice are current here)
+            const bool build = lane_table_on(h) && !h->lanes_fresh;
             with_flag(h->table_lane_skip != 0, [&](auto ls) {
-                launch(k_sweep_stream<true, true, 1, false, true, ls.value>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
+                with_flag(build, [&](auto lb) {
+                    launch(k_sweep_stream<true, true, 1, false, true, ls.value, lb.value>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
+                });
             });
+            if (build) { h->lanes_fresh = true; ++h->cnt_lane_builds; }
         } else if (h->sweep_variant >= 1) {
             auto go = [&](auto k) { launch(k, dim3(sa.group_count * njt), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, ss); };
-            if (h->sweep_variant == 1) with_stream_kernel<true>(rs, go); else with_stream_kernel<false>(rs, go);
+            if (h->sweep_variant == 1 && lane_table_on(h) && !h->lanes_fresh) {      // the building plain launch (half-wave rows)
+                go(k_sweep_stream<true, true, 1, false, false, false, true>);
+                h->lanes_fresh = true; ++h->cnt_lane_builds;
+            }
+            else if (h->sweep_variant == 1) with_stream_kernel<true>(rs, go); else with_stream_kernel<false>(rs, go);
         } else {
             hipLaunchKernelGGL(k_sweep_simple, dim3(v.nloc * njt), dim3(256), shmem0, h->stream, h->kp, v, h->d_ktab, ss);
         }
@@ -1055,12 +1090,12 @@ int launch_select_pend(Handle* h, const BatchCfg& cfg, int64_t cur_hint)
         const SlabView* sel_views = dviews(h);      // the selection reads the current pair
         flip_rows(h);
         const StreamArgs sa = stream_args(h, view_of(h, 0));      // the tiles write the other one
-        with_flag(h->table_lane_skip != 0, [&](auto ls) {
+        with_flag(h->table_lane_skip != 0, [&](auto ls) { with_flag(lane_table_use(h), [&](auto lu) {
             const int G = h->early_blocks > 0 ? std::min(h->early_blocks, E) : E;
-            launch(k_select_pend_tiles<ls.value>, dim3(G + 1), dim3(256), 0, h->stream, nullptr, nullptr, h->kp, sel_views, (int)h->slabs.size(), h->L,
+            launch(k_select_pend_tiles<ls.value, ls.value && lu.value>, dim3(G + 1), dim3(256), 0, h->stream, nullptr, nullptr, h->kp, sel_views, (int)h->slabs.size(), h->L,
                    h->PB, (const BlockEnt*)h->d_blocks, h->d_ss, cfg, (const double*)h->d_u_pick, (const double*)h->d_ktab, h->d_pend,
                    (const double*)h->d_u_defect, (const double*)h->d_u_np, (long long)cur_hint, sa, E);
-        });
+        }); });
         HIPCHK(hipGetLastError());
         h->pend_early = E;
         h->cnt.early_tiles += E;
@@ -1661,7 +1696,7 @@ void destroy_impl(Handle* h)
         (void)hipFree(s.v.state); (void)hipFree(s.v.defects); (void)hipFree(s.prev); (void)hipFree(s.v.row_chg); (void)hipFree(s.v.cls);
         (void)hipFree(s.Tbuf[0]); (void)hipFree(s.Tbuf[1]); (void)hipFree(s.v.theta); (void)hipFree(s.v.phi); (void)hipFree(s.v.ovec);
         (void)hipFree(s.rowsumbuf[0]); (void)hipFree(s.rowsumbuf[1]);
-        (void)hipFree(s.vvalbuf[0]); (void)hipFree(s.vvalbuf[1]); (void)hipFree(s.depbuf[0]); (void)hipFree(s.depbuf[1]); (void)hipFree(s.v.ifc_in); (void)hipFree(s.v.ifc_code); (void)hipFree(s.v.ifc_list); (void)hipFree(s.v.ifc_n);
+        (void)hipFree(s.v.lanesum); (void)hipFree(s.v.lanecnt); (void)hipFree(s.vvalbuf[0]); (void)hipFree(s.vvalbuf[1]); (void)hipFree(s.depbuf[0]); (void)hipFree(s.depbuf[1]); (void)hipFree(s.v.ifc_in); (void)hipFree(s.v.ifc_code); (void)hipFree(s.v.ifc_list); (void)hipFree(s.v.ifc_n);
     }
     if (h->d_solid_block) (void)hipFree(h->d_solid_block);
     if (h->d_origin_block) (void)hipFree(h->d_origin_block);
@@ -1856,6 +1891,35 @@ int cetkmc_lane_needs_values(uint64_t class8)
 {
     return lane_needs_values(make_uint2((unsigned)class8, (unsigned)(class8 >> 32))) ? 1 : 0;
 }
+int cetkmc_lane_request(uint64_t class8, int count_byte)
+{
+    static_assert(LANE_REQ_NONE == CETKMC_LANE_REQ_NONE && LANE_REQ_VALUES == CETKMC_LANE_REQ_VALUES && LANE_REQ_SUM == CETKMC_LANE_REQ_SUM, "cetkmc.h");
+    return lane_request(make_uint2((unsigned)class8, (unsigned)(class8 >> 32)), (unsigned)count_byte & 0xFFu);
+}
+// Inspection of the lane table (tests): whether the deferred launches would read it now, its owned chunks with a count and
+// poisoned (one small kernel and a synchronisation: not for a loop), the building launches so far.
+int cetkmc_lane_table(void* handle, cetkmc_lane_table_info* out)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !out) return fail("null argument");
+    *out = cetkmc_lane_table_info{};
+    out->fresh = lane_table_use(h) ? 1 : 0;
+    out->builds = h->cnt_lane_builds;
+    if (h->slabs.size() != 1 || !h->slabs[0].v.lanecnt) return 0;      // no lane table at this shape
+    HIPCHK(hipSetDevice(h->dev));
+    CHK(ensure_scratch(h, 2 * sizeof(unsigned long long)));
+    unsigned long long* d = (unsigned long long*)h->d_scratch;
+    unsigned long long got[2] = {0, 0};
+    HIPCHK(hipMemsetAsync(d, 0, sizeof got, h->stream));
+    hipLaunchKernelGGL(k_lane_census, dim3(256), dim3(256), 0, h->stream, h->slabs[0].v, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(got, d, sizeof got, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    out->chunks = (int64_t)h->slabs[0].v.nloc * h->L * (h->pitchT / 8);
+    out->usable = (int64_t)got[0];
+    out->poisoned = (int64_t)got[1];
+    return 0;
+}
 int cetkmc_table_tile_of(int L, int gi, int j)
 {
     if (L <= 128 || L > 256 || gi < 0 || gi >= L || j < 0 || j >= L) return -1;
@@ -2005,6 +2069,7 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
     if (!strcmp(key, "thermal_lookahead")) {
         if (value) CHK(thermal_exclusions(h->ts, nullptr));
         h->thermal_ahead = value ? 1 : 0;
+        h->lanes_fresh = false;         // (no lane sums beside the look-ahead: lane_table_on())
         return 0;
     }
     if (!strcmp(key, "substep_block")) {
@@ -2024,6 +2089,12 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         return 0;
     }
     if (!strcmp(key, "table_lane_skip")) { h->table_lane_skip = value ? 1 : 0; return 0; }
+    if (!strcmp(key, "lane_sums")) {
+        if (value < 0 || value > 1) return fail("lane_sums must be 0 (the tiles read table entries) or 1 (lane sums of pristine chunks, default)");
+        h->lane_sums = (int)value;
+        h->lanes_fresh = false;         // the next plain launch builds
+        return 0;
+    }
     if (!strcmp(key, "early_tiles")) {
         if (value < -1 || value > INT32_MAX) return fail("early_tiles must be a tile count >= 0, or -1 (a quarter of the tiles)");
         h->early_tiles = (int)value;

@@ -363,6 +363,8 @@ struct StreamArgs {
     const double* dep_val;    // plane L-1 deposition rates by temperature (SlabView::dep_val)
     double* rowsum;
     int32_t* rowcnt;
+    double* lanesum;          // the slab's lane table (SlabView::lanesum / lanecnt): written by a building sweep (LM_BUILD), read by
+    uint8_t* lanecnt;         // the census-free tiles that use it (LM_USE); null where there is none
 };
 
 // kmc_event_rates.py:116-131 for an empty voxel WITHOUT W/Re/C neighbours: n_imp = 0, hence f_imp = 0 and
@@ -416,6 +418,27 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
     return *reinterpret_cast<const uint2*>(A.cls + ((int64_t)li * A.RJ + (jr + 2)) * A.pitchC + KOFFC + k0);
 }
 
+// ---- lane sums (option lane_sums; one slab, half-wave rows: where the census-free tiles run) ---------------------------------
+// A CHUNK is the 8 table entries a sweep lane owns (load_vals()).  row_reduce() enters them as tree8(ev), ev[h] the entry masked
+// by "voxel h is empty".  For a PRISTINE chunk -- all 8 class bytes 0x01: empty, no count -- that node is a function of the
+// entries alone, and the entries of such voxels change only where the table is rewritten (k_rate_table, the temperature tiles)
+// or where ifc_store() writes one.  So the node is kept: the plain sweep that follows a table write (LM_BUILD) stores, per
+// chunk, lanesum = tree8(ev) and lanecnt = the number of non-zero ev[h], or LANE_POISON for a chunk that is not pristine;
+// ifc_store() poisons the chunk of every entry it writes; the census-free tiles of the deferred launches (LM_USE) request the
+// 8 B of a pristine, unpoisoned chunk instead of its 64 B.  Passed on as v[0] with v[1..7] = +0.0 it gives the same node to the
+// bit (every rate is >= +0.0, and s + 0.0 = s); the count replaces that lane's share of the eight ballots.
+// A poisoned chunk stays poisoned until the next build, and a chunk that is not pristine when it is read takes the entries:
+// a usable lane sum is therefore the node of 8 entries none of which has been written since it was stored.
+constexpr int LM_NONE = 0, LM_BUILD = 1, LM_USE = 2;
+__host__ __device__ __forceinline__ bool lane_pristine(uint2 own) { return own.x == 0x01010101u && own.y == 0x01010101u; }
+// the chunk of lane sl of row jrow of local plane li (load_vals()' clamping)
+__device__ __forceinline__ int64_t lane_chunk(const StreamArgs& A, int li, int jrow, int sl)
+{
+    const int k0 = min(8 * sl, A.pitchT - 8);
+    const int jr = min(jrow, A.L - 1);
+    return (((int64_t)li * A.L + jr) * A.pitchT + k0) >> 3;
+}
+
 // THE row reduction: one lattice row per wave (HW: per half-wave; `jrow` is then the lane's own row) of plane li -- voxel
 // classes, rates, canonical row tree -- results to rowsum/rowcnt.  Every sweep path reduces its rows here, so they agree to
 // the bit.  v0 = load_vals() of chunk 0.  The paths differ only in `cls`, how a voxel is classified:
@@ -426,14 +449,18 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
 // CH2: rows of 513..1024 voxels (two 512-voxel chunks per row; only without HW).
 // SK (the tiles of k_sweep_stream_apply that can hold a stale row of the pending event, sites `sw`): such a row is not stored.
 // lds_sum / lds_cnt ([3][L] of the block's plane, k_sweep_plane): a copy of what is stored.
-template <bool TAB, bool HW, bool CH2, bool SK = false, class CLS>
+// LM (lane sums, above): LM_BUILD stores the lane's node and count into the lane table; LM_USE: a lane with lcnt >= 0 passed its
+// lane sum as v0[0] (v0[1..7] = +0.0) and lcnt is its count; lcnt < 0: the lane's entries, as ever.
+template <bool TAB, bool HW, bool CH2, bool SK = false, int LM = LM_NONE, class CLS>
 __device__ __forceinline__ void row_reduce(const StreamArgs& A, CLS cls, int li, int lp, int jrow, bool top, int lane,
                                            const double (&v0)[8], const StaleWin& sw = StaleWin{},
-                                           double* lds_sum = nullptr, int* lds_cnt = nullptr)
+                                           double* lds_sum = nullptr, int* lds_cnt = nullptr, int lcnt = -1)
 {
     constexpr bool CENSUS = !std::is_same<CLS, uint2>::value;
     static_assert(!(HW && CH2), "half-wave rows have one chunk");
     static_assert(CENSUS || TAB, "the census-free classification reads the rate table");
+    static_assert(LM == LM_NONE || (TAB && HW), "the lane table belongs to the table sweep at half-wave rows");
+    static_assert(LM != LM_USE || !CENSUS, "lane sums are read by the census-free tiles");
     const int L = A.L;
     const int sl = HW ? (lane & 31) : lane;
     constexpr int nch = CH2 ? 2 : 1;                         // chunks of 512 voxels
@@ -557,6 +584,29 @@ __device__ __forceinline__ void row_reduce(const StreamArgs& A, CLS cls, int li,
 #pragma unroll
             for (int h = 0; h < 8; ++h) dv[h] = mask_f64(v[h], h < 4 ? dA.x : dA.y, 8 * (h & 3));
         }
+        if constexpr (LM == LM_BUILD) {
+            if (active) {
+                const int64_t ch = lane_chunk(A, li, jrow, sl);
+                if (lane_pristine(own)) {
+                    int nz = 0;
+#pragma unroll
+                    for (int h = 0; h < 8; ++h) nz += ev[h] != 0.0 ? 1 : 0;
+                    A.lanesum[ch] = tree8(ev);
+                    A.lanecnt[ch] = (uint8_t)nz;
+                } else {
+                    A.lanecnt[ch] = (uint8_t)LANE_POISON;
+                }
+            }
+        }
+        if constexpr (LM == LM_USE) {
+            // the ballots below see a lane sum once if it is non-zero (then lcnt >= 1): the rest of its count joins the
+            // interface voxels' integer sum (order-free).  (A lane outside the lattice read a clamped address: it has no count.)
+            const bool ls = active && lcnt >= 0;
+            if (__any(ls)) {
+                any_ifc = true;
+                if (ls) cI += lcnt - (ev[0] != 0.0 ? 1 : 0);
+            }
+        }
         // ---- counts: scalar popcounts of ballots (bulk voxels count iff their rate is kept) -------------
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
@@ -623,7 +673,7 @@ __device__ __forceinline__ void stream_tile_of(const StreamArgs& A, int b, int& 
     ibr = b / njt; jt = b - ibr * njt;
 }
 // NPF = 16-B chunks of a class slab per thread (1 for L <= 256, up to 3 for L <= 682).  One tile.  SK: row_reduce()
-template <bool TAB, bool HW, int NPF, bool CH2, bool SK = false>
+template <bool TAB, bool HW, int NPF, bool CH2, bool SK = false, int LM = LM_NONE>
 __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, unsigned char* smem, const StaleWin& sw = StaleWin{})
 {
     constexpr int TJ = SWEEP_TJ, TR = TJ + 4;
@@ -700,13 +750,13 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
             load_vals<TAB, HW>(A, min(li + 1, lp1 + 1), j0 + row_of(0), lane, 0, nxt);
             const int r = row_of(0);
             auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-            row_reduce<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
+            row_reduce<TAB, HW, CH2, SK, LM>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
         } else {
             {
                 load_vals<TAB, HW>(A, li, j0 + row_of(1), lane, 0, nxt);
                 const int r = row_of(0);
                 auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-                row_reduce<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
+                row_reduce<TAB, HW, CH2, SK, LM>(A, rowp, li, lp, j0 + r, top, lane, cur, sw);
             }
             {
 #ifdef CETKMC_NO_TAIL_PREFETCH
@@ -715,7 +765,7 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
                 load_vals<TAB, HW>(A, min(li + 1, lp1 + 1), j0 + row_of(0), lane, 0, cur);
                 const int r = row_of(1);
                 auto rowp = [&](int d, int dj) { return (const uint8_t*)smem + so[d + 2] + (r + 2 + dj) * pitchC + KOFFC; };
-                row_reduce<TAB, HW, CH2, SK>(A, rowp, li, lp, j0 + r, top, lane, nxt, sw);
+                row_reduce<TAB, HW, CH2, SK, LM>(A, rowp, li, lp, j0 + r, top, lane, nxt, sw);
             }
         }
 #ifdef CETKMC_NO_TAIL_PREFETCH
@@ -763,6 +813,15 @@ __device__ __forceinline__ void sweep_stream_tile(const StreamArgs& A, int b, un
 // atom without an exposed neighbour) therefore contributes exact zeros whatever it holds in v[]: the tiles of option
 // table_lane_skip do not load its entries.  (A superset of the two masks: a count on a byte with neither bit also asks.)
 __host__ __device__ __forceinline__ bool lane_needs_values(uint2 own) { return ((own.x | own.y) & 0xFDFDFDFDu) != 0u; }
+// What a lane of the tiles that use lane sums (LM_USE) requests behind its class word and its chunk's count byte: the 8 B lane
+// sum of a pristine chunk that is not poisoned, else the 64 B of entries where lane_needs_values() holds, else nothing.  A lane
+// sum is never chosen where row_reduce() would mask with a byte other than 0x01.
+constexpr int LANE_REQ_NONE = 0, LANE_REQ_VALUES = 1, LANE_REQ_SUM = 2;
+__host__ __device__ __forceinline__ int lane_request(uint2 own, unsigned cnt)
+{
+    if (lane_pristine(own) && cnt <= 8u) return LANE_REQ_SUM;       // (a count is 0..8; LANE_POISON and anything else is none)
+    return lane_needs_values(own) ? LANE_REQ_VALUES : LANE_REQ_NONE;
+}
 // An empty statement that the compiler moves nothing across and that holds the two class words and the 2 x 8 (zeroed) value
 // registers of a pair of items: both class words have arrived here, and the zeros are written before the guarded loads below
 // it.  Without it the compiler waits for the second class word only behind the first item's table loads (a wait for those as
@@ -785,11 +844,12 @@ __device__ __forceinline__ void table_item_request(const StreamArgs& A, int lp, 
     load_vals<true, HW>(A, lp + 2, jrow, lane, 0, v);
     c = load_cls8(A, lp + 2, jrow, HW ? (lane & 31) : lane, 0);
 }
-template <bool HW, bool CH2, bool SK = false>
+template <bool HW, bool CH2, bool SK = false, int LM = LM_NONE>
 __device__ __forceinline__ void table_item_reduce(const StreamArgs& A, int lp, int jrow, int lane, const double (&v)[8], uint2 c,
-                                                  const StaleWin& sw = StaleWin{}, double* lds_sum = nullptr, int* lds_cnt = nullptr)
+                                                  const StaleWin& sw = StaleWin{}, double* lds_sum = nullptr, int* lds_cnt = nullptr,
+                                                  int lcnt = -1)
 {
-    row_reduce<true, HW, CH2, SK>(A, c, lp + 2, lp, jrow, A.gi0 + lp == A.L - 1, lane, v, sw, lds_sum, lds_cnt);
+    row_reduce<true, HW, CH2, SK, LM>(A, c, lp + 2, lp, jrow, A.gi0 + lp == A.L - 1, lane, v, sw, lds_sum, lds_cnt, lcnt);
 }
 
 #ifndef CETKMC_TABLE_IPW
@@ -831,10 +891,15 @@ __host__ __device__ constexpr int table_tile_of(int L, bool hw, int lp, int j)
 // measurable, the bytes were (131 MB per launch at 256^3 instead of 157 MB).
 // `first`: block b of the launch's nblk tile blocks runs tile first + b of the mapping above (a launch that runs a part of the
 // tile range: the early tiles of k_select_pend_tiles, the remaining ones of k_sweep_stream_apply).
-template <bool HW, bool CH2, bool SK, int IPW, bool LS = false>
+// LM (lane sums): LM_BUILD, the plain launch that follows a table write, stores the lane table where it reduces; LM_USE (with LS):
+// the count byte of the lane's chunk travels with the class word in the first round trip, and in the second a lane requests
+// what lane_request() says: its 8 B lane sum, its 64 B of entries, or nothing.  Both items' first-trip loads go out together,
+// then both items' second-trip requests back to back, as before.
+template <bool HW, bool CH2, bool SK, int IPW, bool LS = false, int LM = LM_NONE>
 __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int nblk, const StaleWin& sw = StaleWin{}, int first = 0)
 {
     static_assert(IPW % 2 == 0, "two alternating buffers");
+    static_assert(LM != LM_USE || (LS && HW), "lane sums are requested behind the class word, at half-wave rows");
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = A.L;
     const int ipp = table_tile_ipp(L, HW);                       // items per plane (HW: pairs of rows)
@@ -857,24 +922,42 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
             const int lpb = two ? lp2 : lp, jpb = two ? jp2 : jp;
             ca = load_cls8(A, lp + 2, jrow_of(jp), sl, 0);
             cb = load_cls8(A, lpb + 2, jrow_of(jpb), sl, 0);
+            unsigned na8 = LANE_POISON, nb8 = LANE_POISON;      // the chunks' count bytes
+            int64_t cha = 0, chb = 0;
+            if constexpr (LM == LM_USE) {
+                cha = lane_chunk(A, lp + 2, jrow_of(jp), sl);
+                chb = lane_chunk(A, lpb + 2, jrow_of(jpb), sl);
+                na8 = A.lanecnt[cha];
+                nb8 = A.lanecnt[chb];
+            }
+            // the lane sums travel in registers of their own and join va[0] / vb[0] where the item is reduced: a load into a
+            // register that an earlier load still owes makes the compiler wait for that one first (a round trip each; measured:
+            // 46.1 us per step at 256^3 with the sum loaded into va[0] directly, 44.3 with this form)
+            double sa = 0.0, sb = 0.0;
             // lanes that do not load hold +0.0 (whatever they held is masked by row_reduce(), but it must be a value); one wait
             // for the two class words, then the two guarded requests back to back: the loads sit under the lanes' exec mask,
             // so a masked lane requests no bytes
 #pragma unroll
             for (int q = 0; q < 8; ++q) va[q] = vb[q] = 0.0;
             pin_item_pair(ca, cb, va, vb);
+            if constexpr (LM == LM_USE) asm volatile("" : "+v"(na8), "+v"(nb8), "+v"(sa), "+v"(sb));       // (the count bytes have arrived as well)
 #ifdef CETKMC_LANE_SKIP_TIMING
             // TIMING ONLY (results wrong unless k < 56 of every row is idle): lanes 0..6 skipped by lane index, no wait for the
             // class words -- the byte saving at the benchmark's lattice without the dependent request
-            const bool na = sl >= 7, nb = sl >= 7;
+            const int ra = sl >= 7 ? LANE_REQ_VALUES : LANE_REQ_NONE, rb = ra;
 #else
-            const bool na = lane_needs_values(ca), nb = lane_needs_values(cb);
+            const int ra = LM == LM_USE ? lane_request(ca, na8) : lane_needs_values(ca) ? LANE_REQ_VALUES : LANE_REQ_NONE;
+            const int rb = LM == LM_USE ? lane_request(cb, nb8) : lane_needs_values(cb) ? LANE_REQ_VALUES : LANE_REQ_NONE;
 #endif
-            if (na) load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
-            if (nb) load_vals<true, HW>(A, lpb + 2, jrow_of(jpb), lane, 0, vb);
-            table_item_reduce<HW, CH2, SK>(A, lp, jrow_of(jp), lane, va, ca, sw);
+            if (LM == LM_USE && ra == LANE_REQ_SUM) sa = A.lanesum[cha];
+            if (LM == LM_USE && rb == LANE_REQ_SUM) sb = A.lanesum[chb];
+            if (ra == LANE_REQ_VALUES) load_vals<true, HW>(A, lp + 2, jrow_of(jp), lane, 0, va);
+            if (rb == LANE_REQ_VALUES) load_vals<true, HW>(A, lpb + 2, jrow_of(jpb), lane, 0, vb);
+            if (LM == LM_USE && ra == LANE_REQ_SUM) va[0] = sa;
+            table_item_reduce<HW, CH2, SK, LM>(A, lp, jrow_of(jp), lane, va, ca, sw, nullptr, nullptr, ra == LANE_REQ_SUM ? (int)na8 : -1);
             if (!two) break;
-            table_item_reduce<HW, CH2, SK>(A, lpb, jrow_of(jpb), lane, vb, cb, sw);
+            if (LM == LM_USE && rb == LANE_REQ_SUM) vb[0] = sb;
+            table_item_reduce<HW, CH2, SK, LM>(A, lpb, jrow_of(jpb), lane, vb, cb, sw, nullptr, nullptr, rb == LANE_REQ_SUM ? (int)nb8 : -1);
             item += 8;
             if (item >= n_items) break;
             lp = lp2; jp = jp2 + 4;
@@ -891,7 +974,7 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
         const bool more = !last && (item + 4 < n_items);
         const int lpn = more ? lp2 : lp, jpn = more ? jp2 : jp;
         table_item_request<HW>(A, lpn, jrow_of(jpn), lane, nxt, cnxt);
-        table_item_reduce<HW, CH2, SK>(A, lp, jrow_of(jp), lane, cur, ccur, sw);
+        table_item_reduce<HW, CH2, SK, LM>(A, lp, jrow_of(jp), lane, cur, ccur, sw);
         item += 4; lp = lp2; jp = jp2;
     };
 #pragma unroll 1
@@ -905,17 +988,19 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
 
 // TT: the launch's tiles are the census-free ones (sweep_table_tile; table variant only, no dynamic LDS); LS: its option
 // table_lane_skip
-template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false, bool LS = false>
+// LB: the launch builds the lane table (LM_BUILD; the plain launch that follows a table write, either kind of tile)
+template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false, bool LS = false, bool LB = false>
 __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
 {
     static_assert(!TT || TAB, "census-free tiles read the rate table");
     static_assert(!LS || TT, "lanes are skipped by the census-free tiles");
+    constexpr int LM = LB ? LM_BUILD : LM_NONE;
     if (ss && ss->status) return;
     if constexpr (TT) {
-        sweep_table_tile<HW, CH2, false, TABLE_TILE_IPW, LS>(A, blockIdx.x, (int)gridDim.x);
+        sweep_table_tile<HW, CH2, false, TABLE_TILE_IPW, LS, LM>(A, blockIdx.x, (int)gridDim.x);
     } else {
         extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-        sweep_stream_tile<TAB, HW, NPF, CH2>(A, blockIdx.x, smem);
+        sweep_stream_tile<TAB, HW, NPF, CH2, false, LM>(A, blockIdx.x, smem);
     }
 }
 
@@ -924,6 +1009,21 @@ __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_table(StreamArg
 {
     if (ss && ss->status) return;
     sweep_table_tile<HW, CH2, false, TABLE_IPW>(A, blockIdx.x, (int)gridDim.x);
+}
+
+// Inspection (cetkmc_lane_table, tests): the owned chunks of the lane table with a count (<= 8) -> out[0], poisoned -> out[1]
+__global__ __launch_bounds__(256) void k_lane_census(SlabView S, unsigned long long* out)
+{
+    const int cpr = S.pitchT >> 3;                                  // chunks per row
+    const int64_t n = (int64_t)S.nloc * S.L * cpr, first = (int64_t)2 * S.L * cpr;      // owned planes start at li = 2
+    int ok = 0, bad = 0;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned c = S.lanecnt[first + q];
+        ok += c <= 8u ? 1 : 0;
+        bad += c == LANE_POISON ? 1 : 0;
+    }
+    ok = wave_sum_i(ok); bad = wave_sum_i(bad);
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], (unsigned long long)ok); atomicAdd(&out[1], (unsigned long long)bad); }
 }
 
 // k_sweep_plane (variant 4): k_sweep_table with one block per owned plane (16 waves; wave w takes the plane's items w, w + 16, ...),
@@ -1623,6 +1723,8 @@ __device__ __forceinline__ void ifc_store(const SlabView& S, int li, int j, int 
 {
     S.vval[t] = sum;
     S.cls[S.cidx(li, j, k)] = (uint8_t)(class8(code_state(code)) | ((unsigned)cnt << 2));
+    // the entry's chunk leaves the lane table until the next building sweep: one byte, stored without being read
+    if (S.lanecnt) S.lanecnt[t >> 3] = (uint8_t)LANE_POISON;
 }
 
 // after an event changed voxel (i,j,k): it and its 14 neighbours may have become interface voxels,
@@ -2052,7 +2154,13 @@ __global__ __launch_bounds__(256) void k_select_pend(KParams P, const SlabView* 
 // step status and no pending record: behind a stop they store what the rows held anyway.  A.rowsum / A.rowcnt are the row-sum
 // pair the selection block of this launch does NOT read (Handle::row_par): no launch reads a row-sum buffer that another of
 // its blocks writes.
-template <bool LS>
+// LU (option lane_sums, the lane table fresh): the tiles read lane sums (LM_USE), here and in k_sweep_stream_apply.  No new race:
+// nothing in this launch writes the lane table or a table entry; in the next launch the only writer beside the tiles is the
+// apply block, whose ifc_store() writes entries and count bytes of the event's site(s) and their 14 neighbours alone -- voxels of
+// rows at a dirty_offset() from a site, which are the stale rows.  A tile may read such a chunk before or after the poison byte
+// and the new entry, but it does not store that row (SK), and the apply block re-reduces it from the entries after its own
+// stores.  The early tiles' copy of such a row is overwritten in the same way.
+template <bool LS, bool LU = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_select_pend_tiles(
     KParams P, const SlabView* __restrict__ slabs, int nslabs, int L, int PB, const BlockEnt* __restrict__ blocks, StepState* ss,
     BatchCfg cfg, const double* __restrict__ u_pick, const double* __restrict__ ktab_g, PendRec* pend,
@@ -2067,7 +2175,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     // (the early traffic spread over the selection's life instead of one burst beside its first loads)
 #pragma unroll 1
     for (int t = (int)blockIdx.x - 1; t < n_early; t += (int)gridDim.x - 1)
-        sweep_table_tile<true, false, false, TABLE_TILE_IPW, LS>(A, t, n_early);
+        sweep_table_tile<true, false, false, TABLE_TILE_IPW, LS, LU ? LM_USE : LM_NONE>(A, t, n_early);
 }
 
 // The apply block: apply_batch_body of the fused launch (carry from the record instead of LDS), then the stale rows with
@@ -2146,7 +2254,7 @@ __device__ __forceinline__ void sweep_apply_block(const StreamArgs& A, const App
 // block's copy of KParams, SlabView and the pending record alone.  LS: the tiles' option table_lane_skip.  first_tile (TT): the
 // launch's tile blocks run the tiles from first_tile on -- the ones before it ran in the previous launch (k_select_pend_tiles);
 // with first_tile >= the tile count the grid is the apply block alone.
-template <bool HW, int NPF, bool CH2, bool TT = false, bool LS = false>
+template <bool HW, int NPF, bool CH2, bool TT = false, bool LS = false, bool LU = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_sweep_stream_apply(StreamArgs A,
                                                                                                     const StepState* __restrict__ ss,
                                                                                                     ApplyArgs X, int first_tile)
@@ -2159,7 +2267,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
         const int b = (int)blockIdx.x - 1;
         const StaleEv se = stale_ev_of(X.pend->ev);
         if constexpr (TT) {
-            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW, LS>(A, b, (int)gridDim.x - 1, stale_win(se), first_tile);
+            sweep_table_tile<HW, CH2, true, TABLE_TILE_IPW, LS, LU ? LM_USE : LM_NONE>(A, b, (int)gridDim.x - 1, stale_win(se), first_tile);
         } else {
             int ibr, jt;
             stream_tile_of(A, b, ibr, jt);

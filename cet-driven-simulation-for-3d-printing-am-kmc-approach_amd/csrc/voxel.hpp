@@ -45,6 +45,7 @@ struct KParams {
 // Geometry + field pointers of one axis-0 slab as the kernels see it.
 // Local plane index li = i - (gi0 - 2): two halo planes on each side are always allocated
 // (sentinel state when they fall outside the lattice).
+constexpr unsigned LANE_POISON = 0xFFu;      // SlabView::lanecnt of a chunk without a usable lane sum
 struct SlabView {
     int L;        // lattice edge
     int gi0;      // first owned global plane
@@ -78,6 +79,10 @@ struct SlabView {
     uint32_t* ifc_code; // same indexing: packed neighbourhood of a listed voxel (ifc_encode), kept current by apply
     uint32_t* ifc_list; // packed (lp << 20 | j << 10 | k) of the listed voxels (append-only, superset)
     int* ifc_n;         // number of listed voxels
+    // lane table (kernels.hpp, "lane sums"; null where the census-free tiles cannot run): per chunk of 8 table entries, index
+    // tidx >> 3 (pitchT is a multiple of 8)
+    double* lanesum;    // tree8() of the chunk's entries as the last building sweep saw them
+    uint8_t* lanecnt;   // how many of them were non-zero (0..8), or LANE_POISON: the chunk's entries are to be read themselves
     __device__ __forceinline__ int64_t sidx(int li, int j, int k) const {
         return ((int64_t)li * RJ + (j + 2)) * pitchS + KOFF + k;
     }

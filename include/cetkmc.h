@@ -231,6 +231,17 @@ int cetkmc_early_tile_row(int L, int early_tiles, int gi, int j);
  * class8 (byte h = voxel k0 + h, little endian): some byte is empty (bit 0) or holds a non-zero count (bits 7:2).  0: all
  * bytes are 0x00 or 0x02, the row reduction masks every entry of the lane.  Host function; needs no device. */
 int cetkmc_lane_needs_values(uint64_t class8);
+/* What a lane of those tiles requests under option lane_sums while the lane table is fresh, from its 8 class bytes and the
+ * count byte of its chunk (0..8 = the non-zero entries the last building sweep saw, 0xFF = poisoned): CETKMC_LANE_REQ_SUM,
+ * the 8 B lane sum, where every class byte is 0x01 and the count byte is a count; else CETKMC_LANE_REQ_VALUES, the 64 B of
+ * entries, where cetkmc_lane_needs_values() holds; else CETKMC_LANE_REQ_NONE.  Host function; needs no device. */
+enum cetkmc_lane_req { CETKMC_LANE_REQ_NONE = 0, CETKMC_LANE_REQ_VALUES = 1, CETKMC_LANE_REQ_SUM = 2 };
+int cetkmc_lane_request(uint64_t class8, int count_byte);
+/* Inspection of a handle's lane table (tests; one small kernel and a synchronisation): fresh = 1 when the deferred launches
+ * would read lane sums now; chunks = owned chunks of 8 table entries (0: the shape has no lane table), of which `usable` hold a
+ * count and `poisoned` 0xFF; builds = plain sweep launches that have built the table so far. */
+typedef struct cetkmc_lane_table_info { int64_t fresh, chunks, usable, poisoned, builds; } cetkmc_lane_table_info;
+int cetkmc_lane_table(void* handle, cetkmc_lane_table_info* out);
 /* What a handle keeps between calls, as bits of cetkmc_invalidates()'s result. */
 enum cetkmc_cache {
     CETKMC_CACHE_SWEEP = 1,     /* row and block sums of the last rate sweep (cetkmc_select, cetkmc_row_sums read them) */
@@ -294,6 +305,9 @@ int cetkmc_sync(void* handle);
  * 2 = the plain streaming launch at that shape as well, 0 = the ring tiles of sweep_variant 1 in both;
  * "table_lane_skip" 1 (default) = those census-free tiles request a lane's class bytes first and its rate-table entries only if
  * cetkmc_lane_needs_values() holds for them (same bits, fewer bytes), 0 = every lane's entries;
+ * "lane_sums" 1 (default) = with table_lane_skip, a lane whose 8 voxels are empty and unlisted requests one stored sum (8 B, built
+ * by the plain sweep that follows a table write, dropped per chunk wherever an entry is written: cetkmc_lane_request()) instead
+ * of its 8 entries (same bits, fewer bytes; off while thermal_lookahead is on), 0 = entries;
  * "early_tiles" E = the selection launch of a deferred step also runs the first E census-free tiles of the next step's sweep
  * (values past the tile count mean all of them), which the next sweep launch then leaves out; they store into the handle's
  * second pair of row-sum buffers, which becomes the current pair (same bits; DESIGN.md sections 13 and 20), 0 = the selection
