@@ -69,7 +69,7 @@ class LocalArgs(C.Structure):
 
 
 class LaneTableInfo(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("fresh", "chunks", "usable", "poisoned", "builds")]
+    _fields_ = [(n, C.c_int64) for n in ("fresh", "chunks", "usable", "poisoned", "builds", "builds_thermal")]
 
 
 class Counters(C.Structure):
@@ -214,6 +214,9 @@ PROTOTYPES = {
     "cetkmc_lane_needs_values": (C.c_int, [C.c_uint64]),
     "cetkmc_lane_request": (C.c_int, [C.c_uint64, C.c_int]),
     "cetkmc_lane_table": (C.c_int, [C.c_void_p, _P(LaneTableInfo)]),
+    "cetkmc_lane_table_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "cetkmc_lane_quad_node": (None, [_P(C.c_double), C.c_int, _P(C.c_double), _P(C.c_int)]),
+    "cetkmc_tree8": (C.c_double, [_P(C.c_double)]),
     "cetkmc_invalidates": (C.c_int, [C.c_char_p]),
     "cetkmc_device_count": (C.c_int, [_P(C.c_int)]),
     "cetkmc_create": (C.c_int, [_P(Params), C.c_int, C.c_int, _P(C.c_int), _P(C.c_void_p)]),

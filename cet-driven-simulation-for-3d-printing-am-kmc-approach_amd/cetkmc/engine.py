@@ -539,10 +539,18 @@ class Engine(_ThermalSettings):
         return {n: getattr(c, n) for n, _ in Counters._fields_}
 
     def lane_table(self):
-        """cetkmc_lane_table as a dict (tests): fresh, chunks, usable, poisoned, builds."""
+        """cetkmc_lane_table as a dict (tests): fresh, chunks, usable, poisoned, builds, builds_thermal."""
         info = LaneTableInfo()
         self._ck(self.lib.cetkmc_lane_table(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in LaneTableInfo._fields_}
+
+    def lane_table_arrays(self):
+        """cetkmc_lane_table_copy (tests): the owned chunks' sums (f64) and count bytes (u8), each (planes, L, chunks per row)."""
+        n = self.lane_table()["chunks"]
+        sums, counts = np.empty(n, np.float64), np.empty(n, np.uint8)
+        self._ck(self.lib.cetkmc_lane_table_copy(self.h, sums.ctypes.data, counts.ctypes.data, n))
+        shape = (self.i1 - self.i0, self.L, n // ((self.i1 - self.i0) * self.L))
+        return sums.reshape(shape), counts.reshape(shape)
 
     # -- Mode B: synchronous super-steps over (L/box)^3 boxes (not in the reference; include/cetkmc.h) --------
     def run_supersteps(self, step0, n, box, defect_fraction, seed, thermal_mode=1, thermal_dt=1e-6, q_planes=None,

@@ -204,7 +204,12 @@ struct Handle {
                                  // CU, four tiles each at 256^3); 0 = one per tile
     int poison_alt_rows = 0;     // option "poison_alt_rows" (tests): the pair about to be written is filled with 0xFF first
     bool pend_live = false;      // run_steps: the next launch_sweep applies *d_pend (the previous step was deferred)
+    int lane_build = 1;          // option "lane_build": 1 = the temperature tiles that write the rate table store the lane table too
+                                 // (k_thermal_tiles16<.., LANES>: the plain launch behind the update does not build), 0 = that launch builds
+    int lane_sweep = 1;          // option "lane_sweep": 1 = a plain sweep launch reads lane sums while the lane table is fresh
+                                 // (k_sweep_stream<.., LU>), 0 = the plain launch reads every entry
     int64_t cnt_lane_builds = 0; // plain launches that built the lane table (cetkmc_lane_table)
+    int64_t cnt_lane_builds_thermal = 0;   // temperature updates whose tiles built it
     int pend_early = 0;          // ... and leaves out its first pend_early tiles, which the selection launch ran
     BatchCfg pend_cfg{};         // ... with this batch configuration
     double* d_ktab = nullptr;
@@ -833,6 +838,7 @@ TableCfg table_cfg(Handle* h, const Slab& s, int par)
     tb.T_melt = h->kp.T_melt; tb.delta_T_c = h->kp.delta_T_c; tb.kT = h->kp.kT; tb.I0 = h->kp.I0;
     tb.rate_threshold = h->kp.rate_threshold; tb.K0 = host_k_eff(h->p, 0, 0); tb.nu_dep = h->kp.nu_dep;
     tb.vval = s.vvalbuf[par]; tb.dep_val = s.depbuf[par];
+    tb.lanesum = s.v.lanesum; tb.lanecnt = s.v.lanecnt;       // (one copy: a digest of the table that is current)
     return tb;
 }
 
@@ -1009,6 +1015,10 @@ int launch_sweep(Handle* h, bool batch, hipEvent_t ev_a = nullptr, hipEvent_t ev
                 });
             else
                 launch(k_sweep_stream_apply<true, 1, false>, dim3(sa.group_count * njt + 1), dim3(256), h->shmem_stream, h->stream, xa, xb, sa, h->d_ss, X, 0);
+        } else if (h->lane_sweep && lane_table_use(h)) {
+            // a plain launch on a fresh lane table: the lane-sum tiles of the deferred launches over the full tile range
+            // (lane_table_use(): sweep_variant 1, table_tiles(), table_lane_skip)
+            launch(k_sweep_stream<true, true, 1, false, true, true, false, true>, dim3(table_tile_count(h->L, v.nloc, true)), dim3(256), 0, h->stream, xa, xb, sa, ss);
         } else if (h->sweep_variant == 1 && table_tiles(h, 2)) {
             // (a plain launch where the lane table is stale builds it: the table, the interface kernel and the lattice are current here)
             const bool build = lane_table_on(h) && !h->lanes_fresh;
@@ -1186,7 +1196,7 @@ int launch_thermal_one(Handle* h, double dt, int laser, const double* d_q, int u
     if (first) ++h->cnt.thermal_updates;
     for (auto& sl : h->slabs) h->cnt.alg_bytes_thermal += (int64_t)16 * sl.v.nloc * h->L * h->L;   // T read + written
     const int nxt = h->cur ^ 1;
-    size_t n_fused = 0;
+    size_t n_fused = 0, n_lanes = 0;
     const StepState* ssp = batch ? h->d_ss : nullptr;
     for (size_t s = 0; s < h->slabs.size(); ++s) {
         SlabView v = view_of(h, (int)s);
@@ -1202,11 +1212,15 @@ int launch_thermal_one(Handle* h, double dt, int laser, const double* d_q, int u
                 // the default tiles also write the new field's rate table (k_rate_table's work, without reading T again)
                 const bool fuse = h->thermal_table && h->thermal_rpt == 2 && h->thermal_kt == 256 && h->sweep_variant >= 1;
                 if (fuse) { ++n_fused; h->cnt.alg_bytes_table += (int64_t)8 * v.nloc * v.L * v.L; }      // table entry written (T not re-read)
+                // ... and the lane table of those entries (option lane_build): 8 B node + 1 B count per chunk of 8
+                const bool lanes = fuse && h->lane_build && lane_table_on(h);
+                if (lanes) { ++n_lanes; h->cnt.alg_bytes_table += (int64_t)9 * v.nloc * v.L * (v.pitchT / 8); }
                 with_source(laser, use_latent, [&](auto la, auto lt) {
                     auto go = [&](auto k, unsigned threads, const TableCfg& tb) {
                         launch(k, g16, dim3(threads), 0, h->stream, nullptr, nullptr, v, Tin, Tout, prev, d_q, C16, ssp, tb);
                     };
-                    if (fuse) go(k_thermal_tiles16<la.value, lt.value, 2, 256, true>, 1024, table_cfg(h, h->slabs[s], nxt));
+                    if (lanes) go(k_thermal_tiles16<la.value, lt.value, 2, 256, true, true>, 1024, table_cfg(h, h->slabs[s], nxt));
+                    else if (fuse) go(k_thermal_tiles16<la.value, lt.value, 2, 256, true>, 1024, table_cfg(h, h->slabs[s], nxt));
                     else if (h->thermal_rpt == 2 && h->thermal_kt == 128) go(k_thermal_tiles16<la.value, lt.value, 2, 128>, 512, TableCfg{});
                     else if (h->thermal_rpt == 2) go(k_thermal_tiles16<la.value, lt.value, 2, 256>, 1024, TableCfg{});
                     else go(k_thermal_tiles16<la.value, lt.value, 4, 256>, 512, TableCfg{});
@@ -1237,6 +1251,9 @@ int launch_thermal_one(Handle* h, double dt, int laser, const double* d_q, int u
     const bool wrote_table = n_fused == h->slabs.size();      // every slab's update wrote its table as well
     invalidate(h, wrote_table ? Cause::thermal_update_wrote_table : Cause::thermal_update);
     if (wrote_table) { h->table_fresh = true; ++h->cnt.table_updates; }
+    // ... and its lane table (lane_table_on(): one slab).  The interface kernel that has to follow poisons the chunk of every
+    // entry it writes; whatever else writes entries or class bytes outside the batched apply clears the flag again (invalidate())
+    if (wrote_table && n_lanes == h->slabs.size()) { h->lanes_fresh = true; ++h->cnt_lane_builds_thermal; }
     return 0;
 }
 
@@ -1905,6 +1922,7 @@ int cetkmc_lane_table(void* handle, cetkmc_lane_table_info* out)
     *out = cetkmc_lane_table_info{};
     out->fresh = lane_table_use(h) ? 1 : 0;
     out->builds = h->cnt_lane_builds;
+    out->builds_thermal = h->cnt_lane_builds_thermal;
     if (h->slabs.size() != 1 || !h->slabs[0].v.lanecnt) return 0;      // no lane table at this shape
     HIPCHK(hipSetDevice(h->dev));
     CHK(ensure_scratch(h, 2 * sizeof(unsigned long long)));
@@ -1919,6 +1937,33 @@ int cetkmc_lane_table(void* handle, cetkmc_lane_table_info* out)
     out->usable = (int64_t)got[0];
     out->poisoned = (int64_t)got[1];
     return 0;
+}
+// the owned chunks of the lane table as they stand (tests): n = nloc * L * (pitchT / 8) sums and count bytes, row by row
+int cetkmc_lane_table_copy(void* handle, double* sums, uint8_t* counts, int64_t n)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || !sums || !counts) return fail("null argument");
+    if (h->slabs.size() != 1 || !h->slabs[0].v.lanecnt) return fail("cetkmc_lane_table_copy: the shape has no lane table");
+    const SlabView& v = h->slabs[0].v;
+    const int64_t cpr = h->pitchT / 8, owned = (int64_t)v.nloc * h->L * cpr, first = (int64_t)2 * h->L * cpr;
+    if (n != owned) return fail("cetkmc_lane_table_copy: n must be the owned chunks, " + std::to_string(owned));
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipMemcpyAsync(sums, v.lanesum + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(counts, v.lanecnt + first, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+void cetkmc_lane_quad_node(const double* x8, int lane, double* sum, int* count)
+{
+    double x[8];
+    for (int q = 0; q < 8; ++q) x[q] = x8[q];
+    lane_quad_node(x, lane, *sum, *count);
+}
+double cetkmc_tree8(const double* x8)
+{
+    double x[8];
+    for (int q = 0; q < 8; ++q) x[q] = x8[q];
+    return tree8(x);
 }
 int cetkmc_table_tile_of(int L, int gi, int j)
 {
@@ -2095,6 +2140,9 @@ int cetkmc_set_option(void* handle, const char* key, int64_t value)
         h->lanes_fresh = false;         // the next plain launch builds
         return 0;
     }
+    // (neither touches lanes_fresh: the lane table is valid whoever built it, and the plain launch reads it or not)
+    if (!strcmp(key, "lane_build")) { h->lane_build = value ? 1 : 0; return 0; }
+    if (!strcmp(key, "lane_sweep")) { h->lane_sweep = value ? 1 : 0; return 0; }
     if (!strcmp(key, "early_tiles")) {
         if (value < -1 || value > INT32_MAX) return fail("early_tiles must be a tile count >= 0, or -1 (a quarter of the tiles)");
         h->early_tiles = (int)value;

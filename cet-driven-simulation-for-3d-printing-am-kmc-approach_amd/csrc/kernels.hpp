@@ -390,7 +390,7 @@ __device__ __forceinline__ double mask_f64(double v, unsigned w, int b)
     const int m = __builtin_amdgcn_sbfe(w, b, 1);
     return __hiloint2double(__double2hiint(v) & m, __double2loint(v) & m);
 }
-__device__ __forceinline__ double tree8(const double (&x)[8])
+__host__ __device__ __forceinline__ double tree8(const double (&x)[8])
 {
     return ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
 }
@@ -429,6 +429,11 @@ __device__ __forceinline__ uint2 load_cls8(const StreamArgs& A, int li, int jrow
 // bit (every rate is >= +0.0, and s + 0.0 = s); the count replaces that lane's share of the eight ballots.
 // A poisoned chunk stays poisoned until the next build, and a chunk that is not pristine when it is read takes the entries:
 // a usable lane sum is therefore the node of 8 entries none of which has been written since it was stored.
+// The second builder (option lane_build) is the writer of the table itself: the temperature tiles that write it
+// (k_thermal_tiles16<.., TABLE, LANES>) store node and count of the 8 entries of EVERY chunk, no class byte read; the interface
+// kernel, which has to follow a table write, poisons the chunk of every entry it rewrites, and the reader asks for a sum only
+// behind a pristine class word (lane_request()), so the sentence above holds for that table as well.  LM_USE also serves the
+// plain launch on a fresh lane table (option lane_sweep, k_sweep_stream<.., LU>).
 constexpr int LM_NONE = 0, LM_BUILD = 1, LM_USE = 2;
 __host__ __device__ __forceinline__ bool lane_pristine(uint2 own) { return own.x == 0x01010101u && own.y == 0x01010101u; }
 // the chunk of lane sl of row jrow of local plane li (load_vals()' clamping)
@@ -989,12 +994,17 @@ __device__ __forceinline__ void sweep_table_tile(const StreamArgs& A, int b, int
 // TT: the launch's tiles are the census-free ones (sweep_table_tile; table variant only, no dynamic LDS); LS: its option
 // table_lane_skip
 // LB: the launch builds the lane table (LM_BUILD; the plain launch that follows a table write, either kind of tile)
-template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false, bool LS = false, bool LB = false>
+// LU (option lane_sweep, the lane table fresh; with TT and LS): the tiles read lane sums (LM_USE) -- the tile of the deferred
+// launches over the full tile range, without an apply block and without a store predicate.  The plain launch behind a
+// temperature update whose tiles stored the lane table (k_thermal_tiles16<.., LANES>), every immediate step and every
+// cetkmc_rate_sweep on a fresh lane table
+template <bool TAB, bool HW, int NPF, bool CH2, bool TT = false, bool LS = false, bool LB = false, bool LU = false>
 __global__ __launch_bounds__(256) CETKMC_SWEEP_ATTR void k_sweep_stream(StreamArgs A, const StepState* __restrict__ ss)
 {
     static_assert(!TT || TAB, "census-free tiles read the rate table");
     static_assert(!LS || TT, "lanes are skipped by the census-free tiles");
-    constexpr int LM = LB ? LM_BUILD : LM_NONE;
+    static_assert(!LU || (LS && !LB), "lane sums are read by the skipping tiles of a launch that does not build them");
+    constexpr int LM = LB ? LM_BUILD : LU ? LM_USE : LM_NONE;
     if (ss && ss->status) return;
     if constexpr (TT) {
         sweep_table_tile<HW, CH2, false, TABLE_TILE_IPW, LS, LM>(A, blockIdx.x, (int)gridDim.x);
@@ -2324,7 +2334,22 @@ struct TableCfg {
     double T_melt, delta_T_c, kT, I0, rate_threshold, K0, nu_dep;
     double* vval;       // the NEW field's table (the buffer pair is flipped with T)
     double* dep_val;
+    double* lanesum;    // the slab's lane table (LANES: the tiles store it beside the table), else null
+    uint8_t* lanecnt;
 };
+// The node and the count of one chunk as the four lanes that hold its 8 entries form them (k_thermal_tiles16<.., LANES>): lane l
+// of the quad holds x[2l], x[2l+1]; pairs, then the quad_perm partners l ^ 1 and l ^ 2.  In lane 0 that is tree8(x) operand for
+// operand, in the others the same additions with operands swapped (IEEE addition commutes to the bit): one restatement for the
+// host (cetkmc_lane_quad_node, tests) -- the kernel does the two partner steps with DPP.
+__host__ __device__ inline void lane_quad_node(const double (&x)[8], int l, double& sum, int& cnt)
+{
+    double p[4], q[4];
+    int np[4], nq[4];
+    for (int a = 0; a < 4; ++a) { p[a] = x[2 * a] + x[2 * a + 1]; np[a] = (x[2 * a] != 0.0 ? 1 : 0) + (x[2 * a + 1] != 0.0 ? 1 : 0); }
+    for (int a = 0; a < 4; ++a) { q[a] = p[a] + p[a ^ 1]; nq[a] = np[a] + np[a ^ 1]; }
+    sum = q[l & 3] + q[(l & 3) ^ 2];
+    cnt = nq[l & 3] + nq[(l & 3) ^ 2];
+}
 __device__ __forceinline__ double scrub_T(double x, double T_nan, int on)
 {   // np.nan_to_num(T, nan=T_SUB), kmc_simulation.py:249
     if (!on) return x;
@@ -2728,13 +2753,21 @@ constexpr int THERM16_TJ = 16, THERM16_NI = 16;
 // TABLE: the kernel also writes what k_rate_table would compute from the new field -- the rate table entry of every voxel it
 // updates (and plane L-1's deposition rates) -- while the new temperature is still in a register: the field is not read a
 // second time (16 of the pair's 32 B per voxel saved).  Same functions on the same values: same bits.
-template <bool LASER, bool LATENT, int RPT, int KT, bool TABLE = false>
+// LANES (with TABLE, option lane_build): the kernel stores the lane table of the entries it writes as well (kernels.hpp, "lane
+// sums").  A thread owns columns 2 (tid % 128) and the next, so the 8 entries of a chunk sit in 4 consecutive lanes aligned on 4
+// (a quad; a wave never splits one): s = r0 + r1, then the quad_perm partners -- tree8() of the chunk in all four lanes
+// (lane_quad_node()), the count of non-zero entries likewise; lane tid % 4 == 0 stores both, 9 B per chunk.  No class byte is
+// read: EVERY chunk gets a node and a count.  That is sound because the consumer asks for a sum only behind a pristine class
+// word (lane_request()), and a chunk is pristine with stale entries never: k_interface, which follows, poisons the chunk of
+// every entry it writes, as does every later ifc_store().  A terminated batch stores nothing, as with the table.
+template <bool LASER, bool LATENT, int RPT, int KT, bool TABLE = false, bool LANES = false>
 __global__ __launch_bounds__((KT / 2) * (16 / RPT)) CETKMC_THERM16_ATTR void k_thermal_tiles16(SlabView S, const double* __restrict__ Tin, double* __restrict__ Tout,
                                                          uint8_t* __restrict__ prev_state, const double* __restrict__ q_top,
                                                          ThermalCfg C, const StepState* __restrict__ ss, TableCfg TB = TableCfg{})
 {
     constexpr int TJ = THERM16_TJ, LW = KT + 2, HC = KT / 2, NTHR = HC * (16 / RPT);
     static_assert(NTHR >= 2 * KT, "one rim cell per thread");
+    static_assert(!LANES || (TABLE && KT % 8 == 0 && HC % 4 == 0), "the lane table is stored with the table, a chunk per quad of lanes");
     __shared__ double tile[(TJ + 2) * LW];
     const int L = S.L, pitchT = S.pitchT;
     const int tid = threadIdx.x;
@@ -2853,6 +2886,19 @@ __global__ __launch_bounds__((KT / 2) * (16 / RPT)) CETKMC_THERM16_ATTR void k_t
                 const double r0 = nuc_bulk(TB.T_melt, TB.delta_T_c, TB.kT, TB.I0, TB.rate_threshold, TB.K0, out[0]);
                 const double r1 = nuc_bulk(TB.T_melt, TB.delta_T_c, TB.kT, TB.I0, TB.rate_threshold, TB.K0, out[1]);
                 *reinterpret_cast<double2*>(TB.vval + (int64_t)li * pstride + off[q]) = make_double2(r0, r1);
+                if constexpr (LANES) {             // (straight-line code: every lane of the wave is here)
+                    double s = r0 + r1;
+                    s = s + dpp_f64(s, 0);
+                    s = s + dpp_f64(s, 1);
+                    unsigned nz = (r0 != 0.0 ? 1u : 0u) + (r1 != 0.0 ? 1u : 0u);
+                    nz += __builtin_amdgcn_update_dpp(nz, nz, 0xB1, 0xF, 0xF, true);
+                    nz += __builtin_amdgcn_update_dpp(nz, nz, 0x4E, 0xF, 0xF, true);
+                    if ((tid & 3) == 0) {
+                        const int64_t ch = ((int64_t)li * pstride + off[q]) >> 3;
+                        TB.lanesum[ch] = s;
+                        TB.lanecnt[ch] = (uint8_t)nz;
+                    }
+                }
                 if (i == L - 1) {                  // kmc_event_rates.py:59-63 for plane L-1 (block-uniform)
                     double* dp = TB.dep_val + (int64_t)j * pitchT + k0;
                     dp[0] = dep_rate_s(TB.nu_dep, TB.T_melt, TB.kT, pymax(out[0], 1.0));

@@ -239,9 +239,19 @@ enum cetkmc_lane_req { CETKMC_LANE_REQ_NONE = 0, CETKMC_LANE_REQ_VALUES = 1, CET
 int cetkmc_lane_request(uint64_t class8, int count_byte);
 /* Inspection of a handle's lane table (tests; one small kernel and a synchronisation): fresh = 1 when the deferred launches
  * would read lane sums now; chunks = owned chunks of 8 table entries (0: the shape has no lane table), of which `usable` hold a
- * count and `poisoned` 0xFF; builds = plain sweep launches that have built the table so far. */
-typedef struct cetkmc_lane_table_info { int64_t fresh, chunks, usable, poisoned, builds; } cetkmc_lane_table_info;
+ * count and `poisoned` 0xFF; builds = plain sweep launches that have built the table so far; builds_thermal = temperature
+ * updates whose tiles built it (option lane_build). */
+typedef struct cetkmc_lane_table_info { int64_t fresh, chunks, usable, poisoned, builds, builds_thermal; } cetkmc_lane_table_info;
 int cetkmc_lane_table(void* handle, cetkmc_lane_table_info* out);
+/* The owned chunks of the lane table as they stand (tests; two copies and a synchronisation): n = cetkmc_lane_table()'s
+ * `chunks` sums and count bytes, chunk (plane, row, k / 8) at (plane * L + row) * (row pitch / 8) + k / 8. */
+int cetkmc_lane_table_copy(void* handle, double* sums, uint8_t* counts, int64_t n);
+/* The node and the non-zero count of a chunk's 8 entries as the temperature tiles that build the lane table form them, in
+ * `lane` (0..3) of the four lanes that hold the chunk: lane l has x8[2l] + x8[2l+1], adds the pair sum of lane l ^ 1, then the
+ * quad sum of lane l ^ 2.  cetkmc_tree8: the row reduction's expression ((x0+x1)+(x2+x3))+((x4+x5)+(x6+x7)) of the same
+ * entries.  Host functions; need no device. */
+void cetkmc_lane_quad_node(const double* x8, int lane, double* sum, int* count);
+double cetkmc_tree8(const double* x8);
 /* What a handle keeps between calls, as bits of cetkmc_invalidates()'s result. */
 enum cetkmc_cache {
     CETKMC_CACHE_SWEEP = 1,     /* row and block sums of the last rate sweep (cetkmc_select, cetkmc_row_sums read them) */
@@ -308,6 +318,10 @@ int cetkmc_sync(void* handle);
  * "lane_sums" 1 (default) = with table_lane_skip, a lane whose 8 voxels are empty and unlisted requests one stored sum (8 B, built
  * by the plain sweep that follows a table write, dropped per chunk wherever an entry is written: cetkmc_lane_request()) instead
  * of its 8 entries (same bits, fewer bytes; off while thermal_lookahead is on), 0 = entries;
+ * "lane_build" 1 (default) = with lane_sums, the temperature tiles that write the rate table (thermal_table, L a multiple of 256)
+ * store the lane table of the entries they write as well, so the plain sweep behind the update does not build it (same bits),
+ * 0 = that sweep builds; "lane_sweep" 1 (default) = a plain sweep launch reads lane sums while the lane table is fresh, like the
+ * deferred launches (same bits, fewer bytes), 0 = the plain launch reads every entry;
  * "early_tiles" E = the selection launch of a deferred step also runs the first E census-free tiles of the next step's sweep
  * (values past the tile count mean all of them), which the next sweep launch then leaves out; they store into the handle's
  * second pair of row-sum buffers, which becomes the current pair (same bits; DESIGN.md sections 13 and 20), 0 = the selection
