@@ -190,6 +190,15 @@ class BeamInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("updates", "steps", "launches", "table_uploads")]
 
 
+class Shift(C.Structure):
+    _fields_ = [("d", C.c_int32 * 3), ("fill_state", C.c_int32), ("T_mode", C.c_int32), ("pad", C.c_int32),
+                ("fill_T", C.c_double), ("fill_theta", C.c_double), ("fill_phi", C.c_double)]
+
+
+class ShiftInfo(C.Structure):
+    _fields_ = [("calls", C.c_int64), ("kept", C.c_int64), ("exposed", C.c_int64), ("dropped", C.c_int64 * 6)]
+
+
 STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "run_args": RunArgs, "run_result": RunResult,
                   "super_args": SuperArgs, "counters": Counters, "host_comm": HostComm, "ens_args": EnsArgs,
                   "ens_analysis": EnsAnalysis, "front_stats": FrontStats, "layer_rec": LayerRec,
@@ -197,7 +206,7 @@ STRUCT_MIRRORS = {"params": Params, "event": Event, "sweep_info": SweepInfo, "ru
                   "solid_rec": SolidRec, "origin_rec": OriginRec, "local_args": LocalArgs,
                   "remelt_info": RemeltInfo, "substep_info": SubstepInfo, "implicit_info": ImplicitInfo,
                   "thermal_boundary": ThermalBoundary, "boundary_info": BoundaryInfo,
-                  "beam": Beam, "beam_info": BeamInfo}
+                  "beam": Beam, "beam_info": BeamInfo, "shift": Shift, "shift_info": ShiftInfo}
 
 # name -> (restype, argtypes); every symbol include/cetkmc.h declares
 _P = C.POINTER
@@ -315,6 +324,9 @@ PROTOTYPES = {
     "cetkmc_ensemble_set_beam": (C.c_int, [C.c_void_p, C.c_int, _P(Beam), _P(C.c_int32)]),
     "cetkmc_get_beam_info": (C.c_int, [C.c_void_p, _P(BeamInfo)]),
     "cetkmc_thermal_beam": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, C.c_int, C.c_int]),
+    "cetkmc_shift": (C.c_int, [C.c_void_p, _P(Shift), _P(ShiftInfo)]),
+    "cetkmc_ensemble_shift": (C.c_int, [C.c_void_p, _P(Shift), _P(ShiftInfo)]),
+    "cetkmc_time_shift": (C.c_int, [C.c_void_p, _P(Shift), _P(ShiftInfo), _P(C.c_double)]),
     "cetkmc_implicit_coeffs_bc": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, _P(C.c_double), _P(C.c_double)]),
 }
 

@@ -209,6 +209,27 @@ def _beam_struct(table, L, where, keep):
     return b
 
 
+SHIFT_T_MODES = {"value": 0, "edge": 1}      # CETKMC_SHIFT_T_VALUE, _EDGE
+
+
+def _shift_struct(d, fill_state=0, fill_T=None, T_mode="value", fill_theta=0.0, fill_phi=0.0):
+    """a cetkmc_shift record; T_mode by name, or a number passed through for the library to judge"""
+    if fill_T is None:
+        import constants as K
+        fill_T = float(K.T_SUB)
+    s = _lib.Shift()
+    s.d[:] = [int(x) for x in d]
+    s.fill_state = int(fill_state)
+    s.T_mode = SHIFT_T_MODES[T_mode] if isinstance(T_mode, str) else int(T_mode)
+    s.pad = 0
+    s.fill_T, s.fill_theta, s.fill_phi = float(fill_T), float(fill_theta), float(fill_phi)
+    return s
+
+
+def _shift_info(info):
+    return dict(calls=int(info.calls), kept=int(info.kept), exposed=int(info.exposed), dropped=[int(x) for x in info.dropped])
+
+
 def _info_dict(info):
     """an info record of the library (a ctypes structure of integers) as a dict"""
     return {n: int(getattr(info, n)) for n, _ in info._fields_}
@@ -865,6 +886,24 @@ class Engine(_ThermalSettings):
         self._ck(self.lib.cetkmc_time_thermal(self.h, int(bool(laser)), int(n_updates), C.byref(ms)))
         return ms.value
 
+    # -- the lattice shifted on the device ----------------------------------------
+    def shift(self, d, fill_state=0, fill_T=None, T_mode="value", fill_theta=0.0, fill_phi=0.0):
+        """cetkmc_shift: voxel v of the lattice moves to v + d on the device; the exposed voxels take ``fill_state``, mask 0,
+        ``fill_theta`` / ``fill_phi`` and, as T, ``fill_T`` (None: constants.T_SUB) under ``T_mode`` "value" or the old field
+        continued outward under "edge".  The maps move along.  Afterwards the handle stands as after an upload of the five new
+        fields.  Returns dict(calls, kept, exposed, dropped[6])."""
+        info = _lib.ShiftInfo()
+        self._ck(self.lib.cetkmc_shift(self.h, C.byref(_shift_struct(d, fill_state, fill_T, T_mode, fill_theta, fill_phi)), C.byref(info)))
+        return _shift_info(info)
+
+    def time_shift(self, d, **kw):
+        """cetkmc_time_shift: :meth:`shift` between two hipEvents; returns (info, device ms).  Measurement only."""
+        if isinstance(self, _Replica):
+            raise ValueError("Engine.time_shift: a replica is timed through Ensemble.time_shift (replica 0's handle is the ensemble's)")
+        info, ms = _lib.ShiftInfo(), C.c_double(0.0)
+        self._ck(self.lib.cetkmc_time_shift(self.h, C.byref(_shift_struct(d, **kw)), C.byref(info), C.byref(ms)))
+        return _shift_info(info), ms.value
+
     def nucleation_count(self):
         return int(self.lib.cetkmc_nucleation_count(self.h))
 
@@ -1018,6 +1057,29 @@ class Ensemble(_ThermalSettings):
                     nucleation_count=np.array([x.nucleation_count for x in res], np.int64),
                     min_margin=np.array([x.min_margin for x in res], np.float64), totals=totals, dt=dt[:, :n],
                     wall_ms=float(res[0].wall_ms) if R else 0.0)
+
+    def shift(self, records):
+        """cetkmc_ensemble_shift: one record per replica, each a dict of :meth:`Engine.shift`'s arguments (``d`` and the
+        fills) or None, which leaves the replica untouched like d = (0, 0, 0).  Returns one info dict per replica."""
+        records = list(records)
+        if len(records) != self.R:
+            raise ValueError(f"Ensemble.shift: {len(records)} records for {self.R} replicas")
+        buf = (_lib.Shift * max(self.R, 1))()
+        for r, rec in enumerate(records):
+            buf[r] = _shift_struct(**rec) if rec is not None else _shift_struct((0, 0, 0))
+        info = (_lib.ShiftInfo * max(self.R, 1))()
+        self._ck(self.lib.cetkmc_ensemble_shift(self.h, buf, info))
+        return [_shift_info(info[r]) for r in range(self.R)]
+
+    def time_shift(self, records):
+        """cetkmc_time_shift on the ensemble's handle: :meth:`shift` between two hipEvents; returns (infos, device ms)."""
+        records = list(records)
+        if len(records) != self.R:
+            raise ValueError(f"Ensemble.time_shift: {len(records)} records for {self.R} replicas")
+        buf = (_lib.Shift * max(self.R, 1))(*[_shift_struct(**rec) if rec is not None else _shift_struct((0, 0, 0)) for rec in records])
+        info, ms = (_lib.ShiftInfo * max(self.R, 1))(), C.c_double(0.0)
+        self._ck(self.lib.cetkmc_time_shift(self.h, buf, info, C.byref(ms)))
+        return [_shift_info(info[r]) for r in range(self.R)], ms.value
 
     def set_remelt(self, on, threshold=None):
         """cetkmc_ensemble_set_remelt: remelting in ``run`` for every replica, one threshold (default: T_melt, which the

@@ -36,6 +36,7 @@
 #include "melt.hpp"
 #include "thermal_sub.hpp"
 #include "thermal_imp.hpp"
+#include "shift.hpp"
 
 using namespace cetkmc;
 
@@ -305,6 +306,7 @@ struct Handle {
     bool ens_member = false;     // replica r >= 1 of an ensemble (released with it)
     bool in_ensemble = false;    // any replica: stepped by cetkmc_run_ensemble only
     int64_t state_uploads = 0;   // lattice (state) uploads so far: a new lattice in a replica unfreezes it
+    int64_t shift_calls = 0;     // cetkmc_shift: shifts of this lattice so far (d = 0 is none)
     // solidification map (cetkmc_solid_begin .. _end, solid.hpp): the arrays of this lattice; d_solid_block owns them on a
     // single handle (a replica's lie in its ensemble's block)
     SolidMap solid{};
@@ -1867,6 +1869,7 @@ int cetkmc_struct_size(const char* name)
     SZ("thermal_boundary", struct cetkmc_thermal_boundary);
     SZ("boundary_info", struct cetkmc_boundary_info);
     SZ("beam", struct cetkmc_beam); SZ("beam_info", struct cetkmc_beam_info);
+    SZ("shift", struct cetkmc_shift); SZ("shift_info", struct cetkmc_shift_info);
 #undef SZ
     return -1;
 }
@@ -4854,6 +4857,213 @@ int cetkmc_thermal_beam(void* handle, double dt, int64_t u, int use_latent, int 
     CHK(launch_thermal(h, dt, 1, nullptr, use_latent, scrub_nan, false, u));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// ---- the lattice shifted on the device (shift.hpp) -----------------------------------------------------
+static int shift_record_ok(const std::string& f, const struct cetkmc_shift& s, const std::string& which)
+{
+    if (s.fill_state < 0 || s.fill_state > 4) return fail(f + ": " + which + "fill_state " + std::to_string(s.fill_state) + " is outside 0..4");
+    if (s.T_mode != CETKMC_SHIFT_T_VALUE && s.T_mode != CETKMC_SHIFT_T_EDGE) return fail(f + ": " + which + "unknown T_mode " + std::to_string(s.T_mode));
+    if (s.pad != 0) return fail(f + ": " + which + "pad must be 0");
+    return 0;
+}
+static uint64_t bits_of(double x) { uint64_t b; memcpy(&b, &x, 8); return b; }
+
+// The lattices hs[r] moved by s[r].d and brought to the state an upload of the five new fields leaves (upload_impl), in one
+// launch sequence whatever their number: a single handle passes its job by value, an ensemble a device table of jobs, and
+// every kernel takes its lattice from blockIdx.y (shift.hpp).  Every array goes through a spare in its handle's scratch buffer
+// and back; the spare is as large as the largest array moved.  One synchronisation and one copy of the count records.
+static int shift_lattices(const std::vector<Handle*>& hs, const struct cetkmc_shift* s, struct cetkmc_shift_info* info, bool table)
+{
+    Handle* h0 = hs[0];
+    const int L = h0->L, R = (int)hs.size();
+    const int64_t n = (int64_t)L * L * L;
+    std::vector<ShiftJob> jobs((size_t)R);
+    int n_active = 0;
+    for (int r = 0; r < R; ++r) {
+        ShiftJob& J = jobs[(size_t)r];
+        memset(&J, 0, sizeof J);
+        for (int a = 0; a < 3; ++a) J.d[a] = std::max(-L, std::min(L, (int)s[r].d[a]));      // |d_a| >= L: everything is exposed
+        J.active = J.d[0] || J.d[1] || J.d[2];
+        n_active += J.active;
+        if (!J.active && info) { memset(info + r, 0, sizeof *info); info[r].calls = hs[(size_t)r]->shift_calls; info[r].kept = n; }
+    }
+    if (!n_active) return 0;
+    HIPCHK(hipSetDevice(h0->dev));
+    hipStream_t st = h0->stream;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    // one block of count records (and, for an ensemble, the job table) in the scratch buffer of the first lattice; the spares
+    // of every lattice in its own
+    bool solid = false, origin = false, vec_maps = true, vec_g = true;
+    size_t o_cnt0 = 0, o_tab0 = 0;
+    for (int r = 0; r < R; ++r) {
+        Handle* h = hs[(size_t)r];
+        ShiftJob& J = jobs[(size_t)r];
+        const Slab& sl = h->slabs[0];
+        size_t words = sl.nT;
+        if (h->solid_on) words = std::max(words, (size_t)3 * n);
+        if (h->origin_on) words = std::max(words, std::max((size_t)n, (size_t)5 * L));
+        const size_t o_st = up(words * 8), o_df = o_st + up(sl.nS), o_cnt = o_df + up(sl.nS), o_tab = o_cnt + up((size_t)R * SHIFT_NCNT * 8);
+        if (J.active || r == 0) CHK(ensure_scratch(h, o_tab + (size_t)R * sizeof(ShiftJob)));
+        if (r == 0) { o_cnt0 = o_cnt; o_tab0 = o_tab; }
+        if (!J.active) continue;
+        char* sp = (char*)h->d_scratch;
+        J.S = view_of(h, 0);
+        J.prev = sl.prev;
+        J.arr[SHIFT_THETA] = (unsigned long long*)sl.v.theta; J.arr[SHIFT_PHI] = (unsigned long long*)sl.v.phi;
+        J.arr[SHIFT_T] = (unsigned long long*)sl.Tbuf[h->cur];
+        J.fill[SHIFT_THETA] = bits_of(s[r].fill_theta); J.fill[SHIFT_PHI] = bits_of(s[r].fill_phi); J.fill[SHIFT_T] = bits_of(s[r].fill_T);
+        J.sp_w = (unsigned long long*)sp; J.sp_st = (uint8_t*)(sp + o_st); J.sp_df = (uint8_t*)(sp + o_df);
+        J.fill_state = (int)s[r].fill_state; J.edge = s[r].T_mode == CETKMC_SHIFT_T_EDGE;
+        if (h->solid_on) {
+            solid = true;
+            J.arr[SHIFT_STAMP] = (unsigned long long*)h->solid.stamp; J.arr[SHIFT_TS] = (unsigned long long*)h->solid.Ts;
+            J.arr[SHIFT_G] = (unsigned long long*)h->solid.g; J.arr[SHIFT_COOL] = (unsigned long long*)h->solid.cool;
+            J.snap = h->solid.snap; J.Tsnap = h->solid.Tsnap;
+        }
+        if (h->origin_on) {
+            origin = true;
+            J.arr[SHIFT_WORDS] = h->origin.words; J.arr[SHIFT_CENSUS] = (unsigned long long*)h->origin.census;
+        }
+        for (int a = SHIFT_STAMP; a < SHIFT_CENSUS; ++a)
+            if (J.arr[a] && ((uintptr_t)J.arr[a] & 15)) (a == SHIFT_G ? vec_g : vec_maps) = false;
+    }
+    char* sp0 = (char*)h0->d_scratch;           // (ensured above with room for the records and the table, also when lattice 0 rests)
+    unsigned long long* d_cnt = (unsigned long long*)(sp0 + o_cnt0);
+    ShiftJob* d_jobs = table ? (ShiftJob*)(sp0 + o_tab0) : nullptr;
+    for (int r = 0; r < R; ++r) jobs[(size_t)r].cnt = d_cnt + (size_t)r * SHIFT_NCNT;
+    HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)R * SHIFT_NCNT * 8, st));
+    if (table) {
+        HIPCHK(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)R * sizeof(ShiftJob), hipMemcpyHostToDevice, st));
+        h0->cnt.bytes_h2d += (int64_t)R * (int64_t)sizeof(ShiftJob);
+    }
+    const ShiftJob J0 = jobs[0];
+    const unsigned uR = (unsigned)R;
+
+    // state and defect mask, the dropped voxels counted from the old state; prev_state and the class bytes with the copy back
+    const int64_t lanes = (int64_t)L * L * ((L + 7) / 8);
+    const dim3 gb((unsigned)((lanes + 255) / 256), uR);
+    hipLaunchKernelGGL(k_shift_bytes, gb, dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+    hipLaunchKernelGGL(k_shift_bytes_back, gb, dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+    HIPCHK(hipGetLastError());
+
+    // a 64-bit array of every lattice into its spare and back (the same kernel with the identity)
+    auto move = [&](int a, int n0, int n1, int n2, int W, long long base, long long plane, long long row, uint64_t fill, bool vec, bool count) {
+        vec = vec && !(base & 1) && !(plane & 1) && !(row & 1);
+        const int64_t thr = (int64_t)n0 * n1 * ((W * n2 + 7) / 8);
+        const dim3 g((unsigned)((thr + 255) / 256), uR);
+        // (one lattice: its job's share as scalars; `fill` of a map array is the constant)
+        unsigned long long* arr = J0.arr[a];
+        const unsigned long long f1 = a <= SHIFT_T ? J0.fill[a] : (unsigned long long)fill;
+        for (int back = 0; back < 2; ++back) {
+            auto go = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, g, dim3(256), 0, st, (const ShiftJob*)d_jobs, arr, J0.sp_w, f1, J0.d[0], J0.d[1], J0.d[2], J0.edge, J0.cnt, a, back,
+                                   n0, n1, n2, W, base, plane, row, (unsigned long long)fill);
+            };
+            if (count && !back) go(k_shift_words<false, true>);
+            else if (vec) go(k_shift_words<true, false>);
+            else go(k_shift_words<false, false>);
+        }
+    };
+    const long long f_plane = (long long)L * h0->pitchT, f_base = 2 * f_plane;      // plane i is local plane i + 2
+    for (int a = SHIFT_THETA; a <= SHIFT_T; ++a) move(a, L, L, L, 1, f_base, f_plane, h0->pitchT, 0, true, false);
+    HIPCHK(hipGetLastError());
+
+    // the rest of an upload of a state and of orientations
+    const int nloc = L;
+    hipLaunchKernelGGL(k_shift_clear, dim3(1024, uR), dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+    hipLaunchKernelGGL(k_shift_ifc_rebuild, dim3(2048, uR), dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+    hipLaunchKernelGGL(k_shift_ifc_relist, dim3((unsigned)((nloc * L + RELIST_ROWS - 1) / RELIST_ROWS), uR), dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+    hipLaunchKernelGGL(k_shift_orient, dim3(1024, uR), dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+    HIPCHK(hipGetLastError());
+
+    if (solid) {
+        const long long LL = (long long)L * L;
+        move(SHIFT_STAMP, L, L, L, 1, 0, LL, L, ~0ull, false, true);
+        move(SHIFT_TS, L, L, L, 1, 0, LL, L, 0ull, vec_maps, false);
+        move(SHIFT_G, L, L, L, 3, 0, 3 * LL, 3 * L, 0ull, vec_g, false);
+        move(SHIFT_COOL, L, L, L, 1, 0, LL, L, 0ull, vec_maps, false);
+        const dim3 gs = solid_update_grid(L, h0->pitchT, R, 256);
+        hipLaunchKernelGGL(k_shift_snapshot, gs, dim3(256), 0, st, J0, (const ShiftJob*)d_jobs);
+        HIPCHK(hipGetLastError());
+    }
+    if (origin) {
+        move(SHIFT_WORDS, L, L, L, 1, 0, (long long)L * L, L, 0ull, vec_maps, false);
+        move(SHIFT_CENSUS, L, 1, 1, 5, 0, 5, 5, 0ull, false, false);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_shift_finish, dim3((uR + 63) / 64), dim3(64), 0, st, J0, (const ShiftJob*)d_jobs, R);
+    HIPCHK(hipGetLastError());
+
+    std::vector<unsigned long long> c((size_t)R * SHIFT_NCNT);
+    HIPCHK(hipMemcpyAsync(c.data(), d_cnt, c.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    h0->cnt.bytes_d2h += (int64_t)c.size() * 8;
+    for (int r = 0; r < R; ++r) {
+        const ShiftJob& J = jobs[(size_t)r];
+        if (!J.active) continue;
+        Handle* h = hs[(size_t)r];
+        const unsigned long long* cr = c.data() + (size_t)r * SHIFT_NCNT;
+        grow_ifc_grid(h, (int)cr[7]);
+        ++h->state_uploads;
+        ++h->shift_calls;
+        if (h->solid_on) h->solid_recorded = (int64_t)cr[6];
+        invalidate(h, Cause::upload_T_or_state);
+        if (info) {
+            int64_t kept = 1;
+            for (int a = 0; a < 3; ++a) kept *= L - std::abs(J.d[a]);
+            info[r].calls = h->shift_calls; info[r].kept = kept; info[r].exposed = n - kept;
+            for (int x = 0; x < 6; ++x) info[r].dropped[x] = (int64_t)cr[x];
+        }
+    }
+    return 0;
+}
+
+// the checks of the single-lattice calls, before anything is allocated or launched
+static int shift_single_ok(const std::string& f, Handle* h, const struct cetkmc_shift* s)
+{
+    if (!h) return fail(f + ": null handle");
+    if (!s) return fail(f + ": null argument s");
+    CHK(shift_record_ok(f, *s, ""));
+    return one_slab_only(h, f, "");
+}
+
+int cetkmc_shift(void* handle, const struct cetkmc_shift* s, struct cetkmc_shift_info* info)
+{
+    Handle* h = (Handle*)handle;
+    CHK(shift_single_ok("cetkmc_shift", h, s));
+    return shift_lattices({h}, s, info, false);
+}
+
+int cetkmc_time_shift(void* handle, const struct cetkmc_shift* s, struct cetkmc_shift_info* info, double* ms)
+{
+    const std::string f = "cetkmc_time_shift";
+    if (!handle) return fail(f + ": null handle");
+    if (!s || !ms) return fail(f + ": null argument");
+    Ens* e = ens_of(handle);
+    Handle* h = (Handle*)handle;
+    if (e) { for (int r = 0; r < e->R; ++r) CHK(shift_record_ok(f, s[r], "replica " + std::to_string(r) + ": ")); }
+    else CHK(shift_single_ok(f, h, s));
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    CHK(e ? shift_lattices(e->reps, s, info, true) : shift_lattices({h}, s, info, false));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));
+    float t = 0.0f;
+    HIPCHK(hipEventElapsedTime(&t, h->ev0, h->ev1));
+    *ms = (double)t;
+    return 0;
+}
+
+int cetkmc_ensemble_shift(void* handle, const struct cetkmc_shift* s, struct cetkmc_shift_info* info)
+{
+    const std::string f = "cetkmc_ensemble_shift";
+    if (!handle) return fail(f + ": null handle");
+    if (!s) return fail(f + ": null argument s");
+    Ens* e = ens_of(handle);
+    if (!e) return fail(f + ": not an ensemble handle (cetkmc_create_ensemble)");
+    for (int r = 0; r < e->R; ++r) CHK(shift_record_ok(f, s[r], "replica " + std::to_string(r) + ": "));
+    return shift_lattices(e->reps, s, info, true);
 }
 
 }  // extern "C"

@@ -523,11 +523,11 @@ __global__ __launch_bounds__(256) CETKMC_TOUCH_ATTR void k_domain_touch(KParams 
 // Rebuild a slab's interface list from the membership flags, in address order inside each block's 32 rows
 // (one global atomic per block).  *S.ifc_n must be zero at launch.
 constexpr int RELIST_ROWS = 32;
-__global__ __launch_bounds__(256) void k_ifc_relist(SlabView S, const StepState* __restrict__ ss)
+// (the body: blocks of 256 threads, block b of the x dimension takes rows [32 b, 32 b + 32); shared with shift.hpp's replica form)
+__device__ __forceinline__ void ifc_relist_body(const SlabView& S)
 {
     __shared__ int wsum[4], wbase[4];
     __shared__ int base;
-    if (ss && ss->status) return;
     const int L = S.L, nrows = S.nloc * L;
     const int r0 = blockIdx.x * RELIST_ROWS, r1 = min(r0 + RELIST_ROWS, nrows);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -558,6 +558,11 @@ __global__ __launch_bounds__(256) void k_ifc_relist(SlabView S, const StepState*
             off += __popcll(mask);
         }
     }
+}
+__global__ __launch_bounds__(256) void k_ifc_relist(SlabView S, const StepState* __restrict__ ss)
+{
+    if (ss && ss->status) return;
+    ifc_relist_body(S);
 }
 
 __global__ __launch_bounds__(64) void k_super_commit(StepState* ss, unsigned long long* counters, double* log_total, int64_t* log_exec,

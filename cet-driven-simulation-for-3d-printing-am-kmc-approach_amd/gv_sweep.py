@@ -242,10 +242,19 @@ if __name__ == "__main__":
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
+    ap.add_argument("--build-layers", type=int, default=0, metavar="N",
+                    help="a layer-by-layer build of N layers: --steps steps per layer, the part lowered on the device between them "
+                         "(run_kmc build, mode A; with --layer-thickness)")
+    ap.add_argument("--layer-thickness", type=int, default=None, metavar="H", help="--build-layers: planes per layer")
+    ap.add_argument("--layer-T", type=float, default=None, metavar="T", help="--build-layers: temperature of a recoated layer (default T_SUB)")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
     if a.local_events:
         kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
+    if a.build_layers or a.layer_thickness is not None or a.layer_T is not None:
+        if not a.build_layers or a.layer_thickness is None:
+            ap.error("--build-layers N and --layer-thickness H come together (--layer-T is optional)")
+        kw.update(build=dict(layers=a.build_layers, thickness=a.layer_thickness, **({"T": a.layer_T} if a.layer_T is not None else {})))
     print(gv_sweep(a.L, a.steps, tuple(a.temps), tuple(a.nu_dep), a.carbon, seeds=a.seeds, ensemble=a.ensemble, rng=a.rng,
                    laser_powers=a.laser_power, scan_speeds=a.scan_speed, laser_start=a.laser_start, front=a.front,
                    layers=a.layers, texture=a.texture, grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt,

@@ -96,6 +96,57 @@ def _beam_table_of(laser, L, n_steps):
     return beam_table(L, scan_path(L, **laser["path"]), 0, max(1, -(-int(n_steps) // THERMAL_EVERY)), laser["power"], **kw)
 
 
+def _beam_table_of_layer(laser, L, layer, per_layer):
+    """the beam table of build layer ``layer``: the global update ordinals layer * U .. (layer + 1) * U - 1,
+    U = per_layer / 20, scan the path from its beginning again -- row u holds path(u - layer * U)"""
+    kw = {k: laser[k] for k in ("beam_radius", "absorptivity", "depth", "penetration", "cutoff") if k in laser}
+    U = int(per_layer) // THERMAL_EVERY
+    path = scan_path(L, **laser["path"])
+    return beam_table(L, lambda u: path(int(u) - layer * U), layer * U, max(1, U), laser["power"], **kw)
+
+
+BUILD_KEYS = ("layers", "thickness", "T", "state")
+
+
+def _check_build(build, L, n_steps, mode, checkpointing):
+    """run_kmc's ``build`` (layer-by-layer builds): None, or a dict with layers, thickness and optionally T
+    (temperature of a recoated layer, default T_SUB) and state (its state, default 0).  Returns a checked copy."""
+    if build is None:
+        return None
+    if not isinstance(build, dict) or set(build) - set(BUILD_KEYS) or {"layers", "thickness"} - set(build):
+        raise ValueError(f"build must be a dict with keys layers, thickness[, T, state] (got {build!r})")
+    if mode != "A":
+        raise ValueError("build needs mode 'A' (the layers are stepped by the exact loop)")
+    if checkpointing:
+        raise ValueError("build cannot be combined with checkpoint_every / resume_from (a checkpoint does not carry the layer state)")
+    layers, h, state = int(build["layers"]), int(build["thickness"]), int(build.get("state", 0))
+    if layers < 1:
+        raise ValueError(f"build: layers must be >= 1 (got {build['layers']!r})")
+    if not 1 <= h <= L - 1:
+        raise ValueError(f"build: thickness must lie in 1 .. L - 1 = {L - 1} (got {build['thickness']!r})")
+    if not 0 <= state <= 4:
+        raise ValueError(f"build: state must lie in 0 .. 4 (got {build['state']!r})")
+    if int(n_steps) <= 0 or int(n_steps) % THERMAL_EVERY:
+        raise ValueError(f"build: n_steps is the number of steps per layer and must be a positive multiple of {THERMAL_EVERY}, so that "
+                         f"every layer begins on a temperature-update step (got {n_steps})")
+    return dict(layers=layers, thickness=h, T=float(build.get("T", T_SUB)), state=state)
+
+
+def _retired_planes(tables, count, layer, height0):
+    """rows of build_layers.csv: planes 0 .. count - 1 of a metrics row's per-plane tables (``tables``: name -> the
+    "planes" dict of metrics.layer_metrics / solid_metrics / origin_metrics), tagged with the layer that retires them and their
+    height in the finished part, ``height0`` + the plane index"""
+    rows = []
+    for p in range(count):
+        row = {"Layer": int(layer), "BuildHeight": int(height0 + p), "Plane": int(p)}
+        for name, t in tables.items():
+            for col, values in t.items():
+                if col != "plane":
+                    row[f"{name}_{col}"] = values[p].item()
+        rows.append(row)
+    return rows
+
+
 def _check_beam_route(laser, scheme, L):
     """a laser with a path needs the implicit scheme (the explicit kernels read a source plane), and a path and a depth profile
     that thermal_solver accepts for this L (checked on a one-row table, before any device call)"""
@@ -481,6 +532,7 @@ def run_kmc(
     thermal_boundary=None,
     local_events: int = 0,
     local_horizon: float = 1.0,
+    build: dict = None,
 ):
     """KMC microstructure evolution with natural defect injection (same contract as the
     reference).  ``defect_fraction`` is the per-event probability that the just-updated voxel
@@ -615,8 +667,24 @@ def run_kmc(
     of the update -- or a dict from ``thermal_solver.thermal_boundary`` (a substrate sink, convective faces, a cooling rate);
     cetkmc_set_thermal_boundary, DESIGN.md section 27.  ``last_run_info["thermal_boundary"]`` reports the dict (None without).
     Checkpoints carry it (``extra["thermal_bc"]``) only when it is set, and a resumed run must ask for the same.  Refused with
-    ValueError: ``mode="B"``, any other ``thermal_scheme``, ``thermal_updates=False``."""
+    ValueError: ``mode="B"``, any other ``thermal_scheme``, ``thermal_updates=False``.
+
+    ``build=dict(layers=N, thickness=h, T=T_layer, state=0)`` (mode "A" only, with or without ``laser``): a layer-by-layer
+    build.  ``n_steps`` becomes the number of steps PER LAYER, a positive multiple of 20, and the global
+    step index runs on across the layers.  Behind the last metrics row of every layer but the last, the part is lowered by
+    ``h`` planes on the device -- ``Engine.shift((-h, 0, 0), fill_state=state, fill_T=T)``: the bottom h planes leave, h planes
+    of state ``state`` (default 0) at temperature ``T`` (default T_SUB) appear on top, the maps move along.  With
+    ``layer_metrics``, ``solid_metrics`` or ``origin_metrics`` the per-plane records of the planes about to leave are appended
+    to ``outputs/<prefix>/build_layers.csv`` with ``Layer`` and ``BuildHeight`` (plane index + h * the layers retired before),
+    and at the end the remaining L planes: the file holds the whole part, L + (N - 1) h planes.  A laser with a ``path`` scans
+    the path from its beginning in every layer (a fresh beam table per layer); the plane route goes on unchanged.  Every
+    metrics row gains ``Layer`` behind every other column; ``last_run_info["build"]`` carries layers, thickness, the retired
+    planes, the voxels that left, by species, and ``complete`` (False when the run terminated early: build_layers.csv then ends with the
+    retired planes).  Refused with ValueError: ``mode="B"``; ``checkpoint_every`` / ``resume_from``
+    (a checkpoint does not carry the layer state); ``thickness`` outside 1 .. L - 1; ``layers`` < 1; ``n_steps`` not a
+    positive multiple of 20."""
     import cetkmc
+    bld = _check_build(build, L, n_steps, mode, bool(checkpoint_every or resume_from))
     n_sub = _thermal_substeps(thermal_substeps)
     _check_substeps(n_sub, mode == "A", thermal_updates)
     _check_scheme(thermal_scheme, mode == "A", thermal_updates)
@@ -691,7 +759,7 @@ def run_kmc(
     _apply_thermal_options(engine, n_sub, thermal_scheme, face_bc, remelt_thr)
     beam = laser is not None and "path" in laser
     if beam:
-        engine.set_beam(_beam_table_of(laser, L, n_steps))
+        engine.set_beam(_beam_table_of_layer(laser, L, 0, n_steps) if bld else _beam_table_of(laser, L, n_steps))
     n_flagged = int(np.sum(defects_mask))
     if mode == "B" and not (box == L or (box in (8, 10, 12, 14, 16) and L % box == 0)):
         engine.close()
@@ -751,6 +819,15 @@ def run_kmc(
             origin_planes.append(planes)
         if remelt_thr is not None:
             _add_remelt_columns(row, engine.remelt_info(), remelt_off)
+        if bld:
+            row["Layer"] = layer
+            plane_tables.clear()
+            if layer_metrics:
+                plane_tables["layer"] = layer_planes
+            if solid_metrics:
+                plane_tables["solid"] = solid_planes[-1]
+            if origin_metrics:
+                plane_tables["origin"] = origin_planes[-1]
         metrics_data.append(row)
         _print_row(step, row)
 
@@ -768,12 +845,15 @@ def run_kmc(
                         engine.download(state=False, theta=False, phi=False, T=False, defects=True)["defects"],
                         at, total_time, nuc_offset + engine.nucleation_count(), metrics_data, cet_detected, extra=extra)
 
-    while mode == "A" and next_step < n_steps:
+    # a build: n_steps per layer, the global step index runs on; n_end = end of the current layer
+    layer, n_layers, n_end = 0, (bld["layers"] if bld else 1), n_steps
+    plane_tables, build_rows, retired, dropped = {}, [], 0, [0] * 6
+    while mode == "A" and next_step < n_end:
         # next step after which the host has work: metrics (and, on multiples of
         # metrics_every, the defect-mask refresh) -- kmc_simulation.py:335-341
         stop = next_step if next_step % metrics_every == 0 else \
-            min((next_step // metrics_every + 1) * metrics_every, n_steps - 1)
-        stop = min(stop, n_steps - 1)
+            min((next_step // metrics_every + 1) * metrics_every, n_end - 1)
+        stop = min(stop, n_end - 1)
         if checkpoint_every > 0:      # also stop right before every checkpoint boundary
             stop = min(stop, (next_step // checkpoint_every + 1) * checkpoint_every - 1)
         if solid_metrics:             # ... and right before every map update
@@ -792,7 +872,7 @@ def run_kmc(
 
         if solid_metrics and next_step % solid_every == 0:
             solid_update(next_step, _updates_between(0, next_step) if thermal_updates else 0)
-        is_metric_step = (step % metrics_every == 0) or (step == n_steps - 1)
+        is_metric_step = (step % metrics_every == 0) or (step == n_end - 1)
         if not is_metric_step:        # a pure checkpoint (or map-update) stop
             if checkpoint_every > 0:
                 checkpoint(next_step)
@@ -800,6 +880,22 @@ def run_kmc(
         metrics_row(step, step % metrics_every == 0)
         if checkpoint_every > 0 and next_step % checkpoint_every == 0:
             checkpoint(next_step)
+        if bld and next_step == n_end and layer < n_layers - 1:
+            # the layer is complete and its row is written: the planes about to leave go to build_layers.csv, the part is
+            # lowered by a layer on the device, and the next layer's scan begins
+            h = bld["thickness"]
+            if plane_tables:
+                build_rows += _retired_planes(plane_tables, h, layer, retired)
+            info = engine.shift((-h, 0, 0), fill_state=bld["state"], fill_T=bld["T"], T_mode="value")
+            dropped = [a + b for a, b in zip(dropped, info["dropped"])]
+            retired, layer, n_end = retired + h, layer + 1, n_end + n_steps
+            if beam:
+                engine.set_beam(_beam_table_of_layer(laser, L, layer, n_steps))
+    # the planes that remain, from the last metrics row -- unless the run terminated behind that row: then the lattice has moved on
+    # since, the file ends with the retired planes and last_run_info["build"]["complete"] says so
+    build_complete = bool(bld) and next_step == n_end and layer == n_layers - 1
+    if bld and plane_tables and build_complete:
+        build_rows += _retired_planes(plane_tables, L, layer, retired)
 
     if mode == "B":
         # Super-step loop.  executed = events executed so far = index of the next event; g = super-step index (octant
@@ -890,6 +986,8 @@ def run_kmc(
         _write_origin_csv(os.path.join(output_dir, "origin_layers.csv"), origin_planes)
     if origin_grain_rows is not None:
         _write_origin_csv(os.path.join(output_dir, "origin_grains.csv"), [origin_grain_rows])
+    if bld and build_rows:
+        pd.DataFrame(build_rows).to_csv(os.path.join(output_dir, "build_layers.csv"), index=False)
 
     fields = engine.download()
     state, theta, phi = fields["state"], fields["theta"], fields["phi"]
@@ -906,6 +1004,9 @@ def run_kmc(
         last_run_info.update(beam=beam_report)
     if local_events:
         last_run_info.update(horizon_time=horizon_time, capped_boxes=capped_boxes)
+    if bld:
+        last_run_info.update(build=dict(layers=n_layers, thickness=bld["thickness"], retired_planes=retired, dropped=dropped,
+                                         complete=build_complete))
     if mode == "A" and min_margin < MARGIN_WARN:
         print(f"Note: smallest selection margin {min_margin:.2e} < {MARGIN_WARN:.0e} of the total rate -- a pick this close to an "
               "event boundary may differ from the reference's sequential scan")

@@ -18,6 +18,7 @@ outside the accelerated path and are not part of this package.
     python main.py --thermal-scheme implicit --thermal-boundary gradient|sink    # held gradient / substrate sink (run_kmc thermal_boundary)
     python main.py --thermal-scheme implicit --laser-power P --scan raster|serpentine|line|diagonal [--scan-speed V] [--hatch H]
                    [--beam-depth D] [--penetration M]      # a laser scan path with a volumetric beam (run_kmc laser with a path)
+    python main.py --build-layers N --layer-thickness H [--layer-T T]    # a build of N layers, --steps steps each (run_kmc build)
     python main.py --origin                       # origin columns in every metrics.csv and an origin_layers.csv per level (run_kmc origin_metrics)
 
 ``--ensemble`` with the default ``--rng reference`` writes the same files as the sequential run; ``--rng counter`` runs
@@ -185,10 +186,19 @@ if __name__ == "__main__":
     ap.add_argument("--local-events", type=int, default=0,
                     help="--mode B --box 8: local event loop, up to K events per box and super-step (run_kmc local_events)")
     ap.add_argument("--local-horizon", type=float, default=1.0, help="its time horizon in units of 1 / R_max (run_kmc local_horizon)")
+    ap.add_argument("--build-layers", type=int, default=0, metavar="N",
+                    help="a layer-by-layer build of N layers: --steps steps per layer, the part lowered on the device between them "
+                         "(run_kmc build, mode A; with --layer-thickness)")
+    ap.add_argument("--layer-thickness", type=int, default=None, metavar="H", help="--build-layers: planes per layer")
+    ap.add_argument("--layer-T", type=float, default=None, metavar="T", help="--build-layers: temperature of a recoated layer (default T_SUB)")
     a = ap.parse_args()
     kw = dict(mode="B", box=a.box) if a.mode == "B" else {}
     if a.local_events:
         kw.update(local_events=a.local_events, local_horizon=a.local_horizon)
+    if a.build_layers or a.layer_thickness is not None or a.layer_T is not None:
+        if not a.build_layers or a.layer_thickness is None:
+            ap.error("--build-layers N and --layer-thickness H come together (--layer-T is optional)")
+        kw.update(build=dict(layers=a.build_layers, thickness=a.layer_thickness, **({"T": a.layer_T} if a.layer_T is not None else {})))
     main(a.L, a.steps, tuple(a.levels), a.plots, ensemble=a.ensemble, rng=a.rng, front=a.front, layers=a.layers, texture=a.texture,
          grains=a.grains, solid=a.solid, origin=a.origin, remelt=a.remelt, thermal_substeps=a.thermal_substeps,
          thermal_scheme=a.thermal_scheme, thermal_boundary=a.thermal_boundary, scan=a.scan, laser_power=a.laser_power,

@@ -206,7 +206,7 @@ const char* cetkmc_source_hash(void);
 /* sizeof of an ABI struct by name ("params", "event", "sweep_info", "run_args", "run_result", "super_args", "counters",
  * "host_comm", "ens_args", "ens_analysis", "front_stats", "layer_rec", "texture_args", "grain_rec",
  * "solid_info", "solid_args", "solid_rec", "origin_rec", "local_args", "remelt_info", "substep_info", "implicit_info",
- * "thermal_boundary", "boundary_info", "beam", "beam_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
+ * "thermal_boundary", "boundary_info", "beam", "beam_info", "shift", "shift_info"); -1 for an unknown name.  Lets a binding check its mirrors against the library it loaded. */
 int cetkmc_struct_size(const char* name);
 /* 1 when the sums of row (plane i + di, row j + dj) depend on voxel (i, j, k), else 0: the rule the incremental mode's dirty
  * list and the stale rows of a deferred event are built from (at most 11 offsets, all within [-2, 2]^2).  Host function; needs no
@@ -1035,6 +1035,48 @@ int cetkmc_set_beam(void* handle, const struct cetkmc_beam* beam);
 int cetkmc_ensemble_set_beam(void* handle, int n_sets, const struct cetkmc_beam* sets, const int32_t* set_of);
 int cetkmc_get_beam_info(void* handle, struct cetkmc_beam_info* info);
 int cetkmc_thermal_beam(void* handle, double dt, int64_t u, int use_latent, int scrub_nan);
+
+/* The lattice shifted on the device (not in the reference): a layer recoated, a frame that follows the beam.
+ * No field crosses to the host: bytes_h2d + bytes_d2h of cetkmc_counters grow by at most 256 per lattice.
+ * For every voxel v of the new lattice let s = v - d.
+ *   s inside [0, L)^3: state, defect mask, theta, phi and T at v take the old values at s, bit for bit (NaN payloads, -0.0).
+ *   s outside:         v is exposed: state = fill_state, mask 0, theta = fill_theta, phi = fill_phi, and T = fill_T under
+ *                      CETKMC_SHIFT_T_VALUE, the old T at s clamped per axis to [0, L - 1] under CETKMC_SHIFT_T_EDGE.
+ * A component |d[a]| >= L exposes everything.  info: exposed = the exposed voxels, kept = L^3 - exposed, dropped[x] = the old
+ * voxels of state x whose v + d lies outside, calls = the shifts made on this lattice so far.
+ * d = (0, 0, 0) is a no-op: nothing is written, nothing goes stale, calls is unchanged, kept = L^3 and the other counts 0.
+ * Any other d leaves the handle exactly as cetkmc_upload of all five new fields would: prev_state := state, row flags cleared,
+ * class bytes, interface flags, list and grid and the unit vectors rebuilt, cause "upload_T_or_state" of cetkmc_invalidates
+ * raised, a frozen replica unfrozen.  What an upload leaves alone it leaves alone: a staged batch, the nucleation count,
+ * cetkmc_counters' step counts, the row-sum parity, every option and thermal setting.
+ * The maps move with the lattice.  Solidification map: stamps (exposed: -1) and the five doubles (exposed: +0.0) move, the
+ * snapshot becomes the new state and T, so a cetkmc_solid_update right behind reports n_new = n_cleared = 0.  Origin map: the
+ * words move (exposed: 0), the census rows move along axis 0 by d[0] with zero fill, cetkmc_origin_seq is unchanged.
+ * Ordered behind the handle's pending work on its stream; returns synchronised.
+ *   cetkmc_shift            one lattice: a single-slab, single-process handle or a replica handle.
+ *   cetkmc_ensemble_shift   an ensemble handle: s[R], one record per replica (d = 0 leaves that replica untouched), info[R] or NULL;
+ *                           one launch sequence, one synchronisation and one copy of the counts whatever R.
+ * Refused, before anything is allocated or launched, each naming its entry point: a NULL s; fill_state outside 0..4; an unknown
+ * T_mode; a non-zero pad; handles with several slabs and rank handles; a single-lattice handle given to the ensemble call.
+ * Non-finite fill values are allowed, as the lattice admits them. */
+enum { CETKMC_SHIFT_T_VALUE = 0, CETKMC_SHIFT_T_EDGE = 1 };
+struct cetkmc_shift {            /* 48 bytes */
+    int32_t d[3];                /* voxel v = (i, j, k) of the old lattice moves to v + d */
+    int32_t fill_state;          /* 0..4: state of the exposed voxels */
+    int32_t T_mode;              /* CETKMC_SHIFT_T_VALUE or _EDGE */
+    int32_t pad;                 /* 0 */
+    double  fill_T, fill_theta, fill_phi;
+};
+struct cetkmc_shift_info {       /* 72 bytes; this call's counts, and calls = running total on the handle */
+    int64_t calls, kept, exposed;
+    int64_t dropped[6];          /* old voxels that left the lattice, by old state 0..4, [5] = other */
+};
+int cetkmc_shift(void* handle, const struct cetkmc_shift* s, struct cetkmc_shift_info* info /* may be NULL */);
+int cetkmc_ensemble_shift(void* handle, const struct cetkmc_shift* s /* [R] */, struct cetkmc_shift_info* info /* [R] or NULL */);
+/* Measurement helper (tools/shift_timing.py): cetkmc_shift -- or, on an ensemble's handle, cetkmc_ensemble_shift with s[R] and
+ * info[R] -- between two hipEvents on the handle's stream; *ms = the time between them, from the first launch to the end of
+ * the call's last copy.  The shift is real. */
+int cetkmc_time_shift(void* handle, const struct cetkmc_shift* s, struct cetkmc_shift_info* info /* may be NULL */, double* ms);
 
 #ifdef __cplusplus
 }
