@@ -382,3 +382,32 @@ def assert_supersteps_match_oracle(e, lat, rg, ro, rate_rtol, tag=""):
     assert rg["q_used"] == ro["q_used"], (tag, "q_used", rg["q_used"], ro["q_used"])
     assert rg["nucleation_count"] == lat.nuc_count, (tag, "nucleation_count", rg["nucleation_count"], lat.nuc_count)
     assert_fields_match_oracle(e, lat, rate_rtol, tag)
+
+
+def assert_local_matches_ref(e, lat, rg, ro, rate_rtol, tag=""):
+    """One run_supersteps_local call (result rg, with want_events) against tests/local_ref.run on the oracle lattice (ro), as
+    tests/test_gpu_local_vs_ref.py compares: stop state, per-box event sequences, counts, totals, horizons, then the fields."""
+    assert (rg["done"], rg["status"]) == (ro["done"], ro["status"]), (tag, rg["done"], rg["status"], ro["done"], ro["status"])
+    done, ge, oe = ro["done"], rg["events"], ro["events"]
+    assert ge.shape == oe.shape, (tag, "event log shape", ge.shape, oe.shape)
+    for f in ("type", "pos", "target", "atom"):
+        if not np.array_equal(ge[f], oe[f]):
+            bad = np.argwhere((ge[f] != oe[f]).reshape(done, ge.shape[1], ge.shape[2], -1).any(axis=3))[0]
+            raise AssertionError(f"{tag}: event field {f} differs first at super-step {bad[0]} of the call, box {bad[1]}, event {bad[2]}: "
+                                 f"engine {ge[tuple(bad)]} comparator {oe[tuple(bad)]}")
+    live = oe["type"] >= 0
+    if live.any():
+        assert relerr(ge["rate"][live], oe["rate"][live]).max() <= rate_rtol, (tag, "event rates")
+        assert np.array_equal(ge["theta"][live], oe["theta"][live]) and np.array_equal(ge["phi"][live], oe["phi"][live]), (tag, "angles")
+    assert np.array_equal(rg["n_exec"], ro["n_exec"]) and np.array_equal(rg["n_capped"], ro["n_capped"]), (tag, "n_exec, n_capped")
+    assert len(rg["totals"]) == len(ro["totals"]), (tag, "log lengths")
+    if len(ro["totals"]):
+        assert relerr(rg["totals"], ro["totals"]).max() <= rate_rtol, (tag, "totals")
+    if done:
+        fin = np.isfinite(ro["horizon"])
+        assert np.array_equal(np.isfinite(rg["horizon"]), fin) and np.array_equal(rg["horizon"][~fin], ro["horizon"][~fin]), (tag, "horizon")
+        if fin.any():
+            assert relerr(rg["horizon"][fin], ro["horizon"][fin]).max() <= rate_rtol, (tag, "horizon")
+        assert relerr(rg["dt_event"], ro["dt_event"]).max() <= rate_rtol, (tag, "dt_event")
+    assert rg["nucleation_count"] == lat.nuc_count, (tag, "nucleation_count", rg["nucleation_count"], lat.nuc_count)
+    assert_fields_match_oracle(e, lat, rate_rtol, tag)

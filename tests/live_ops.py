@@ -679,6 +679,7 @@ class Runner:
         self.last = {}                        # the last operation, for the host conditions
         self.values = dict(BASE_PARAMS)
         self.opt = dict(OPTION_DEFAULTS)
+        self.opt_defaults = dict(OPTION_DEFAULTS)
         self.sweep_auto = True                # sweep_variant never set: L <= 128 runs the one-launch sweep, which does not defer
         self.deferred_expected = 0
         self.deferred_reset = 0               # deferred_steps that counters(reset=True) took away
@@ -810,10 +811,12 @@ class Runner:
         self.tag = tag or op["name"]
         try:
             return self._do(op)
-        except AssertionError as ex:          # where the handle stood: what the tag's three operations do not say
+        except (AssertionError, RuntimeError) as ex:      # (a call the library refused unasked: its message carries no tag)
+            # where the handle stood: what the tag's three operations do not say
             alt = {k: v for k, v in self.values.items() if v != BASE_PARAMS.get(k)}
-            opt = {k: v for k, v in self.opt.items() if v != OPTION_DEFAULTS[k]}
-            raise AssertionError(f"{ex}\nhandle: parameters off their base {alt}, options off their default {opt}, "
+            opt = {k: v for k, v in self.opt.items() if v != self.opt_defaults[k]}
+            what = f"{self.tag}: {ex}" if isinstance(ex, RuntimeError) else f"{ex}"
+            raise AssertionError(f"{what}\nhandle: parameters off their base {alt}, options off their default {opt}, "
                                  f"sweep_variant {'never set' if self.sweep_auto else 'set'}, slabs {self.n_slabs}") from ex
 
     def _do(self, op):
@@ -1139,20 +1142,31 @@ class Runner:
                 self.sub[k] += st.stats[k] - before[k]
         return ro, inp
 
+    def _inputs(self, spec, op):
+        """the host inputs of the stepping call ``op`` (a subclass may withhold the planes)"""
+        return step_inputs(self.L, spec, op["seed"])
+
+    def _engine_call(self, spec, inp):
+        """the engine's call of a stepping path, for the refusals: nothing of its result is read"""
+        e = self.e
+        if spec["kind"] == "local":
+            return lambda: e.run_supersteps_local(spec["step0"], spec["n"], DEFECT_FRACTION, COUNTER_SEED, spec["K"], spec["horizon"],
+                                                  thermal_mode=spec["thermal_mode"], thermal_dt=THERMAL_DT)
+        if spec["kind"] == "super":
+            return lambda: e.run_supersteps(spec["step0"], spec["n"], spec["box"], DEFECT_FRACTION, COUNTER_SEED,
+                                            thermal_mode=spec["thermal_mode"], thermal_dt=THERMAL_DT, q_planes=inp["q"],
+                                            null_events=spec["null_events"])
+        return lambda: e.run_steps(spec["step0"], spec["n"], DEFECT_FRACTION, inp["u_pick"], inp["u_def"], inp["u_np"],
+                                   rng_mode=spec["rng_mode"], seed=COUNTER_SEED, thermal_mode=spec["thermal_mode"], thermal_dt=THERMAL_DT,
+                                   q_planes=inp["q"], incremental=spec["incremental"])
+
     def step(self, op):
         spec = self.paths[op["name"]]
-        inp = step_inputs(self.L, spec, op["seed"])
+        inp = self._inputs(spec, op)
         e = self.e
         frag = self._step_refusal(spec)
         if frag is not None:         # refused before anything is launched: the handle is what it was
-            if spec["kind"] == "local":
-                call = lambda: e.run_supersteps_local(spec["step0"], spec["n"], DEFECT_FRACTION, COUNTER_SEED, spec["K"], spec["horizon"],
-                                                      thermal_mode=spec["thermal_mode"], thermal_dt=THERMAL_DT)
-            else:
-                call = lambda: e.run_supersteps(spec["step0"], spec["n"], spec["box"], DEFECT_FRACTION, COUNTER_SEED,
-                                                thermal_mode=spec["thermal_mode"], thermal_dt=THERMAL_DT, q_planes=inp["q"],
-                                                null_events=spec["null_events"])
-            self._refused(call, frag)
+            self._refused(self._engine_call(spec, inp), frag)
             self._verify()
             return None
         ais = self.opt["apply_in_sweep"]

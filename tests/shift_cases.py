@@ -1,6 +1,8 @@
 """Inputs shared by the cetkmc_shift tests (tests/test_shift_ref_host.py asserts, on the comparator alone, what they claim)."""
 import numpy as np
 
+import shift_ref
+
 CALL_SIZES = (1, 2, 3, 7, 8, 9, 33, 64, 65, 129, 136, 264)
 MIXED = ((3, -5, 9), (-2, 0, 1), (0, 8, -8))
 NAN_PAYLOAD_BITS = 0x7FF8DEADBEEF1234          # a quiet NaN with a payload
@@ -54,3 +56,31 @@ def physical_fields(L, seed):
     from helpers import random_lattice
     st, th, ph, T, df = random_lattice(L, seed)
     return dict(state=st, theta=th, phi=ph, T=T, defects=df)
+
+
+def seam_zone(L, d):
+    """exposed voxels and every voxel within two voxels (any direction) of the seam"""
+    ex = ~shift_ref.inside_mask(L, d)
+
+    def grown(m):
+        p = np.pad(m, 2)
+        out = np.zeros_like(m)
+        for a in range(5):
+            for b in range(5):
+                for c in range(5):
+                    out |= p[a:a + L, b:b + L, c:c + L]
+        return out
+    return ex | (grown(ex) & grown(~ex))
+
+
+def events_in_zone(L, d, events):
+    zone = seam_zone(L, d)
+    ev = np.asarray(events).reshape(-1)
+    n = 0
+    for x in ev:
+        if x["type"] < 0:
+            continue
+        n += int(zone[tuple(x["pos"])])
+        if x["type"] == 1 and x["target"][0] >= 0:
+            n += int(zone[tuple(x["target"])])
+    return n

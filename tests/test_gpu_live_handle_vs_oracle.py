@@ -15,11 +15,10 @@ Pinned as the code does it today (include/cetkmc.h): the nucleation count and ce
 new lattice; a staged batch survives every mutator and then steps the mutated lattice."""
 import os
 
-import numpy as np
 import pytest
 
 import live_ops as lo
-from helpers import assert_call_matches_oracle, assert_fields_match_oracle, assert_supersteps_match_oracle
+from helpers import assert_call_matches_oracle, assert_fields_match_oracle, assert_local_matches_ref, assert_supersteps_match_oracle
 from test_gpu_parity import RATE_RTOL
 
 pytestmark = pytest.mark.gpu
@@ -117,36 +116,6 @@ def test_staged_batch_is_consumed_once_and_dropped_by_buffer_moves(oracle_mod):
 
 # ---- the second vocabulary: remelting, sub-stepped updates, the local Mode B loop, the timers (live_ops.py) ------------------------
 CASES2 = [(L, n_slabs, name) for L, n_slabs in ((16, 1), (24, 3)) for name in lo.script_names2(L)]
-
-
-def assert_local_matches_ref(e, lat, rg, ro, rate_rtol, tag=""):
-    """One run_supersteps_local call (result rg, with want_events) against tests/local_ref.run on the oracle lattice (ro), as
-    tests/test_gpu_local_vs_ref.py compares: stop state, per-box event sequences, counts, totals, horizons, then the fields."""
-    from helpers import relerr
-    assert (rg["done"], rg["status"]) == (ro["done"], ro["status"]), (tag, rg["done"], rg["status"], ro["done"], ro["status"])
-    done, ge, oe = ro["done"], rg["events"], ro["events"]
-    assert ge.shape == oe.shape, (tag, "event log shape", ge.shape, oe.shape)
-    for f in ("type", "pos", "target", "atom"):
-        if not np.array_equal(ge[f], oe[f]):
-            bad = np.argwhere((ge[f] != oe[f]).reshape(done, ge.shape[1], ge.shape[2], -1).any(axis=3))[0]
-            raise AssertionError(f"{tag}: event field {f} differs first at super-step {bad[0]} of the call, box {bad[1]}, event {bad[2]}: "
-                                 f"engine {ge[tuple(bad)]} comparator {oe[tuple(bad)]}")
-    live = oe["type"] >= 0
-    if live.any():
-        assert relerr(ge["rate"][live], oe["rate"][live]).max() <= rate_rtol, (tag, "event rates")
-        assert np.array_equal(ge["theta"][live], oe["theta"][live]) and np.array_equal(ge["phi"][live], oe["phi"][live]), (tag, "angles")
-    assert np.array_equal(rg["n_exec"], ro["n_exec"]) and np.array_equal(rg["n_capped"], ro["n_capped"]), (tag, "n_exec, n_capped")
-    assert len(rg["totals"]) == len(ro["totals"]), (tag, "log lengths")
-    if len(ro["totals"]):
-        assert relerr(rg["totals"], ro["totals"]).max() <= rate_rtol, (tag, "totals")
-    if done:
-        fin = np.isfinite(ro["horizon"])
-        assert np.array_equal(np.isfinite(rg["horizon"]), fin) and np.array_equal(rg["horizon"][~fin], ro["horizon"][~fin]), (tag, "horizon")
-        if fin.any():
-            assert relerr(rg["horizon"][fin], ro["horizon"][fin]).max() <= rate_rtol, (tag, "horizon")
-        assert relerr(rg["dt_event"], ro["dt_event"]).max() <= rate_rtol, (tag, "dt_event")
-    assert rg["nucleation_count"] == lat.nuc_count, (tag, "nucleation_count", rg["nucleation_count"], lat.nuc_count)
-    assert_fields_match_oracle(e, lat, rate_rtol, tag)
 
 
 def _play2(oracle_mod, L, n_slabs, name, paths=None):

@@ -22,6 +22,7 @@ import beam_cases as bm
 import beam_ref
 import implicit_cases as ic
 import shift_ref as SR
+from shift_cases import events_in_zone
 from helpers import (FOUR_KIND_PARAMS, assert_call_matches_oracle, batch_calls, face_lattice, oracle_lattice, random_lattice)
 from test_gpu_parity import RATE_RTOL
 
@@ -51,34 +52,6 @@ def shift_by_host(e, d, **kw):
     """what the parent offers: download, comparator, upload"""
     out, _ = SR.shift_fields(e.download(defects=True), d, **kw)
     e.upload(out["state"], out["theta"], out["phi"], out["T"], out["defects"])
-
-
-def seam_zone(L, d):
-    """exposed voxels and every voxel within two voxels (any direction) of the seam"""
-    ex = ~SR.inside_mask(L, d)
-
-    def grown(m):
-        p = np.pad(m, 2)
-        out = np.zeros_like(m)
-        for a in range(5):
-            for b in range(5):
-                for c in range(5):
-                    out |= p[a:a + L, b:b + L, c:c + L]
-        return out
-    return ex | (grown(ex) & grown(~ex))
-
-
-def events_in_zone(L, d, events):
-    zone = seam_zone(L, d)
-    ev = np.asarray(events).reshape(-1)
-    n = 0
-    for x in ev:
-        if x["type"] < 0:
-            continue
-        n += int(zone[tuple(x["pos"])])
-        if x["type"] == 1 and x["target"][0] >= 0:
-            n += int(zone[tuple(x["target"])])
-    return n
 
 
 def assert_twins_agree(rg, rg2, e, e2, tag):
